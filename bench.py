@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the MI355X-native batched LoIK solver.
 
-  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+  python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
 
 `--gpus N` runs N GPUs BY ITSELF: the batch shards into independent contiguous ranges with no exchange step
 (SURVEY.md 8(e)), so one process drives N devices with one host thread + one solver handle + one stream per device
@@ -360,6 +360,57 @@ def run_shards(shards, steps, warmup, barrier=None):
     if barrier is not None:
         barrier()
     return elapsed
+
+
+DUMP_MAX_BYTES = 64 * 10**6   # --dump-outputs: at most 64 MB in all; above that a fixed sample of the instances
+DUMP_SAMPLE_SEED = 0xD0D0
+
+
+def dump_outputs(out_dir, shards, dist=None):
+    """--dump-outputs DIR: what a caller of the timed path receives after the last timed step -- the result members of the handle
+    that ran it (get_results: z, nu, w, vis, fis, yis and the [B][33] scalar block), every shard of the job in device order, instance
+    axis first -- as DIR/<name>.npy in float64, and DIR/instance.npy: each row's index in the job's whole batch.  When all of it would
+    exceed DUMP_MAX_BYTES, the rows are a fixed, seeded sample of the instances, the same rows for every member.  The inputs are seeded:
+    the same arguments give the same files on any build, so that two builds can be compared output for output.  Runs on every rank
+    (the rows travel to rank 0 through the gloo group, after the timed region); returns a summary on rank 0, None elsewhere."""
+    sizes = [sh.B for sh in shards]
+    offset = 0
+    if dist is not None:
+        every = [None] * dist.get_world_size()
+        dist.all_gather_object(every, sizes)
+        offset = sum(sum(s) for s in every[:dist.get_rank()])
+        total = sum(sum(s) for s in every)
+    else:
+        total = sum(sizes)
+    rows = parts = None
+    for sh in shards:
+        h = sh.timed[-1] if sh.timed else sh.solver
+        res = h.get_results(h.RESULT_FIELDS)
+        if rows is None:
+            row_bytes = 8 + sum(a.nbytes // max(a.shape[0], 1) for a in res.values())   # (8: instance.npy)
+            k = min(total, (DUMP_MAX_BYTES - 256 * (len(res) + 1)) // row_bytes)     # (256: room for each file's .npy header)
+            rows = np.arange(total) if k == total else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(total, k, replace=False))
+            parts = {name: [] for name in res}
+            parts["instance"] = []
+        mine = rows[(rows >= offset) & (rows < offset + sh.B)]
+        for name, a in res.items():
+            parts[name].append(np.asarray(a, dtype=np.float64)[mine - offset])
+        parts["instance"].append(mine.astype(np.float64))
+        offset += sh.B
+    parts = {name: np.concatenate(p) for name, p in parts.items()}
+    if dist is not None:
+        got = [None] * dist.get_world_size() if dist.get_rank() == 0 else None
+        dist.gather_object(parts, got, dst=0)
+        if dist.get_rank() != 0:
+            return None
+        parts = {name: np.concatenate([g[name] for g in got]) for name in parts}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in parts.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in parts), "instances": int(rows.size), "of": int(total),
+            "bytes": int(sum(a.nbytes for a in parts.values())), "dtype": "float64",
+            "what": "result members of the last timed step (get_results), rows = instance.npy of the whole batch" +
+                    (" (a sample seeded with %d)" % DUMP_SAMPLE_SEED if rows.size < total else "")}
 
 
 def csrc_sha16():
@@ -797,7 +848,12 @@ def main(argv=None, solver_factory=None, device_count=None):
                     help="with --repeat-batch: LOIKB_FLAT_ORDER=0, every solve in arrival order")
     ap.add_argument("--flags", type=int, default=0)
     ap.add_argument("--max-launch-iters", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one to DIR/<name>.npy (float64, at most 64 MB: a fixed, "
+                         "seeded sample of the instances when the batch's results are larger)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch is None:
         args.batch = HEADLINE_BATCH if args.config == "c3" else 131072
     if args.config == "c4":
@@ -880,6 +936,7 @@ def main(argv=None, solver_factory=None, device_count=None):
         return sorted((c for part in buf for c in part), key=lambda c: c["gpu"])
 
     shards, res, elapsed, tot = measure(args.scaling)
+    dumped = dump_outputs(args.dump_outputs, shards, dist) if args.dump_outputs else None
     chains = gather_chains(shards)
     plan0 = shards[0].solver.plan() if hasattr(shards[0].solver, "plan") else None   # which kernels ran, and why
     strong = None
@@ -976,6 +1033,8 @@ def main(argv=None, solver_factory=None, device_count=None):
             # two bounds a shard (the chain does not shrink with the shard: DESIGN.md 6)
             "per_shard": chains,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if strong is not None:
             # both legs as objects of their own, so that whichever a reader of the line wants is labelled: the top-level
             # value / ms_per_step are the weak leg's

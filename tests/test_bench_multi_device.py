@@ -58,6 +58,13 @@ class FakeSolver:
         return {"converged": self.out["converged"].astype(np.int32), "iter": self.out["iters"],
                 "primal_infeasible": self.out["primal_infeasible"].astype(np.int32)}[name]
 
+    RESULT_FIELDS = ("z", "scalars")
+
+    def get_results(self, fields):
+        o = self.out
+        res = {"z": o["z"].copy(), "scalars": np.stack([o["primal_residual"], o["dual_residual"], o["iters"], o["converged"]], axis=1)}
+        return {k: res[k].astype(np.float64) for k in fields}
+
     def close(self):
         self.closed = True
 
@@ -140,6 +147,40 @@ def test_config_c4_runs_tailored_steps_over_its_targets(capsys, monkeypatch):
         assert np.array_equal(s.tailored[0], s.tailored[4]) and not np.array_equal(s.tailored[0], s.tailored[1])   # T = 4, cycled
     assert not np.array_equal(CREATED[0].tailored[0], CREATED[1].tailored[0])                                     # every share its own sequence
     assert line["config"]["batch_total"] == 24 and 0.0 <= line["config"]["solved_fraction"] <= 1.0
+
+
+def test_dump_outputs_writes_the_last_timed_step(capsys, monkeypatch, tmp_path):
+    """--dump-outputs DIR: the results of every shard's last timed step, as a caller of that path receives them, in device order; the
+    same arguments give the same files; above the byte budget a fixed, seeded sample of the instances, the same rows in every file"""
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "12", "--no-cpu-baseline", "--no-strong-leg"]
+    line = _run(argv + ["--dump-outputs", str(tmp_path / "a")], capsys)
+    last = [[s for s in CREATED if s.device == d][-1] for d in (0, 1)]   # the handle of each shard's last timed step
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("z", "scalars", "instance")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["z"], np.concatenate([s.out["z"] for s in last]))
+    assert np.array_equal(got["scalars"][:, 2], np.concatenate([s.out["iters"] for s in last]))
+    assert np.array_equal(got["instance"], np.arange(24))
+    assert line["dump_outputs"]["instances"] == 24 and line["dump_outputs"]["of"] == 24
+    _run(argv + ["--dump-outputs", str(tmp_path / "b")], capsys)
+    for n, a in got.items():
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / (n + ".npy")))), n
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 256 + 10 * (8 + 8 * 32 + 8 * 4))   # room for 10 instances of 24
+    line = _run(argv + ["--dump-outputs", str(tmp_path / "c")], capsys)
+    small = {n: np.load(str(tmp_path / "c" / (n + ".npy"))) for n in got}
+    idx = small["instance"].astype(int)
+    assert len(idx) == 10 and np.array_equal(idx, np.unique(idx)) and line["dump_outputs"]["instances"] == 10
+    assert np.array_equal(small["z"], got["z"][idx]) and np.array_equal(small["scalars"], got["scalars"][idx])
+    assert sum(os.path.getsize(str(tmp_path / "c" / (n + ".npy"))) for n in got) <= bench.DUMP_MAX_BYTES
+
+
+def test_steps_sets_the_number_of_timed_steps(capsys, monkeypatch):
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for steps in (1, 4):
+        line = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "2", "--batch", "8", "--no-cpu-baseline", "--repeat-batch"], capsys, ndev=1)
+        assert line["steps"] == steps and CREATED[0].nsolve == steps + 2
+    with pytest.raises(SystemExit):
+        bench.main(["--gpus", "1", "--steps", "0", "--batch", "8", "--no-cpu-baseline"], solver_factory=FakeSolver, device_count=1)
 
 
 def test_more_shards_than_devices_needs_opt_in(capsys, monkeypatch):
