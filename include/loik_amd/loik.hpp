@@ -16,6 +16,7 @@
 #pragma once
 
 #include "../loik_amd.h"
+#include "../loik_amd_pose.h"
 
 #include <array>
 #include <map>
@@ -332,6 +333,47 @@ public:
     if (bis.size() == 1 && batch_ > 1) flags |= LOIKB_B_SHARED;
     check(loikb_solve_tailored(h_, nullptr, (int)c_id, Ai.data(), b.data(), flags));
     solved();
+  }
+  // ---- batched pose IK (include/loik_amd_pose.h): per step e_c = log6(oMi_c^-1 oMdes_c), b_c = A_c (gain / dt) e_c, the tailored
+  //      Solve on the resident q, q <- q (+) dt z for the instances not yet reached.  A placement is R row-major, then t.
+  using SE3 = std::array<double, 12>;
+  struct PoseResult {
+    std::vector<int> reached, steps, status;  // [batch]; status: LOIKB_POSE_ST_* bits
+    DVec err;                                 // [batch][nc][6]: e_c of the final q, [linear; angular]
+  };
+  // targets: one per active constraint (active_task_constraint_ids order) for the whole batch, or batch * nc instance-major;
+  // q: nullptr = the resident configurations, else [batch][nq] replaces them first
+  PoseResult SolvePose(const std::vector<SE3>& targets, double dt = 1.0, double gain = 1.0, double tol_pose = 1e-6, int max_steps = 100,
+                       const DVec* q = nullptr)
+  {
+    const std::size_t nc = (std::size_t)loikb_num_eq_c(h_);
+    int flags = 0;
+    if (targets.size() == nc && batch_ > 1) flags |= LOIKB_POSE_TARGET_SHARED;
+    else if (targets.size() != (std::size_t)batch_ * nc)
+      throw std::runtime_error("loik_amd: SolvePose needs one target per active constraint, shared or per instance");
+    if (q && q->size() != (std::size_t)batch_ * model_.nq) throw std::runtime_error("loik_amd: q must hold batch * model.nq values");
+    DVec t(targets.size() * 12);
+    for (std::size_t i = 0; i < targets.size(); ++i) std::copy(targets[i].begin(), targets[i].end(), t.begin() + 12 * i);
+    const loikb_pose_params p{dt, gain, tol_pose, max_steps, 0};
+    check(loikb_solve_pose(h_, q ? q->data() : nullptr, t.data(), flags, &p));
+    solved();
+    PoseResult r;
+    r.steps.resize(batch_); r.status.resize(batch_); r.reached.resize(batch_); r.err.resize((std::size_t)batch_ * nc * 6);
+    check(loikb_pose_get(h_, LOIKB_POSE_F_STEPS, r.steps.data(), 0));
+    check(loikb_pose_get(h_, LOIKB_POSE_F_STATUS, r.status.data(), 0));
+    check(loikb_pose_get(h_, LOIKB_POSE_F_ERR, r.err.data(), 0));
+    for (int b = 0; b < batch_; ++b) r.reached[b] = (r.status[b] & LOIKB_POSE_ST_REACHED) ? 1 : 0;
+    return r;
+  }
+  // world placements oMi of `links` for the resident q: [batch][links.size()]
+  std::vector<SE3> ForwardKinematics(const std::vector<Index>& links) const
+  {
+    std::vector<int> l(links.begin(), links.end());
+    DVec out((std::size_t)batch_ * l.size() * 12);
+    check(loikb_forward_kinematics(h_, l.data(), (int)l.size(), out.data(), 0));
+    std::vector<SE3> M((std::size_t)batch_ * l.size());
+    for (std::size_t i = 0; i < M.size(); ++i) std::copy(out.begin() + 12 * i, out.begin() + 12 * (i + 1), M[i].begin());
+    return M;
   }
   // the resident configurations, [batch][nq]
   DVec q_resident() const

@@ -88,6 +88,18 @@ EXPORTED_SYMBOLS = [
     "loikb_num_eq_c", "loikb_eq_c_capacity", "loikb_active_constraint_ids", "loikb_get_solver_info", "loikb_solver_info_rows_cap", "loikb_solver_info_truncated", "loikb_builtin_model", "loikb_builtin_joint_name",
     "loikb_builtin_joint_id", "loikb_flat_schedule"]
 
+# include/loik_amd_pose.h: batched pose IK, its own header and version (EXPORTED_SYMBOLS stays the two headers above)
+POSE_ABI_VERSION = 1
+POSE_SYMBOLS = ["loikb_pose_version", "loikb_solve_pose", "loikb_forward_kinematics", "loikb_pose_get"]
+POSE_TARGET_SHARED = 32
+POSE_F_STEPS, POSE_F_STATUS, POSE_F_ERR, POSE_F_TIMING = 0, 1, 2, 3
+POSE_ST_REACHED, POSE_ST_NOT_CONVERGED, POSE_ST_INFEASIBLE, POSE_ST_STOPPED = 1, 2, 4, 8
+
+
+class PoseParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
+
+
 _lib = None
 
 
@@ -144,6 +156,9 @@ def lib():
     L.loikb_builtin_joint_name.restype = C.c_char_p
     L.loikb_builtin_joint_id.argtypes = [C.c_char_p, C.c_char_p]
     L.loikb_flat_schedule.argtypes = [_ip, C.c_int, _ip, C.c_int, _ip]
+    L.loikb_solve_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseParams)]
+    L.loikb_forward_kinematics.argtypes = [C.c_void_p, _ip, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_pose_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -577,6 +592,85 @@ class BatchedLoik:
     def integrate(self, dt):
         """outer loop on the device: q <- q (+) dt * z of the last solve, q stays resident in HBM"""
         _check(self.L.loikb_integrate(self.h, float(dt)))
+
+    # ---- batched pose IK (include/loik_amd_pose.h) ----------------------------------------------------------
+    def _placements12(self, a, what):
+        """host placements [..][4][4] or [..][12] -> float64 [..][12] (R row-major, then t)"""
+        a = _f64(a)
+        if a.shape[-2:] == (4, 4):
+            a = np.concatenate([a[..., :3, :3].reshape(a.shape[:-2] + (9,)), a[..., :3, 3]], axis=-1)
+        elif a.shape[-1] != 12:
+            raise ValueError("%s: placements are [..][4][4] or [..][12], got shape %s" % (what, a.shape))
+        return np.ascontiguousarray(a)
+
+    def SolvePose(self, targets, dt=1.0, gain=1.0, tol_pose=1e-6, max_steps=100, q=None):
+        """global IK on the device (loikb_solve_pose): per step e_c = log6(oMi_c^-1 oMdes_c), b_c = A_c (gain / dt) e_c, the
+        tailored Solve on the resident q (warm_start as the handle says), q <- q (+) dt z for the instances not yet reached.
+        targets: one placement per active constraint (active_task_constraint_ids order), [B][nc][4][4] / [B][nc][12], or
+        [nc][4][4] / [nc][12] (/ [4][4] / [12] for one constraint) shared by the batch; a device tensor is [B][nc][12] or
+        [nc][12] by its numel.  q: None = the resident configurations, else [B][nq] replaces them first.
+        Returns dict(reached [B] bool, steps [B], err [B][nc][6] = e_c of the final q, status [B] POSE_ST_* bits)."""
+        B, nc = self.batch, int(self.L.loikb_num_eq_c(self.h))
+        flags, keep = 0, []
+        if isinstance(targets, int) or (hasattr(targets, "data_ptr") and getattr(targets, "is_cuda", False)):
+            n = None if isinstance(targets, int) else int(targets.numel())
+            if n is not None and n not in (B * nc * 12, nc * 12):
+                raise ValueError("targets: device tensor has %d elements, expected batch * nc * 12 or nc * 12" % n)
+            tp = C.c_void_p(targets if isinstance(targets, int) else targets.data_ptr())
+            flags |= IN_DEVICE
+            if n == nc * 12 and B > 1:
+                flags |= POSE_TARGET_SHARED
+        else:
+            t = self._placements12(targets.numpy() if hasattr(targets, "numpy") else targets, "targets")
+            if t.size == B * nc * 12:
+                pass
+            elif t.size == nc * 12:
+                flags |= POSE_TARGET_SHARED
+            else:
+                raise ValueError("targets: %d placements, expected batch * nc = %d or nc = %d" % (t.size // 12, B * nc, nc))
+            keep.append(t)
+            tp = t.ctypes.data_as(C.c_void_p)
+        qp = None
+        if q is not None:
+            if isinstance(q, int) or (hasattr(q, "data_ptr") and getattr(q, "is_cuda", False)):
+                if not flags & IN_DEVICE:
+                    raise ValueError("q and targets must both be host arrays or both device pointers")
+                qp = C.c_void_p(q if isinstance(q, int) else q.data_ptr())
+            else:
+                if flags & IN_DEVICE:
+                    raise ValueError("q and targets must both be host arrays or both device pointers")
+                qa = _f64(q)
+                if qa.size != B * self.model.nq:
+                    raise ValueError("q has %d elements, expected batch * nq = %d" % (qa.size, B * self.model.nq))
+                keep.append(qa)
+                qp = qa.ctypes.data_as(C.c_void_p)
+        prm = PoseParams(float(dt), float(gain), float(tol_pose), int(max_steps), 0)
+        _check(self.L.loikb_solve_pose(self.h, qp, tp, flags, C.byref(prm)))
+        status = np.empty(B, dtype=np.int32)
+        steps = np.empty(B, dtype=np.int32)
+        err = np.empty((B, nc, 6))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_STATUS, status.ctypes.data_as(C.c_void_p), 0))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_STEPS, steps.ctypes.data_as(C.c_void_p), 0))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_ERR, err.ctypes.data_as(C.c_void_p), 0))
+        return dict(reached=(status & POSE_ST_REACHED) != 0, steps=steps, err=err, status=status)
+
+    def pose_timing(self):
+        """of the last SolvePose: dict(steps, total_ms, solve_ms, other_ms) -- wall clock; other = re-target, b, integrate, read-backs"""
+        t = np.zeros(4)
+        _check(self.L.loikb_pose_get(self.h, POSE_F_TIMING, t.ctypes.data_as(C.c_void_p), 0))
+        return dict(steps=int(t[0]), total_ms=float(t[1]), solve_ms=float(t[2]), other_ms=float(t[3]))
+
+    def forward_kinematics(self, links):
+        """world placements oMi of `links` (the caller's joint ids) for the resident q: [B][n][4][4]"""
+        links = np.ascontiguousarray(np.atleast_1d(links), dtype=np.int32)
+        n = int(links.size)
+        out = np.empty((self.batch, n, 12))
+        _check(self.L.loikb_forward_kinematics(self.h, links.ctypes.data_as(_ip), n, out.ctypes.data_as(C.c_void_p), 0))
+        M = np.zeros((self.batch, n, 4, 4))
+        M[..., :3, :3] = out[..., :9].reshape(self.batch, n, 3, 3)
+        M[..., :3, 3] = out[..., 9:]
+        M[..., 3, 3] = 1.0
+        return M
 
     # ------------------------------------------------------------------------------------------------------
     def set_max_iter(self, n):

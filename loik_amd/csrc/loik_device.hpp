@@ -1501,54 +1501,51 @@ __device__ __forceinline__ T* elem_ptr(char* lp, int pair, int half)
 
 // FwdPassInit (hxx:253-283): joint configuration -> per-joint (cos q, sin q) | (q, 0); the first joint of the chain of
 // a multi-DoF joint spreads that joint's (t, quat) over the JP_CS pairs of the chain (layout: see ROT_FREE).
+// joint_q_pairs is that map for one device joint: qs = the joint's coordinates, p[2k], p[2k+1] = the pair of chain record k;
+// returns the number of pairs (1 .. 4).  Not for JF_NOQ joints, whose pair belongs to the first joint of the chain.  Both
+// FwdPassInit (fk_init_joint) and the world placements of loik_pose.hpp read q through it.
+__device__ __forceinline__ int joint_q_pairs(const double* __restrict__ qs, const JointDesc& d, double* p)
+{
+  const int rot = d.rot;
+  if (rot == ROT_FREE) {
+    for (int k = 0; k < 7; ++k) p[k] = qs[k];
+    p[7] = 0.0;
+    return 4;
+  }
+  if (rot == ROT_SPH || rot == ROT_PLANAR) {
+    for (int k = 0; k < 4; ++k) p[k] = qs[k];
+    return 2;
+  }
+  if (rot == ROT_TRANS) {
+    for (int k = 0; k < 3; ++k) p[k] = qs[k];
+    p[3] = 0.0;
+    return 2;
+  }
+  if (d.flags & JF_CS_DIRECT) {  // JointModelRevoluteUnbounded: q = (cos, sin)
+    p[0] = qs[0]; p[1] = qs[1];
+    return 1;
+  }
+  const double qi = qs[0];
+  if ((d.flags & JF_REVOLUTE) && !(d.flags & JF_HELICAL)) {
+    double sd, cd;
+    sincos(qi, &sd, &cd);
+    p[0] = cd; p[1] = sd;
+  } else {
+    p[0] = qi; p[1] = 0.0;
+  }
+  return 1;
+}
 // q is instance-major [B][nq] (the caller's layout) or one shared [nq]; idx_q[i] = where joint i's coordinates start.
 template <typename T>
 __device__ __forceinline__ void fk_init_joint(const double* __restrict__ qrow, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q,
                                               char* lp, int i)
 {
   constexpr size_t RB = (size_t)JREC * pair_bytes<T>();
-  {
-    if (jd[i].flags & JF_NOQ) return;  // its pair belongs to the first joint of the chain
-    const double* qs = qrow + idx_q[i];
-    char* rec = lp + (size_t)(i - 1) * RB;
-    const int rot = jd[i].rot;
-    if (rot == ROT_FREE) {
-      stp<T>(rec, JP_CS, (T)qs[0], (T)qs[1]);
-      stp<T>(rec + RB, JP_CS, (T)qs[2], (T)qs[3]);
-      stp<T>(rec + 2 * RB, JP_CS, (T)qs[4], (T)qs[5]);
-      stp<T>(rec + 3 * RB, JP_CS, (T)qs[6], T(0));
-      return;
-    }
-    if (rot == ROT_SPH) {
-      stp<T>(rec, JP_CS, (T)qs[0], (T)qs[1]);
-      stp<T>(rec + RB, JP_CS, (T)qs[2], (T)qs[3]);
-      return;
-    }
-    if (rot == ROT_TRANS) {
-      stp<T>(rec, JP_CS, (T)qs[0], (T)qs[1]);
-      stp<T>(rec + RB, JP_CS, (T)qs[2], T(0));
-      return;
-    }
-    if (rot == ROT_PLANAR) {
-      stp<T>(rec, JP_CS, (T)qs[0], (T)qs[1]);
-      stp<T>(rec + RB, JP_CS, (T)qs[2], (T)qs[3]);
-      return;
-    }
-    if (jd[i].flags & JF_CS_DIRECT) {  // JointModelRevoluteUnbounded: q = (cos, sin)
-      stp<T>(rec, JP_CS, (T)qs[0], (T)qs[1]);
-      return;
-    }
-    const double qi = qs[0];
-    T c, s;
-    if ((jd[i].flags & JF_REVOLUTE) && !(jd[i].flags & JF_HELICAL)) {
-      double sd, cd;
-      sincos(qi, &sd, &cd);
-      c = (T)cd; s = (T)sd;
-    } else {
-      c = (T)qi; s = T(0);
-    }
-    stp<T>(rec, JP_CS, c, s);
-  }
+  if (jd[i].flags & JF_NOQ) return;  // its pair belongs to the first joint of the chain
+  char* rec = lp + (size_t)(i - 1) * RB;
+  double p[8];
+  const int n = joint_q_pairs(qrow + idx_q[i], jd[i], p);
+  for (int k = 0; k < n; ++k) stp<T>(rec + k * RB, JP_CS, (T)p[2 * k], (T)p[2 * k + 1]);
 }
 template <typename T>
 __global__ void k_fk_init(const double* __restrict__ q, int nq, int q_shared, const JointDesc* __restrict__ jd,
@@ -1640,23 +1637,16 @@ __device__ __forceinline__ void se3_integrate(double* q7, const double* v)
 // outer loop: q <- q (+) dt * z on the resident configurations (1-DoF and translation joints: a plain sum; free-flyer
 // and spherical joints: the Lie-group update above), `src` != nullptr first (re)fills the resident copy from a
 // caller's q (one shared row or one row per instance)
+// one instance of it: q_row <- q_row (+) dt * z, z read from the instance's joint records `lp`
 template <typename T>
-__global__ void k_advance_q(double* __restrict__ q_res, const double* __restrict__ src, int src_shared, int nq,
-                            const JointDesc* __restrict__ jd, const int* __restrict__ idx_q, Layout L, int B,
-                            const char* tiles, double dt)
+__device__ __forceinline__ void advance_q_instance(double* __restrict__ q_row, const JointDesc* __restrict__ jd,
+                                                   const int* __restrict__ idx_q, int nb, const char* lp, double dt)
 {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  if (src) {
-    for (int k = 0; k < nq; ++k) q_res[(size_t)b * nq + k] = src[(src_shared ? 0 : (size_t)b * nq) + k];
-    return;
-  }
-  const char* lp = lane_ptr<T>(const_cast<char*>(tiles), L, b);
   constexpr size_t RB = (size_t)JREC * pair_bytes<T>();
-  for (int i = 1; i <= L.nb; ++i) {
+  for (int i = 1; i <= nb; ++i) {
     if (jd[i].flags & JF_NOQ) continue;
     const char* rec = lp + (size_t)(i - 1) * RB;
-    double* qs = q_res + (size_t)b * nq + idx_q[i];
+    double* qs = q_row + idx_q[i];
     const int rot = jd[i].rot;
     const int n = rot == ROT_FREE ? 6 : (rot == ROT_SPH || rot == ROT_TRANS || rot == ROT_PLANAR) ? 3 : 1;
     double v[6];
@@ -1693,6 +1683,19 @@ __global__ void k_advance_q(double* __restrict__ q_res, const double* __restrict
       for (int k = 0; k < n; ++k) qs[k] += v[k];
     }
   }
+}
+template <typename T>
+__global__ void k_advance_q(double* __restrict__ q_res, const double* __restrict__ src, int src_shared, int nq,
+                            const JointDesc* __restrict__ jd, const int* __restrict__ idx_q, Layout L, int B,
+                            const char* tiles, double dt)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  if (src) {
+    for (int k = 0; k < nq; ++k) q_res[(size_t)b * nq + k] = src[(src_shared ? 0 : (size_t)b * nq) + k];
+    return;
+  }
+  advance_q_instance<T>(q_res + (size_t)b * nq, jd, idx_q, L.nb, lane_ptr<T>(const_cast<char*>(tiles), L, b), dt);
 }
 
 // instance-major [B][n] doubles (or one shared [n]) -> tile elements given by rowmap[r] = pair*2 + half

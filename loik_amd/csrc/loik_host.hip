@@ -18,6 +18,7 @@
 #include "loik_flat.hpp"
 #include "loik_flat2.hpp"
 #include "loik_passes.hpp"
+#include "loik_pose.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
 #include "loik_flat_inst.hpp"
@@ -29,8 +30,10 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #endif
 
 #include "../../include/loik_amd.h"
+#include "../../include/loik_amd_pose.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -351,6 +354,19 @@ struct loikb_solver_impl {
   int* d_log_rows = nullptr;
   int log_rows_cap = 0;
   bool have_log = false;
+  // batched pose IK (loik_pose.hpp): buffers of loikb_solve_pose, allocated by its first call (sizes: batch and slot capacity)
+  struct PoseState {
+    double* d_tgt = nullptr;           // [B][nc][12] targets (shared: the first nc rows)
+    double* d_b = nullptr;             // [nc][B][6] b of the next inner solve, constraint-major: one [B][6] input per constraint
+    double* d_err = nullptr;           // [B][nc][6] e_c of the last retarget
+    double* d_A = nullptr;             // [nc][36] the shared A in fp64 (the uniform copy is in the solve precision)
+    int* d_status = nullptr;           // [B] POSE_* bits
+    int* d_steps = nullptr;            // [B]
+    int* d_clink = nullptr;            // [nc] device joint that carries the body of each active constraint
+    unsigned int* d_count = nullptr;   // [2] instances still running, target rotations rejected
+    int nc = 0;                        // constraints of the last pose solve (0: none yet)
+    double timing[4] = {0, 0, 0, 0};   // LOIKB_POSE_F_TIMING
+  } pose;
 };
 using Chunk = loikb_solver_impl::Chunk;
 
@@ -4028,5 +4044,171 @@ int loikb_debug_tail_prof_all(unsigned long long* out, int reset)   // the phase
   return LOIKB_OK;
 }
 #endif
+
+}  // extern "C"
+
+// ---- batched pose IK (include/loik_amd_pose.h, kernels in loik_pose.hpp) ---------------------------------------------------
+static int pose_alloc(loikb_solver_impl* S)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (P.d_tgt) return LOIKB_OK;
+  const size_t B = (size_t)S->B, nc = (size_t)std::max(S->nc, 1);
+  int rc;
+  if ((rc = alloc_dev(S, (void**)&P.d_tgt, sizeof(double) * B * nc * 12)) || (rc = alloc_dev(S, (void**)&P.d_b, sizeof(double) * B * nc * 6)) ||
+      (rc = alloc_dev(S, (void**)&P.d_err, sizeof(double) * B * nc * 6)) || (rc = alloc_dev(S, (void**)&P.d_A, sizeof(double) * nc * 36)) ||
+      (rc = alloc_dev(S, (void**)&P.d_status, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&P.d_steps, sizeof(int) * B)) ||
+      (rc = alloc_dev(S, (void**)&P.d_clink, sizeof(int) * nc)) || (rc = alloc_dev(S, (void**)&P.d_count, sizeof(unsigned int) * 2))) {
+    P.d_tgt = nullptr;   // (what was allocated stays in `allocs` and goes with the handle; the next call allocates afresh)
+    return rc;
+  }
+  return LOIKB_OK;
+}
+
+static double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+extern "C" {
+
+int loikb_pose_version(void) { return LOIKB_POSE_VERSION; }
+
+int loikb_forward_kinematics(loikb_solver* S, const int* links, int n, double* out, int out_flags)
+{
+  if (!S || n < 0 || (n > 0 && (!links || !out))) return LOIKB_ERR_ARG;
+  for (int e = 0; e < n; ++e)
+    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = "forward_kinematics: link id out of range"; return LOIKB_ERR_ARG; }
+  if (!S->have_q) { g_last_error = "forward_kinematics: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  std::vector<int> dl(n);
+  for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
+  const size_t bytes = sizeof(double) * (size_t)S->B * n * 12;
+  int rc;
+  if ((rc = ensure_getscr(S, 1, sizeof(int) * (size_t)n))) return rc;
+  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) return rc;
+  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  HIPCHK(hipMemcpyAsync(S->d_getscr[1], dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
+  hipLaunchKernelGGL(k_link_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
+                     S->d_idx_q, (const int*)S->d_getscr[1], n, S->B, dst);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (dl is a local)
+  return LOIKB_OK;
+}
+
+int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, int in_flags, const loikb_pose_params* p)
+{
+  if (!S || !targets || !p) return LOIKB_ERR_ARG;
+  if (!(p->dt > 0.0) || !(p->gain > 0.0) || !(p->tol_pose >= 0.0) || p->max_steps < 0 || std::isinf(p->dt) || std::isinf(p->gain)) {
+    g_last_error = "solve_pose: need dt > 0, gain > 0, tol_pose >= 0, max_steps >= 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (!S->have_problem) { g_last_error = "solve_pose before SolveInit()"; return LOIKB_ERR_STATE; }
+  if (S->nc_active < 1) { g_last_error = "solve_pose: no active task constraint"; return LOIKB_ERR_STATE; }
+  if (!q && !S->have_q) { g_last_error = "solve_pose: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  const auto t_call = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if ((rc = pose_alloc(S))) return rc;
+  loikb_solver_impl::PoseState& P = S->pose;
+  const int B = S->B, nc = S->nc_active;
+  const bool dev = in_flags & LOIKB_IN_DEVICE, tgt_shared = in_flags & LOIKB_POSE_TARGET_SHARED;
+  // the targets, checked before anything of the handle changes
+  const size_t ntgt = (size_t)(tgt_shared ? 1 : B) * nc;
+  HIPCHK(hipMemcpyAsync(P.d_tgt, targets, sizeof(double) * 12 * ntgt, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_count, 0, 2 * sizeof(unsigned int), S->stream));
+  hipLaunchKernelGGL(k_pose_check_targets, grid1(ntgt), dim3(256), 0, S->stream, (const double*)P.d_tgt, (int)ntgt, 1e-9, P.d_count + 1);
+  HIPCHK(hipGetLastError());
+  unsigned int counts[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(counts, P.d_count, sizeof(counts), hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  if (counts[1]) { g_last_error = "solve_pose: a target rotation is not orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+  ++S->inputs_epoch;
+  if (q) {   // (the copy path of k_advance_q: the resident configurations are replaced; FwdPassInit runs in the first solve)
+    const void* dq = nullptr;
+    if ((rc = to_device(S, q, sizeof(double) * (size_t)B * S->nq, dev, &dq))) return rc;
+    if (S->f32) hipLaunchKernelGGL(k_advance_q<float>, grid1(B), dim3(256), 0, S->stream, S->d_q, (const double*)dq, 0, S->nq, S->d_jd, S->d_idx_q, S->L, B, S->home.tiles, 0.0);
+    else hipLaunchKernelGGL(k_advance_q<double>, grid1(B), dim3(256), 0, S->stream, S->d_q, (const double*)dq, 0, S->nq, S->d_jd, S->d_idx_q, S->L, B, S->home.tiles, 0.0);
+    HIPCHK(hipGetLastError());
+    S->have_q = true;
+  }
+  std::vector<int> cl(nc);
+  for (int c = 0; c < nc; ++c) cl[c] = S->link_of[S->active_ids[c]];
+  HIPCHK(hipMemcpyAsync(P.d_clink, cl.data(), sizeof(int) * nc, hipMemcpyHostToDevice, S->stream));
+  if (S->a_shared) HIPCHK(hipMemcpyAsync(P.d_A, S->A_host.data(), sizeof(double) * 36 * nc, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_status, 0, sizeof(int) * B, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_steps, 0, sizeof(int) * B, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (q, cl are the caller's / locals)
+  P.nc = nc;
+  const double k = p->gain / p->dt;
+  double solve_ms = 0.0;
+  int steps_run = 0;
+  for (int step = 0;; ++step) {
+    const int go = step < p->max_steps;
+    HIPCHK(hipMemsetAsync(P.d_count, 0, sizeof(unsigned int), S->stream));
+    if (S->f32)
+      hipLaunchKernelGGL(k_pose_retarget<float>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                         (const int*)P.d_clink, nc, (const double*)P.d_tgt, (int)tgt_shared, S->a_shared ? (const double*)P.d_A : nullptr,
+                         (const char*)S->home.tiles, S->L, B, k, p->tol_pose, go, P.d_b, P.d_err, P.d_status, P.d_steps, P.d_count);
+    else
+      hipLaunchKernelGGL(k_pose_retarget<double>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                         (const int*)P.d_clink, nc, (const double*)P.d_tgt, (int)tgt_shared, S->a_shared ? (const double*)P.d_A : nullptr,
+                         (const char*)S->home.tiles, S->L, B, k, p->tol_pose, go, P.d_b, P.d_err, P.d_status, P.d_steps, P.d_count);
+    HIPCHK(hipGetLastError());
+    if (!go) break;
+    unsigned int running = 0;
+    HIPCHK(hipMemcpyAsync(&running, P.d_count, sizeof(running), hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    if (running == 0) break;
+    // UpdateEqConstraint(c, NULL, b_c, LOIKB_IN_DEVICE) for every active constraint, queued behind each other (the solve below
+    // synchronises), then the tailored Solve on the resident q without a constraint rewrite
+    S->defer_sync = true;
+    for (int c = 0; c < nc && rc == LOIKB_OK; ++c) rc = update_eq_single(S, S->active_ids[c], nullptr, P.d_b + (size_t)c * B * 6, LOIKB_IN_DEVICE);
+    S->defer_sync = false;
+    if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
+    S->pass_active = false;
+    const auto t_solve = std::chrono::steady_clock::now();
+    if ((rc = loikb_solve_tailored(S, nullptr, -1, nullptr, nullptr, 0))) return rc;
+    solve_ms += ms_since(t_solve);
+    if (S->f32)
+      hipLaunchKernelGGL(k_pose_integrate<float>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
+                         (const char*)S->home.tiles, p->dt, P.d_status);
+    else
+      hipLaunchKernelGGL(k_pose_integrate<double>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
+                         (const char*)S->home.tiles, p->dt, P.d_status);
+    HIPCHK(hipGetLastError());
+    ++S->inputs_epoch;
+    ++steps_run;
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));
+  const double total = ms_since(t_call);
+  P.timing[0] = steps_run; P.timing[1] = total; P.timing[2] = solve_ms; P.timing[3] = total - solve_ms;
+  return LOIKB_OK;
+}
+
+int loikb_pose_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  if (S->pose.nc == 0) { g_last_error = "pose_get before solve_pose"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (field) {
+  case LOIKB_POSE_F_STEPS: src = S->pose.d_steps; bytes = sizeof(int) * (size_t)S->B; break;
+  case LOIKB_POSE_F_STATUS: src = S->pose.d_status; bytes = sizeof(int) * (size_t)S->B; break;
+  case LOIKB_POSE_F_ERR: src = S->pose.d_err; bytes = sizeof(double) * (size_t)S->B * S->pose.nc * 6; break;
+  case LOIKB_POSE_F_TIMING:
+    if (!to_dev) { memcpy(out, S->pose.timing, sizeof(S->pose.timing)); return LOIKB_OK; }
+    HIPCHK(hipMemcpy(out, S->pose.timing, sizeof(S->pose.timing), hipMemcpyHostToDevice));
+    return LOIKB_OK;
+  default: g_last_error = "pose_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  HIPCHK(hipMemcpyAsync(out, src, bytes, to_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
+}
 
 }  // extern "C"

@@ -1,0 +1,250 @@
+// Batched pose IK (include/loik_amd_pose.h): the per-step work around the tailored Solve when the library drives
+// "take these B seeds to this pose" itself.
+//
+//   k_link_placements : oMi of requested links from the RESIDENT q (not the tiles' JP_CS pairs, which belong to the q of the
+//                       last FwdPassInit), one thread per (instance, link)
+//   k_pose_retarget   : e_c = log6(oMi_c^-1 oMdes_c) per active constraint, b_c = A_c (gain / dt) e_c, the reached / stopped
+//                       bookkeeping and the count of instances still running, one thread per instance
+//   k_pose_integrate  : q <- q (+) dt z for the running instances only (advance_q_instance: the arithmetic of loikb_integrate)
+//
+// Everything here is fp64 whatever the handle's precision: the configurations are fp64 on the device anyway, and the
+// tolerances a pose solve is asked for (1e-6 and below) are out of fp32's reach in a 30-joint chain.  These kernels are a few
+// microseconds beside a solve of milliseconds and are not tuned.
+#pragma once
+
+#include "loik_device.hpp"
+
+namespace loikb {
+
+// pose status bits (loik_amd_pose.h)
+enum : int { POSE_REACHED = 1, POSE_NOT_CONVERGED = 2, POSE_INFEASIBLE = 4, POSE_STOPPED = 8 };
+
+// liMi of device joint i from its coordinates: the fp64 twin of joint_xform (which reads the same numbers from the tiles'
+// JP_CS pairs).  p = joint_q_pairs(q of the joint) for a joint that reads q; JF_NOQ joints (the later joints of a free-flyer /
+// spherical / translation / planar chain) are their placement alone.
+__device__ __forceinline__ void pose_joint_xform(const JointDesc& d, const double* p, double* R, double* t)
+{
+  if (d.flags & JF_NOQ) {
+    make_liMi<double>(d, (d.flags & JF_REVOLUTE) ? 1.0 : 0.0, 0.0, R, t);
+    return;
+  }
+  if (d.rot >= ROT_FREE) {
+    double Rq[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, tq[3] = {0, 0, 0}, rt[3];
+    if (d.rot == ROT_FREE) {
+      tq[0] = p[0]; tq[1] = p[1]; tq[2] = p[2];
+      quat_to_rot<double>(p[3], p[4], p[5], p[6], Rq);
+    } else if (d.rot == ROT_SPH) {
+      quat_to_rot<double>(p[0], p[1], p[2], p[3], Rq);
+    } else if (d.rot == ROT_PLANAR) {   // (x, y, cos, sin)
+      tq[0] = p[0]; tq[1] = p[1];
+      Rq[0] = p[2]; Rq[1] = -p[3]; Rq[3] = p[3]; Rq[4] = p[2];
+    } else {
+      tq[0] = p[0]; tq[1] = p[1]; tq[2] = p[2];
+    }
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) R[3 * i + j] = d.Rp[3 * i] * Rq[j] + d.Rp[3 * i + 1] * Rq[3 + j] + d.Rp[3 * i + 2] * Rq[6 + j];
+    mat3_vec(d.Rp, tq, rt);
+    for (int k = 0; k < 3; ++k) t[k] = d.tp[k] + rt[k];
+    return;
+  }
+  if (d.flags & JF_HELICAL) {   // p = (q, 0): Rot(axis, q), translation pitch q axis
+    double s, c, ra[3];
+    sincos(p[0], &s, &c);
+    make_liMi<double>(d, c, s, R, t);
+    mat3_vec(d.Rp, d.axis, ra);
+    for (int k = 0; k < 3; ++k) t[k] += (d.pitch * p[0]) * ra[k];
+    return;
+  }
+  make_liMi<double>(d, p[0], p[1], R, t);
+}
+
+// oMi of device joint j for one configuration row: the product of liMi along the root path, composed leaf-side first
+__device__ __forceinline__ void link_placement(const double* __restrict__ q_row, const JointDesc* __restrict__ jd,
+                                               const int* __restrict__ idx_q, int j, double* Ra, double* ta)
+{
+  for (int k = 0; k < 9; ++k) Ra[k] = (k % 4 == 0) ? 1.0 : 0.0;
+  for (int k = 0; k < 3; ++k) ta[k] = 0.0;
+  while (j > 0) {
+    const JointDesc& d = jd[j];
+    double p[8] = {0, 0, 0, 0, 0, 0, 0, 0}, R[9], t[3], Rn[9], tn[3];
+    if (!(d.flags & JF_NOQ)) (void)joint_q_pairs(q_row + idx_q[j], d, p);
+    pose_joint_xform(d, p, R, t);
+    for (int r = 0; r < 3; ++r) {   // (R, t) * (Ra, ta)
+      for (int c = 0; c < 3; ++c) Rn[3 * r + c] = R[3 * r] * Ra[c] + R[3 * r + 1] * Ra[3 + c] + R[3 * r + 2] * Ra[6 + c];
+      tn[r] = t[r] + R[3 * r] * ta[0] + R[3 * r + 1] * ta[1] + R[3 * r + 2] * ta[2];
+    }
+    for (int k = 0; k < 9; ++k) Ra[k] = Rn[k];
+    for (int k = 0; k < 3; ++k) ta[k] = tn[k];
+    j = d.parent;
+  }
+}
+
+// out[b][e] = (R row-major, t) of device joint dev_link[e] (0: the universe, the identity)
+__global__ void k_link_placements(const double* __restrict__ q, int nq, const JointDesc* __restrict__ jd,
+                                  const int* __restrict__ idx_q, const int* __restrict__ dev_link, int n, int B,
+                                  double* __restrict__ out)
+{
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long long)B * n) return;
+  const int b = (int)(idx / n), e = (int)(idx - (long long)b * n);
+  double R[9], t[3];
+  link_placement(q + (size_t)b * nq, jd, idx_q, dev_link[e], R, t);
+  double* o = out + (size_t)idx * 12;
+  for (int k = 0; k < 9; ++k) o[k] = R[k];
+  for (int k = 0; k < 3; ++k) o[9 + k] = t[k];
+}
+
+// log3 (pinocchio::log3): w with exp([w]x) = R, |w| <= pi.  theta = atan2(|vee(R - R^T)| / 2, (tr R - 1) / 2) is accurate on
+// the whole range; w = theta / (2 sin theta) vee(R - R^T) with the series of theta / sin theta for theta -> 0, and for
+// theta -> pi (where vee(R - R^T) = 2 sin theta a vanishes) the axis from the symmetric part, a a^T = (sym R - cos I) / (1 - cos),
+// its sign from vee(R - R^T).  The same branches are restated in tests/pose_numpy.py.
+__device__ __forceinline__ void pose_log3(const double* R, double* w)
+{
+  const double vx = R[7] - R[5], vy = R[2] - R[6], vz = R[3] - R[1];
+  const double s = 0.5 * sqrt(vx * vx + vy * vy + vz * vz);
+  const double c = 0.5 * (R[0] + R[4] + R[8] - 1.0);
+  const double theta = atan2(s, c);
+  if (c < -0.8) {
+    int k = 0;
+    if (R[4] > R[3 * k + k]) k = 1;
+    if (R[8] > R[3 * k + k]) k = 2;
+    const double omc = 1.0 - c;
+    double a[3];
+    a[k] = sqrt(fmax(0.0, (R[4 * k] - c) / omc));
+    for (int j = 0; j < 3; ++j)
+      if (j != k) a[j] = 0.5 * (R[3 * k + j] + R[3 * j + k]) / (omc * a[k]);
+    const double sg = (a[0] * vx + a[1] * vy + a[2] * vz) < 0.0 ? -theta : theta;
+    for (int j = 0; j < 3; ++j) w[j] = sg * a[j];
+    return;
+  }
+  const double t2 = theta * theta;
+  const double f = theta < 1e-4 ? 0.5 * (1.0 + t2 / 6.0 + 7.0 * t2 * t2 / 360.0) : 0.5 * theta / s;
+  w[0] = f * vx; w[1] = f * vy; w[2] = f * vz;
+}
+
+// log6 (pinocchio::log6) of (R, p): [v; w], w = log3(R), v = V^-1(w) p = p - w x p / 2 + beta w x (w x p),
+// beta = (1 - (theta / 2) cot(theta / 2)) / theta^2, its series below theta = 1e-3
+__device__ __forceinline__ void pose_log6(const double* R, const double* p, double* nu)
+{
+  double w[3];
+  pose_log3(R, w);
+  const double t2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+  const double theta = sqrt(t2);
+  double beta;
+  if (theta < 1e-3) {
+    beta = 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0;
+  } else {
+    double sh, ch;
+    sincos(0.5 * theta, &sh, &ch);
+    beta = (1.0 - 0.5 * theta * ch / sh) / t2;
+  }
+  const double wp[3] = {w[1] * p[2] - w[2] * p[1], w[2] * p[0] - w[0] * p[2], w[0] * p[1] - w[1] * p[0]};
+  const double wwp[3] = {w[1] * wp[2] - w[2] * wp[1], w[2] * wp[0] - w[0] * wp[2], w[0] * wp[1] - w[1] * wp[0]};
+  for (int k = 0; k < 3; ++k) {
+    nu[k] = p[k] - 0.5 * wp[k] + beta * wwp[k];
+    nu[3 + k] = w[k];
+  }
+}
+
+// targets [n][12]: counts the rotations that are not orthonormal with determinant +1 (tolerance `tol` per entry of R^T R - I,
+// and of det R - 1) or not finite
+__global__ void k_pose_check_targets(const double* __restrict__ tgt, int n, double tol, unsigned int* __restrict__ bad)
+{
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double* R = tgt + (size_t)i * 12;
+  bool ok = true;
+  for (int k = 0; k < 12; ++k) ok = ok && isfinite(R[k]);
+  for (int a = 0; a < 3 && ok; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double g = R[a] * R[b] + R[3 + a] * R[3 + b] + R[6 + a] * R[6 + b] - (a == b ? 1.0 : 0.0);
+      ok = ok && fabs(g) <= tol;
+    }
+  const double det = R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6]) + R[2] * (R[3] * R[7] - R[4] * R[6]);
+  ok = ok && fabs(det - 1.0) <= tol;
+  if (!ok) atomicAdd(bad, 1u);
+}
+
+// One step of the pose loop for instance b.  Instances already reached or stopped keep their status; the others get
+// err = e_c of the resident q, are marked reached (max_c |e_c|_inf <= tol) or stopped (e or q not finite), and otherwise stay
+// running: with `step` set, b_c = A_c k e_c (k = gain / dt) goes to b_out, steps[b] counts the step and `running` the instance.
+// Instances that do not run get b_c = 0 (their inner solve is idle work: their q does not move).
+// A: `A_sh` [nc][36] (shared A), else the per-instance A of the constraint record in the tiles.
+template <typename T>
+__global__ void k_pose_retarget(const double* __restrict__ q, int nq, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q,
+                                const int* __restrict__ c_link, int nc, const double* __restrict__ tgt, int tgt_shared,
+                                const double* __restrict__ A_sh, const char* tiles, Layout L, int B, double k, double tol, int step,
+                                double* __restrict__ b_out, double* __restrict__ err, int* __restrict__ status,
+                                int* __restrict__ steps, unsigned int* __restrict__ running)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int st = status[b];
+  bool run = !(st & (POSE_REACHED | POSE_STOPPED));
+  if (run) {
+    const double* q_row = q + (size_t)b * nq;
+    bool finite = true;
+    for (int i = 0; i < nq; ++i) finite = finite && isfinite(q_row[i]);
+    double emax = 0.0;
+    for (int c = 0; c < nc; ++c) {
+      double R[9], t[3], Re[9], pe[3], e[6];
+      link_placement(q_row, jd, idx_q, c_link[c], R, t);
+      const double* D = tgt + ((tgt_shared ? 0 : (size_t)b * nc) + c) * 12;
+      for (int r = 0; r < 3; ++r) {   // oMi^-1 oMdes = (R^T Rd, R^T (td - t))
+        for (int cc = 0; cc < 3; ++cc) Re[3 * r + cc] = R[r] * D[cc] + R[3 + r] * D[3 + cc] + R[6 + r] * D[6 + cc];
+        pe[r] = R[r] * (D[9] - t[0]) + R[3 + r] * (D[10] - t[1]) + R[6 + r] * (D[11] - t[2]);
+      }
+      pose_log6(Re, pe, e);
+      double* eo = err + ((size_t)b * nc + c) * 6;
+      for (int r = 0; r < 6; ++r) {
+        eo[r] = e[r];
+        finite = finite && isfinite(e[r]);
+        emax = fmax(emax, fabs(e[r]));
+      }
+      if (step) {
+        const char* crec = lane_ptr<T>(const_cast<char*>(tiles), L, b) + (size_t)(L.off_c + c * L.crec) * pair_bytes<T>();
+        double* bo = b_out + ((size_t)c * B + b) * 6;
+        for (int r = 0; r < 6; ++r) {
+          double a = 0.0;
+          for (int m = 0; m < 6; ++m) {
+            const int x = 6 * r + m;
+            const double A = A_sh ? A_sh[c * 36 + x] : (double)*elem_ptr<T>(const_cast<char*>(crec), CP_A + x / 2, x & 1);
+            a += A * (k * e[m]);
+          }
+          bo[r] = a;
+        }
+      }
+    }
+    if (!finite) st |= POSE_STOPPED;
+    else if (emax <= tol) st |= POSE_REACHED;
+    run = !(st & (POSE_REACHED | POSE_STOPPED));
+    status[b] = st;
+  }
+  if (!step) return;
+  if (run) {
+    steps[b] += 1;
+    atomicAdd(running, 1u);
+  } else {
+    for (int c = 0; c < nc; ++c)
+      for (int r = 0; r < 6; ++r) b_out[((size_t)c * B + b) * 6 + r] = 0.0;
+  }
+}
+
+// q <- q (+) dt z for the instances still running, and the inner solve's outcome into their pose status
+template <typename T>
+__global__ void k_pose_integrate(double* __restrict__ q, int nq, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q,
+                                 Layout L, int B, const char* tiles, double dt, int* __restrict__ status)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int st = status[b];
+  if (st & (POSE_REACHED | POSE_STOPPED)) return;
+  const char* lp = lane_ptr<T>(const_cast<char*>(tiles), L, b);
+  const int inner = (int)*elem_ptr<T>(const_cast<char*>(lp) + (size_t)L.off_s * pair_bytes<T>(), SP_ST, 0);
+  if (!(inner & ST_CONVERGED)) st |= POSE_NOT_CONVERGED;
+  if (inner & ST_PRIMAL_INF) st |= POSE_INFEASIBLE;
+  status[b] = st;
+  advance_q_instance<T>(q + (size_t)b * nq, jd, idx_q, L.nb, lp, dt);
+}
+
+}  // namespace loikb
