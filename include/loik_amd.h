@@ -360,9 +360,9 @@ typedef struct loikb_stats {
   int lean_escaped;                       /* instances whose mu left the precomputed decades in a lean launch and were
                                              finished by the other tail kernel                                         */
   double hslots_ms;                       /* HIP-event time of the decade-slot precomputation (part of tail_ms); 0 in
-                                             the short sequence of a small batch unless LOIKB_SMALL_SLOT_EVENT=1       */
-  int lean_requeues;                      /* time slices that ended with the instance going to the back of the lean kernel's
-                                             work queue (round-robin among the instances waiting for a slot)                */
+                                             the short sequence of a small batch                                       */
+  int lean_requeues;                      /* time slices that ended with the instance going to the back of the flat engine's
+                                             work queue (round-robin among the instances waiting for a wavefront)           */
   int flat_launches;                      /* of lean_launches: those that ran the flat engine (k_fslots + k_flat: no loops over the
                                              tree levels, loik_amd/csrc/loik_flat.hpp) instead of k_hslots + k_lean             */
   double queue_dry_ms;                    /* flat engine: time from the start of its (last) launch until a lane group first found the
@@ -374,11 +374,9 @@ typedef struct loikb_stats {
   int flat_built;                         /* decade slots (W / Dinv of one instance for one mu) built by the instance's own wavefront
                                              inside k_flat2: every change of mu under the OSQP rule, decades outside the table
                                              with LOIKB_FLAT_BUILD=1 (round 5)                                                  */
-  int flat_probe_launches;                /* of flat_split_launches: those that ran as TWO launches -- every instance for
-                                             LOIKB_FLAT_PROBE=p iterations at most, then the survivors to completion, longest
-                                             predicted first (round 6; an experiment kept as an option: the default is one launch
-                                             with round-robin time slices, which it does not beat)                              */
-  double probe_ms;                        /* HIP-event time of those probe launches incl. the sort of the survivors (part of tail_ms) */
+  int flat_probe_launches;                /* always 0 (the two-launch probe + finish schedule of round 6 is retired; the field
+                                             keeps the layout of this struct)                                                   */
+  double probe_ms;                        /* always 0 (as flat_probe_launches)                                                  */
 } loikb_stats;
 int loikb_get_stats(loikb_solver *s, loikb_stats *out);
 /* which kernels the solves of this handle use and why (the engine plan is made in one place, from (nb, nc, sharing mode of

@@ -1047,7 +1047,7 @@ template <typename T, int NA>
 __global__ void __launch_bounds__(WAVE)
 k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, const TailTopo* __restrict__ topo,
          const int* __restrict__ child_list, const FlatLane* __restrict__ fl, int maxdepth, int nanc, int frows, int njmp,
-         const int* __restrict__ slots, int nslots, int G, T* __restrict__ fslots, int kexp_lo, int ndec, int dgrp, int dw0, int nw,
+         const int* __restrict__ slots, int nslots, int G, T* __restrict__ fslots, int kexp_lo, int ndec, int dw0, int nw,
          unsigned int* __restrict__ fmask)
 {
   // dw0, nw: the decades to build NOW, [dw0, dw0 + nw) of the table's [0, ndec) -- the table is addressed for its whole range and
@@ -1155,23 +1155,14 @@ k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, 
   if (lane < ndec && lane < 16) mutab[lane] = (T)flat_decade_mu((double)P.mu0, kexp_lo + lane);
   tail_sync();
   if (lane < HX) xch[WAVE * HX + lane] = T(0);
-  // The decades go through the two passes in groups of `dgrp` (LOIKB_FSLOT_DGRP, default: all at once): a group's rows of pass A
-  // are read back by pass B while they are still in the L2 of the XCD (ten wavefronts x two instances x eight decades x 2 KB per CU
-  // is 10 MB per XCD, its L2 has 4), at the price of refilling the pipeline over the tree levels once per group.
   if (fmask != nullptr && has_inst && jlane == 0) fmask[sidx] = (nw >= 32 ? 0xFFFFu : ((1u << nw) - 1u)) << dw0;
-  for (int d0 = dw0; d0 < dw0 + nw; d0 += dgrp) {
-  const int nd = (dw0 + nw - d0 < dgrp) ? dw0 + nw - d0 : dgrp;
-  if (d0 > dw0) {
-    tail_sync();
-    if (lane < HX) xch[WAVE * HX + lane] = T(0);
-  }
   // ---- pass A
   {
     const int lag = maxdepth - depth;
     tail_sync();
-    for (int st = 0; st < maxdepth + nd - 1; ++st) {
-      const int dsl = d0 + st - lag;
-      const bool on = isj && depth > 0 && dsl >= d0 && dsl < d0 + nd;
+    for (int st = 0; st < maxdepth + nw - 1; ++st) {
+      const int dsl = dw0 + st - lag;
+      const bool on = isj && depth > 0 && dsl >= dw0 && dsl < dw0 + nw;
       T hh[21];
 #pragma unroll
       for (int k = 0; k < 21; ++k) hh[k] = base0[k];
@@ -1186,6 +1177,8 @@ k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, 
 #pragma unroll
           for (int k = 0; k < 21; ++k) hh[k] += x[k];
         }
+        // (rare: a joint with more than NCH_REG children.  Kept rolled: unrolled, it costs the whole kernel registers)
+#pragma unroll 1
         for (int c = NCH_REG; c < tp.nchild; ++c) {
           const T* x = xch + (gbase + child_list[tp.child_start + c]) * HX;
 #pragma unroll
@@ -1224,7 +1217,7 @@ k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, 
   lb[NA * WAVE + lane] = T(0);
   __builtin_amdgcn_s_waitcnt(0);
   tail_sync();
-  for (int dsl = d0; dsl < d0 + nd; ++dsl) {
+  for (int dsl = dw0; dsl < dw0 + nw; ++dsl) {
     T UDw[6], dinv = T(0);
 #pragma unroll
     for (int k = 0; k < 6; ++k) UDw[k] = isj ? fslots[fslotA_at(sidx, ndec, dsl, frows, G, k, jlane)] : T(0);
@@ -1254,7 +1247,6 @@ k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, 
         if (k < depth - 1) fslots[base + k] = Wc[k];
       fslots[base + depth - 1] = dinv;
     }
-  }
   }
 }
 

@@ -16,14 +16,14 @@
   (const loikb::Params<double>, const loikb::Bufs<double>, const loikb::JointDesc* __restrict__, const loikb::FlatLane* __restrict__, int, int, int, int*, \
    int, const double* __restrict__, int, int, int, double, int, int, int, const void* const* __restrict__)
 
-// k_flat2<NA, WPE, SLICED, HM, LOG, MUR>
+// k_flat2<FLAT_NA_SMALL, SLICED, HM, LOG, MUR>
 #define LOIKB_FLAT2_INSTANCES(X)                                                                                                    \
-  X(2, false, 0, false, 0) X(2, true, 0, false, 0) X(3, false, 0, false, 0) X(3, true, 0, false, 0)                                 \
-  X(2, false, 1, false, 0) X(2, true, 1, false, 0) X(2, false, 2, false, 0) X(2, true, 2, false, 0)                                 \
-  X(2, false, 3, false, 0) X(2, true, 3, false, 0)                                                                                  \
-  X(2, false, 0, true, 0) X(2, false, 2, true, 0) X(2, false, 3, true, 0)                                                           \
-  X(2, false, 0, false, 1) X(2, true, 0, false, 1) X(2, false, 1, false, 1) X(2, false, 2, false, 1) X(2, false, 3, false, 1)      \
-  X(2, false, 0, false, 2) X(2, true, 0, false, 2)
+  X(false, 0, false, 0) X(true, 0, false, 0)                                                                                        \
+  X(false, 1, false, 0) X(true, 1, false, 0) X(false, 2, false, 0) X(true, 2, false, 0)                                             \
+  X(false, 3, false, 0) X(true, 3, false, 0)                                                                                        \
+  X(false, 0, true, 0) X(false, 2, true, 0) X(false, 3, true, 0)                                                                    \
+  X(false, 0, false, 1) X(true, 0, false, 1) X(false, 1, false, 1) X(false, 2, false, 1) X(false, 3, false, 1)                      \
+  X(false, 0, false, 2) X(true, 0, false, 2)
 // k_flat1<NA, SLICED, HM, LOG, MUR>, for NA = FLAT_NA_SMALL and FLAT_MAXA
 #define LOIKB_FLAT1_INSTANCES_NA(X, NA)                                                                                             \
   X(NA, false, 0, false, 0) X(NA, true, 0, false, 0) X(NA, false, 1, false, 0) X(NA, true, 1, false, 0)                             \
@@ -32,9 +32,9 @@
   X(NA, false, 0, false, 1) X(NA, false, 2, false, 1) X(NA, false, 3, false, 1)
 #define LOIKB_FLAT1_INSTANCES(X) LOIKB_FLAT1_INSTANCES_NA(X, loikb::FLAT_NA_SMALL) LOIKB_FLAT1_INSTANCES_NA(X, loikb::FLAT_MAXA)
 
-#define LOIKB_FLAT2_DECL(WPE, SLICED, HM, LOG, MUR) \
-  extern template __global__ void loikb::k_flat2<loikb::FLAT_NA_SMALL, WPE, SLICED, HM, LOG, MUR> LOIKB_FLAT2_ARGS;
-#define LOIKB_FLAT2_DEF(WPE, SLICED, HM, LOG, MUR) \
-  template __global__ void loikb::k_flat2<loikb::FLAT_NA_SMALL, WPE, SLICED, HM, LOG, MUR> LOIKB_FLAT2_ARGS;
+#define LOIKB_FLAT2_DECL(SLICED, HM, LOG, MUR) \
+  extern template __global__ void loikb::k_flat2<loikb::FLAT_NA_SMALL, SLICED, HM, LOG, MUR> LOIKB_FLAT2_ARGS;
+#define LOIKB_FLAT2_DEF(SLICED, HM, LOG, MUR) \
+  template __global__ void loikb::k_flat2<loikb::FLAT_NA_SMALL, SLICED, HM, LOG, MUR> LOIKB_FLAT2_ARGS;
 #define LOIKB_FLAT1_DECL(NA, SLICED, HM, LOG, MUR) extern template __global__ void loikb::k_flat1<NA, SLICED, HM, LOG, MUR> LOIKB_FLAT1_ARGS;
 #define LOIKB_FLAT1_DEF(NA, SLICED, HM, LOG, MUR) template __global__ void loikb::k_flat1<NA, SLICED, HM, LOG, MUR> LOIKB_FLAT1_ARGS;

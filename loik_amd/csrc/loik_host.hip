@@ -63,7 +63,7 @@ namespace {
 constexpr int ROWMAP_CAP = 8192;
 
 // Developer overrides from the environment, read ONCE in loikb_create (never inside a solve).  Defaults are the measured
-// choices; the variables exist for the experiments recorded in DESIGN.md / profiles/ and for tests/test_engines.py.
+// choices.  A switch stays only if a test uses it to reach or check a path that runs by default, or if the benchmark uses it.
 struct Tuning {
   int team = MAX_TEAM;          // LOIKB_TEAM          wavefronts per tile of k_solve
   int team_max = 1 << 30;       // LOIKB_TEAM_MAX      use the team schedule only up to this many slots
@@ -71,25 +71,16 @@ struct Tuning {
   bool lean = true;             // LOIKB_LEAN=0        never use k_lean nor k_flat (the engines with precomputed decade slots)
   bool flat = true;             // LOIKB_FLAT=0        never use k_flat (the engine without level loops, loik_flat.hpp)
   bool flat_split = true;       // LOIKB_FLAT_SPLIT=0: k_flat (one joint per lane) also where k_flat2 (two lanes per joint) applies
-  int flat_split_wpe = 2;       // LOIKB_FLAT_WPE=3: k_flat2 built for three wavefronts per SIMD
   int flat_win_lo = 0, flat_win_n = 0;   // LOIKB_FLAT_WINDOW=lo,n: (with LOIKB_FLAT_BUILD=1) k_fslots builds decades lo .. lo + n - 1 only, the rest lazily
   int flat_build = 2;           // (default 2 since the end of round 5; 0: the full table always) LOIKB_FLAT_BUILD=1: the lazily populated table on every k_flat2 launch (window: LOIKB_FLAT_WINDOW, else all of it), 2: on time-sliced launches, window from the handle's history; k_flat2 builds a decade slot its table lacks in-wave (flat_build_slot) instead of handing the instance to k_tail
-  int fslot_dgrp = 0;           // LOIKB_FSLOT_DGRP=g: k_fslots takes the decades through its two passes g at a time (default: all)
-  int flat_slice2 = 0;          // LOIKB_FLAT_SLICE2=q: an instance's later slices (0: as the first)
   int flat_small_batch = 2048;  // LOIKB_FLAT_SMALL_BATCH=n: up to n instances a Solve() on k_flat2 / k_flat1 is the short sequence (fused queue set-up, no order pass)
   int flat_min_batch = 1;       // LOIKB_FLAT_MIN_BATCH=n: k_flat2 / k_flat1 take batches from n instances (round 5: 64; below, k_tail)
   int small_finish = 1;         // LOIKB_SMALL_FINISH=0: the short sequence ends with k_list_unfinished + a copy of the counters + run_main_loop's own event and
                                 //   synchronisation, as before (1: k_small_finish writes the counters into the pinned host copy; one synchronisation per Solve())
-  int small_slot_event = 0;     // LOIKB_SMALL_SLOT_EVENT=1: an event between k_fslots and the engine in the short sequence too (default: none, loikb_stats::hslots_ms reads 0
-                                //   there -- an event costs a lone problem's Solve() 2.5 us of 116: profiles/r06_o_small_finish_ab.jsonl)
-  int flat_probe = 0;           // (default 0: measured a wash against the round robin, profiles/r06_a_probe_and_finish_ab.txt; given: wherever LOIKB_FLAT_SLICE / the default slices it) LOIKB_FLAT_PROBE=p: a time-sliced k_flat2 launch without an order becomes TWO launches -- every instance for p iterations at
-                                // most, then the survivors to completion, longest predicted first (0: one launch, round robin: round 5's)
-  int flat_probe_mark = 32;     // LOIKB_FLAT_PROBE_MARK=k: the probe's first mark (the residual's rate of fall is taken between it and the probe's end)
   int flat_slice = -1;          // LOIKB_FLAT_SLICE=q: k_flat2's / k_flat1's round-robin time slice in iterations (0: never; default: 288 for
                                 // launches in arrival order of >= 32 768 instances, see flat_slice_for / run_tail)
   bool flat_zero_state = true;  // LOIKB_FLAT_ZERO_STATE=0: k_flat2 / k_flat1 fetch vis, fis, g, w, z of every instance even straight after a cold reset
   int flat_order_holdoff = 4;   // LOIKB_FLAT_ORDER_HOLDOFF=n: solves in arrival order after an ordered launch that was not shorter (0: never hold off)
-  int flat_one_slot = 1;        // LOIKB_FLAT_ONE_SLOT=0: k_flat1 always keeps two decade slots in LDS
   bool flat_order = true;       // LOIKB_FLAT_ORDER=0: the flat engine takes its instances in arrival order even when the handle's previous
                                 // solve left an order (longest first, k_order_*: loik_lean.hpp)
   int tail_waves = TAIL_WAVES;  // LOIKB_TAIL_WAVES    wavefronts per k_tail workgroup
@@ -98,8 +89,6 @@ struct Tuning {
   int lean_wg_per_cu = 0;       // LOIKB_LEAN_WG_PER_CU (0: what registers and LDS allow)
   int lean_wg_waves = 0;        // LOIKB_LEAN_WG_WAVES wavefronts per k_lean workgroup (0: by plan)
   bool lean_adapt = true;       // LOIKB_LEAN_ADAPT=0  always build the whole configured range of decade slots
-  std::vector<int> lean_quanta; // LOIKB_LEAN_QUANTA   host-side rounds of the lean launch (default: none)
-  int lean_slice = 0;           // LOIKB_LEAN_SLICE    in-kernel round-robin time slice (0: run to completion)
   double compact_ratio = 0.85;  // LOIKB_COMPACT_RATIO repack k_solve's tiles when at most this share of the slots is live
   bool direct_tail = true;      // LOIKB_NO_DIRECT_TAIL small batches go to the on-chip engines from the first iteration
   int lat_iters = 16;           // LOIKB_LAT_ITERS     iterations per k_solve launch in its latency-bound regime
@@ -115,21 +104,14 @@ struct Tuning {
     if (const char* e = getenv("LOIKB_FLAT")) flat = atoi(e) != 0;
     if (!lean) flat = false;  // (LOIKB_LEAN=0 asks for the engines without precomputed factors: k_solve / k_tail)
     if (const char* e = getenv("LOIKB_FLAT_SPLIT")) flat_split = atoi(e) != 0;
-    if (const char* e = getenv("LOIKB_FLAT_WPE")) flat_split_wpe = atoi(e) == 3 ? 3 : 2;
     if (const char* e = getenv("LOIKB_FLAT_BUILD")) flat_build = std::max(0, std::min(2, atoi(e)));
     if (const char* e = getenv("LOIKB_FLAT_WINDOW")) { if (sscanf(e, "%d,%d", &flat_win_lo, &flat_win_n) != 2) flat_win_n = 0; }
     if (const char* e = getenv("LOIKB_FLAT_SLICE")) flat_slice = std::min(65535, std::max(-1, atoi(e)));
-    if (const char* e = getenv("LOIKB_FLAT_SLICE2")) flat_slice2 = std::min(8191, std::max(0, atoi(e)));
-    if (const char* e = getenv("LOIKB_FLAT_PROBE")) flat_probe = std::min(8000, std::max(0, atoi(e)));
     if (const char* e = getenv("LOIKB_FLAT_MIN_BATCH")) flat_min_batch = std::max(1, atoi(e));
     if (const char* e = getenv("LOIKB_SMALL_FINISH")) small_finish = atoi(e);
-    if (const char* e = getenv("LOIKB_SMALL_SLOT_EVENT")) small_slot_event = atoi(e);
     if (const char* e = getenv("LOIKB_FLAT_SMALL_BATCH")) flat_small_batch = std::max(0, atoi(e));
-    if (const char* e = getenv("LOIKB_FLAT_PROBE_MARK")) flat_probe_mark = std::max(1, atoi(e));
-    if (const char* e = getenv("LOIKB_FSLOT_DGRP")) fslot_dgrp = std::max(0, atoi(e));
     if (const char* e = getenv("LOIKB_FLAT_ORDER")) flat_order = atoi(e) != 0;
     if (const char* e = getenv("LOIKB_FLAT_ZERO_STATE")) flat_zero_state = atoi(e) != 0;
-    if (const char* e = getenv("LOIKB_FLAT_ONE_SLOT")) flat_one_slot = atoi(e);
     if (const char* e = getenv("LOIKB_FLAT_ORDER_HOLDOFF")) flat_order_holdoff = std::max(0, atoi(e));
     geti("LOIKB_TAIL_WAVES", tail_waves); tail_waves = std::max(1, std::min(TAIL_WAVES, tail_waves));
     geti("LOIKB_LEAN_DECADES", lean_decades); lean_decades = std::max(1, std::min(15, lean_decades));   // (15: a parked instance's ring entry says "no slot" with decade code 15 -- ADVICE r05)
@@ -137,9 +119,6 @@ struct Tuning {
     geti("LOIKB_LEAN_WG_PER_CU", lean_wg_per_cu);
     geti("LOIKB_LEAN_WG_WAVES", lean_wg_waves);
     if (const char* e = getenv("LOIKB_LEAN_ADAPT")) lean_adapt = atoi(e) != 0;
-    if (const char* e = getenv("LOIKB_LEAN_QUANTA"))
-      for (const char* p = e; *p;) { lean_quanta.push_back(atoi(p)); while (*p && *p != ',') ++p; if (*p == ',') ++p; }
-    geti("LOIKB_LEAN_SLICE", lean_slice); lean_slice = std::max(0, lean_slice);
     if (const char* e = getenv("LOIKB_COMPACT_RATIO")) compact_ratio = atof(e);
     direct_tail = getenv("LOIKB_NO_DIRECT_TAIL") == nullptr;
     geti("LOIKB_LAT_ITERS", lat_iters);
@@ -291,7 +270,7 @@ struct loikb_solver_impl {
     Set set[3];                          // [0] view of the home tiles of the range, [1],[2] work sets of the compaction
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_k2 = nullptr, ev_k3 = nullptr;
+    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_k2 = nullptr;
     unsigned int* d_counters = nullptr;
     unsigned int* h_counters = nullptr;  // pinned
     int* d_slots = nullptr;              // list of the live instances handed to the tail kernel
@@ -1206,7 +1185,6 @@ void destroy_chunks(loikb_solver_impl* S)
     if (C.d_aux) (void)hipFree(C.d_aux);
     if (C.ev_k0) (void)hipEventDestroy(C.ev_k0);
     if (C.ev_k2) (void)hipEventDestroy(C.ev_k2);
-    if (C.ev_k3) (void)hipEventDestroy(C.ev_k3);
     if (C.ev_k1) (void)hipEventDestroy(C.ev_k1);
     if (C.own_stream && C.stream) (void)hipStreamDestroy(C.stream);
     void* ptrs[6] = {C.d_counters, C.d_slots, C.d_slots2, C.d_ring, C.d_order, C.d_order_bins};
@@ -1235,7 +1213,6 @@ int build_chunks(loikb_solver_impl* S, int nchunks)
   int rc;
   for (Chunk& C : S->chunks) {
     HIPCHK(hipEventCreate(&C.ev_k2));
-    HIPCHK(hipEventCreate(&C.ev_k3));
     HIPCHK(hipEventCreate(&C.ev_k0));
     HIPCHK(hipEventCreate(&C.ev_k1));
     HIPCHK(hipHostMalloc((void**)&C.h_counters, NCOUNTERS * sizeof(unsigned int)));
@@ -1316,7 +1293,7 @@ constexpr int FLAT_SLICE_LATER = 96;   // (an instance's later slices: 9.44 -> 9
 constexpr int FLAT_SLICE_DEFAULT = 288, FLAT_SLICE_MIN_BATCH = 32768, FLAT_SLICE_MAX_BATCH = 262144;   // (above: 19 KB of park record per instance for 1.5 %)
 int flat_slice_for(const loikb_solver_impl* S, int n, bool ordered)
 {
-  if (S->tune.flat_slice >= 0) return S->tune.flat_slice | (S->tune.flat_slice2 << 16);   // (LOIKB_FLAT_SLICE[2]: as asked, whatever the launch)
+  if (S->tune.flat_slice >= 0) return S->tune.flat_slice;   // (LOIKB_FLAT_SLICE: as asked, whatever the launch; the later slices as the first)
   if (ordered || n < FLAT_SLICE_MIN_BATCH || n > FLAT_SLICE_MAX_BATCH || (S->opt.flags & LOIKB_OPT_OWN_STREAM) || (S->opt.flags & LOIKB_OPT_FIXED_ITERS) || S->opt.logging) return 0;
   return FLAT_SLICE_DEFAULT | (FLAT_SLICE_LATER << 16);
 }
@@ -1792,8 +1769,8 @@ void plan_engines(loikb_solver_impl* S)
     // (the builds with one instance per wavefront have their own LDS layouts: what counts is the kernel that would run)
     if (flat_takes_diagonal(S)) {
       const size_t pw = S->flat.G == F2G ? flat2_lds_bytes<FLAT_NA_SMALL>(S->nc, true)
-                        : S->flat.nanc <= FLAT_NA_SMALL ? flat1_lds_bytes<FLAT_NA_SMALL>(S->nc, true, S->tune.flat_one_slot ? 1 : 2)
-                                                        : flat1_lds_bytes<FLAT_MAXA>(S->nc, true, S->tune.flat_one_slot ? 1 : 2);
+                        : S->flat.nanc <= FLAT_NA_SMALL ? flat1_lds_bytes<FLAT_NA_SMALL>(S->nc, true, 1)
+                                                        : flat1_lds_bytes<FLAT_MAXA>(S->nc, true, 1);
       pl.flat_waves_cu = std::max(pl.flat_waves_cu, (int)std::min<size_t>(8, (160 * 1024) / pw));
     }
   }
@@ -2020,19 +1997,20 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
         if (small_na)
           hipLaunchKernelGGL((k_fslots<T, FLAT_NA_SMALL>), hgrid, dim3(WAVE), slds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
                              (const TailTopo*)S->d_topo, (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth,
-                             nanc, frows, S->flat.njmp, list, n, G, (T*)C->d_fslots, kexp_lo, ndec, S->tune.fslot_dgrp > 0 ? S->tune.fslot_dgrp : nw,
-                             dw0, nw, mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
+                             nanc, frows, S->flat.njmp, list, n, G, (T*)C->d_fslots, kexp_lo, ndec, dw0, nw,
+                             mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
         else
           hipLaunchKernelGGL((k_fslots<T, FLAT_MAXA>), hgrid, dim3(WAVE), slds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
                              (const TailTopo*)S->d_topo, (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth,
-                             nanc, frows, S->flat.njmp, list, n, G, (T*)C->d_fslots, kexp_lo, ndec, S->tune.fslot_dgrp > 0 ? S->tune.fslot_dgrp : nw,
-                             dw0, nw, mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
+                             nanc, frows, S->flat.njmp, list, n, G, (T*)C->d_fslots, kexp_lo, ndec, dw0, nw,
+                             mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
         HIPCHK(hipGetLastError());
       }
-      const bool slot_event = !small_flat || S->tune.small_slot_event || S->tune.flat_probe > 0;   // (the probe launch's time is taken from this event)
-      if (slot_event) HIPCHK(hipEventRecord(C->ev_k2, C->stream));
+      // (no event between k_fslots and the engine in the short sequence: loikb_stats::hslots_ms reads 0 there -- an event costs a lone
+      //  problem's Solve() 2.5 us of 116: profiles/r06_o_small_finish_ab.jsonl)
+      if (!small_flat) HIPCHK(hipEventRecord(C->ev_k2, C->stream));
       const int n_first = n;
-      bool probe_timed = false, small_finish = false;
+      bool small_finish = false;
       dim3 grid((unsigned)std::min((n + ipw - 1) / ipw, cap_lat));
       {
         if (!small_flat) hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, list, n, C->d_counters);
@@ -2047,10 +2025,9 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
           }
         }
         if (split) {
-          // k_flat2: two lanes per joint, one instance per wavefront, two or three wavefronts per SIMD (loik_flat2.hpp)
+          // k_flat2: two lanes per joint, one instance per wavefront, two wavefronts per SIMD (loik_flat2.hpp)
           const size_t lds2 = flat2_lds_bytes<FLAT_NA_SMALL>(S->nc, has_hv != 0, mur == 1);
-          const int wpe = S->tune.flat_split_wpe;
-          int per_cu = (int)std::min<size_t>((size_t)4 * wpe, (160 * 1024) / lds2);
+          int per_cu = (int)std::min<size_t>((size_t)8, (160 * 1024) / lds2);
           if (S->tune.lean_wg_per_cu > 0) per_cu = std::min(per_cu, S->tune.lean_wg_per_cu);
           grid = dim3((unsigned)std::min(n, per_cu * (int)(cu_sh + 0.5)));
           // Round-robin time slicing inside the launch (k_flat2<.., SLICED>).  Iteration counts are heavy-tailed and unknown: run to
@@ -2081,67 +2058,43 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
           // (not for a handle on a stream of its own: that is how batches are kept in flight side by side, and then the other
           //  batch's bulk fills this one's ragged end -- slicing only adds its switches, and its wavefronts that wait for queue
           //  entries hold slots the other launch could use: two headline batches in flight 21.5 ms per pair without, 24.9 with)
-#define LOIKB_LAUNCH_FLAT2(WPE, ...)                                                                                            \
-  hipLaunchKernelGGL((k_flat2<FLAT_NA_SMALL, WPE, ##__VA_ARGS__>), grid, dim3(WAVE), lds2, C->stream,                            \
+#define LOIKB_LAUNCH_FLAT2(...)                                                                                                 \
+  hipLaunchKernelGGL((k_flat2<FLAT_NA_SMALL, ##__VA_ARGS__>), grid, dim3(WAVE), lds2, C->stream,                                 \
                      *reinterpret_cast<const Params<double>*>(&P), *reinterpret_cast<const Bufs<double>*>(&Bf),                  \
                      (const JointDesc*)S->d_jd, (const FlatLane*)S->flat.d_lanes, nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, \
                      (const double*)C->d_fslots, frows, kexp_lo, ndec, (double)S->Href[0], (int)((unsigned int)has_hv | ((unsigned int)(S->maxdepth & 0xFF) << 8) | ((unsigned int)win_bits << 16)), C->ring_cap - 1, quantum,       \
                      (double*)C->d_park, flat2_park_stride(S->nc, true), (const void* const*)C->d_aux)
           const int hm = S->per_link ? 3 : href_is_scalar(S) ? 0 : href_is_diagonal(S) ? 1 : 2;
-          // Two launches instead of one time-sliced one (FLAT_Q_PROBE / FLAT_Q_FINISH, loik_flat2.hpp): the probe, k_probe_sort, the survivors.
-          const int probe_len = S->tune.flat_probe, probe_mark = std::min(S->tune.flat_probe_mark, std::max(1, probe_len / 2));
-          const bool two_launches = quantum > 0 && probe_len >= 2 && !ordered && mur != 1 && !S->opt.logging && wpe != 3 &&
-                                    S->opt.max_iter > probe_len && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
-          const int quantum_one = quantum;
-          auto launch_flat2 = [&](int quantum) {
           if (mur == 1) {
             // (OSQP's rule runs unsliced unless LOIKB_FLAT_SLICE asks: a parked instance rebuilds its factors when it is taken up again --
             //  headline batch, first solve: 12.7 ms with the default slices, 11.4 without: profiles/r05_d_mu_rules.jsonl)
             if (S->tune.flat_slice < 0) quantum = 0;
-            if (hm == 3) { quantum = 0; LOIKB_LAUNCH_FLAT2(2, false, 3, false, 1); }
-            else if (hm == 2) { quantum = 0; LOIKB_LAUNCH_FLAT2(2, false, 2, false, 1); }
-            else if (hm == 1) { quantum = 0; LOIKB_LAUNCH_FLAT2(2, false, 1, false, 1); }
-            else if (quantum > 0) LOIKB_LAUNCH_FLAT2(2, true, 0, false, 1);
-            else LOIKB_LAUNCH_FLAT2(2, false, 0, false, 1);
+            if (hm == 3) { quantum = 0; LOIKB_LAUNCH_FLAT2(false, 3, false, 1); }
+            else if (hm == 2) { quantum = 0; LOIKB_LAUNCH_FLAT2(false, 2, false, 1); }
+            else if (hm == 1) { quantum = 0; LOIKB_LAUNCH_FLAT2(false, 1, false, 1); }
+            else if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 0, false, 1);
+            else LOIKB_LAUNCH_FLAT2(false, 0, false, 1);
           }
           else if (mur == 2) {
-            if (quantum > 0) LOIKB_LAUNCH_FLAT2(2, true, 0, false, 2); else LOIKB_LAUNCH_FLAT2(2, false, 0, false, 2);
+            if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 0, false, 2); else LOIKB_LAUNCH_FLAT2(false, 0, false, 2);
           }
           else if (S->opt.logging) {   // (the SolverInfo lists: unsliced; a diagonal reference weight goes as a general one)
             quantum = 0;
-            if (hm == 3) LOIKB_LAUNCH_FLAT2(2, false, 3, true);
-            else if (hm >= 1) LOIKB_LAUNCH_FLAT2(2, false, 2, true);
-            else LOIKB_LAUNCH_FLAT2(2, false, 0, true);
+            if (hm == 3) LOIKB_LAUNCH_FLAT2(false, 3, true);
+            else if (hm >= 1) LOIKB_LAUNCH_FLAT2(false, 2, true);
+            else LOIKB_LAUNCH_FLAT2(false, 0, true);
           }
-          else if (hm == 3) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(2, true, 3); else LOIKB_LAUNCH_FLAT2(2, false, 3); }
-          else if (hm == 2) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(2, true, 2); else LOIKB_LAUNCH_FLAT2(2, false, 2); }
-          else if (hm == 1) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(2, true, 1); else LOIKB_LAUNCH_FLAT2(2, false, 1); }
-          else if (quantum > 0) { if (wpe == 3) LOIKB_LAUNCH_FLAT2(3, true); else LOIKB_LAUNCH_FLAT2(2, true); }
-          else if (wpe == 3) LOIKB_LAUNCH_FLAT2(3);
-          else LOIKB_LAUNCH_FLAT2(2);
-          };
-          if (two_launches) {
-            launch_flat2(probe_mark | ((probe_len - probe_mark) << 16) | FLAT_Q_PROBE);
-            HIPCHK(hipGetLastError());
-            const int nl_ = (has_hv ? F2G * 6 : 0) + S->nc * C2D;   // (the record's LDS blocks: shv | constraint blocks | the scalar block)
-            hipLaunchKernelGGL(k_probe_sort, dim3(1), dim3(1024), 0, C->stream, C->d_ring, n, C->ring_cap - 1, (const double*)C->d_park,
-                               flat2_park_stride(S->nc, true), FLAT2_PARK_ROWS * WAVE + nl_, FLAT2_PARK_ROWS * WAVE + nl_ + FISC, C->d_counters,
-                               probe_mark, probe_len - probe_mark > FLAT_PROBE_LAST ? probe_len - FLAT_PROBE_LAST : probe_len, probe_len, S->opt.max_iter,
-                               (double)S->opt.tol_abs);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(C->ev_k3, C->stream));
-            launch_flat2(FLAT_Q_FINISH);
-            C->stats.flat_probe_launches++;
-            probe_timed = true;
-          } else {
-            launch_flat2(quantum_one);
-          }
+          else if (hm == 3) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 3); else LOIKB_LAUNCH_FLAT2(false, 3); }
+          else if (hm == 2) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 2); else LOIKB_LAUNCH_FLAT2(false, 2); }
+          else if (hm == 1) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 1); else LOIKB_LAUNCH_FLAT2(false, 1); }
+          else if (quantum > 0) LOIKB_LAUNCH_FLAT2(true);
+          else LOIKB_LAUNCH_FLAT2();
 #undef LOIKB_LAUNCH_FLAT2
         } else if (one) {
           // one decade slot in LDS instead of two when that buys wavefronts per CU (whole body, four task constraints: 6 -> 8)
           auto lds_of = [&](int bufs) { return small_na ? flat1_lds_bytes<FLAT_NA_SMALL>(S->nc, has_hv != 0, bufs) : flat1_lds_bytes<FLAT_MAXA>(S->nc, has_hv != 0, bufs); };
           // (OSQP's rule: the in-wave builder's rows lie over both slots -- two it is)
-          const int one_buf = mur != 1 && (S->tune.flat_one_slot != 0) && std::min<size_t>(8, (160 * 1024) / lds_of(1)) > std::min<size_t>(8, (160 * 1024) / lds_of(2));
+          const int one_buf = mur != 1 && std::min<size_t>(8, (160 * 1024) / lds_of(1)) > std::min<size_t>(8, (160 * 1024) / lds_of(2));
           const size_t lds1 = lds_of(one_buf ? 1 : 2);
           int per_cu1 = (int)std::min<size_t>(8, (160 * 1024) / lds1);
           if (S->tune.lean_wg_per_cu > 0) per_cu1 = std::min(per_cu1, S->tune.lean_wg_per_cu);
@@ -2232,7 +2185,7 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
       float ms = 0.f, t0 = 0.f, hms = 0.f;
       HIPCHK(hipEventElapsedTime(&ms, ev_first, C->ev_k1));
       if (!queue_ready) HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
-      if (slot_event) HIPCHK(hipEventElapsedTime(&hms, ev_first, C->ev_k2));
+      if (!small_flat) HIPCHK(hipEventElapsedTime(&hms, ev_first, C->ev_k2));
       iters += C->h_counters[1];
       if (C->h_counters[FLAT_COUNTERS_ERR]) {
         g_last_error = (C->h_counters[FLAT_COUNTERS_ERR] & 4u) ? "internal: the flat engine's dynamic LDS does not start at LDS address 0 (lds_abs)"
@@ -2259,7 +2212,6 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
         S->ud_stale = true;
       }
       C->stats.hslots_ms += hms;
-      if (probe_timed) { float pms = 0.f; HIPCHK(hipEventElapsedTime(&pms, C->ev_k2, C->ev_k3)); C->stats.probe_ms += pms; }
       if (C->h_counters[FLAT_COUNTERS_DRY])  // (100 MHz clock, low words: from the ring fill of the last stage to the first empty fetch)
         C->stats.queue_dry_ms += (double)(unsigned int)(C->h_counters[FLAT_COUNTERS_TDRY] - C->h_counters[FLAT_COUNTERS_T0]) * 1e-5;
       if ((split || one) && whole_set && n_first == n_cur) {
@@ -2302,130 +2254,98 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
       const int ltw = S->plan.lean_wg_waves;  // wavefronts per workgroup
       const size_t lds = ltw * wave_lds;
       if (lds > 64 * 1024) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       }
       const int wg_per_cu = S->tune.lean_wg_per_cu > 0 ? S->tune.lean_wg_per_cu : waves_cu / ltw;
       const int wg_cap = wg_per_cu * std::max(1, (int)(S->ncu * ((double)C->B / (double)S->B) + 0.5));
-      // Optional rounds with a bounded share of iterations per instance (LOIKB_LEAN_QUANTA="24,64,160,400"; default: one
-      // launch).  Iteration counts are heavy-tailed and unpredictable: in one launch the work queue drains after ~60 % of
-      // the launch time and the rest is waiting for long runners that were fetched late.  Bounded rounds make every long
-      // runner advance from the start -- but it then only advances `quantum` iterations per round, i.e. it shares the
-      // machine instead of running flat out from an early start.  Measured: Talos headline (1.2 % of the instances run
-      // all 1000 iterations) 22.85 -> 21.99 ms, B = 131072 36.9 -> 36.2 ms; floating-base Talos (a handful of long runners)
-      // 36.5 -> 44.1 ms.  Not a default.
-      std::vector<int> quanta = S->tune.lean_quanta;
-      quanta.push_back(S->opt.max_iter + 1);
-      // (default 0: run to completion in arrival order -- DESIGN.md, scheduling study)
-      const int lean_quantum = S->tune.lean_slice;
       HIPCHK(hipEventRecord(C->ev_k0, C->stream));
-      // longest first, as in the flat engine: the order the handle's previous solve left, for a single whole-set launch that is not
-      // time-sliced (the decade slots are indexed by the instance: k_hslots and k_lean see the same list)
-      const bool lean_ordered = whole_set && list == C->d_slots && n == n_cur && quanta.size() == 1 && lean_quantum == 0 && order_usable(S, C, n_cur);
+      // longest first, as in the flat engine: the order the handle's previous solve left, for a whole-set launch (the decade slots are
+      // indexed by the instance: k_hslots and k_lean see the same list)
+      const bool lean_ordered = whole_set && list == C->d_slots && n == n_cur && order_usable(S, C, n_cur);
       const bool lean_order_was_stale = lean_ordered && C->order_epoch != S->inputs_epoch;
       if (whole_set && C->order_holdoff > 0) --C->order_holdoff;
       if (lean_ordered) HIPCHK(hipMemcpyAsync(C->d_slots, C->d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, C->stream));
       C->stats.flat_ordered += lean_ordered ? 1 : 0;
-      const int n_first_lean = n;
-      float t_first = -1.f;
-      unsigned int escaped = 0;
-      bool slots_built = false, first_timed = false;
-      for (size_t round = 0; round < quanta.size() && n > 0; ++round) {
-        if (quanta[round] <= 0) continue;
-        P.max_launch_iters = quanta[round];
-        const int wg_needed = (n + ipw * ltw - 1) / (ipw * ltw);
-        const dim3 grid((unsigned)std::min(wg_needed, wg_cap));
-        HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
-        if (!slots_built) {
-          slots_built = true;
-          const dim3 hgrid((unsigned)((n + ipw - 1) / ipw));
-          const size_t hlds = (size_t)(WAVE + 1) * 22 * sizeof(T);
-          if (per_link)
-            hipLaunchKernelGGL((k_hslots<T, false, true>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                               (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
-                               (T*)C->d_hslots, kexp_lo, ndec);
-          else if (S->href_diag)
-            hipLaunchKernelGGL((k_hslots<T, true>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                               (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
-                               (T*)C->d_hslots, kexp_lo, ndec);
-          else
-            hipLaunchKernelGGL((k_hslots<T, false>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                               (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
-                               (T*)C->d_hslots, kexp_lo, ndec);
-          HIPCHK(hipEventRecord(C->ev_k2, C->stream));
-        }
-        hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, list, n, C->d_counters);
-        // time slice of the in-kernel round-robin queue (0 = run every instance to completion in arrival order); bounded
-        // host-side rounds (LOIKB_LEAN_QUANTA) bring their own bound and switch it off
-        const int quantum = quanta.size() > 1 ? 0 : lean_quantum;
-#define LOIKB_LAUNCH_LEAN(HD, SL, ...)                                                                                        \
-  hipLaunchKernelGGL((k_lean<T, HD, SL, ##__VA_ARGS__>), grid, dim3(WAVE * ltw), lds, C->stream, P, Bf, (const JointDesc*)S->d_jd,             \
-                     (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, C->d_ring,              \
-                     C->ring_cap - 1, n, G, (const T*)C->d_hslots, kexp_lo, ndec, quantum, S->multi_from)
-        if (per_link) { if (quantum > 0) LOIKB_LAUNCH_LEAN(false, true, true); else LOIKB_LAUNCH_LEAN(false, false, true); }
-        else if (quantum > 0) { if (S->href_diag) LOIKB_LAUNCH_LEAN(true, true); else LOIKB_LAUNCH_LEAN(false, true); }
-        else { if (S->href_diag) LOIKB_LAUNCH_LEAN(true, false); else LOIKB_LAUNCH_LEAN(false, false); }
+      P.max_launch_iters = S->opt.max_iter + 1;
+      const int wg_needed = (n + ipw * ltw - 1) / (ipw * ltw);
+      const dim3 grid((unsigned)std::min(wg_needed, wg_cap));
+      HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
+      const dim3 hgrid((unsigned)((n + ipw - 1) / ipw));
+      const size_t hlds = (size_t)(WAVE + 1) * 22 * sizeof(T);
+      if (per_link)
+        hipLaunchKernelGGL((k_hslots<T, false, true>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
+                           (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
+                           (T*)C->d_hslots, kexp_lo, ndec);
+      else if (S->href_diag)
+        hipLaunchKernelGGL((k_hslots<T, true>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
+                           (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
+                           (T*)C->d_hslots, kexp_lo, ndec);
+      else
+        hipLaunchKernelGGL((k_hslots<T, false>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
+                           (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
+                           (T*)C->d_hslots, kexp_lo, ndec);
+      HIPCHK(hipEventRecord(C->ev_k2, C->stream));
+      hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, list, n, C->d_counters);
+#define LOIKB_LAUNCH_LEAN(...)                                                                                                  \
+  hipLaunchKernelGGL((k_lean<T, ##__VA_ARGS__>), grid, dim3(WAVE * ltw), lds, C->stream, P, Bf, (const JointDesc*)S->d_jd,               \
+                     (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, C->d_ring, n, G,            \
+                     (const T*)C->d_hslots, kexp_lo, ndec, S->multi_from)
+      if (per_link) LOIKB_LAUNCH_LEAN(false, true);
+      else if (S->href_diag) LOIKB_LAUNCH_LEAN(true);
+      else LOIKB_LAUNCH_LEAN(false);
 #undef LOIKB_LAUNCH_LEAN
+      HIPCHK(hipGetLastError());
+      // the instances that are still iterating: k_tail's list (ping-pong between the two list buffers)
+      int* next = (list == C->d_slots) ? C->d_slots2 : C->d_slots;
+      hipLaunchKernelGGL(k_list_unfinished<T>, grid1(n), dim3(256), 0, C->stream, A.tiles, S->L, list, n, next, C->d_counters + 3);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipEventRecord(C->ev_k1, C->stream));
+      HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
+      const bool lean_orders = S->tune.flat_order && whole_set && n == n_cur && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
+      if (lean_orders) {  // the order for the handle's next solve (k_order_*)
+        HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
+        hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins);
+        hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_BINS), 0, C->stream, C->d_order_bins);
+        hipLaunchKernelGGL(k_order_scatter<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins, C->d_order);
         HIPCHK(hipGetLastError());
-        // the instances that are still iterating: the next round's list (ping-pong between the two list buffers)
-        int* next = (list == C->d_slots) ? C->d_slots2 : C->d_slots;
-        hipLaunchKernelGGL(k_list_unfinished<T>, grid1(n), dim3(256), 0, C->stream, A.tiles, S->L, list, n, next, C->d_counters + 3);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(C->ev_k1, C->stream));
-        HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
-        const bool lean_orders = S->tune.flat_order && whole_set && n_first_lean == n_cur && quanta.size() == 1 && lean_quantum == 0 &&
-                                 !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
-        if (lean_orders) {  // the order for the handle's next solve (k_order_*)
-          HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
-          hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins);
-          hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_BINS), 0, C->stream, C->d_order_bins);
-          hipLaunchKernelGGL(k_order_scatter<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins, C->d_order);
-          HIPCHK(hipGetLastError());
-          C->order_n = n_cur;
-          C->order_epoch = S->inputs_epoch;
-        }
-        HIPCHK(hipStreamSynchronize(C->stream));
-        float ms = 0.f, t0 = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, C->ev_k0, C->ev_k1));  // since the start of the first round
-        if (lean_orders) {  // (held off like the flat engine's: compared with the handle's last launch in arrival order)
-          if (C->arrival_n != n_cur) { C->arrival_n = n_cur; C->arrival_ms = 0.0; }
-          if (!lean_ordered) C->arrival_ms = (double)ms;
-          else if (lean_order_was_stale && C->arrival_ms > 0.0 && (double)ms > 0.985 * C->arrival_ms) C->order_holdoff = S->tune.flat_order_holdoff;
-        }
-        if (t_first < 0.f) { HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0)); t_first = t0; }
-        iters += C->h_counters[1];
-        escaped = C->h_counters[2];
-        {
-          std::lock_guard<std::mutex> lock(S->alloc_mu);
-          const unsigned int seen = C->h_counters[LEAN_DECADES_SEEN];
-          for (int d = 0; d < 16; ++d)
-            if (seen & (1u << d)) { S->seen_lo = std::min(S->seen_lo, kexp_lo + d); S->seen_hi = std::max(S->seen_hi, kexp_lo + d); }
-          if (escaped) { S->seen_lo = S->plan.kexp_lo; S->seen_hi = S->plan.kexp_lo + S->plan.ndec - 1; }  // the table was too narrow
-        }
-        C->stats.lean_requeues += (int)C->h_counters[LEAN_Q_REQUEUES];
-        if (!first_timed) {
-          first_timed = true;
-          float hms = 0.f;
-          HIPCHK(hipEventElapsedTime(&hms, C->ev_k0, C->ev_k2));
-          C->stats.hslots_ms += hms;
-        }
-        if (trace)
-          fprintf(stderr, "[loikb] lean tail round %zu (<= %d iterations each): %6d instances on %u workgroups, done at %8.3f ms"
-                          "  inst-iters %9u  wave-iters %7u slot loads %7u  escaped %u  still iterating %u  requeued %u\n",
-                  round, quanta[round], n, grid.x, ms, C->h_counters[1], C->h_counters[5], C->h_counters[6], escaped,
-                  C->h_counters[3], C->h_counters[LEAN_Q_REQUEUES]);
-        C->stats.launches++;
-        C->stats.tail_launches++;
-        C->stats.lean_launches++;
-        total_ms = ms;
-        n = (int)C->h_counters[3];
-        list = next;
+        C->order_n = n_cur;
+        C->order_epoch = S->inputs_epoch;
       }
-      C->tail_iv.emplace_back(t_first, t_first + (float)total_ms);
+      HIPCHK(hipStreamSynchronize(C->stream));
+      float ms = 0.f, t0 = 0.f, hms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, C->ev_k0, C->ev_k1));
+      if (lean_orders) {  // (held off like the flat engine's: compared with the handle's last launch in arrival order)
+        if (C->arrival_n != n_cur) { C->arrival_n = n_cur; C->arrival_ms = 0.0; }
+        if (!lean_ordered) C->arrival_ms = (double)ms;
+        else if (lean_order_was_stale && C->arrival_ms > 0.0 && (double)ms > 0.985 * C->arrival_ms) C->order_holdoff = S->tune.flat_order_holdoff;
+      }
+      HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
+      iters += C->h_counters[1];
+      const unsigned int escaped = C->h_counters[2];
+      {
+        std::lock_guard<std::mutex> lock(S->alloc_mu);
+        const unsigned int seen = C->h_counters[LEAN_DECADES_SEEN];
+        for (int d = 0; d < 16; ++d)
+          if (seen & (1u << d)) { S->seen_lo = std::min(S->seen_lo, kexp_lo + d); S->seen_hi = std::max(S->seen_hi, kexp_lo + d); }
+        if (escaped) { S->seen_lo = S->plan.kexp_lo; S->seen_hi = S->plan.kexp_lo + S->plan.ndec - 1; }  // the table was too narrow
+      }
+      C->stats.lean_requeues += (int)C->h_counters[LEAN_Q_REQUEUES];
+      HIPCHK(hipEventElapsedTime(&hms, C->ev_k0, C->ev_k2));
+      C->stats.hslots_ms += hms;
+      if (trace)
+        fprintf(stderr, "[loikb] lean engine: %6d instances on %u workgroups, done at %8.3f ms"
+                        "  inst-iters %9u  wave-iters %7u slot loads %7u  escaped %u  still iterating %u  requeued %u\n",
+                n, grid.x, ms, C->h_counters[1], C->h_counters[5], C->h_counters[6], escaped,
+                C->h_counters[3], C->h_counters[LEAN_Q_REQUEUES]);
+      C->stats.launches++;
+      C->stats.tail_launches++;
+      C->stats.lean_launches++;
+      total_ms = ms;
+      n = (int)C->h_counters[3];
+      list = next;
+      C->tail_iv.emplace_back(t0, t0 + (float)total_ms);
       C->stats.lean_escaped += (int)escaped;
       if (n == 0) { *ms_out = total_ms; *iters_out = iters; return LOIKB_OK; }
       // what is left escaped the precomputed decades: k_tail below finishes it
@@ -2719,8 +2639,6 @@ int run_main_loop_t(loikb_solver_impl* S)
     S->stats.flat_split_launches += C.stats.flat_split_launches;
     S->stats.flat_ordered += C.stats.flat_ordered;
     S->stats.flat_built += C.stats.flat_built;
-    S->stats.flat_probe_launches += C.stats.flat_probe_launches;
-    S->stats.probe_ms += C.stats.probe_ms;
     S->stats.queue_dry_ms += C.stats.queue_dry_ms;
     S->stats.lean_escaped += C.stats.lean_escaped;
     S->stats.hslots_ms += C.stats.hslots_ms;
@@ -3633,15 +3551,15 @@ const char* loikb_plan_string(loikb_solver* S)
              "CU, decades mu0*10^%d..%d, %d ancestors per joint, %d scan steps, %d jump rounds)%s; k_solve above that; %d chunk(s)",
              split ? "k_flat2" : one ? "k_flat1" : "k_flat",
              split ? "; two lanes per joint, one instance per wavefront" : one ? "; one instance per wavefront" : "", pl.tail_max,
-             split ? std::min(4 * S->tune.flat_split_wpe, pl.flat_waves_cu * 2) : one ? std::min(8, pl.flat_waves_cu) : pl.flat_waves_cu,
+             split ? std::min(8, pl.flat_waves_cu * 2) : one ? std::min(8, pl.flat_waves_cu) : pl.flat_waves_cu,
              pl.kexp_lo, pl.kexp_lo + pl.ndec - 1,
              S->flat.nanc, S->flat.nscan, S->flat.njmp,
              (split || one) ? ", any reference cost" : S->have_problem ? "" : " when H_ref = h I", pl.nchunks);
   }
   else if (pl.lean)
     snprintf(buf, sizeof(buf), "k_hslots + k_lean for whole batches up to %d instances (%d wavefronts per CU in workgroups of %d, "
-             "decades mu0*10^%d..%d, time slice %d); k_solve above that; %d chunk(s)", pl.tail_max, pl.lean_waves_cu,
-             pl.lean_wg_waves, pl.kexp_lo, pl.kexp_lo + pl.ndec - 1, S->tune.lean_slice, pl.nchunks);
+             "decades mu0*10^%d..%d); k_solve above that; %d chunk(s)", pl.tail_max, pl.lean_waves_cu,
+             pl.lean_wg_waves, pl.kexp_lo, pl.kexp_lo + pl.ndec - 1, pl.nchunks);
   else
     snprintf(buf, sizeof(buf), "k_solve (team of %d), hand-over to k_tail at %d live instances; %d chunk(s); no k_lean: %s",
              S->sched[1].nw, pl.tail_max, pl.nchunks, pl.why_not_lean);

@@ -28,7 +28,6 @@ ENGINES = {
     "handover": ({}, dict(max_launch_iters=3, tail_max_instances=1 << 20)),
     "lean": ({"LOIKB_FLAT": "0"}, {}),
     "lean_escapes": ({"LOIKB_FLAT": "0", "LOIKB_LEAN_KLO": "1", "LOIKB_LEAN_DECADES": "3"}, {}),
-    "lean_sliced": ({"LOIKB_FLAT": "0", "LOIKB_LEAN_SLICE": "9"}, {}),
     "flat_escapes": ({"LOIKB_LEAN_KLO": "1", "LOIKB_LEAN_DECADES": "3"}, {}),
     # k_flat2's round-robin time slicing forced (one wavefront per CU so that instances wait: requeues from the 7th iteration)
     "flat_sliced": ({"LOIKB_FLAT_SLICE": "7", "LOIKB_LEAN_WG_PER_CU": "1"}, {}),
@@ -42,7 +41,7 @@ ENGINES = {
     "flat_lazy": ({"LOIKB_FLAT_BUILD": "1", "LOIKB_FLAT_WINDOW": "0,1"}, {}),
     "flat_lazy_sliced": ({"LOIKB_FLAT_BUILD": "1", "LOIKB_FLAT_WINDOW": "1,1", "LOIKB_FLAT_SLICE": "7", "LOIKB_LEAN_WG_PER_CU": "1"}, {}),
 }
-ENV_KEYS = ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_FLAT_SPLIT", "LOIKB_FLAT_SLICE", "LOIKB_LEAN_KLO", "LOIKB_LEAN_DECADES", "LOIKB_LEAN_SLICE",
+ENV_KEYS = ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_FLAT_SPLIT", "LOIKB_FLAT_SLICE", "LOIKB_LEAN_KLO", "LOIKB_LEAN_DECADES",
             "LOIKB_LEAN_WG_PER_CU", "LOIKB_FLAT_ORDER_HOLDOFF", "LOIKB_FLAT_BUILD", "LOIKB_FLAT_WINDOW", "LOIKB_LEAN_ADAPT")
 
 

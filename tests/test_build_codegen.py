@@ -91,9 +91,9 @@ def test_flat_kernels_iteration_loops_hold_no_more_scratch_reloads_than_known():
         cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-ffp-contract=on", "-std=c++17", "-fPIC", "-I", os.path.join(root, "include"), "-DLOIKB_FLAT_SEPARATE_TU",
                "-x", "hip", os.path.join(root, "loik_amd", "csrc", "loik_flat_kernels.hip"), "-S", "--cuda-device-only", "-o", asm] + list(_build.FLAT_FLAGS)
         subprocess.run(cmd, check=True, capture_output=True)
-        # (mangled template arguments: k_flat2<NA 10, WPE 2, SLICED, HM 0, LOG 0, MUR>, k_flat1<NA 10, SLICED, HM 0, LOG 0, MUR 0>)
-        kernels = {"k_flat2ILi10ELi2ELb1ELi0ELb0ELi2E": "headline: time-sliced, lazily populated table", "k_flat2ILi10ELi2ELb0ELi0ELb0ELi0E": "ordered / small batches",
-                   "k_flat2ILi10ELi2ELb1ELi0ELb0ELi0E": "time-sliced, full table", "k_flat1ILi10ELb1ELi0ELb0ELi0E": "whole body, time-sliced",
+        # (mangled template arguments: k_flat2<NA 10, SLICED, HM 0, LOG 0, MUR>, k_flat1<NA 10, SLICED, HM 0, LOG 0, MUR 0>)
+        kernels = {"k_flat2ILi10ELb1ELi0ELb0ELi2E": "headline: time-sliced, lazily populated table", "k_flat2ILi10ELb0ELi0ELb0ELi0E": "ordered / small batches",
+                   "k_flat2ILi10ELb1ELi0ELb0ELi0E": "time-sliced, full table", "k_flat1ILi10ELb1ELi0ELb0ELi0E": "whole body, time-sliced",
                    "k_flat1ILi10ELb0ELi0ELb0ELi0E": "whole body, ordered"}
         for key, what in kernels.items():
             out = subprocess.run([sys.executable, os.path.join(root, "scripts", "r05", "loopstat.py"), asm, key], check=True, capture_output=True, text=True).stdout

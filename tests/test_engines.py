@@ -102,57 +102,6 @@ def test_every_engine_matches_the_oracle(which, engine, request, monkeypatch):
     s.close()
 
 
-def test_lean_rounds_with_iteration_quanta(talos, monkeypatch):
-    """LOIKB_LEAN_QUANTA: the lean kernel in rounds of at most q iterations per instance (decade slots are indexed by the
-    instance's slot, the lists shrink from round to round) -- same answers as one launch"""
-    link = talos.getJointId("arm_left_7_joint")
-    B = 300
-    wl = feasible_batch(talos, B, link, 17, nu_scale=0.5)
-    args = (wl["q"], wl["H_ref"], wl["v_ref"], wl["c_ids"], wl["Ais"], wl["bis"], wl["lb"], wl["ub"])
-    prm = dict(FIXTURE, max_iter=600, tol_abs=1e-6, tol_rel=0.0)
-    monkeypatch.setenv("LOIKB_FLAT", "0")  # (a mechanism of k_lean)
-    monkeypatch.delenv("LOIKB_LEAN_QUANTA", raising=False)
-    a = loik_amd.BatchedLoik(talos, B, **prm)
-    a.Solve(*args)
-    monkeypatch.setenv("LOIKB_LEAN_QUANTA", "5,11,40")
-    b = loik_amd.BatchedLoik(talos, B, **prm)
-    b.Solve(*args)
-    assert b.stats()["lean_launches"] >= 3 and a.stats()["lean_launches"] == 1
-    for name in ["iter", "converged", "primal_infeasible", "mu"]:
-        assert np.array_equal(a.get(name), b.get(name)), name
-    for name in ["z", "nu", "w", "vis", "fis", "primal_residual", "dual_residual", "delta_vis_inf_norm", "g_inf_norm"]:
-        assert np.max(np.abs(a.get(name) - b.get(name))) < 1e-10, name
-    a.close(); b.close()
-
-
-def test_lean_time_slicing_changes_nothing(talos, monkeypatch):
-    """LOIKB_LEAN_SLICE=q: round-robin time slicing inside the lean launch (k_lean<.., SLICED = true>): an instance that used
-    q iterations while others wait for a slot is written back and re-queued -- it migrates between lane groups, i.e. between
-    CUs of different XCDs, within one launch (coherent record accesses).  Per-instance results are bit-identical."""
-    link = talos.getJointId("arm_left_7_joint")
-    B = 12000  # more instances than resident lane groups (4096): the queue is never empty at the first slice boundaries
-    wl = feasible_batch(talos, B, link, 23, nu_scale=0.5)
-    args = (wl["q"], wl["H_ref"], wl["v_ref"], wl["c_ids"], wl["Ais"], wl["bis"], wl["lb"], wl["ub"])
-    prm = dict(FIXTURE, max_iter=400, tol_abs=1e-6, tol_rel=0.0)
-    monkeypatch.setenv("LOIKB_FLAT", "0")  # (a mechanism of k_lean)
-    monkeypatch.delenv("LOIKB_LEAN_SLICE", raising=False)
-    a = loik_amd.BatchedLoik(talos, B, **prm)
-    a.Solve(*args)
-    assert a.stats()["lean_requeues"] == 0
-    for q in ("7", "40"):
-        monkeypatch.setenv("LOIKB_LEAN_SLICE", q)
-        b = loik_amd.BatchedLoik(talos, B, **prm)
-        for _ in range(2):
-            b.Solve(*args)
-            st = b.stats()
-            assert st["lean_requeues"] > 0 and st["lean_escaped"] == 0
-            assert st["instance_iterations"] == a.stats()["instance_iterations"]
-            for name in ["iter", "converged", "primal_infeasible", "mu", "z", "nu", "w", "vis", "fis", "g", "yis", "primal_residual",
-                         "dual_residual", "delta_vis_inf_norm", "g_inf_norm", "mu_updates"]:
-                assert np.array_equal(a.get(name), b.get(name)), (q, name)
-        b.close()
-    a.close()
-
 
 @pytest.mark.parametrize("robot", ["talos32", "talos44", "talos32_lean"])
 def test_longest_first_order_changes_nothing_but_the_schedule(robot, monkeypatch):
@@ -249,7 +198,7 @@ def test_zero_state_launch_fetches_less_and_computes_the_same(monkeypatch):
 def test_engine_plan_is_made_in_one_place(talos, panda7, monkeypatch):
     """loikb_plan_string: the dispatch (nb, nc, A shared?, children, options) -> engines, re-made at SolveInit when the sharing
     mode of A is known (round 1 fixed the chunk count at create with the default mode)"""
-    for v in ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_CHUNKS", "LOIKB_LEAN_SLICE"):
+    for v in ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_CHUNKS"):
         monkeypatch.delenv(v, raising=False)
     s = loik_amd.BatchedLoik(talos, 256, **FIXTURE)
     assert "k_flat2" in s.plan() and "1 chunk" in s.plan() and "any reference cost" in s.plan(), s.plan()
@@ -413,7 +362,7 @@ def test_fuzz_slice_every_engine(monkeypatch):
     """a bounded slice of scripts/fuzz_engines.py inside the suite: random trees (1-DoF / multi-DoF / composite joints, depth- and
     breadth-first numbering), 0..4 constraints, shared / per-instance data, reference costs, tolerances, penalty rules, every engine
     configuration -- against the oracle, no instance dropped.  (The long runs live in profiles/r03_*_fuzz_summary.txt.)"""
-    for k in ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_FLAT_SPLIT", "LOIKB_FLAT_SLICE", "LOIKB_LEAN_KLO", "LOIKB_LEAN_DECADES", "LOIKB_LEAN_SLICE"):
+    for k in ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_FLAT_SPLIT", "LOIKB_FLAT_SLICE", "LOIKB_LEAN_KLO", "LOIKB_LEAN_DECADES"):
         monkeypatch.delenv(k, raising=False)   # (the fuzzer sets and clears them itself; restored after the test)
     out = _fuzz().fuzz(40, 31337, verbose=False, max_batch=700)
     assert out["cases"] + out["refused"] == 40 and out["instances"] > 5000, out
@@ -427,7 +376,7 @@ def test_fuzz_slice_every_engine(monkeypatch):
 def test_fuzz_slice_flat_engine(monkeypatch):
     """the same, drawn inside the flat engine's domain (> 16 joints numbered depth-first, H_ref = h I with or without a target,
     DEFAULT penalty rule; default plan, hand-over from k_solve, forced escapes, two stages)"""
-    for k in ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_FLAT_SPLIT", "LOIKB_FLAT_SLICE", "LOIKB_LEAN_KLO", "LOIKB_LEAN_DECADES", "LOIKB_LEAN_SLICE"):
+    for k in ("LOIKB_LEAN", "LOIKB_FLAT", "LOIKB_FLAT_SPLIT", "LOIKB_FLAT_SLICE", "LOIKB_LEAN_KLO", "LOIKB_LEAN_DECADES"):
         monkeypatch.delenv(k, raising=False)
     out = _fuzz().fuzz(30, 4242, verbose=False, max_batch=700, flat_bias=1.0)
     for c in out["unconverged_cases"]:
@@ -673,47 +622,6 @@ def test_whole_body_osqp_rule_on_the_flat_engine(weight, monkeypatch):
     mu = s.get("mu")
     assert np.unique(np.round(np.log10(mu), 9)).size > 12
     s.close()
-
-
-def test_flat_probe_and_finish_in_two_launches_changes_nothing(talos, monkeypatch):
-    """Round 6: a time-sliced k_flat2 launch without an order runs as TWO launches -- the probe (every instance for LOIKB_FLAT_PROBE
-    iterations at most, the residual noted at three marks, survivors parked), k_probe_sort (survivors ordered by the iterations they
-    are predicted to need still), and the launch that takes that list front to back, every instance to completion.  A parked instance
-    continues exactly where it stopped, so every result is bit-identical to the single unsliced launch; forced here on 1500 instances
-    with short probes (5, 40 iterations) and with longer ones, with and without the lazily populated table."""
-    from loik_amd import workloads
-    B = 1500
-    wl = workloads.talos_c3(B, seed=321)
-    prm = dict(wl["params"], max_iter=400)
-    args = (wl["q"], wl["H_ref"], wl["v_ref"], wl["c_ids"], wl["Ais"], wl["bis"], wl["lb"], wl["ub"])
-    keys = ("LOIKB_FLAT_SLICE", "LOIKB_FLAT_PROBE", "LOIKB_FLAT_PROBE_MARK", "LOIKB_FLAT_BUILD", "LOIKB_FLAT_WINDOW")
-    res = {}
-    cases = (("plain", dict(LOIKB_FLAT_SLICE="0")),
-             ("probe5", dict(LOIKB_FLAT_SLICE="288", LOIKB_FLAT_PROBE="5", LOIKB_FLAT_PROBE_MARK="2")),
-             ("probe40", dict(LOIKB_FLAT_SLICE="288", LOIKB_FLAT_PROBE="40")),
-             ("probe128_full_table", dict(LOIKB_FLAT_SLICE="288", LOIKB_FLAT_PROBE="128", LOIKB_FLAT_BUILD="0")),
-             ("probe320", dict(LOIKB_FLAT_SLICE="288", LOIKB_FLAT_PROBE="320")),
-             ("probe40_window", dict(LOIKB_FLAT_SLICE="288", LOIKB_FLAT_PROBE="40", LOIKB_FLAT_BUILD="1", LOIKB_FLAT_WINDOW="0,2")))
-    for name, env in cases:
-        for k in keys:
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        s = loik_amd.BatchedLoik(talos, B, **prm)
-        s.Solve(*args)
-        st = s.stats()
-        assert st["flat_split_launches"] >= 1 and st["tail_instances"] == B
-        assert st["flat_probe_launches"] == (0 if name == "plain" else 1), (name, st)
-        if name != "plain":
-            assert st["lean_requeues"] > (100 if name != "probe320" else 10), (name, st)   # (the survivors were parked once each)
-        if name == "probe40_window":
-            assert st["flat_built"] > 0, st   # (decades outside the window: built in-wave, in either launch)
-        res[name] = {k: s.get(k) for k in ("iter", "converged", "primal_infeasible", "z", "nu", "mu", "yis", "fis", "vis")}
-        assert st["instance_iterations"] == int(res[name]["iter"].sum()), (name, st["instance_iterations"], int(res[name]["iter"].sum()))
-        s.close()
-    for name, _ in cases[1:]:
-        for k in res["plain"]:
-            assert np.array_equal(res["plain"][k], res[name][k]), (name, k)
 
 
 @pytest.mark.parametrize("B", [1, 5, 63])
