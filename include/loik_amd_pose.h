@@ -20,14 +20,16 @@
  * joint acts on.
  *
  * Preconditions of loikb_solve_pose: loikb_solve_init has set the formulation (task links, A, H_ref, v_ref, velocity box), else
- * LOIKB_ERR_STATE; at least one active constraint.  The problem is left as it was but for the b_c, which hold the last step's.
+ * LOIKB_ERR_STATE; at least one active constraint.  The problem is left as it was but for the b_c, which hold the last inner
+ * solve's (0 for the instances that did not run in it).
  * After the call:
  *   - q (LOIKB_F_Q) is the resident configuration: the last step's for running instances, the one they reached / stopped at
  *     for the others (reached instances do not move);
  *   - every inner solve runs on the whole batch: instances that no longer run solve with b = 0 and their z is discarded.  So
  *     the data object (z, yis, iter, ... of loikb_get) is that of the LAST inner solve for every instance: for an instance
- *     still running then, the solve of its final step; for the others, a solve with b = 0 at their final q.  max_steps = 0 runs
- *     no solve: the data object is left as it was;
+ *     still running then, the solve of its final step (made at the q before that step's integrate), also when the re-target
+ *     after it finds the instance reached and the call ends without another solve; for the others, a solve with b = 0 at
+ *     their final q.  max_steps = 0 runs no solve: the data object is left as it was;
  *   - the pose fields below describe each instance's final q.
  * Errors: LOIKB_ERR_ARG for dt <= 0, gain <= 0, tol_pose < 0, max_steps < 0, a target rotation that is not orthonormal with
  * determinant 1 within 1e-9 per entry (or not finite), a link id out of range, NULL pointers.

@@ -1,6 +1,6 @@
 """numpy restatement of the pose layer (loik_amd/csrc/loik_pose.hpp) for the tests: forward kinematics over the model tables,
-exp6 / log6 (Pinocchio's conventions: 6-vectors [linear; angular], twists in the local frame), the pose error and the
-host-driven pose loop on the CPU oracle."""
+exp6 / log6 (Pinocchio's conventions: 6-vectors [linear; angular], twists in the local frame), the pose error, the configuration
+integrator, and the pose loop on the CPU oracle: host-driven one instance at a time, and lock-step as the device runs it."""
 import numpy as np
 
 from loik_amd import workloads as W
@@ -202,3 +202,95 @@ def host_pose_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, targets, dt, 
             q[b] = integrate(model, q[b], dt * r.field("z"))
             steps[b] += 1
     return q, steps, reached
+
+
+POSE_REACHED, POSE_NOT_CONVERGED, POSE_INFEASIBLE, POSE_STOPPED = 1, 2, 4, 8
+
+
+def integrate(model, q, v):
+    """pinocchio::integrate of one configuration for every joint the device integrates (k_advance_q): the free-flyer, spherical and
+    translation joints as test_multidof._np_integrate has them, the planar joint on SE(2), the (cos, sin) joints on SO(2), plain
+    sums for the others (ZYX angles, prismatic, revolute, helical); a composite integrates sub-joint by sub-joint"""
+    from test_multidof import _np_integrate
+    if getattr(model, "composite", None):
+        return integrate(W._Chain(model), q, v)
+    out = _np_integrate(model, q, v)
+    for i in range(1, model.njoints):
+        jt, iq, iv = int(model.jtype[i]), int(model.idx_q[i]), int(model.idx_v[i])
+        if jt == J_SPHERICAL_ZYX:
+            out[iq:iq + 3] = q[iq:iq + 3] + v[iv:iv + 3]
+        elif jt == J_PLANAR:
+            vx, vy, w = v[iv:iv + 3]
+            c0, s0 = q[iq + 2], q[iq + 3]
+            sw, cw = np.sin(w), np.cos(w)
+            tx, ty = ((sw * vx - (1 - cw) * vy) / w, ((1 - cw) * vx + sw * vy) / w) if abs(w) > 1e-14 else (vx, vy)
+            out[iq], out[iq + 1] = q[iq] + c0 * tx - s0 * ty, q[iq + 1] + s0 * tx + c0 * ty
+            c1, s1 = c0 * cw - s0 * sw, s0 * cw + c0 * sw
+            n = 0.5 * (3 - (c1 * c1 + s1 * s1))
+            out[iq + 2], out[iq + 3] = c1 * n, s1 * n
+        elif jt in (J_RUBX, J_RUBY, J_RUBZ, J_RUBU):
+            c0, s0, w = q[iq], q[iq + 1], v[iv]
+            c1, s1 = c0 * np.cos(w) - s0 * np.sin(w), s0 * np.cos(w) + c0 * np.sin(w)
+            n = 0.5 * (3 - (c1 * c1 + s1 * s1))
+            out[iq], out[iq + 1] = c1 * n, s1 * n
+    return out
+
+
+def lockstep_pose_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, targets, dt, gain, tol, max_steps, integrate=integrate):
+    """the pose loop as the device runs it, step-major on the CPU oracle: each step computes the errors of every instance and marks
+    it reached (max_c |e_c|_inf <= tol) or stopped (e or q not finite); the loop ends at max_steps or when none is running; otherwise
+    EVERY instance runs the tailored Solve (warm_start as prm says), with b_c = A_c (gain / dt) e_c when running and b = 0 when not,
+    and only the running ones integrate q <- q (+) dt z and take the inner solve's outcome into their status.
+    A: [nc][6][6] shared or [B][nc][6][6] per instance; targets [B][nc][12].  Instances are independent but for the number of solves,
+    which is the batch's: run the oracle on the whole batch for `z` / `iter`.
+    Returns dict(q, steps, status (POSE_* bits), reached, err [B][nc][6] (of the last re-target each instance took part in),
+    z [B][nv], iter [B] (the oracle's after its last inner solve; 0 / zeros when there was none))."""
+    from oracle import ref
+    B, nc = q0.shape[0], len(links)
+    A = np.asarray(A, dtype=float)
+    A_of = (lambda b: A[b]) if A.ndim == 4 else (lambda b: A)
+    k = gain / dt
+    q = np.array(q0, dtype=float)
+    steps = np.zeros(B, dtype=np.int32)
+    status = np.zeros(B, dtype=np.int32)
+    err = np.zeros((B, nc, 6))
+    z = np.zeros((B, model.nv))
+    it = np.zeros(B, dtype=np.int32)
+    solvers, end = [], np.zeros(B, dtype=np.int32)
+    for b in range(B):   # each instance until it leaves the loop: the retarget at which it is reached / stopped, or max_steps
+        r = ref.RefSolver(model, **dict(prm, num_eq_c=nc))
+        r.SolveInit(q[b], H_ref, v_ref, np.asarray(links, dtype=np.int32), A_of(b), np.zeros((nc, 6)), lb, ub)
+        solvers.append(r)
+        for step in range(max_steps + 1):
+            end[b] = step
+            with np.errstate(all="ignore"):
+                e = pose_errors(model, q[b:b + 1], links, targets[b:b + 1])[0]
+            err[b] = e
+            if not (np.all(np.isfinite(e)) and np.all(np.isfinite(q[b]))):
+                status[b] |= POSE_STOPPED
+                break
+            if np.max(np.abs(e)) <= tol:
+                status[b] |= POSE_REACHED
+                break
+            if step == max_steps:
+                break
+            for c, l in enumerate(links):
+                r.UpdateEqConstraint(l, A_of(b)[c] @ (k * e[c]))
+            r.Solve(q[b], -1, None, None)
+            if not r.get_convergence_status():
+                status[b] |= POSE_NOT_CONVERGED
+            if r.get_primal_infeasibility_status():
+                status[b] |= POSE_INFEASIBLE
+            q[b] = integrate(model, q[b], dt * r.field("z"))
+            steps[b] += 1
+    n_solves = int(end.max()) if B else 0   # the step at which none is running any more (or max_steps)
+    for b in range(B):   # the idle b = 0 solves at the final q of the instances that left the loop before the batch did
+        r = solvers[b]
+        if end[b] < n_solves and not status[b] & POSE_STOPPED:
+            for l in links:
+                r.UpdateEqConstraint(l, np.zeros(6))
+            for _ in range(n_solves - end[b]):
+                r.Solve(q[b], -1, None, None)
+        if n_solves > 0 and not status[b] & POSE_STOPPED:
+            z[b], it[b] = r.field("z"), r.get_iter()
+    return dict(q=q, steps=steps, status=status, reached=(status & POSE_REACHED) != 0, err=err, z=z, iter=it)

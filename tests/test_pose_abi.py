@@ -47,6 +47,107 @@ def test_numpy_log6_inverts_exp6(theta):
         assert np.max(np.abs(P.log6(R, p) - nu)) < 1e-12
 
 
+# ---- the numpy log6 against an independent high-precision reference ----------------------------------------------------------
+# (pose_numpy.log3 / log6 restate the device's branches: a wrong series coefficient there would agree with itself.  mpmath at 40
+#  digits knows none of them.)  The branch switches: log3's series below theta = 1e-4 and its symmetric-part axis below
+#  cos theta = -0.8 (theta = 2.49809...), log6's series of beta below theta = 1e-3.
+THETA_SWITCH_PI = float(np.arccos(-0.8))
+LOGM_THETAS = [1e-9, 1e-4 * (1 - 1e-3), 1e-4 * (1 + 1e-3), 1e-3 * (1 - 1e-3), 1e-3 * (1 + 1e-3), THETA_SWITCH_PI - 1e-6,
+               THETA_SWITCH_PI + 1e-6, 1.0, 3.0]
+NEAR_PI = [1e-3, 1e-6, 1e-9, 1e-12]
+TRANSLATIONS = [1e-9, 1.0, 1e3]
+
+
+def _mp():
+    import mpmath
+    mpmath.mp.dps = 40
+    return mpmath
+
+
+def _twist(rng, theta, tnorm, axis=None):
+    a = rng.normal(size=3) if axis is None else np.asarray(axis, dtype=float)
+    v = rng.normal(size=3)
+    return np.r_[tnorm * v / np.linalg.norm(v), theta * a / np.linalg.norm(a)]
+
+
+def _mp_log6(mpmath, R, p):
+    """[v; w] of the principal matrix logarithm of the homogeneous matrix (R, p), the double entries taken exactly"""
+    M = mpmath.matrix(4, 4)
+    for i in range(3):
+        for j in range(3):
+            M[i, j] = mpmath.mpf(float(R[i, j]))
+        M[i, 3] = mpmath.mpf(float(p[i]))
+    M[3, 3] = 1
+    L = mpmath.logm(M)
+    w = [(L[2, 1] - L[1, 2]) / 2, (L[0, 2] - L[2, 0]) / 2, (L[1, 0] - L[0, 1]) / 2]
+    return np.array([float(mpmath.re(x)) for x in [L[0, 3], L[1, 3], L[2, 3]] + w])
+
+
+def _mp_exp6(mpmath, nu):
+    """(R, p) of exp6 of a double twist, in 40-digit arithmetic"""
+    v = mpmath.matrix([mpmath.mpf(float(x)) for x in nu[:3]])
+    w = [mpmath.mpf(float(x)) for x in nu[3:]]
+    th = mpmath.sqrt(w[0] ** 2 + w[1] ** 2 + w[2] ** 2)
+    K = mpmath.matrix([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    I = mpmath.eye(3)
+    a, b, c = mpmath.sin(th) / th, (1 - mpmath.cos(th)) / th ** 2, (th - mpmath.sin(th)) / th ** 3
+    R = I + a * K + b * K * K
+    p = (I + b * K + c * K * K) * v
+    return (np.array([[float(R[i, j]) for j in range(3)] for i in range(3)]), np.array([float(p[i]) for i in range(3)]))
+
+
+@pytest.mark.parametrize("tnorm", TRANSLATIONS)
+@pytest.mark.parametrize("theta", LOGM_THETAS)
+def test_numpy_log6_matches_mpmath_logm(theta, tnorm):
+    """theta <= 3: the numpy log6 is the principal logarithm of the homogeneous matrix, to a few ulps of |nu|; the angular part to a
+    few ulps of theta (an absolute bound cannot see a wrong theta^2 / 6 term: below theta = 1e-4 it changes w by < 2e-13)"""
+    mpmath = _mp()
+    rng = np.random.default_rng(int(theta * 1e9) % 7919 + int(tnorm * 10))
+    for _ in range(3):
+        nu = _twist(rng, theta, tnorm)
+        R, p = P.exp6(nu)
+        got, want = P.log6(R, p), _mp_log6(mpmath, R, p)
+        scale = np.linalg.norm(want)
+        assert np.max(np.abs(got - want)) <= 1e-14 * scale, (theta, tnorm, got - want)
+        assert np.max(np.abs(got[3:] - want[3:])) <= 1e-14 * theta, (theta, tnorm, got[3:] - want[3:])
+        assert abs(np.linalg.norm(got[3:]) - theta) <= 1e-14 * theta + 1e-15
+
+
+def _assert_exp6_reproduces(mpmath, R, p, what):
+    got = P.log6(R, p)
+    assert np.linalg.norm(got[3:]) <= np.pi, what
+    Rg, pg = _mp_exp6(mpmath, got)
+    assert np.max(np.abs(Rg - R)) <= 1e-14, (what, Rg - R)
+    assert np.max(np.abs(pg - p)) <= 1e-14 * max(1.0, np.linalg.norm(p)), (what, pg - p)
+
+
+@pytest.mark.parametrize("tnorm", TRANSLATIONS)
+@pytest.mark.parametrize("delta", NEAR_PI)
+def test_numpy_log6_near_pi_inverts_mpmath_exp6(delta, tnorm):
+    """theta = pi - delta: logm is no reference there (near the cut it returns logarithms of the other sheet), so the check is that
+    exp6 evaluated in 40 digits takes the numpy log6 back to its input, with |w| <= pi"""
+    mpmath = _mp()
+    rng = np.random.default_rng(int(-np.log10(delta)) * 31 + int(tnorm * 10))
+    for _ in range(3):
+        R, p = P.exp6(_twist(rng, np.pi - delta, tnorm))
+        _assert_exp6_reproduces(mpmath, R, p, (delta, tnorm))
+
+
+@pytest.mark.parametrize("tnorm", TRANSLATIONS)
+@pytest.mark.parametrize("axis", [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (0, -1, 1), (1, 2, -3)])
+def test_numpy_log6_at_pi_exactly_inverts_mpmath_exp6(axis, tnorm):
+    """theta = pi: R = 2 a a^T - I, the axis' sign is free; exp6 of the answer must still be the input"""
+    mpmath = _mp()
+    a = np.asarray(axis, dtype=float) / np.linalg.norm(axis)
+    R = 2.0 * np.outer(a, a) - np.eye(3)
+    rng = np.random.default_rng(sum(axis) + 17)
+    v = rng.normal(size=3)
+    p = tnorm * v / np.linalg.norm(v)
+    w = P.log6(R, p)[3:]
+    assert abs(np.linalg.norm(w) - np.pi) <= 1e-15 * np.pi and abs(abs(w @ a) - np.pi) <= 1e-14
+    _assert_exp6_reproduces(mpmath, R, p, (axis, tnorm))
+
+
 def test_numpy_fk_matches_oracle_placements():
     """the tests' FK agrees with the CPU oracle's data.oMi (one more independent restatement)"""
     from oracle import ref

@@ -75,7 +75,19 @@ def test_forward_kinematics_matches_numpy(k):
 
 
 # ---- 2. the device log6 -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", ["random", "near_identity", "near_pi"])
+# the branch switches of pose_log3 (series below theta = 1e-4, symmetric-part axis below cos theta = -0.8) and pose_log6 (series of
+# beta below theta = 1e-3), both sides of each; pi approached and met (the numpy log6 is pinned to mpmath at these: test_pose_abi)
+EDGE_THETAS = [1e-9, 1e-4 * (1 - 1e-3), 1e-4 * (1 + 1e-3), 1e-3 * (1 - 1e-3), 1e-3 * (1 + 1e-3), np.arccos(-0.8) - 1e-6,
+               np.arccos(-0.8) + 1e-6, np.pi - 1e-3, np.pi - 1e-6, np.pi - 1e-9, np.pi - 1e-12]
+EDGE_AXES = [(1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 2, -3)]
+EDGE_TRANSLATIONS = [1e-9, 1e3]
+# |dw| <= EDGE_REL theta + EDGE_ABS, |d nu| <= EDGE_REL |nu| + EDGE_ABS.  The floor covers what the device's and numpy's FK leave in
+# oMi^-1 oMdes; measured on an MI355X: |dw| <= 2.4e-16 below theta = 2e-3, |dw| / theta <= 4.5e-16 above.  A wrong theta^2 / 6 term
+# in the theta -> 0 series changes w by theta^3 / 6 = 1.7e-13 at theta = 1e-4, which an absolute bound of 1e-10 does not see.
+EDGE_REL, EDGE_ABS = 1e-12, 2e-15
+
+
+@pytest.mark.parametrize("case", ["random", "near_identity", "near_pi", "edges", "pi_exactly"])
 def test_err_matches_numpy_log6(case):
     model = loik_amd.builtin_model("talos32")
     links = _links(model, 1)
@@ -84,6 +96,7 @@ def test_err_matches_numpy_log6(case):
     q = model.random_configurations(rng, B)
     R, t = P.fk(model, q, links[0])
     tg = np.empty((B, 1, 12))
+    theta = np.empty(B)
     for b in range(B):
         a = rng.normal(size=3)
         a /= np.linalg.norm(a)
@@ -91,16 +104,42 @@ def test_err_matches_numpy_log6(case):
             nu = np.r_[rng.normal(size=3), rng.uniform(0, np.pi) * a]
         elif case == "near_identity":
             nu = np.r_[1e-3 * rng.normal(size=3), rng.uniform(0, 1e-7) * a]
-        else:
+        elif case == "near_pi":
             nu = np.r_[rng.normal(size=3), (np.pi - rng.uniform(0, 1e-6)) * a]
+        else:
+            th = np.pi if case == "pi_exactly" else EDGE_THETAS[b % len(EDGE_THETAS)]
+            if b % 3 == 0:
+                a = np.asarray(EDGE_AXES[(b // 3) % len(EDGE_AXES)], dtype=float)
+                a /= np.linalg.norm(a)
+            v = rng.normal(size=3)
+            nu = np.r_[EDGE_TRANSLATIONS[(b // 2) % 2] * v / np.linalg.norm(v), th * a]
+        theta[b] = np.linalg.norm(nu[3:])
         Rd, pd = P.exp6(nu)
+        if case == "pi_exactly":
+            Rd = 2.0 * np.outer(a, a) - np.eye(3)
         tg[b, 0] = np.r_[(R[b] @ Rd).ravel(), t[b] + R[b] @ pd]
     s, _ = _handle(model, B, links, q)
     out = s.SolvePose(tg, max_steps=0)
-    want = P.pose_errors(model, q, links, tg)
-    assert np.max(np.abs(out["err"] - want)) < 1e-10, np.max(np.abs(out["err"] - want))
-    assert not out["steps"].any()
     s.close()
+    assert not out["steps"].any()
+    want = P.pose_errors(model, q, links, tg)
+    got = out["err"]
+    if case == "pi_exactly":   # (the sign of the axis is free at pi: compare the placements exp6 gives back)
+        for b in range(B):
+            (Rg, pg), (Rw, pw) = P.exp6(got[b, 0]), P.exp6(want[b, 0])
+            assert np.max(np.abs(Rg - Rw)) < 1e-10 and np.max(np.abs(pg - pw)) < 1e-10, b
+            assert abs(np.linalg.norm(got[b, 0, 3:]) - np.pi) < 1e-7
+        return
+    assert np.max(np.abs(got - want)) < 1e-10, np.max(np.abs(got - want))
+    if case == "edges":
+        dw = np.abs(got[:, 0, 3:] - want[:, 0, 3:]).max(axis=1)
+        dnu = np.abs(got[:, 0] - want[:, 0]).max(axis=1)
+        nrm = np.linalg.norm(want[:, 0], axis=1)
+        small = theta < 2e-3
+        print("log6 edges: max |dw| = %.3e below theta = 2e-3, max |dw| / theta = %.3e above; max |dnu| / |nu| = %.3e"
+              % (dw[small].max(), (dw / theta)[~small].max(), (dnu / nrm).max()))
+        assert np.all(dw <= EDGE_REL * theta + EDGE_ABS), (theta[np.argmax(dw - EDGE_REL * theta)], dw.max())
+        assert np.all(dnu <= EDGE_REL * nrm + EDGE_ABS), (dnu / nrm).max()
 
 
 # ---- 3. step by step against the CPU oracle ------------------------------------------------------------------------------------
