@@ -351,3 +351,27 @@ def composite_tree(seed, nb, which, kinds=None):
                 subs.append((t, a, P))
         comp[i] = subs
     return loik_amd.Model(m.parents, jt, m.axis, m.placement, composite=comp, name="composite_tree_%d_%d" % (seed, nb))
+
+
+# ---- single precision (precision = F32: the `float` instantiation of the device kernels) ------------------------------------------------
+U32 = 2.0 ** -24   # unit roundoff of IEEE binary32
+
+
+def f32_exact(wl, keys=("q", "H_ref", "v_ref", "Ais", "bis", "lb", "ub")):
+    """a copy of the workload whose inputs are float32 numbers (rounded, widened back to float64): an fp32 handle's tiles hold them
+    exactly, so the fp64 oracle given the same arrays solves the problem the device solves, and what is left between the two is the
+    device's own fp32 arithmetic"""
+    out = dict(wl)
+    for k in keys:
+        out[k] = np.asarray(wl[k], dtype=np.float64).astype(np.float32).astype(np.float64)
+    return out
+
+
+def normwise_error(x32, x64, floor):
+    """per instance (first axis): ||x32 - x64||_inf / max(||x64||_inf, floor) over the other axes"""
+    a = np.asarray(x32, dtype=float).reshape(len(x32), -1)
+    b = np.asarray(x64, dtype=float).reshape(len(x64), -1)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    if a.shape[1] == 0:
+        return np.zeros(a.shape[0])
+    return np.abs(a - b).max(axis=1) / np.maximum(np.abs(b).max(axis=1), floor)
