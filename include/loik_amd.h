@@ -67,7 +67,17 @@ enum { LOIKB_F64 = 0, LOIKB_F32 = 1 };
 
 /* option flags */
 enum {
-  LOIKB_OPT_FIXED_ITERS = 1, /* run exactly max_iter-1 ADMM iterations, mu frozen, no stopping logic       */
+  LOIKB_OPT_FIXED_ITERS = 1, /* run exactly max_iter-1 ADMM iterations (none for max_iter <= 1), mu frozen at the
+                                 solve's start value (MAXEIGENVALUE: the spectral one), no stopping logic -- on every
+                                 engine and route, logging = 1 and the engine of last resort (k_pass_solve) included.
+                                 Afterwards every instance has iter = max_iter-1, converged = primal_infeasible = 0,
+                                 tail_solve_iter = 0, and counts in loikb_stats::n_unfinished (= the batch);
+                                 loikb_stats::instance_iterations = batch x (max_iter-1).  What only the stopping
+                                 logic sets is not evaluated and keeps the value the solve's reset gave it, 0:
+                                 tol_primal, tol_dual and CheckFeasibility's certificate (delta_y_qp_inf_norm,
+                                 A_qp_T_delta_y_qp_inf_norm, ub_qp_T_delta_y_qp_plus, lb_qp_T_delta_y_qp_minus,
+                                 primal_infeasibility_cond_1, primal_infeasibility_cond_2).  Any mu_update_strat is
+                                 accepted: none is applied.                                                     */
   LOIKB_OPT_NO_H_CACHE = 2,  /* recompute H_i/UDinv/Dinv every iteration like upstream (default: reuse them
                                  while mu is unchanged -- bit-identical results, fewer HBM bytes)            */
   LOIKB_OPT_OWN_STREAM = 8,  /* the handle creates its own non-blocking HIP stream instead of launching on the null stream:

@@ -1656,6 +1656,20 @@ __global__ void k_count_unfinished(char* tiles, Layout L, int B, unsigned int* _
   if ((threadIdx.x & (WAVE - 1)) == 0 && m) atomicAdd(counter, (unsigned int)__popcll(m));
 }
 
+// iterations of the home set's instances summed (every solve starts from iter = 0: the iterations this solve ran)
+template <typename T>
+__global__ void k_sum_iters(char* tiles, Layout L, int B, unsigned long long* __restrict__ sum)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long it = 0;
+  if (b < B) {
+    char* sp = lane_ptr<T>(tiles, L, b);
+    it = (unsigned long long)ldp<T>(sp + (size_t)L.off_s * pair_bytes<T>(), SP_BI).y;
+  }
+  for (int off = WAVE / 2; off > 0; off >>= 1) it += __shfl_down(it, off);
+  if ((threadIdx.x & (WAVE - 1)) == 0 && it) atomicAdd(sum, it);
+}
+
 // move the live instances of set `src` (n_src slots) to the first slots of set `dst`; finished ones go home.
 // dst < 0: end of the solve, everything still in a work set goes home.
 template <typename T>
@@ -1816,11 +1830,26 @@ void plan_engines(loikb_solver_impl* S)
   S->plan = pl;
 }
 
-// a robot k_solve cannot take (EnginePlan::solve_ok): does this solve go to the on-chip engines whole?  (run_chunk's direct_tail)
-static bool bushy_goes_on_chip(const loikb_solver_impl* S)
+// the hand-over threshold of the tail kernels for the whole batch: the caller's tail_max_instances when > 0, else the plan's
+// (run_tail scales it by a chunk's share of the batch)
+static int batch_tail_max(const loikb_solver_impl* S)
+{
+  return S->opt.tail_max_instances > 0 ? S->opt.tail_max_instances : S->plan.tail_max;
+}
+
+// does a chunk of n instances go to the on-chip engines from the first iteration (run_chunk's direct_tail)?  tail_max: the chunk's
+// share of batch_tail_max.  Also the route of a robot k_solve cannot take (EnginePlan::solve_ok): where this is false, k_pass_solve.
+static bool direct_tail_of(const loikb_solver_impl* S, int n, int tail_max)
 {
   return S->nb <= WAVE && S->opt.tail_max_instances >= 0 && S->opt.max_launch_iters <= 0 &&
-         !(S->opt.flags & (LOIKB_OPT_NO_COMPACTION | LOIKB_OPT_NO_H_CACHE)) && S->B <= S->plan.tail_max && S->tune.direct_tail;
+         !(S->opt.flags & (LOIKB_OPT_NO_COMPACTION | LOIKB_OPT_NO_H_CACHE)) && n <= tail_max && S->tune.direct_tail;
+}
+
+// a robot k_solve cannot take (EnginePlan::solve_ok): does this solve go to the on-chip engines whole?  (one chunk: run_chunk's
+// direct_tail with the same threshold; a tail_max_instances below the batch is one of k_solve's own controls -> k_pass_solve)
+static bool bushy_goes_on_chip(const loikb_solver_impl* S)
+{
+  return direct_tail_of(S, S->B, std::max(1, batch_tail_max(S)));
 }
 
 template <typename T>
@@ -2436,8 +2465,7 @@ int run_chunk(loikb_solver_impl* S, Chunk* C)
   const double share = (double)C->B / (double)S->B;
   // (with the lean tail kernel, whole batches up to 2^20 instances go to it directly: it is as fast as the solve kernel's
   //  bulk phase and has neither ragged tiles nor compaction; without it the hand-over is at 32768 live instances)
-  const int tail_max = std::max(1, (int)((S->opt.tail_max_instances > 0 ? S->opt.tail_max_instances
-                                                                         : S->plan.tail_max) * share));
+  const int tail_max = std::max(1, (int)(batch_tail_max(S) * share));
   const bool trace = S->tune.trace;
   // a team of wavefronts per tile walks independent chains of the tree concurrently: a sweep costs the tree's
   // critical path instead of nb joint visits, and four wavefronts keep four times the loads of a tile in flight.
@@ -2470,9 +2498,7 @@ int run_chunk(loikb_solver_impl* S, Chunk* C)
   // A batch that is below the hand-over threshold from the start never fills the machine with one instance per lane:
   // it goes to the tail kernel (a lane group per instance, 12 us instead of 30-55 us per iteration) for the whole
   // solve.  (Not when the caller fixed the launch length or asked for the solve kernel's bit-exact behaviour.)
-  const bool direct_tail = S->nb <= WAVE && S->opt.tail_max_instances >= 0 && S->opt.max_launch_iters <= 0 &&
-                           !(S->opt.flags & (LOIKB_OPT_NO_COMPACTION | LOIKB_OPT_NO_H_CACHE)) && C->B <= tail_max &&
-                           S->tune.direct_tail;
+  const bool direct_tail = direct_tail_of(S, C->B, tail_max);
   if (!S->plan.solve_ok && !direct_tail) {   // (run_main_loop sends such a solve to k_pass_solve: never here)
     g_last_error = "internal: a tree too bushy for k_solve's LDS slots reached the streaming engine"; return LOIKB_ERR_STATE;
   }
@@ -3236,6 +3262,7 @@ static PassParams pass_params(const loikb_solver_impl* S)
   P.max_iter = S->opt.max_iter;
   P.mu_osqp = S->opt.mu_update_strat == LOIKB_MU_OSQP;
   P.a_shared = S->a_shared; P.bnd_shared = S->bnd_shared;
+  P.fixed = (S->opt.flags & LOIKB_OPT_FIXED_ITERS) ? 1 : 0;
   return P;
 }
 
@@ -3287,8 +3314,8 @@ static int finish_logged(loikb_solver_impl* S, const PassParams& P);
 // any; k_flat: h I), one chunk, the batch goes to it directly
 static bool logged_on_flat(const loikb_solver_impl* S)
 {
-  return S->opt.logging && !S->f32 && flat_applicable(S) && S->plan.nchunks == 1 && S->B >= 64 && S->B <= S->plan.tail_max &&
-         !(S->opt.flags & (LOIKB_OPT_NO_H_CACHE | LOIKB_OPT_FIXED_ITERS));
+  return S->opt.logging && !S->f32 && flat_applicable(S) && S->plan.nchunks == 1 && S->B >= 64 &&
+         direct_tail_of(S, S->B, std::max(1, batch_tail_max(S))) && !(S->opt.flags & (LOIKB_OPT_NO_H_CACHE | LOIKB_OPT_FIXED_ITERS));
 }
 
 // Solve with logging_ = true: SolverInfo lists filled.  On the flat engine when the solve qualifies (logged_on_flat), else the
@@ -3385,14 +3412,27 @@ static int finish_logged(loikb_solver_impl* S, const PassParams& P)
   S->stats.launches = 1;
   S->stats.kernel_ms = ms; S->stats.total_ms = ms;
   {
+    // n_unfinished, and instance_iterations as the other engines count it: the iterations of every instance, tail solve included
     Chunk* C0 = &S->chunks[0];
+    int rc;
+    if ((rc = ensure_stage(S, sizeof(unsigned long long)))) return rc;
+    unsigned long long* d_sum = (unsigned long long*)S->d_stage;
     HIPCHK(hipMemsetAsync(C0->d_counters, 0, sizeof(unsigned int), S->stream));
-    if (S->f32) hipLaunchKernelGGL(k_count_unfinished<float>, grid1(S->B), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, C0->d_counters);
-    else hipLaunchKernelGGL(k_count_unfinished<double>, grid1(S->B), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, C0->d_counters);
+    HIPCHK(hipMemsetAsync(d_sum, 0, sizeof(unsigned long long), S->stream));
+    if (S->f32) {
+      hipLaunchKernelGGL(k_count_unfinished<float>, grid1(S->B), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, C0->d_counters);
+      hipLaunchKernelGGL(k_sum_iters<float>, grid1(S->B), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, d_sum);
+    } else {
+      hipLaunchKernelGGL(k_count_unfinished<double>, grid1(S->B), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, C0->d_counters);
+      hipLaunchKernelGGL(k_sum_iters<double>, grid1(S->B), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, d_sum);
+    }
     HIPCHK(hipGetLastError());
+    unsigned long long sum = 0;
     HIPCHK(hipMemcpyAsync(C0->h_counters, C0->d_counters, sizeof(unsigned int), hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(&sum, d_sum, sizeof(unsigned long long), hipMemcpyDeviceToHost, S->stream));
     HIPCHK(hipStreamSynchronize(S->stream));
     S->stats.n_unfinished = (int)C0->h_counters[0];
+    S->stats.instance_iterations = sum;
   }
   S->have_log = true;
   return LOIKB_OK;

@@ -59,6 +59,7 @@ struct PassParams {
   double Hv_inf_norm;
   double rho, mu0, mu_scale, tol_abs, tol_rel, tol_primal_inf, tol_tail_solve;
   int max_iter, mu_osqp, a_shared, bnd_shared;
+  int fixed;  // LOIKB_OPT_FIXED_ITERS: exactly max_iter - 1 iteration bodies, no stopping logic, mu frozen (k_pass_solve)
 };
 
 // ---- 6-D helpers on plain arrays (Pinocchio conventions) ---------------------------------------------
@@ -489,6 +490,9 @@ __global__ void k_pass_solve(PassLayout L, PassParams P, const JointDesc* __rest
       for (int l = 0; l < LOG_NLIST; ++l) log[((size_t)l * L.B + b) * rows_cap + n] = v[l];
       ++n;
     }
+    // fixed iterations (the other engines' MODE_FIXED_ITERS): no CheckConvergence / CheckFeasibility / tail solve / UpdateMu -- the
+    // converged and infeasible flags stay as loaded (clear after the solve's reset), the scalars those tests set keep their values
+    if (P.fixed) continue;
     pass_one(PASS_CHECK_CONV, L, P, jd, cslot_of, s);
     if (i > 1) pass_one(PASS_CHECK_FEAS, L, P, jd, cslot_of, s);
     if (sc[PS_CONVERGED] != 0.0) break;

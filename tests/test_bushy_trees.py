@@ -134,3 +134,62 @@ def test_bushy_tree_with_options_that_ask_for_k_solve_takes_the_engine_of_last_r
         assert "k_pass_solve" in s.plan(), s.plan()
         assert_end_to_end(fetch_end_to_end(s), out, prm, same_frac=0.99, ztol=2e-10, what=str(kw))
         s.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["42_joints_10_children", "100_joints_9_children"])
+def test_bushy_tree_routing_sweep(case):
+    """Every combination of k_solve's own controls (tail_max_instances, max_launch_iters) and the flags that keep a solve off the on-chip
+    engines, on a batch of 130: the solve returns OK on the engine plan() names -- the on-chip engines whole only where the batch goes to
+    them directly (tail_max_instances 0 or >= B, no launch length, neither flag; a tail_max_instances below B is one of k_solve's controls),
+    k_pass_solve otherwise and always above 64 joints -- and matches the oracle end to end."""
+    c = CASES[case]
+    model = bushy_tree(77, c["nb"], c["hub"], c["children"], c["depth_first"])
+    B = 130
+    wl = multi_task_batch(model, B, [model.njoints - 1], 17, nu_scale=0.3)
+    args = (wl["q"], wl["H_ref"], wl["v_ref"], wl["c_ids"], wl["Ais"], wl["bis"], wl["lb"], wl["ub"])
+    prm = dict(FIXTURE, num_eq_c=1, max_iter=200, tol_abs=1e-6, tol_rel=0.0)
+    out = ref.solve_batch(model, *args, nthreads=8, want_nu=True, **prm)
+    for tmi in (-1, 0, 1, 50, 130, 1 << 20):
+        for mli in (0, 7):
+            for flags in (0, loik_amd.capi.OPT_NO_COMPACTION, loik_amd.capi.OPT_NO_H_CACHE):
+                what = "%s tail_max_instances=%d max_launch_iters=%d flags=%d" % (case, tmi, mli, flags)
+                s = loik_amd.BatchedLoik(model, B, **prm, tail_max_instances=tmi, max_launch_iters=mli, flags=flags)
+                s.Solve(*args)
+                on_chip = c["engine"] == "flat" and (tmi == 0 or tmi >= B) and mli == 0 and flags == 0
+                st = s.stats()
+                _check_engine(s, st, "flat" if on_chip else "pass", B)
+                assert st["instance_iterations"] == int(s.get("iter").sum()), (what, st["instance_iterations"])
+                assert ("whole batches go to the on-chip engines" in s.plan()) == on_chip, (what, s.plan())
+                assert_end_to_end(fetch_end_to_end(s), out, prm, same_frac=0.99, ztol=2e-10, what=what)
+                s.close()
+
+
+@pytest.mark.gpu
+def test_logged_bushy_tree_fills_the_lists_on_every_route():
+    """logging = 1 on a tree too bushy for k_solve: the flat engine writes the SolverInfo lists only where the batch goes to it whole (the
+    predicate of run_chunk's direct hand-over); k_solve's own controls send the logged solve to k_pass_solve, which writes them too --
+    never an OK with empty lists.  Rows = main-loop iterations of each instance; end to end against the oracle."""
+    model = bushy_tree(77, 42, 2, 10)
+    B = 130
+    wl = multi_task_batch(model, B, [model.njoints - 1], 23, nu_scale=0.3)
+    args = (wl["q"], wl["H_ref"], wl["v_ref"], wl["c_ids"], wl["Ais"], wl["bis"], wl["lb"], wl["ub"])
+    prm = dict(FIXTURE, num_eq_c=1, max_iter=200, tol_abs=1e-6, tol_rel=0.0)
+    out = ref.solve_batch(model, *args, nthreads=8, want_nu=True, **prm)
+    for kw in (dict(), dict(tail_max_instances=B), dict(tail_max_instances=-1), dict(tail_max_instances=1), dict(tail_max_instances=50),
+               dict(max_launch_iters=7)):
+        s = loik_amd.BatchedLoik(model, B, logging=True, **prm, **kw)
+        s.Solve(*args)
+        on_flat = kw in (dict(), dict(tail_max_instances=B))
+        assert ("the flat engine writes the SolverInfo lists" in s.plan()) == on_flat, (kw, s.plan())
+        st = s.stats()
+        assert (st["flat_launches"] >= 1) == on_flat, (kw, st)
+        info = s.solver_info()
+        it, tail = s.get("iter"), s.get("tail_solve_iter")
+        assert info["truncated_instances"] == 0, kw
+        assert np.array_equal(info["rows"], it - tail) and info["rows"].min() >= 1, (kw, info["rows"][:10], it[:10])
+        assert st["instance_iterations"] == int(it.sum()), (kw, st["instance_iterations"], int(it.sum()))
+        for b in range(0, B, 19):
+            assert np.all(info["mu_list"][b, :info["rows"][b]] > 0) and np.all(info["primal_residual_list"][b, info["rows"][b]:] == 0), (kw, b)
+        assert_end_to_end(fetch_end_to_end(s), out, prm, same_frac=0.99, ztol=2e-10, what="logged %s" % kw)
+        s.close()
