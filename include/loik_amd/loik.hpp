@@ -17,6 +17,7 @@
 
 #include "../loik_amd.h"
 #include "../loik_amd_pose.h"
+#include "../loik_amd_limits.h"
 
 #include <array>
 #include <map>
@@ -374,6 +375,29 @@ public:
     std::vector<SE3> M((std::size_t)batch_ * l.size());
     for (std::size_t i = 0; i < M.size(); ++i) std::copy(out.begin() + 12 * i, out.begin() + 12 * (i + 1), M[i].begin());
     return M;
+  }
+  // ---- joint position limits of the pose loop, the velocity-box update (include/loik_amd_limits.h)
+  // q_lo, q_hi: [nv], -inf / +inf = no limit on that side; honoured by every later SolvePose.  clearJointLimits(): as if never set.
+  void setJointLimits(const DVec& q_lo, const DVec& q_hi)
+  {
+    if (q_lo.size() != q_hi.size()) throw std::runtime_error("loik_amd: q_lo and q_hi differ in size");
+    check(loikb_set_joint_limits(h_, q_lo.data(), q_hi.data(), (int)q_lo.size()));
+  }
+  void clearJointLimits() { check(loikb_set_joint_limits(h_, nullptr, nullptr, 0)); }
+  // UpdateIneqConstraints(lb, ub) of the problem formulation (ik-id-description-optimized.hpp:325-339): [nv] = one box for the batch,
+  // [batch][nv] = one per instance; any other size is the library's LOIKB_ERR_INEQ_DIM
+  void UpdateIneqConstraints(const DVec& lb, const DVec& ub)
+  {
+    if (lb.size() != ub.size()) throw std::runtime_error("loik_amd: lb and ub differ in size");
+    const bool per_inst = batch_ > 1 && lb.size() == (std::size_t)batch_ * model_.nv;
+    check(loikb_update_ineq_constraints(h_, lb.data(), ub.data(), per_inst ? model_.nv : (int)lb.size(), per_inst ? 0 : LOIKB_BOUNDS_SHARED));
+  }
+  // [batch][nv] LOIKB_LIMIT_LOWER / LOIKB_LIMIT_UPPER bits of the last SolvePose with limits (throws when it ran without)
+  std::vector<int> PoseLimitFlags() const
+  {
+    std::vector<int> f((std::size_t)batch_ * model_.nv);
+    check(loikb_pose_get_limit_flags(h_, f.data(), 0));
+    return f;
   }
   // the resident configurations, [batch][nq]
   DVec q_resident() const

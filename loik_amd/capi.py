@@ -96,6 +96,12 @@ POSE_F_STEPS, POSE_F_STATUS, POSE_F_ERR, POSE_F_TIMING = 0, 1, 2, 3
 POSE_ST_REACHED, POSE_ST_NOT_CONVERGED, POSE_ST_INFEASIBLE, POSE_ST_STOPPED = 1, 2, 4, 8
 
 
+# include/loik_amd_limits.h: joint position limits for the pose loop, the velocity-box update; its own header and version again
+LIMITS_ABI_VERSION = 1
+LIMITS_SYMBOLS = ["loikb_limits_version", "loikb_set_joint_limits", "loikb_update_ineq_constraints", "loikb_pose_get_limit_flags"]
+LIMIT_LOWER, LIMIT_UPPER = 1, 2
+
+
 class PoseParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
 
@@ -159,6 +165,9 @@ def lib():
     L.loikb_solve_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseParams)]
     L.loikb_forward_kinematics.argtypes = [C.c_void_p, _ip, C.c_int, C.c_void_p, C.c_int]
     L.loikb_pose_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_set_joint_limits.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
+    L.loikb_update_ineq_constraints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    L.loikb_pose_get_limit_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -416,6 +425,7 @@ class BatchedLoik:
         h = C.c_void_p()
         _check(self.L.loikb_create(C.byref(self._desc), C.byref(self.opts), C.byref(h)))
         self.h = h
+        self._limits = False   # set_joint_limits left a finite limit on the handle: SolvePose returns limit_flags
 
     def close(self):
         if getattr(self, "h", None):
@@ -435,6 +445,45 @@ class BatchedLoik:
     def SolveInit(self, q, H_ref, v_ref, active_task_constraint_ids, Ais, bis, lb, ub):
         keep, args = self._raw_args(q, H_ref, v_ref, active_task_constraint_ids, Ais, bis, lb, ub)
         _check(self.L.loikb_solve_init(*args))
+
+    def UpdateIneqConstraints(self, lb, ub):
+        """UpdateIneqConstraints(lb, ub) of the problem formulation (hpp:325-339; loikb_update_ineq_constraints): replaces the
+        velocity box SolveInit set and nothing else.  [nv] = one box for the batch, [batch][nv] (host or device) = per instance."""
+        nv = self.model.nv
+        nbound = nv
+        if not (isinstance(lb, int) or hasattr(lb, "data_ptr")):
+            n = int(np.asarray(lb).size)
+            if n != nv and n != nv * self.batch:
+                if int(np.asarray(ub).size) != n:
+                    raise ValueError("lb and ub differ in size")
+                nbound = n   # (the library answers with the reference's error)
+        lp, ld, lf, k0 = self._prep(lb, "lb", nbound, BOUNDS_SHARED)
+        up, ud, uf, k1 = self._prep(ub, "ub", nbound, BOUNDS_SHARED)
+        if lf != uf or bool(ld) != bool(ud):
+            raise ValueError("lb and ub must both be shared ([nv]) or both be per instance ([batch][nv]), both host or both device")
+        _check(self.L.loikb_update_ineq_constraints(self.h, lp, up, nbound, lf | (IN_DEVICE if ld and not lf else 0)))
+
+    def set_joint_limits(self, q_lo, q_hi):
+        """joint position limits [nv] (idx_v order, -inf / +inf = none) honoured by every later SolvePose (loikb_set_joint_limits);
+        None, None clears them.  Only DoFs whose coordinate a plain sum advances can carry a finite limit."""
+        if q_lo is None and q_hi is None:
+            _check(self.L.loikb_set_joint_limits(self.h, None, None, 0))
+            self._limits = False
+            return
+        lo = None if q_lo is None else _f64(q_lo).reshape(-1)
+        hi = None if q_hi is None else _f64(q_hi).reshape(-1)
+        n = int((lo if lo is not None else hi).size)
+        if lo is not None and hi is not None and lo.size != hi.size:
+            raise ValueError("q_lo and q_hi differ in size")
+        _check(self.L.loikb_set_joint_limits(self.h, None if lo is None else lo.ctypes.data_as(_dp),
+                                             None if hi is None else hi.ctypes.data_as(_dp), n))
+        self._limits = bool(np.isfinite(lo).any() or np.isfinite(hi).any())
+
+    def pose_limit_flags(self):
+        """[B][nv] int of the last SolvePose with limits: LIMIT_LOWER / LIMIT_UPPER bits (loikb_pose_get_limit_flags)"""
+        out = np.empty((self.batch, self.model.nv), dtype=np.int32)
+        _check(self.L.loikb_pose_get_limit_flags(self.h, out.ctypes.data_as(C.c_void_p), 0))
+        return out
 
     def _prep(self, a, what, per, shared_flag):
         """One per-instance input: (void*, is_device, flag).  The C-ABI takes bare pointers without lengths, so the sizes are
@@ -609,7 +658,8 @@ class BatchedLoik:
         targets: one placement per active constraint (active_task_constraint_ids order), [B][nc][4][4] / [B][nc][12], or
         [nc][4][4] / [nc][12] (/ [4][4] / [12] for one constraint) shared by the batch; a device tensor is [B][nc][12] or
         [nc][12] by its numel.  q: None = the resident configurations, else [B][nq] replaces them first.
-        Returns dict(reached [B] bool, steps [B], err [B][nc][6] = e_c of the final q, status [B] POSE_ST_* bits)."""
+        Returns dict(reached [B] bool, steps [B], err [B][nc][6] = e_c of the final q, status [B] POSE_ST_* bits), and with joint
+        position limits on the handle (set_joint_limits) limit_flags [B][nv]."""
         B, nc = self.batch, int(self.L.loikb_num_eq_c(self.h))
         flags, keep = 0, []
         if isinstance(targets, int) or (hasattr(targets, "data_ptr") and getattr(targets, "is_cuda", False)):
@@ -652,7 +702,10 @@ class BatchedLoik:
         _check(self.L.loikb_pose_get(self.h, POSE_F_STATUS, status.ctypes.data_as(C.c_void_p), 0))
         _check(self.L.loikb_pose_get(self.h, POSE_F_STEPS, steps.ctypes.data_as(C.c_void_p), 0))
         _check(self.L.loikb_pose_get(self.h, POSE_F_ERR, err.ctypes.data_as(C.c_void_p), 0))
-        return dict(reached=(status & POSE_ST_REACHED) != 0, steps=steps, err=err, status=status)
+        out = dict(reached=(status & POSE_ST_REACHED) != 0, steps=steps, err=err, status=status)
+        if self._limits:
+            out["limit_flags"] = self.pose_limit_flags()
+        return out
 
     def pose_timing(self):
         """of the last SolvePose: dict(steps, total_ms, solve_ms, other_ms) -- wall clock; other = re-target, b, integrate, read-backs"""

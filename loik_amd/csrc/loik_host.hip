@@ -31,6 +31,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 
 #include "../../include/loik_amd.h"
 #include "../../include/loik_amd_pose.h"
+#include "../../include/loik_amd_limits.h"
 
 #include <algorithm>
 #include <chrono>
@@ -164,6 +165,9 @@ struct loikb_solver_impl {
   // M(q) of joint i (the last / first joint of its chain; both i's own image for a 1-DoF joint)
   int ext_nj = 0;
   std::vector<int> link_of, first_of;
+  // per DoF (device joint - 1), for loikb_set_joint_limits: where its configuration coordinate sits in a row of q when
+  // loikb_integrate advances it by a plain sum (else -1), the caller's joint it belongs to and its elementary joint type
+  std::vector<int> lim_q, dof_ext, dof_jt;
   int* d_link_sel = nullptr;  // [ext_nj - 1] link_of[1..] - 1 on the device (getters)
   int* d_first_sel = nullptr;
   // step schedules of the sweeps: [0] one wavefront per tile, [1] a team of wavefronts per tile
@@ -345,6 +349,14 @@ struct loikb_solver_impl {
     unsigned int* d_count = nullptr;   // [2] instances still running, target rotations rejected
     int nc = 0;                        // constraints of the last pose solve (0: none yet)
     double timing[4] = {0, 0, 0, 0};   // LOIKB_POSE_F_TIMING
+    // joint position limits (loik_amd_limits.h)
+    bool have_limits = false;          // loikb_set_joint_limits left at least one finite limit on the handle
+    bool flags_valid = false;          // the last pose solve ran with limits: d_lflags is its result
+    std::vector<PoseLimit> lim;        // [nb] host copy of d_lim
+    PoseLimit* d_lim = nullptr;        // [nb]
+    int* d_lflags = nullptr;           // [B][nv] limit flags
+    unsigned char* d_inrange = nullptr;  // [nb][B] the coordinate was in range before the step
+    double2* d_box = nullptr;          // [nb][B] the per-instance base box while a pose solve with limits runs
   } pose;
 };
 using Chunk = loikb_solver_impl::Chunk;
@@ -657,6 +669,7 @@ int build_schedule(loikb_solver_impl* S, const loikb_model_desc* m)
   S->jtype.assign(1, LOIKB_J_NONE);
   S->idx_q.assign(1, 0);
   S->jd.assign(1, JointDesc{});
+  S->lim_q.clear(); S->dof_ext.clear(); S->dof_jt.clear();
   for (int i = 1; i < enj; ++i) {
     // the ELEMENTARY joints of joint i: itself, or the sub-joints of a JointModelComposite -- literally the chain of its
     // sub-joints, each with its own placement and coordinates (a multi-DoF sub-joint expands into its own chain below); the
@@ -738,6 +751,10 @@ int build_schedule(loikb_solver_impl* S, const loikb_model_desc* m)
         S->jtype.push_back(sub);
         S->idx_q.push_back(jt == LOIKB_J_SPHERICAL_ZYX ? elem_q + k : (k == 0 ? elem_q : 0));
         S->jd.push_back(d);
+        const bool plain_sum = jt == LOIKB_J_SPHERICAL_ZYX || jt == LOIKB_J_TRANSLATION || (n == 1 && !(flags & JF_CS_DIRECT));
+        S->lim_q.push_back(plain_sum ? elem_q + k : -1);
+        S->dof_ext.push_back(i);
+        S->dof_jt.push_back(jt);
       }
       elem_q += jt_nq(jt);
     }
@@ -1569,6 +1586,24 @@ int validate_problem(const loikb_solver_impl* S, const double* H_ref, const int*
   return LOIKB_OK;
 }
 
+// UpdateIneqConstraints (hpp:325-339): the velocity box, shared [nv] (host) or per instance [B][nv], and the sharing mode
+int update_ineq(loikb_solver_impl* S, const double* lb, const double* ub, int in_flags)
+{
+  const bool dev = in_flags & LOIKB_IN_DEVICE;
+  int rc;
+  S->bnd_shared = in_flags & LOIKB_BOUNDS_SHARED;
+  if (S->bnd_shared) {
+    if ((rc = upload_uni(S, S->nc * 57, lb, S->nv))) return rc;
+    if ((rc = upload_uni(S, S->nc * 57 + S->nb, ub, S->nv))) return rc;
+  } else {
+    std::vector<int> rl(S->nb), ru(S->nb);
+    for (int j = 0; j < S->nb; ++j) { rl[j] = (j * JREC + JP_LBUB) * 2; ru[j] = rl[j] + 1; }
+    if ((rc = upload_rows(S, lb, rl, dev, false))) return rc;
+    if ((rc = upload_rows(S, ub, ru, dev, false))) return rc;
+  }
+  return LOIKB_OK;
+}
+
 int set_problem(loikb_solver_impl* S, const double* H_ref, const double* v_ref, const int* c_ids, int nc,
                 const double* Ais, const double* bis, const double* lb, const double* ub, int nbound, int in_flags)
 {
@@ -1602,16 +1637,7 @@ int set_problem(loikb_solver_impl* S, const double* H_ref, const double* v_ref, 
     S->tab_bcast = true;
   }
   // UpdateIneqConstraints
-  S->bnd_shared = in_flags & LOIKB_BOUNDS_SHARED;
-  if (S->bnd_shared) {
-    if ((rc = upload_uni(S, S->nc * 57, lb, S->nv))) return rc;
-    if ((rc = upload_uni(S, S->nc * 57 + S->nb, ub, S->nv))) return rc;
-  } else {
-    std::vector<int> rl(S->nb), ru(S->nb);
-    for (int j = 0; j < S->nb; ++j) { rl[j] = (j * JREC + JP_LBUB) * 2; ru[j] = rl[j] + 1; }
-    if ((rc = upload_rows(S, lb, rl, dev, false))) return rc;
-    if ((rc = upload_rows(S, ub, ru, dev, false))) return rc;
-  }
+  if ((rc = update_ineq(S, lb, ub, in_flags))) return rc;
   // UpdateEqConstraints
   S->active_ids.assign(c_ids, c_ids + nc);
   if ((rc = bind_constraint_slots(S))) return rc;
@@ -4022,6 +4048,59 @@ static int pose_alloc(loikb_solver_impl* S)
   return LOIKB_OK;
 }
 
+// ---- joint position limits (include/loik_amd_limits.h) --------------------------------------------------------------------
+// buffers of a pose solve with limits; the [nb][B] copy of the base box only for a handle whose box is per instance
+static int pose_limits_alloc(loikb_solver_impl* S, bool need_box)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  const size_t n = (size_t)S->B * S->nb;
+  int rc;
+  if (!P.d_lflags && (rc = alloc_dev(S, (void**)&P.d_lflags, sizeof(int) * n))) return rc;
+  if (!P.d_inrange && (rc = alloc_dev(S, (void**)&P.d_inrange, n))) return rc;
+  if (need_box && !P.d_box && (rc = alloc_dev(S, (void**)&P.d_box, sizeof(double2) * n))) return rc;
+  return LOIKB_OK;
+}
+
+static dim3 grid_dof(const loikb_solver_impl* S) { return dim3((unsigned)((S->B + 255) / 256), (unsigned)S->nb); }
+
+// JP_LBUB of the home tiles <-> PoseState::d_box
+static int pose_box_copy(loikb_solver_impl* S, int restore)
+{
+  if (S->f32) hipLaunchKernelGGL(k_box_copy<float>, grid_dof(S), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, S->pose.d_box, restore);
+  else hipLaunchKernelGGL(k_box_copy<double>, grid_dof(S), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, S->pose.d_box, restore);
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+// The handle while a pose solve with limits runs: per-instance-box mode (every engine, the compaction's move_bounds and the
+// pass-level path read S->bnd_shared when a solve is launched: make_params in run_chunk, compact, pass_params), the base box
+// kept in the uniform buffer (shared) or in d_box (per instance).  Leaving the scope puts the base box back in force in the
+// mode it had, on every return path.
+struct PoseBoxScope {
+  loikb_solver_impl* S;
+  bool active = false, was_shared = false;
+  int enter()
+  {
+    was_shared = S->bnd_shared;
+    int rc;
+    if ((rc = pose_limits_alloc(S, !was_shared))) return rc;
+    if (!was_shared && (rc = pose_box_copy(S, 0))) return rc;
+    S->bnd_shared = false;
+    active = true;
+    return LOIKB_OK;
+  }
+  int leave()
+  {
+    if (!active) return LOIKB_OK;
+    active = false;
+    S->bnd_shared = was_shared;
+    S->pass_active = false;
+    ++S->inputs_epoch;
+    return was_shared ? LOIKB_OK : pose_box_copy(S, 1);
+  }
+  ~PoseBoxScope() { if (active) { (void)leave(); (void)hipStreamSynchronize(S->stream); } }
+};
+
 static double ms_since(std::chrono::steady_clock::time_point t0)
 {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -4100,6 +4179,12 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
   HIPCHK(hipMemsetAsync(P.d_steps, 0, sizeof(int) * B, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));   // (q, cl are the caller's / locals)
   P.nc = nc;
+  P.flags_valid = P.have_limits;
+  PoseBoxScope box{S};
+  if (P.have_limits) {
+    if ((rc = box.enter())) return rc;
+    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
+  }
   const double k = p->gain / p->dt;
   double solve_ms = 0.0;
   int steps_run = 0;
@@ -4120,6 +4205,17 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
     HIPCHK(hipMemcpyAsync(&running, P.d_count, sizeof(running), hipMemcpyDeviceToHost, S->stream));
     HIPCHK(hipStreamSynchronize(S->stream));
     if (running == 0) break;
+    if (box.active) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
+      if (S->f32)
+        hipLaunchKernelGGL(k_pose_limit_box<float>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                           p->dt, (const int*)P.d_status, box.was_shared ? (const float*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
+                           S->home.tiles, S->L, P.d_lflags, P.d_inrange);
+      else
+        hipLaunchKernelGGL(k_pose_limit_box<double>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                           p->dt, (const int*)P.d_status, box.was_shared ? (const double*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
+                           S->home.tiles, S->L, P.d_lflags, P.d_inrange);
+      HIPCHK(hipGetLastError());
+    }
     // UpdateEqConstraint(c, NULL, b_c, LOIKB_IN_DEVICE) for every active constraint, queued behind each other (the solve below
     // synchronises), then the tailored Solve on the resident q without a constraint rewrite
     S->defer_sync = true;
@@ -4137,9 +4233,15 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
       hipLaunchKernelGGL(k_pose_integrate<double>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
                          (const char*)S->home.tiles, p->dt, P.d_status);
     HIPCHK(hipGetLastError());
+    if (box.active) {
+      hipLaunchKernelGGL(k_pose_limit_clamp, grid_dof(S), dim3(256), 0, S->stream, S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                         (const unsigned char*)P.d_inrange);
+      HIPCHK(hipGetLastError());
+    }
     ++S->inputs_epoch;
     ++steps_run;
   }
+  if ((rc = box.leave())) return rc;
   HIPCHK(hipStreamSynchronize(S->stream));
   const double total = ms_since(t_call);
   P.timing[0] = steps_run; P.timing[1] = total; P.timing[2] = solve_ms; P.timing[3] = total - solve_ms;
@@ -4165,6 +4267,71 @@ int loikb_pose_get(loikb_solver* S, int field, void* out, int out_flags)
   default: g_last_error = "pose_get: unknown field"; return LOIKB_ERR_ARG;
   }
   HIPCHK(hipMemcpyAsync(out, src, bytes, to_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
+}
+
+// ---- include/loik_amd_limits.h ----------------------------------------------------------------------------------------------
+int loikb_limits_version(void) { return LOIKB_LIMITS_VERSION; }
+
+int loikb_set_joint_limits(loikb_solver* S, const double* q_lo, const double* q_hi, int n)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!q_lo && !q_hi) { P.have_limits = false; return LOIKB_OK; }
+  if (!q_lo || !q_hi) { g_last_error = "set_joint_limits: q_lo and q_hi must both be given, or both be NULL (clear)"; return LOIKB_ERR_ARG; }
+  if (n != S->nv) { g_last_error = "set_joint_limits: need one (q_lo, q_hi) pair per DoF, n == model.nv"; return LOIKB_ERR_ARG; }
+  std::vector<PoseLimit> lim(S->nb);
+  bool any = false;
+  for (int j = 0; j < n; ++j) {
+    char what[96];
+    snprintf(what, sizeof(what), "set_joint_limits: DoF %d (joint %d)", j, S->dof_ext[j]);
+    if (std::isnan(q_lo[j]) || std::isnan(q_hi[j])) { g_last_error = std::string(what) + ": a limit is NaN"; return LOIKB_ERR_ARG; }
+    if (q_lo[j] > q_hi[j]) { g_last_error = std::string(what) + ": q_lo > q_hi"; return LOIKB_ERR_ARG; }
+    const bool finite = std::isfinite(q_lo[j]) || std::isfinite(q_hi[j]);
+    if (finite && S->lim_q[j] < 0) {
+      const int jt = S->dof_jt[j];
+      const char* kind = jt == LOIKB_J_FREEFLYER ? "free-flyer" : jt == LOIKB_J_SPHERICAL ? "spherical" : jt == LOIKB_J_PLANAR ? "planar" : "unbounded (cos, sin) revolute";
+      g_last_error = std::string(what) + " belongs to a " + kind + " joint: its configuration is not a scalar that a plain sum advances, it cannot carry a position limit";
+      return LOIKB_ERR_ARG;
+    }
+    lim[j].qi = finite ? S->lim_q[j] : -1;
+    lim[j].pad = 0;
+    lim[j].lo = q_lo[j];
+    lim[j].hi = q_hi[j];
+    any = any || finite;
+  }
+  if (!any) { P.have_limits = false; return LOIKB_OK; }   // (no finite limit anywhere: the handle runs what it runs without limits)
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if (!P.d_lim && (rc = alloc_dev(S, (void**)&P.d_lim, sizeof(PoseLimit) * S->nb))) return rc;
+  P.lim.swap(lim);
+  HIPCHK(hipMemcpyAsync(P.d_lim, P.lim.data(), sizeof(PoseLimit) * S->nb, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  P.have_limits = true;
+  return LOIKB_OK;
+}
+
+int loikb_update_ineq_constraints(loikb_solver* S, const double* lb, const double* ub, int nbound, int in_flags)
+{
+  if (!S || !lb || !ub) return LOIKB_ERR_ARG;
+  if (!S->have_problem) { g_last_error = "UpdateIneqConstraints() before SolveInit()"; return LOIKB_ERR_STATE; }
+  if (nbound != S->nv) { g_last_error = "lb/ub dimension differs from model.nv"; return LOIKB_ERR_INEQ_DIM; }
+  HIPCHK(hipSetDevice(S->device));
+  ++S->inputs_epoch;
+  S->pass_active = false;   // (the pass-level path re-reads the problem on its next call)
+  int rc;
+  if ((rc = update_ineq(S, lb, ub, in_flags))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
+  return LOIKB_OK;
+}
+
+int loikb_pose_get_limit_flags(loikb_solver* S, int* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  if (S->pose.nc == 0 || !S->pose.flags_valid) { g_last_error = "pose_get_limit_flags: the last solve_pose ran without joint limits (or there was none)"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  HIPCHK(hipMemcpyAsync(out, S->pose.d_lflags, sizeof(int) * (size_t)S->B * S->nb, (out_flags & LOIKB_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
   return LOIKB_OK;
 }

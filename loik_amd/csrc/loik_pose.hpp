@@ -6,6 +6,13 @@
 //   k_pose_retarget   : e_c = log6(oMi_c^-1 oMdes_c) per active constraint, b_c = A_c (gain / dt) e_c, the reached / stopped
 //                       bookkeeping and the count of instances still running, one thread per instance
 //   k_pose_integrate  : q <- q (+) dt z for the running instances only (advance_q_instance: the arithmetic of loikb_integrate)
+// and, on a handle with joint position limits (include/loik_amd_limits.h), around the same solve:
+//   k_pose_limit_box  : the step's velocity box [lo, hi] = the base box cut to the velocities that keep q (+) dt z in range, into
+//                       JP_LBUB of the home tiles, one thread per (instance, DoF)
+//   k_pose_limit_clamp: after k_pose_integrate (a kernel of its own: the integrate a handle without limits runs is untouched), a
+//                       limited coordinate that was in range before the step is clamped to its range
+//   k_box_copy        : JP_LBUB of every joint of every instance <-> a [nb][B] scratch: a per-instance base box is saved before
+//                       the first step and restored after the last
 //
 // Everything here is fp64 whatever the handle's precision: the configurations are fp64 on the device anyway, and the
 // tolerances a pose solve is asked for (1e-6 and below) are out of fp32's reach in a 30-joint chain.  These kernels are a few
@@ -245,6 +252,77 @@ __global__ void k_pose_integrate(double* __restrict__ q, int nq, const JointDesc
   if (inner & ST_PRIMAL_INF) st |= POSE_INFEASIBLE;
   status[b] = st;
   advance_q_instance<T>(q + (size_t)b * nq, jd, idx_q, L.nb, lp, dt);
+}
+
+// ---- joint position limits (include/loik_amd_limits.h) ----------------------------------------------------------------------
+// One entry per DoF j (device joint j + 1), built by loikb_set_joint_limits: qi = where the DoF's coordinate sits in a row of
+// q, or -1 when the DoF has no finite limit (the kernels do no joint-type dispatch: only plain-sum coordinates get here).
+struct PoseLimit {
+  int qi, pad;
+  double lo, hi;
+};
+
+// The box of the next inner solve, thread (b, j = blockIdx.y): lanes run over the instances, so the stores into the tiles are
+// the 64 side-by-side pairs of one record row.  Base box: `base_sh` (lb[nb], ub[nb] of the uniform buffer) or `base_pi`
+// ([nb][B] pairs saved by k_box_copy).  A running instance's limited DoF gets
+//   lo = clamp((q_lo - q) / dt, lb, ub), hi = clamp((q_hi - q) / dt, lb, ub)      (fp64; rounded to T by the store)
+// its flags (bit 0: lo > lb, bit 1: hi < ub) and `inrange` (the coordinate is inside its range before the step: what
+// k_pose_limit_clamp keys off); everything else gets the base box, flags 0 (instances that do not run keep the flags of the
+// last step that moved them).
+template <typename T>
+__global__ void k_pose_limit_box(const double* __restrict__ q, int nq, const PoseLimit* __restrict__ lim, int B, double dt,
+                                 const int* __restrict__ status, const T* __restrict__ base_sh, const double2* __restrict__ base_pi,
+                                 char* tiles, Layout L, int* __restrict__ flags, unsigned char* __restrict__ inrange)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+  if (b >= B) return;
+  double lb, ub;
+  if (base_sh) { lb = (double)base_sh[j]; ub = (double)base_sh[L.nb + j]; }
+  else { const double2 v = base_pi[(size_t)j * B + b]; lb = v.x; ub = v.y; }
+  double lo = lb, hi = ub;
+  unsigned char in = 0;
+  if (!(status[b] & (POSE_REACHED | POSE_STOPPED))) {
+    const PoseLimit m = lim[j];
+    int f = 0;
+    if (m.qi >= 0) {
+      const double qj = q[(size_t)b * nq + m.qi];
+      lo = fmin(fmax((m.lo - qj) / dt, lb), ub);
+      hi = fmin(fmax((m.hi - qj) / dt, lb), ub);
+      f = (lo > lb ? 1 : 0) | (hi < ub ? 2 : 0);
+      in = (m.lo <= qj && qj <= m.hi) ? 1 : 0;
+    }
+    flags[(size_t)b * L.nb + j] = f;
+  }
+  inrange[(size_t)j * B + b] = in;
+  stp<T>(lane_ptr<T>(tiles, L, b) + (size_t)j * JREC * pair_bytes<T>(), JP_LBUB, (T)lo, (T)hi);
+}
+
+// after the step's integrate: q_j <- clamp(q_j, q_lo, q_hi) where `inrange` says so (a NaN stays: the next re-target stops the instance)
+__global__ void k_pose_limit_clamp(double* __restrict__ q, int nq, const PoseLimit* __restrict__ lim, int B,
+                                   const unsigned char* __restrict__ inrange)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+  if (b >= B || !inrange[(size_t)j * B + b]) return;
+  const PoseLimit m = lim[j];
+  double* x = q + (size_t)b * nq + m.qi;
+  const double v = *x;
+  *x = v < m.lo ? m.lo : (v > m.hi ? m.hi : v);
+}
+
+// JP_LBUB of DoF j of instance b -> scratch[j][b] (restore = 0) or back (restore = 1); fp64 holds a T exactly
+template <typename T>
+__global__ void k_box_copy(char* tiles, Layout L, int B, double2* __restrict__ scratch, int restore)
+{
+  const int b = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y;
+  if (b >= B) return;
+  char* rec = lane_ptr<T>(tiles, L, b) + (size_t)j * JREC * pair_bytes<T>();
+  if (restore) {
+    const double2 v = scratch[(size_t)j * B + b];
+    stp<T>(rec, JP_LBUB, (T)v.x, (T)v.y);
+  } else {
+    const typename Vec2<T>::type lu = ldp<T>(rec, JP_LBUB);
+    scratch[(size_t)j * B + b] = make_double2((double)lu.x, (double)lu.y);
+  }
 }
 
 }  // namespace loikb
