@@ -18,11 +18,13 @@
 #include "../loik_amd.h"
 #include "../loik_amd_pose.h"
 #include "../loik_amd_limits.h"
+#include "../loik_amd_tasks.h"
 
 #include <array>
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <algorithm>
 #include <vector>
 
@@ -398,6 +400,44 @@ public:
     std::vector<int> f((std::size_t)batch_ * model_.nv);
     check(loikb_pose_get_limit_flags(h_, f.data(), 0));
     return f;
+  }
+  // ---- tool frames and position-only / orientation-only tasks of the pose loop (include/loik_amd_tasks.h)
+  // kinds: LOIKB_TASK_POSE / _POSITION / _ORIENTATION, one per active constraint (active_task_constraint_ids order); frames: iMf of
+  // the task frame on the constrained link, one per kind, or empty = the joint frame.  A formulation edit: every active constraint's
+  // A becomes the shared A_c = S_c X_c^-1 and its b zero.  clearPoseTasks(): the specification goes, A stays.
+  void setPoseTasks(const std::vector<int>& kinds, const std::vector<SE3>& frames = {})
+  {
+    if (!frames.empty() && frames.size() != kinds.size()) throw std::runtime_error("loik_amd: kinds and frames differ in size");
+    DVec f(frames.size() * 12);
+    for (std::size_t i = 0; i < frames.size(); ++i) std::copy(frames[i].begin(), frames[i].end(), f.begin() + 12 * i);
+    check(loikb_pose_set_tasks(h_, (int)kinds.size(), kinds.data(), frames.empty() ? nullptr : f.data()));
+  }
+  void clearPoseTasks() { check(loikb_pose_clear_tasks(h_)); }
+  // the tasks in force: (kind, iMf) per active constraint; empty when there are none
+  std::vector<std::pair<int, SE3>> PoseTasks() const
+  {
+    const int n = loikb_pose_get_tasks(h_, nullptr, nullptr, 0);
+    std::vector<int> k((std::size_t)std::max(n, 0));
+    DVec f(k.size() * 12);
+    if (n > 0) (void)loikb_pose_get_tasks(h_, k.data(), f.data(), n);
+    std::vector<std::pair<int, SE3>> out(k.size());
+    for (std::size_t i = 0; i < out.size(); ++i) {
+      out[i].first = k[i];
+      std::copy(f.begin() + 12 * i, f.begin() + 12 * (i + 1), out[i].second.begin());
+    }
+    return out;
+  }
+  // world placements oMf = oMi(links[e]) * frames[e] for the resident q: [batch][links.size()]; frames empty = ForwardKinematics
+  std::vector<SE3> FramePlacements(const std::vector<Index>& links, const std::vector<SE3>& frames = {}) const
+  {
+    if (!frames.empty() && frames.size() != links.size()) throw std::runtime_error("loik_amd: links and frames differ in size");
+    std::vector<int> l(links.begin(), links.end());
+    DVec f(frames.size() * 12), out((std::size_t)batch_ * l.size() * 12);
+    for (std::size_t i = 0; i < frames.size(); ++i) std::copy(frames[i].begin(), frames[i].end(), f.begin() + 12 * i);
+    check(loikb_frame_placements(h_, l.data(), frames.empty() ? nullptr : f.data(), (int)l.size(), out.data(), 0));
+    std::vector<SE3> M((std::size_t)batch_ * l.size());
+    for (std::size_t i = 0; i < M.size(); ++i) std::copy(out.begin() + 12 * i, out.begin() + 12 * (i + 1), M[i].begin());
+    return M;
   }
   // the resident configurations, [batch][nq]
   DVec q_resident() const

@@ -102,6 +102,13 @@ LIMITS_SYMBOLS = ["loikb_limits_version", "loikb_set_joint_limits", "loikb_updat
 LIMIT_LOWER, LIMIT_UPPER = 1, 2
 
 
+# include/loik_amd_tasks.h: tool frames and position-only / orientation-only tasks of the pose loop; its own header and version again
+TASKS_ABI_VERSION = 1
+TASKS_SYMBOLS = ["loikb_tasks_version", "loikb_pose_set_tasks", "loikb_pose_clear_tasks", "loikb_pose_get_tasks", "loikb_frame_placements"]
+TASK_POSE, TASK_POSITION, TASK_ORIENTATION = 0, 1, 2
+TASK_KINDS = {"pose": TASK_POSE, "position": TASK_POSITION, "orientation": TASK_ORIENTATION}
+
+
 class PoseParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
 
@@ -168,6 +175,10 @@ def lib():
     L.loikb_set_joint_limits.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
     L.loikb_update_ineq_constraints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.loikb_pose_get_limit_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_pose_set_tasks.argtypes = [C.c_void_p, C.c_int, _ip, _dp]
+    L.loikb_pose_clear_tasks.argtypes = [C.c_void_p]
+    L.loikb_pose_get_tasks.argtypes = [C.c_void_p, _ip, _dp, C.c_int]
+    L.loikb_frame_placements.argtypes = [C.c_void_p, _ip, _dp, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -485,6 +496,50 @@ class BatchedLoik:
         _check(self.L.loikb_pose_get_limit_flags(self.h, out.ctypes.data_as(C.c_void_p), 0))
         return out
 
+    def set_pose_tasks(self, kinds, frames=None):
+        """one task per active constraint (active_task_constraint_ids order) for every later SolvePose (loikb_pose_set_tasks).
+        kinds: TASK_POSE / TASK_POSITION / TASK_ORIENTATION or "pose" / "position" / "orientation"; frames: iMf of the task frame
+        on the constrained link, [nc][4][4] / [nc][12], None = the joint frame.  A formulation edit: every active constraint's A
+        becomes the shared A_c = S_c X_c^-1 and its b zero; the handle's A must be shared."""
+        kinds = [kinds] if isinstance(kinds, (str, int, np.integer)) else list(kinds)
+        k = np.empty(len(kinds), dtype=np.int32)
+        for i, x in enumerate(kinds):
+            if isinstance(x, str):
+                if x not in TASK_KINDS:
+                    raise ValueError("task kind %r: expected one of %s" % (x, sorted(TASK_KINDS)))
+                x = TASK_KINDS[x]
+            k[i] = int(x)
+        fp = None
+        if frames is not None:
+            f = self._placements12(frames, "frames").reshape(-1, 12)
+            if f.shape[0] != k.size:
+                raise ValueError("frames: %d placements for %d kinds" % (f.shape[0], k.size))
+            fp = f.ctypes.data_as(_dp)
+        _check(self.L.loikb_pose_set_tasks(self.h, int(k.size), k.ctypes.data_as(_ip), fp))
+
+    def clear_pose_tasks(self):
+        """drops the task specification (loikb_pose_clear_tasks); A and b stay as they are"""
+        _check(self.L.loikb_pose_clear_tasks(self.h))
+
+    def pose_tasks(self):
+        """the tasks in force (loikb_pose_get_tasks): a list of (kind name, iMf [4][4]) per active constraint; [] when there are none"""
+        n = int(self.L.loikb_pose_get_tasks(self.h, None, None, 0))
+        if n <= 0:
+            return []
+        k, f = np.zeros(n, dtype=np.int32), np.zeros((n, 12))
+        self.L.loikb_pose_get_tasks(self.h, k.ctypes.data_as(_ip), f.ctypes.data_as(_dp), n)
+        names = {v: key for key, v in TASK_KINDS.items()}
+        return [(names[int(k[c])], self._to44(f[c:c + 1])[0]) for c in range(n)]
+
+    @staticmethod
+    def _to44(a12):
+        """[..][12] (R row-major, t) -> [..][4][4]"""
+        M = np.zeros(a12.shape[:-1] + (4, 4))
+        M[..., :3, :3] = a12[..., :9].reshape(a12.shape[:-1] + (3, 3))
+        M[..., :3, 3] = a12[..., 9:]
+        M[..., 3, 3] = 1.0
+        return M
+
     def _prep(self, a, what, per, shared_flag):
         """One per-instance input: (void*, is_device, flag).  The C-ABI takes bare pointers without lengths, so the sizes are
         validated HERE: a host array must hold exactly `per` elements (one value shared by the whole batch -> `shared_flag`)
@@ -724,6 +779,21 @@ class BatchedLoik:
         M[..., :3, 3] = out[..., 9:]
         M[..., 3, 3] = 1.0
         return M
+
+    def frame_placements(self, links, frames=None):
+        """world placements oMf = oMi(links[e]) * frames[e] for the resident q (loikb_frame_placements): [B][n][4][4]; frames
+        [n][4][4] / [n][12], None = forward_kinematics(links)"""
+        links = np.ascontiguousarray(np.atleast_1d(links), dtype=np.int32)
+        n = int(links.size)
+        fp = None
+        if frames is not None:
+            f = self._placements12(frames, "frames").reshape(-1, 12)
+            if f.shape[0] != n:
+                raise ValueError("frames: %d placements for %d links" % (f.shape[0], n))
+            fp = f.ctypes.data_as(_dp)
+        out = np.empty((self.batch, n, 12))
+        _check(self.L.loikb_frame_placements(self.h, links.ctypes.data_as(_ip), fp, n, out.ctypes.data_as(C.c_void_p), 0))
+        return self._to44(out)
 
     # ------------------------------------------------------------------------------------------------------
     def set_max_iter(self, n):

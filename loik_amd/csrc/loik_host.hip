@@ -19,6 +19,7 @@
 #include "loik_flat2.hpp"
 #include "loik_passes.hpp"
 #include "loik_pose.hpp"
+#include "loik_pose_tasks.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
 #include "loik_flat_inst.hpp"
@@ -32,6 +33,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd.h"
 #include "../../include/loik_amd_pose.h"
 #include "../../include/loik_amd_limits.h"
+#include "../../include/loik_amd_tasks.h"
 
 #include <algorithm>
 #include <chrono>
@@ -357,6 +359,10 @@ struct loikb_solver_impl {
     int* d_lflags = nullptr;           // [B][nv] limit flags
     unsigned char* d_inrange = nullptr;  // [nb][B] the coordinate was in range before the step
     double2* d_box = nullptr;          // [nb][B] the per-instance base box while a pose solve with limits runs
+    // tool frames and task kinds (loik_amd_tasks.h)
+    bool have_tasks = false;           // loikb_pose_set_tasks wrote the A the handle holds: `tasks` describes it
+    std::vector<PoseTask> tasks;       // [nc_active] host copy of d_tasks
+    PoseTask* d_tasks = nullptr;       // [nc] (slot capacity), allocated by the first loikb_pose_set_tasks
   } pose;
 };
 using Chunk = loikb_solver_impl::Chunk;
@@ -1557,6 +1563,7 @@ int update_eq_single(loikb_solver_impl* S, int c_id, const double* Ai, const dou
       g_last_error = "UpdateEqConstraint: A sharing mode must match SolveInit";
       return LOIKB_ERR_ARG;
     }
+    S->pose.have_tasks = false;   // (loik_amd_tasks.h: an A is rewritten, the task specification no longer describes it)
     if (a_shared_in) {
       memcpy(S->A_host.data() + 36 * found, Ai, 36 * sizeof(double));
       rc = upload_shared_A(S, Ai, found);
@@ -3060,6 +3067,7 @@ static int solve_init_impl(loikb_solver* S, const double* q, const double* H_ref
   HIPCHK(hipSetDevice(S->device));
   int rc;
   if ((rc = validate_problem(S, H_ref, c_ids, nc, nbound))) return rc;   // (nothing of the handle has changed yet)
+  S->pose.have_tasks = false;   // (loik_amd_tasks.h: SolveInit replaces every A)
   memcpy(S->Href, H_ref, 36 * sizeof(double));   // (the plan looks at the reference weight: set_problem stores it again)
   S->href_known = true;
   S->per_link = false;   // (UpdateReference replaces a per-link table: the plan and the slot buffers are sized for the problem being set)
@@ -3198,6 +3206,7 @@ int loikb_add_eq_constraint(loikb_solver* S, int c_id, const double* Ai, const d
   }
   HIPCHK(hipSetDevice(S->device));
   ++S->inputs_epoch;
+  S->pose.have_tasks = false;   // (loik_amd_tasks.h: the constraint set changes)
   int rc;
   const int k = S->nc_active;
   if ((rc = null_constraint_slots(S, k, k + 1))) return rc;  // the new constraint's dual starts at zero
@@ -3226,6 +3235,7 @@ int loikb_remove_eq_constraint(loikb_solver* S, int c_id)
   }
   HIPCHK(hipSetDevice(S->device));
   ++S->inputs_epoch;
+  S->pose.have_tasks = false;   // (loik_amd_tasks.h: the constraint set changes)
   int rc;
   // the entries behind it move down with their duals; the freed last slot becomes a null constraint
   if ((rc = edit_constraints(S, found, S->nc_active, 1))) return rc;
@@ -4191,7 +4201,11 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
   for (int step = 0;; ++step) {
     const int go = step < p->max_steps;
     HIPCHK(hipMemsetAsync(P.d_count, 0, sizeof(unsigned int), S->stream));
-    if (S->f32)
+    if (P.have_tasks)   // (loik_amd_tasks.h: the task-frame error by kind, b = k S e; needs neither the tiles nor A)
+      hipLaunchKernelGGL(k_pose_retarget_tasks, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                         (const int*)P.d_clink, nc, (const PoseTask*)P.d_tasks, (const double*)P.d_tgt, (int)tgt_shared, B, k,
+                         p->tol_pose, go, P.d_b, P.d_err, P.d_status, P.d_steps, P.d_count);
+    else if (S->f32)
       hipLaunchKernelGGL(k_pose_retarget<float>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
                          (const int*)P.d_clink, nc, (const double*)P.d_tgt, (int)tgt_shared, S->a_shared ? (const double*)P.d_A : nullptr,
                          (const char*)S->home.tiles, S->L, B, k, p->tol_pose, go, P.d_b, P.d_err, P.d_status, P.d_steps, P.d_count);
@@ -4333,6 +4347,124 @@ int loikb_pose_get_limit_flags(loikb_solver* S, int* out, int out_flags)
   HIPCHK(hipSetDevice(S->device));
   HIPCHK(hipMemcpyAsync(out, S->pose.d_lflags, sizeof(int) * (size_t)S->B * S->nb, (out_flags & LOIKB_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
+}
+
+// ---- include/loik_amd_tasks.h -----------------------------------------------------------------------------------------------
+int loikb_tasks_version(void) { return LOIKB_TASKS_VERSION; }
+
+// iMf [12] = (R row-major, p): finite, R orthonormal with determinant 1 within 1e-9 per entry (k_pose_check_targets' rule)
+static bool frame_ok(const double* F)
+{
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(F[k])) return false;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double g = F[a] * F[b] + F[3 + a] * F[3 + b] + F[6 + a] * F[6 + b] - (a == b ? 1.0 : 0.0);
+      if (!(std::fabs(g) <= 1e-9)) return false;
+    }
+  const double det = F[0] * (F[4] * F[8] - F[5] * F[7]) - F[1] * (F[3] * F[8] - F[5] * F[6]) + F[2] * (F[3] * F[7] - F[4] * F[6]);
+  return std::fabs(det - 1.0) <= 1e-9;
+}
+
+int loikb_pose_set_tasks(loikb_solver* S, int nc, const int* kinds, const double* frames)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (!S->have_problem) { g_last_error = "pose_set_tasks before SolveInit()"; return LOIKB_ERR_STATE; }
+  if (!S->a_shared) { g_last_error = "pose_set_tasks: the handle's A is per instance; a task matrix is one per constraint for the whole batch (SolveInit with a shared A)"; return LOIKB_ERR_STATE; }
+  if (nc != S->nc_active) { g_last_error = "pose_set_tasks: need one task per active constraint, nc == loikb_num_eq_c()"; return LOIKB_ERR_ARG; }
+  if (!kinds) { g_last_error = "pose_set_tasks: kinds is NULL"; return LOIKB_ERR_ARG; }
+  static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  std::vector<PoseTask> tasks(nc);
+  for (int c = 0; c < nc; ++c) {
+    char what[64];
+    snprintf(what, sizeof(what), "pose_set_tasks: task %d", c);
+    if (kinds[c] < LOIKB_TASK_POSE || kinds[c] > LOIKB_TASK_ORIENTATION) { g_last_error = std::string(what) + ": unknown kind (LOIKB_TASK_POSE / POSITION / ORIENTATION)"; return LOIKB_ERR_ARG; }
+    const double* F = frames ? frames + 12 * c : ident;
+    if (!frame_ok(F)) { g_last_error = std::string(what) + ": the frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+    tasks[c].kind = kinds[c];
+    tasks[c].pad = 0;
+    memcpy(tasks[c].Rf, F, 9 * sizeof(double));
+    memcpy(tasks[c].pf, F + 9, 3 * sizeof(double));
+  }
+  HIPCHK(hipSetDevice(S->device));
+  loikb_solver_impl::PoseState& P = S->pose;
+  int rc;
+  if (!P.d_tasks && (rc = alloc_dev(S, (void**)&P.d_tasks, sizeof(PoseTask) * std::max(S->nc, 1)))) return rc;
+  // A_c = S_c X_c^-1, X^-1 = [[Rf^T, -Rf^T [pf]x], [0, Rf^T]], b_c = 0: UpdateEqConstraint(c, A_c, 0) for every active constraint
+  const double zero[6] = {0, 0, 0, 0, 0, 0};
+  for (int c = 0; c < nc; ++c) {
+    const double *Rf = tasks[c].Rf, *pf = tasks[c].pf;
+    const double px[9] = {0, -pf[2], pf[1], pf[2], 0, -pf[0], -pf[1], pf[0], 0};
+    double A[36] = {0};
+    for (int r = 0; r < 3; ++r)
+      for (int m = 0; m < 3; ++m) {
+        const double rt = Rf[3 * m + r];   // Rf^T
+        A[6 * r + m] = rt;
+        A[6 * (3 + r) + 3 + m] = rt;
+        A[6 * r + 3 + m] = -(Rf[r] * px[m] + Rf[3 + r] * px[3 + m] + Rf[6 + r] * px[6 + m]);
+      }
+    const int r0 = tasks[c].kind == LOIKB_TASK_ORIENTATION ? 0 : 3, r1 = tasks[c].kind == LOIKB_TASK_POSE ? 0 : r0 + 3;
+    for (int x = 6 * r0; x < 6 * r1; ++x) A[x] = 0.0;   // S_c: the masked-out rows
+    if ((rc = update_eq_single(S, S->active_ids[c], A, zero, LOIKB_A_SHARED | LOIKB_B_SHARED))) return rc;
+  }
+  S->pass_active = false;
+  if ((rc = reset_home(S, RS_HCACHE))) return rc;
+  P.tasks.swap(tasks);
+  HIPCHK(hipMemcpyAsync(P.d_tasks, P.tasks.data(), sizeof(PoseTask) * nc, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  P.have_tasks = true;   // (last: update_eq_single drops the specification it is given an A under)
+  return LOIKB_OK;
+}
+
+int loikb_pose_clear_tasks(loikb_solver* S)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  S->pose.have_tasks = false;
+  return LOIKB_OK;
+}
+
+int loikb_pose_get_tasks(const loikb_solver* S, int* kinds, double* frames, int cap)
+{
+  if (!S || !S->pose.have_tasks) return 0;
+  const int n = (int)S->pose.tasks.size();
+  for (int c = 0; c < std::min(n, cap); ++c) {
+    const PoseTask& t = S->pose.tasks[c];
+    if (kinds) kinds[c] = t.kind;
+    if (frames) { memcpy(frames + 12 * c, t.Rf, 9 * sizeof(double)); memcpy(frames + 12 * c + 9, t.pf, 3 * sizeof(double)); }
+  }
+  return n;
+}
+
+int loikb_frame_placements(loikb_solver* S, const int* links, const double* frames, int n, double* out, int out_flags)
+{
+  if (!frames) return loikb_forward_kinematics(S, links, n, out, out_flags);
+  if (!S || n < 0 || (n > 0 && (!links || !out))) return LOIKB_ERR_ARG;
+  for (int e = 0; e < n; ++e) {
+    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = "frame_placements: link id out of range"; return LOIKB_ERR_ARG; }
+    if (!frame_ok(frames + 12 * e)) { g_last_error = "frame_placements: a frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+  }
+  if (!S->have_q) { g_last_error = "frame_placements: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  // scratch 1: the frames [n][12], then the device joints [n]
+  std::vector<int> dl(n);
+  for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
+  const size_t bytes = sizeof(double) * (size_t)S->B * n * 12, fbytes = sizeof(double) * (size_t)n * 12;
+  int rc;
+  if ((rc = ensure_getscr(S, 1, fbytes + sizeof(int) * (size_t)n))) return rc;
+  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) return rc;
+  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  double* d_fr = (double*)S->d_getscr[1];
+  int* d_dl = (int*)((char*)S->d_getscr[1] + fbytes);
+  HIPCHK(hipMemcpyAsync(d_fr, frames, fbytes, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(d_dl, dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
+  hipLaunchKernelGGL(k_frame_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
+                     S->d_idx_q, (const int*)d_dl, (const double*)d_fr, n, S->B, dst);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (dl and the caller's frames have been read)
   return LOIKB_OK;
 }
 
