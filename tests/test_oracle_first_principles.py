@@ -2,7 +2,11 @@
 the converged answer must (i) satisfy the kinematics v_i = J_i(q) nu with an independently computed Jacobian,
 (ii) satisfy the task and box constraints, (iii) coincide with the solution of the reduced dense QP
    min_nu sum_i 1/2 |J_i nu - v_ref|^2_Href  s.t.  A J_c nu = b,  lb <= nu <= ub
-obtained from scipy's SLSQP -- an algorithm that shares nothing with LoIK's ADMM / tree recursion."""
+obtained from scipy's SLSQP -- an algorithm that shares nothing with LoIK's ADMM / tree recursion.
+
+Narrow on purpose (three 1-DoF robots, one constraint, H_ref = I, SLSQP good to 2e-4): tests/test_qp_optimum_cpu.py pins the oracles'
+converged primal and dual answer to the certified QP optimum (tests/qp_numpy.py) on the joint types and formulations of
+tests/qp_cases.py, six orders tighter, and tests/test_qp_optimum_gpu.py does the same for every engine.  Neither file pins iteration counts, the stopping and infeasibility logic, the tail solve or bit-parity with upstream."""
 import numpy as np
 import pytest
 from scipy.optimize import minimize
