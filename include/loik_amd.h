@@ -405,6 +405,11 @@ const char *loikb_plan_string(loikb_solver *s);
  * (lanes whose partial sums the lane collects); -1 = none.  Returns 0, or the number of ints `out` needs when cap is smaller;
  * not applicable (meta[0] == 0): loikb_last_error() says why. */
 int loikb_flat_schedule(const int *parents, int njoints, int *out, int cap, int *meta);
+/* Which instantiation of the flat iteration kernels a launch runs (inspection / tests; no device).  kind: 2 = k_flat2, 1 = k_flat1;
+ * hm: the reference weight, 0 = h I, 1 = diagonal, 2 = general, 3 = per link; sliced: the launch wants time slices; logging: the
+ * SolverInfo lists are written; mur: the rule that moves mu, 0 = decade steps from the table, 1 = OSQP's, 2 = decade steps with the
+ * lazily populated table.  out4 = the kernel's template arguments {SLICED, HM, LOG, MUR}; the kernel gets a time slice iff SLICED. */
+int loikb_flat_variant(int kind, int hm, int sliced, int logging, int mur, int *out4);
 
 /* introspection */
 int loikb_batch(const loikb_solver *s);

@@ -86,7 +86,7 @@ EXPORTED_SYMBOLS = [
     "loikb_device_count", "loikb_sweep_schedule", "loikb_integrate", "loikb_synchronize", "loikb_plan_string", "loikb_pass",
     "loikb_update_references", "loikb_update_eq_constraint", "loikb_add_eq_constraint", "loikb_remove_eq_constraint",
     "loikb_num_eq_c", "loikb_eq_c_capacity", "loikb_active_constraint_ids", "loikb_get_solver_info", "loikb_solver_info_rows_cap", "loikb_solver_info_truncated", "loikb_builtin_model", "loikb_builtin_joint_name",
-    "loikb_builtin_joint_id", "loikb_flat_schedule"]
+    "loikb_builtin_joint_id", "loikb_flat_schedule", "loikb_flat_variant"]
 
 # include/loik_amd_pose.h: batched pose IK, its own header and version (EXPORTED_SYMBOLS stays the two headers above)
 POSE_ABI_VERSION = 1
@@ -169,6 +169,7 @@ def lib():
     L.loikb_builtin_joint_name.restype = C.c_char_p
     L.loikb_builtin_joint_id.argtypes = [C.c_char_p, C.c_char_p]
     L.loikb_flat_schedule.argtypes = [_ip, C.c_int, _ip, C.c_int, _ip]
+    L.loikb_flat_variant.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _ip]
     L.loikb_solve_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseParams)]
     L.loikb_forward_kinematics.argtypes = [C.c_void_p, _ip, C.c_int, C.c_void_p, C.c_int]
     L.loikb_pose_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -226,6 +227,13 @@ def flat_schedule(parents):
     return dict(G=G, nanc=int(meta[2]), nscan=int(meta[3]), njmp=int(meta[4]), depth=rec[:, 0].copy(), size=rec[:, 1].copy(),
                 jmp=rec[:, 2:7].copy(), anc=rec[:, 7:23].copy(), red=rec[:, 23:31].copy(), helper=rec[:, 31].copy(),
                 part=rec[:, 32:40].copy())
+
+
+def flat_variant(kind, hm, sliced, logging, mur):
+    """(SLICED, HM, LOG, MUR) of the k_flat2 (kind 2) / k_flat1 (kind 1) instantiation a launch runs (host-only, loikb_flat_variant)."""
+    out = (C.c_int * 4)()
+    _check(lib().loikb_flat_variant(int(kind), int(hm), int(sliced), int(logging), int(mur), out))
+    return bool(out[0]), int(out[1]), bool(out[2]), int(out[3])
 
 
 def _check(rc):

@@ -4,8 +4,9 @@
 // where two ds_read_b64 take 4.8 (scripts/ubench/lds_rate.hip, profiles/r05_i_lds_rate.txt), and the loops of these kernels are LDS-pipe
 // bound beside their fp64 issue (k_flat1: pipe busy 63 % of the whole launch).  k_fslots, k_solve, k_lean and the record movers keep the
 // default code generation: their global loads want the merging (k_fslots +0.2 ms without).
-// This header lists the instantiations the host launches (loik_host.hip: LOIKB_LAUNCH_FLAT2 / LOIKB_LAUNCH_FLAT1); X(...) is
-// `template` in loik_flat_kernels.hip and `extern template` in loik_host.hip.
+// This header lists the instantiations the host launches; X(...) is `template` in loik_flat_kernels.hip, and in loik_host.hip both
+// `extern template` and an entry {variant, kernel pointer} of the launch tables (FLAT2_TABLE / FLAT1_TABLE): a variant that
+// flat_variant there can return and these lists lack fails the build, one it never returns fails tests/test_flat_variant.py.
 #pragma once
 #include "loik_flat2.hpp"
 

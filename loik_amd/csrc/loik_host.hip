@@ -20,9 +20,9 @@
 #include "loik_passes.hpp"
 #include "loik_pose.hpp"
 #include "loik_pose_tasks.hpp"
+#include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
-#include "loik_flat_inst.hpp"
 LOIKB_FLAT2_INSTANCES(LOIKB_FLAT2_DECL)
 LOIKB_FLAT1_INSTANCES(LOIKB_FLAT1_DECL)
 #ifdef LOIKB_TAIL_PROF
@@ -1281,24 +1281,77 @@ bool href_is_diagonal(const loikb_solver_impl* S)
       if (i != j && S->Href[6 * i + j] != 0.0) return false;
   return true;
 }
-// the builds with one instance per wavefront (k_flat2: 17..32 joints, <= FLAT_NA_SMALL ancestors; k_flat1: 33..64) also take a
-// diagonal or a general reference weight shared by the links (their HM = 1 / 2 instantiations); k_flat (other trees,
-// LOIKB_FLAT_SPLIT=0) takes h I only
-bool flat_takes_diagonal(const loikb_solver_impl* S)
+// the reference weight as the flat kernels' HM: 0 = h I, 1 = diagonal, 2 = general (shared by the links), 3 = per link
+static int href_mode(const loikb_solver_impl* S) { return S->per_link ? 3 : href_is_scalar(S) ? 0 : href_is_diagonal(S) ? 1 : 2; }
+// lanes per instance of the on-chip engines: the smallest power of two >= nb, at least 8
+int lanes_per_instance(const loikb_solver_impl* S)
 {
-  if (!S->tune.flat_split || S->f32 || !S->flat.ok) return false;   // (round 4: logging handles too -- the LOG builds)
-  return (S->flat.G == F2G && S->flat.nanc <= FLAT_NA_SMALL) || S->flat.G == WAVE;
+  int G = 8;
+  while (G < S->nb) G <<= 1;
+  return G;
 }
+// THE classification of the flat engine's build for a handle.  One instance per wavefront where the layout applies, fp64 and
+// LOIKB_FLAT_SPLIT permitting: k_flat2 (17..32 joints, <= FLAT_NA_SMALL ancestors: two lanes per joint) and k_flat1 (33..64 joints);
+// k_flat, two instances per wavefront, for every other tree the flat schedule takes; None: no flat schedule (FlatSched::why).
+enum class FlatKind { None, Flat, Flat2, Flat1 };
+FlatKind flat_kind(const loikb_solver_impl* S)
+{
+  if (!S->flat.ok) return FlatKind::None;
+  if (!S->tune.flat_split || S->f32) return FlatKind::Flat;
+  if (S->flat.G == F2G && S->flat.nanc <= FLAT_NA_SMALL) return FlatKind::Flat2;
+  return S->flat.G == WAVE ? FlatKind::Flat1 : FlatKind::Flat;
+}
+constexpr bool one_per_wave(FlatKind k) { return k == FlatKind::Flat2 || k == FlatKind::Flat1; }
+// the builds with one instance per wavefront also take a diagonal or a general reference weight shared by the links, or one per link
+// (their HM = 1 / 2 / 3 instantiations), logging handles too (the LOG builds); k_flat takes h I only
+bool flat_takes_diagonal(const loikb_solver_impl* S) { return one_per_wave(flat_kind(S)); }
+
+// ---- the variant of k_flat2 / k_flat1 a launch runs: template arguments <SLICED, HM, LOG, MUR> (loik_flat2.hpp) ----
+struct FlatVariant { bool sliced; int hm; bool log; int mur; };
+// (kind: Flat2 or Flat1; hm: href_mode; sliced: the launch wants time slices, flat_launch_slice; mur: the rule that moves mu, FlatLaunch)
+// OSQP's rule (mur 1) and the SolverInfo lists (logging) run unsliced, and but for k_flat2 under OSQP's rule a diagonal reference
+// weight goes as a general one there; the lazily populated table (mur 2) is k_flat2's with h I.
+constexpr FlatVariant flat_variant(FlatKind kind, int hm, bool sliced, bool logging, int mur)
+{
+  const int hm_general = hm == 3 ? 3 : hm >= 1 ? 2 : 0;
+  if (kind == FlatKind::Flat2 && mur == 1) return hm >= 1 ? FlatVariant{false, hm, false, 1} : FlatVariant{sliced, 0, false, 1};
+  if (kind == FlatKind::Flat2 && mur == 2) return {sliced, 0, false, 2};
+  if (mur == 1) return {false, hm_general, false, 1};
+  if (logging) return {false, hm_general, true, 0};
+  return {sliced, hm, false, 0};
+}
+constexpr int flat_variant_key(FlatVariant v) { return (v.sliced ? 1 : 0) | (v.hm << 1) | (v.log ? 8 : 0) | (v.mur << 4); }
+// The launch tables ARE the instantiation lists (loik_flat_inst.hpp): a variant flat_variant can return that a list lacks fails the build.
+template <typename Fn> struct FlatEntry { int key, na; Fn* fn; };
+using Flat2Entry = FlatEntry<void LOIKB_FLAT2_ARGS>;
+using Flat1Entry = FlatEntry<void LOIKB_FLAT1_ARGS>;
+#define LOIKB_FLAT2_ENTRY(SLICED, HM, LOG, MUR) {flat_variant_key({SLICED, HM, LOG, MUR}), FLAT_NA_SMALL, &k_flat2<FLAT_NA_SMALL, SLICED, HM, LOG, MUR>},
+#define LOIKB_FLAT1_ENTRY(NA, SLICED, HM, LOG, MUR) {flat_variant_key({SLICED, HM, LOG, MUR}), NA, &k_flat1<NA, SLICED, HM, LOG, MUR>},
+constexpr Flat2Entry FLAT2_TABLE[] = {LOIKB_FLAT2_INSTANCES(LOIKB_FLAT2_ENTRY)};
+constexpr Flat1Entry FLAT1_TABLE[] = {LOIKB_FLAT1_INSTANCES(LOIKB_FLAT1_ENTRY)};
+template <typename Fn, size_t N>
+constexpr Fn* flat_kernel(const FlatEntry<Fn> (&table)[N], FlatVariant v, int na)
+{
+  for (const FlatEntry<Fn>& e : table) if (e.key == flat_variant_key(v) && e.na == na) return e.fn;
+  return nullptr;   // (never at run time: the static_assert below)
+}
+constexpr bool flat_tables_complete()
+{
+  for (int i = 0; i < 2 * 4 * 2 * 2 * 3; ++i) {
+    const FlatKind kind = i % 2 ? FlatKind::Flat1 : FlatKind::Flat2;
+    const FlatVariant v = flat_variant(kind, i / 2 % 4, i / 8 % 2, i / 16 % 2, i / 32);
+    if (kind == FlatKind::Flat2 ? !flat_kernel(FLAT2_TABLE, v, FLAT_NA_SMALL) : !(flat_kernel(FLAT1_TABLE, v, FLAT_NA_SMALL) && flat_kernel(FLAT1_TABLE, v, FLAT_MAXA))) return false;
+  }
+  return true;
+}
+static_assert(flat_tables_complete(), "flat_variant returns a variant that LOIKB_FLAT2_INSTANCES / LOIKB_FLAT1_INSTANCES do not list");
 // OSQP's rule takes mu off the decade grid: no table of slots; k_flat2 builds the factors in-wave at every change of mu
 // (k_flat2<.., MUR = 1> / k_flat1<.., MUR = 1>: robots of 17..64 joints, fp64, no SolverInfo lists)
 bool flat_any_mu(const loikb_solver_impl* S)
 {
   return S->opt.mu_update_strat == LOIKB_MU_OSQP;
 }
-bool flat_any_mu_ok(const loikb_solver_impl* S)
-{
-  return S->tune.flat_split && !S->f32 && S->flat.ok && ((S->flat.G == F2G && S->flat.nanc <= FLAT_NA_SMALL) || S->flat.G == WAVE) && !S->opt.logging;
-}
+bool flat_any_mu_ok(const loikb_solver_impl* S) { return flat_takes_diagonal(S) && !S->opt.logging; }
 bool flat_applicable(const loikb_solver_impl* S)
 {
   if (flat_any_mu(S) && !flat_any_mu_ok(S)) return false;
@@ -1306,12 +1359,34 @@ bool flat_applicable(const loikb_solver_impl* S)
   return S->plan.flat && (flat_takes_diagonal(S) || (!S->per_link && href_is_scalar(S)));
 }
 
-// The time slice of a flat launch over n instances (0: run to completion).  End of round 4, once the SLICED builds' iteration cost
+// The time slice of a flat launch over n instances (0: run to completion): round-robin inside the launch (k_flat2<.., SLICED>).  Iteration counts are heavy-tailed and unknown: run to
+// completion in arrival order, the 999-iteration instances that are fetched late keep the launch alive ~3 ms after
+// the queue ran dry.  With a slice of 160 iterations every long runner has done ~500 by then.  Measured (Talos-32,
+// one GPU, ms per batch without / with): 8192: 4.23 / 4.39, 16 384: 5.46 / 5.61, 32 768: 8.13 / 7.80, 65 536: 13.28 /
+// 12.29, 131 072: 23.13 / 22.24, 262 144: 44.19 / 44.48 -- a switch costs a store, an agent-scope reload and the set-up of
+// an instance (~25 us), small batches are one straggler chain whatever the order, large ones hide it in their bulk:
+// on by default between 12 and 96 instances per resident wavefront.  Slices of 32 / 64 / 96 / 128 / 192 / 256 / 384
+// iterations on the headline: 19.6 / 13.7 / 12.40 / 12.36 / 12.33 / 12.45 / 12.76 ms.
+// Round 4: OFF by default.  A sliced-out instance is now parked (its lane state and LDS blocks in a lane-contiguous record of
+// its own, ~40 row accesses each way, the ticket for the next entry drawn with the stores, the decade slot fetched with the
+// record: three round trips instead of ten through the tile records) -- and with the iteration at 2.9 instead of 3.6 us the
+// slices still bring only 0..2.5 %: headline batch in arrival order, k_flat2 alone, ms: unsliced 9.47, slices of 192 / 128 /
+// 96 / 64 / 48 / 32: 9.32 / 9.28 / 9.32 / 9.76 / 11.45 / 13.9; 131 072 instances 16.73 -> 16.31 (128); 32 768: 5.87 -> 5.82;
+// 16 384 and below: slower (one straggler chain whatever the order).  A switch costs ~27 us of a wavefront under load (five
+// dependent trips to the L2 / HBM at ~2.5 us each when 2048 wavefronts share them), a slice of 64 iterations 190 us.
+// LOIKB_FLAT_SLICE=q switches it on.
+// End of round 4: ON again for arrival-order launches of >= 32 768 instances, once the SLICED builds' iteration cost
 // what the plain builds' costs (it re-fetched the stopping test's tolerances from the kernel arguments every iteration): headline
 // batch in arrival order 10.1 -> 9.4 ms at 288 (160 / 224 / 352 / 448: 9.6 / 9.5 / 9.5 / 9.8), 131 072: 17.5 -> 16.7, 262 144:
 // 33.7 -> 32.2, 32 768: 6.1 -> 6.0, whole body 20.6 -> 19.6; 16 384: 4.16 -> 4.37 and 8192: 3.08 -> 3.32 (one straggler chain
 // whatever the order: no slices below 32 768).  Not for ordered launches (their long runners start first and must not go to the
 // back of the queue) and not for a handle on a stream of its own (the other batch in flight fills this one's ragged end).
+// (an ordered launch runs to completion: its long runners start first and must not go to the back of the queue.  Time
+//  slices for everything behind the predicted-long prefix were tried: the SLICED build's agent-scope loads / stores of
+//  the records cost the short instances more than the slices bring -- 12.2 ms against 10.6)
+// (not for a handle on a stream of its own: that is how batches are kept in flight side by side, and then the other
+//  batch's bulk fills this one's ragged end -- slicing only adds its switches, and its wavefronts that wait for queue
+//  entries hold slots the other launch could use: two headline batches in flight 21.5 ms per pair without, 24.9 with)
 constexpr int FLAT_SLICE_LATER = 96;   // (an instance's later slices: 9.44 -> 9.38 ms; a SHORT first slice -- 64 / 96 / 128, then 288 -- is slower: 9.9 / 9.6 / 9.8)
 constexpr int FLAT_SLICE_DEFAULT = 288, FLAT_SLICE_MIN_BATCH = 32768, FLAT_SLICE_MAX_BATCH = 262144;   // (above: 19 KB of park record per instance for 1.5 %)
 int flat_slice_for(const loikb_solver_impl* S, int n, bool ordered)
@@ -1348,7 +1423,7 @@ int ensure_hslots(loikb_solver_impl* S)
       }
       C.fslots_bytes = need;
     }
-    if (S->flat.G == F2G && flat_takes_diagonal(S) && S->tune.flat_build) {   // (the lazily populated table's per-instance masks)
+    if (flat_kind(S) == FlatKind::Flat2 && S->tune.flat_build) {   // (the lazily populated table's per-instance masks)
       for (Chunk& C : S->chunks) {
         if ((size_t)C.B <= C.fmask_n) continue;
         if (C.d_fmask) HIPCHK(hipFree(C.d_fmask));
@@ -1359,7 +1434,7 @@ int ensure_hslots(loikb_solver_impl* S)
     }
     // park records of the time-sliced launch (k_flat2 only: 17..32 joints): ~19 KB per instance, allocated for the batch sizes the
     // slices are used on (flat_slice_window); a handle that cannot have them simply runs unsliced
-    if (S->flat.G == F2G && flat_takes_diagonal(S) && flat_slice_for(S, S->B, false) > 0) {
+    if (flat_kind(S) == FlatKind::Flat2 && flat_slice_for(S, S->B, false) > 0) {
       for (Chunk& C : S->chunks) {
         const size_t need = (size_t)C.B * flat2_park_stride(S->nc, true) * sizeof(double);
         if (need <= C.park_bytes) continue;
@@ -1373,8 +1448,7 @@ int ensure_hslots(loikb_solver_impl* S)
     if (!S->have_problem) return LOIKB_OK;  // (the lean engine's slots are only needed once a solve cannot use the flat engine)
   }
   if (!S->plan.lean) return LOIKB_OK;
-  int G = 8;
-  while (G < S->nb) G <<= 1;
+  const int G = lanes_per_instance(S);
   for (Chunk& C : S->chunks) {
     const size_t need = (size_t)C.B * S->plan.ndec * HSLOT_PAIRS * G * 2 * S->esz;
     if (need <= C.hslots_bytes) continue;
@@ -1753,8 +1827,7 @@ int compact(loikb_solver_impl* S, Chunk* C, int src, int dst, int n_src, int* n_
 // with four task constraints -- a whole-body task set stays in this engine at 7/8 of the residency).
 int lean_waves_per_cu(const loikb_solver_impl* S)
 {
-  int G = 8;
-  while (G < S->nb) G <<= 1;
+  const int G = lanes_per_instance(S);
   const size_t per_wave = S->f32 ? lean_lds_bytes<float>(S->nc, G, S->a_shared) : lean_lds_bytes<double>(S->nc, G, S->a_shared);
   return (int)std::min<size_t>(8, (160 * 1024) / per_wave);
 }
@@ -1815,7 +1888,7 @@ void plan_engines(loikb_solver_impl* S)
     pl.flat_waves_cu = (int)std::min<size_t>(8, (160 * 1024) / per_wave);
     // (the builds with one instance per wavefront have their own LDS layouts: what counts is the kernel that would run)
     if (flat_takes_diagonal(S)) {
-      const size_t pw = S->flat.G == F2G ? flat2_lds_bytes<FLAT_NA_SMALL>(S->nc, true)
+      const size_t pw = flat_kind(S) == FlatKind::Flat2 ? flat2_lds_bytes<FLAT_NA_SMALL>(S->nc, true)
                         : S->flat.nanc <= FLAT_NA_SMALL ? flat1_lds_bytes<FLAT_NA_SMALL>(S->nc, true, 1)
                                                         : flat1_lds_bytes<FLAT_MAXA>(S->nc, true, 1);
       pl.flat_waves_cu = std::max(pl.flat_waves_cu, (int)std::min<size_t>(8, (160 * 1024) / pw));
@@ -1885,26 +1958,466 @@ static bool bushy_goes_on_chip(const loikb_solver_impl* S)
   return direct_tail_of(S, S->B, std::max(1, batch_tail_max(S)));
 }
 
+// ---- the on-chip engines: k_fslots + k_flat2 / k_flat1 / k_flat (launch_flat), else k_hslots + k_lean (launch_lean), and k_tail for what
+// they leave (launch_tail_kernel).  run_tail below prepares the list and drives them.
+// What the engines of one run_tail share.  An engine that leaves instances unfinished moves `list` / `n` on to them.
+template <typename T>
+struct TailCtx {
+  loikb_solver_impl* S; Chunk* C; Params<T>& P; Bufs<T> Bf;
+  loikb_solver_impl::Set& A; int cur, n_cur;   // the set the list's slots index, its size
+  bool whole_set, small_flat;   // the list is every slot of the set; the short sequence of a small batch (run_tail)
+  int G, ipw;                   // lanes per instance, instances per wavefront
+  int ndec, kexp_lo;            // the decade table the handle's history asks for
+  const int* list; int n;       // the instances still iterating
+  double total_ms = 0.0;
+  unsigned long long iters = 0;
+};
+
+// ---- longest first: the bookkeeping the three engines share.  A whole-set launch takes the set in the order the handle's previous solve
+// left (order_usable), leaves the order of this solve's iteration counts for the next one, and is judged against the handle's last launch
+// in arrival order: a batch that resembles the previous one runs 5..35 % shorter ordered (no ragged end); one that does not is arrival
+// order without the slices that would have softened it, a few per cent LONGER -- then the next flat_order_holdoff solves go back to
+// arrival order, which also refreshes the figure to compare with.
+struct OrderUse { bool ordered = false, was_stale = false; };
+
+// Takes up the previous solve's order when the launch is `eligible` (it takes the same whole set) and the order is usable; counts the
+// hold-off down when `count_down` (the flat engine: every launch; k_lean: whole-set launches; k_tail: launches that also leave an order).
+// The decade slots are indexed by the INSTANCE slot, so k_fslots / k_hslots and the engine find them under any order of the list.
+static int take_up_order(const loikb_solver_impl* S, Chunk* C, bool eligible, bool count_down, int n_cur, OrderUse* use)
+{
+  use->ordered = eligible && order_usable(S, C, n_cur);
+  use->was_stale = use->ordered && C->order_epoch != S->inputs_epoch;
+  if (count_down && C->order_holdoff > 0) --C->order_holdoff;
+  if (use->ordered) HIPCHK(hipMemcpyAsync(C->d_slots, C->d_order, sizeof(int) * (size_t)n_cur, hipMemcpyDeviceToDevice, C->stream));
+  C->stats.flat_ordered += use->ordered ? 1 : 0;
+  return LOIKB_OK;
+}
+
+// The order for the handle's next solve: longest first by the iteration counts of this one (k_order_*, loik_lean.hpp; an instance that
+// escaped to k_tail counts with what it had when it left).  flat_engine: k_order_count also takes the histogram of the decades the
+// instances ended in (the next sliced launch's table window), and the launch's counters go to the host between count and scan.
+template <typename T>
+static int leave_order(const loikb_solver_impl* S, Chunk* C, const loikb_solver_impl::Set& A, int n_cur, bool flat_engine)
+{
+  HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
+  hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins,
+                     flat_engine ? C->d_counters + ORDER_DEC_HIST : (unsigned int*)nullptr);
+  if (flat_engine) HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
+  hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_BINS), 0, C->stream, C->d_order_bins);
+  hipLaunchKernelGGL(k_order_scatter<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins, C->d_order);
+  HIPCHK(hipGetLastError());
+  C->order_n = n_cur;
+  C->order_epoch = S->inputs_epoch;
+  return LOIKB_OK;
+}
+
+// Did the order predict this solve?  `ms`: the launch's duration (the flat engine: without k_fslots; the others: the whole sequence).
+// (What the launch leaves after its queue ran dry does not tell: a small batch's queue is empty long before its long runners are done.)
+static void judge_order(const loikb_solver_impl* S, Chunk* C, int n_cur, OrderUse use, double ms)
+{
+  if (C->arrival_n != n_cur) { C->arrival_n = n_cur; C->arrival_ms = 0.0; }
+  if (!use.ordered) C->arrival_ms = ms;
+  else if (use.was_stale && C->arrival_ms > 0.0 && ms > 0.985 * C->arrival_ms) C->order_holdoff = S->tune.flat_order_holdoff;
+}
+
+// The decades of mu this launch's instances were seen in (the next solve's table covers those +- 1); an instance that escaped the table
+// brings the whole configured range back.  The caller holds S->alloc_mu.
+static void record_decades(loikb_solver_impl* S, unsigned int seen, int kexp_lo, unsigned int escaped)
+{
+  for (int d = 0; d < 16; ++d)
+    if (seen & (1u << d)) { S->seen_lo = std::min(S->seen_lo, kexp_lo + d); S->seen_hi = std::max(S->seen_hi, kexp_lo + d); }
+  if (escaped) { S->seen_lo = S->plan.kexp_lo; S->seen_hi = S->plan.kexp_lo + S->plan.ndec - 1; }
+}
+
+// ---- the flat engine ----
+// what one launch of the flat engine settles before its kernels go
+struct FlatLaunch {
+  FlatKind kind; int nanc, frows, has_hv; bool small_na;
+  // the rule that moves mu (k_flat2's MUR): 1 = OSQP's -- no table, every change of mu is an in-wave build --, 2 = decade steps with
+  // the in-wave builder for the decades the table lacks (LOIKB_FLAT_BUILD=1), 0 = decade steps, the table or k_tail
+  // (k_flat2 only: for k_flat1 -- 33..64 joints -- it was built and measured in round 6 and did not pay: loik_flat2.hpp)
+  int mur;
+  int ndec, kexp_lo, dw0, nw;   // the table's range, the window of it k_fslots builds now
+  int slice;                    // flat_launch_slice
+  double cu_sh; dim3 grid;      // the chunk's share of the CUs, the iteration kernel's grid
+};
+
+// The time slice of THIS launch (flat_slice_for's encoding; 0: run to completion), decided once, the park buffer's size included: the
+// table window and the kernel variant both follow it.
+static int flat_launch_slice(const loikb_solver_impl* S, const Chunk* C, FlatKind kind, int mur, int n, int n_cur, bool ordered)
+{
+  if (kind == FlatKind::Flat) return 0;
+  // (k_flat1: time slicing as in k_flat2, same window: whole body, four tasks, B = 65 536: 34.7 ms without; OSQP's rule: unsliced)
+  if (kind == FlatKind::Flat1) return mur == 1 ? 0 : flat_slice_for(S, n, ordered);
+  int q = flat_slice_for(S, n, ordered);
+  if (q > 0 && (C->d_park == nullptr || (size_t)n_cur * flat2_park_stride(S->nc, true) * sizeof(double) > C->park_bytes)) q = 0;
+  // (OSQP's rule runs unsliced unless LOIKB_FLAT_SLICE asks: a parked instance rebuilds its factors when it is taken up again --
+  //  headline batch, first solve: 12.7 ms with the default slices, 11.4 without: profiles/r05_d_mu_rules.jsonl)
+  if (mur == 1 && S->tune.flat_slice < 0) q = 0;
+  return q;
+}
+
+// The decades k_fslots builds now (MUR = 2): all of the table, or a window of it -- the rest is populated by the instances that get
+// there (k_flat2<.., MUR = 2>, loik_flat2.hpp).  The window: LOIKB_FLAT_WINDOW=lo,n as given (any launch); else, for a time-sliced
+// launch of a handle with a history, from the decade its previous solve's instances STARTED in (0 after a cold reset) to the one
+// 97 % of them had ENDED in or below (k_order_count's histogram) -- the headline's instances end in decades 0..3 (8.7 / 23.8 / 60.6 /
+// 6.9 %) of the 0..6 the handle's history says were visited by somebody: four decades built instead of nine, k_fslots 0.9 -> 0.55 ms,
+// and the 0.2 % that go further build their slot once each (70 us).  Without a window the launch runs the build without the builder
+// (F.mur = 0: its iteration loop is 1-3 % shorter).
+static void flat_table_window(const loikb_solver_impl* S, FlatLaunch& F, int n)
+{
+  int wlo = 0, whi = -1;
+  const bool win_ok = F.slice > 0;   // (a window on time-sliced launches only: the builder beside the unsliced loop costs more than k_fslots saves)
+  if (S->tune.flat_win_n > 0) { wlo = S->tune.flat_win_lo; whi = wlo + S->tune.flat_win_n - 1; }
+  else if (S->tune.flat_build == 2 && win_ok && S->end_hist_n > 0) {
+    unsigned long long cum = 0;
+    int k03 = 99, k97 = 99;
+    for (int k = 0; k < 32; ++k) {
+      cum += S->end_hist[k];
+      if (k03 == 99 && cum * 100 >= 3ull * S->end_hist_n) k03 = k - 16;
+      if (k97 == 99 && cum * 100 >= 97ull * S->end_hist_n) k97 = k - 16;
+    }
+    wlo = std::min(0, k03); whi = std::max(0, k97);
+  }
+  else if (S->tune.flat_build == 2 && win_ok && n >= 49152) {
+    // No history (a handle's first solve): the five decades from mu0's upwards.  The rule moves mu up far more often than down, and
+    // rarely more than three decades; whoever leaves the window builds the slot once (results are bit-identical whatever the window:
+    // tests/test_engines.py::test_flat_lazy_table_*).  Measured, time-sliced headline launches, ms per solve incl. k_fslots, full
+    // table / this window: 65 536 instances 8.67 / 8.32, 131 072: 14.96 / 14.64, 262 144: 29.16 / 28.63; 32 768 and below no gain
+    // (5.45 / 5.49), nor on unsliced launches (the builder beside an unsliced loop costs it more than k_fslots saves:
+    // 65 536 ordered 7.44 / 7.59): profiles/r05_i_lazy_window_sizes.txt
+    wlo = 0; whi = 4;
+  }
+  const int lo = std::max(wlo, F.kexp_lo), hi = std::min(whi, F.kexp_lo + F.ndec - 1);
+  if (hi >= lo && (hi - lo + 1) < F.ndec) { F.dw0 = lo - F.kexp_lo; F.nw = hi - lo + 1; }
+  else if (S->tune.flat_build == 2) F.mur = 0;   // (auto: nothing to leave out -- the build without the builder)
+}
+
+// the iteration kernel of the launch: k_flat2 / k_flat1 in the variant flat_variant picks, or k_flat.  Sets F.grid.
+template <typename T>
+static int launch_flat_kernel(TailCtx<T>& X, FlatLaunch& F)
+{
+  loikb_solver_impl* S = X.S; Chunk* C = X.C;
+  const int n = X.n, has_hv = F.has_hv;
+  const int cus = (int)(F.cu_sh + 0.5);
+  if (one_per_wave(F.kind)) {   // (what only the in-wave builder / the lazily populated table read, behind one kernel argument)
+    // (uploaded when one of the pointers changes -- synchronously, from the chunk's own copy: ADVICE r05)
+    if (C->d_aux == nullptr) HIPCHK(hipMalloc((void**)&C->d_aux, 4 * sizeof(void*)));
+    const void* auxh[4] = {S->d_topo, S->d_child_list, C->d_fmask, nullptr};
+    if (memcmp(auxh, C->aux_h, sizeof(auxh)) != 0) {
+      memcpy(C->aux_h, auxh, sizeof(auxh));
+      HIPCHK(hipStreamSynchronize(C->stream));
+      HIPCHK(hipMemcpy(C->d_aux, C->aux_h, sizeof(auxh), hipMemcpyHostToDevice));
+    }
+  }
+  const Params<double>& Pd = *reinterpret_cast<const Params<double>*>(&X.P);
+  const Bufs<double>& Bd = *reinterpret_cast<const Bufs<double>*>(&X.Bf);
+  const FlatVariant v = flat_variant(F.kind, href_mode(S), F.slice > 0, S->opt.logging != 0, F.mur);
+  const int quantum = v.sliced ? F.slice : 0;
+  if (F.kind == FlatKind::Flat2) {
+    // k_flat2: two lanes per joint, one instance per wavefront, two wavefronts per SIMD (loik_flat2.hpp)
+    const size_t lds2 = flat2_lds_bytes<FLAT_NA_SMALL>(S->nc, has_hv != 0, F.mur == 1);
+    int per_cu = (int)std::min<size_t>((size_t)8, (160 * 1024) / lds2);
+    if (S->tune.lean_wg_per_cu > 0) per_cu = std::min(per_cu, S->tune.lean_wg_per_cu);
+    F.grid = dim3((unsigned)std::min(n, per_cu * cus));
+    const int win_bits = (int)(((F.nw >= 16 ? 0xFFFFu : ((1u << F.nw) - 1u)) << F.dw0) & 0xFFFFu);
+    hipLaunchKernelGGL(flat_kernel(FLAT2_TABLE, v, FLAT_NA_SMALL), F.grid, dim3(WAVE), lds2, C->stream, Pd, Bd, (const JointDesc*)S->d_jd, (const FlatLane*)S->flat.d_lanes,
+                       F.nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, (const double*)C->d_fslots, F.frows, F.kexp_lo, F.ndec, (double)S->Href[0],
+                       (int)((unsigned int)has_hv | ((unsigned int)(S->maxdepth & 0xFF) << 8) | ((unsigned int)win_bits << 16)), C->ring_cap - 1,
+                       quantum, (double*)C->d_park, flat2_park_stride(S->nc, true), (const void* const*)C->d_aux);
+  } else if (F.kind == FlatKind::Flat1) {
+    // k_flat1, one instance per wavefront anyway (33..64 joints): the build with nested loops, prefix-sum subtree sums, DPP fold
+    // one decade slot in LDS instead of two when that buys wavefronts per CU (whole body, four task constraints: 6 -> 8)
+    auto lds_of = [&](int bufs) { return F.small_na ? flat1_lds_bytes<FLAT_NA_SMALL>(S->nc, has_hv != 0, bufs) : flat1_lds_bytes<FLAT_MAXA>(S->nc, has_hv != 0, bufs); };
+    // (OSQP's rule: the in-wave builder's rows lie over both slots -- two it is)
+    const int one_buf = F.mur != 1 && std::min<size_t>(8, (160 * 1024) / lds_of(1)) > std::min<size_t>(8, (160 * 1024) / lds_of(2));
+    const size_t lds1 = lds_of(one_buf ? 1 : 2);
+    int per_cu1 = (int)std::min<size_t>(8, (160 * 1024) / lds1);
+    if (S->tune.lean_wg_per_cu > 0) per_cu1 = std::min(per_cu1, S->tune.lean_wg_per_cu);
+    F.grid = dim3((unsigned)std::min(n, per_cu1 * cus));
+    hipLaunchKernelGGL(flat_kernel(FLAT1_TABLE, v, F.small_na ? FLAT_NA_SMALL : FLAT_MAXA), F.grid, dim3(WAVE), lds1, C->stream, Pd, Bd, (const JointDesc*)S->d_jd,
+                       (const FlatLane*)S->flat.d_lanes, F.nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, (const double*)C->d_fslots, F.frows,
+                       F.kexp_lo, F.ndec, (double)S->Href[0], has_hv | (one_buf ? 2 : 0) | ((S->maxdepth & 0xFF) << 8), C->ring_cap - 1, quantum,
+                       (const void* const*)C->d_aux);
+  } else {
+    // k_flat: two instances per wavefront, one wavefront per SIMD
+    const size_t flds = F.small_na ? flat_lds_bytes<T, FLAT_NA_SMALL>(S->nc, X.G, S->a_shared, has_hv) : flat_lds_bytes<T, FLAT_MAXA>(S->nc, X.G, S->a_shared, has_hv);
+    int lgG = 3;
+    while ((1 << lgG) < X.G) ++lgG;
+    F.grid = dim3((unsigned)std::min((n + X.ipw - 1) / X.ipw, (int)std::min<size_t>(4, (160 * 1024) / flds) * cus));
+    auto* kernel = S->opt.logging ? (F.small_na ? k_flat<T, FLAT_NA_SMALL, true> : k_flat<T, FLAT_MAXA, true>)
+                                  : (F.small_na ? k_flat<T, FLAT_NA_SMALL> : k_flat<T, FLAT_MAXA>);
+    hipLaunchKernelGGL(kernel, F.grid, dim3(WAVE), flds, C->stream, X.P, X.Bf, (const JointDesc*)S->d_jd, (const FlatLane*)S->flat.d_lanes, F.nanc,
+                       S->flat.nscan, S->flat.njmp, (const int*)C->d_ring, n, lgG, (const T*)C->d_fslots, F.frows, F.kexp_lo, F.ndec, (T)S->Href[0], has_hv);
+  }
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+// what the finished launch reported (the counters are on the host): the handle's history, the statistics, the instances left for k_tail
+template <typename T>
+static int flat_read_back(TailCtx<T>& X, const FlatLaunch& F, OrderUse use, bool order_pass, bool small_finish, bool queue_ready, int* next)
+{
+  loikb_solver_impl* S = X.S; Chunk* C = X.C;
+  const int n_first = X.n, n_cur = X.n_cur;
+  const hipEvent_t ev_first = queue_ready ? S->ev_t0 : C->ev_k0;
+  float ms = 0.f, t0 = 0.f, hms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, ev_first, C->ev_k1));
+  if (!queue_ready) HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
+  if (!X.small_flat) HIPCHK(hipEventElapsedTime(&hms, ev_first, C->ev_k2));
+  X.iters += C->h_counters[1];
+  if (C->h_counters[FLAT_COUNTERS_ERR]) {
+    g_last_error = (C->h_counters[FLAT_COUNTERS_ERR] & 4u) ? "internal: the flat engine's dynamic LDS does not start at LDS address 0 (lds_abs)"
+                                                           : "internal: a wavefront of the flat engine gave up waiting on its work queue";
+    return LOIKB_ERR_STATE;
+  }
+  C->stats.lean_requeues += (int)C->h_counters[LEAN_Q_REQUEUES];
+  const unsigned int escaped = C->h_counters[2];
+  C->stats.flat_built += (int)C->h_counters[FLAT_COUNTERS_BUILT];
+  {
+    std::lock_guard<std::mutex> lock(S->alloc_mu);
+    record_decades(S, C->h_counters[LEAN_DECADES_SEEN], F.kexp_lo, escaped);
+    if (order_pass) {   // (summed over the chunks of one solve: the first chunk to report starts the histogram anew -- ADVICE r05)
+      if (S->end_hist_epoch != S->solve_serial) { S->end_hist_epoch = S->solve_serial; S->end_hist_n = 0; for (int k = 0; k < 32; ++k) S->end_hist[k] = 0; }
+      for (int k = 0; k < 32; ++k) { S->end_hist[k] += C->h_counters[ORDER_DEC_HIST + k]; S->end_hist_n += C->h_counters[ORDER_DEC_HIST + k]; }
+    }
+    if (F.mur == 2) {   // (the decades somebody took up, loaded or built: the handle's history as the table's range sees it)
+      for (int k = 0; k < 32; ++k)
+        if (C->h_counters[FLAT_COUNTERS_DEC + k]) { S->seen_lo = std::min(S->seen_lo, k - 16); S->seen_hi = std::max(S->seen_hi, k - 16); }
+    }
+    S->ud_stale = true;
+  }
+  C->stats.hslots_ms += hms;
+  if (C->h_counters[FLAT_COUNTERS_DRY])  // (100 MHz clock, low words: from the ring fill of the last stage to the first empty fetch)
+    C->stats.queue_dry_ms += (double)(unsigned int)(C->h_counters[FLAT_COUNTERS_TDRY] - C->h_counters[FLAT_COUNTERS_T0]) * 1e-5;
+  if (one_per_wave(F.kind) && X.whole_set && n_first == n_cur) judge_order(S, C, n_cur, use, (double)ms - (double)hms);
+  if (S->tune.trace)
+    fprintf(stderr, "[loikb] flat engine: %6d instances on %u workgroups, done at %8.3f ms (slots %6.3f ms)  "
+                    "inst-iters %9u  wave-iters %7u  slot loads %7u (+ %u served from LDS)  escaped %u  still iterating %u\n",
+            n_first, F.grid.x, ms, hms, C->h_counters[1], C->h_counters[5], C->h_counters[6],
+            C->h_counters[FLAT_COUNTERS_SLOT_HITS], escaped, C->h_counters[3]);
+  C->stats.lean_escaped += (int)escaped;
+  C->tail_iv.emplace_back(t0, t0 + ms);
+  X.total_ms = ms; X.n = (int)C->h_counters[3]; X.list = next;
+  // (the launch took the chunk's whole home set and nothing is still iterating: k_list_unfinished has counted loikb_stats::n_unfinished)
+  if (X.n == 0 && X.whole_set && X.cur == 0 && n_first == n_cur && S->chunks.size() == 1) { C->stats.n_unfinished = (int)C->h_counters[4]; C->unfinished_counted = true; C->small_finished = small_finish; }
+  return LOIKB_OK;
+}
+
+// The flat engine (loik_flat.hpp: no loops over the tree levels) takes the place of k_hslots + k_lean when the solve's reference cost
+// allows (flat_applicable).  What is left afterwards escaped the precomputed decades: k_tail finishes it.
+template <typename T>
+static int launch_flat(TailCtx<T>& X)
+{
+  loikb_solver_impl* S = X.S; Chunk* C = X.C;
+  Params<T>& P = X.P;
+  const int n = X.n, n_cur = X.n_cur;
+  const bool small_flat = X.small_flat, whole_set = X.whole_set;
+  FlatLaunch F;
+  F.kind = flat_kind(S); F.nanc = S->flat.nanc; F.small_na = F.nanc <= FLAT_NA_SMALL; F.has_hv = S->Hv_inf_norm != 0.0;
+  F.frows = S->flat.fblk;  // (scalars per decade slot of an instance, packed columns: loik_flat.hpp)
+  F.cu_sh = std::max(1.0, S->ncu * ((double)C->B / (double)S->B));
+  F.ndec = X.ndec; F.kexp_lo = X.kexp_lo; F.dw0 = 0;
+  const bool can_build2 = S->tune.flat_build && F.kind == FlatKind::Flat2 && C->d_fmask != nullptr && !S->opt.logging && !S->per_link && href_is_scalar(S);
+  F.mur = flat_any_mu(S) ? 1 : (can_build2 ? 2 : 0);
+  if (F.mur == 1) { F.ndec = 1; F.kexp_lo = 0; }   // (the table holds mu0's slot: where every cold solve starts)
+  if (F.mur == 2) { F.ndec = S->plan.ndec; F.kexp_lo = S->plan.kexp_lo; }   // (the lazily populated table keeps its whole range: addresses, not work)
+  const size_t need = (size_t)n_cur * F.ndec * F.frows * sizeof(T);
+  if (need > C->fslots_bytes) { g_last_error = "internal: decade-slot buffer of the flat engine smaller than the chunk"; return LOIKB_ERR_STATE; }
+  P.max_launch_iters = S->opt.max_iter + 1;
+  const int mode_keep = P.mode;
+  if (whole_set && S->zero_state && S->tune.flat_zero_state) P.mode |= MODE_ZERO_STATE;
+  // (queue_ready: this solve's reset launch left list, ring and counters -- nothing lies between the solve's first event and this point)
+  const bool queue_ready = small_flat && C->queue_ready && n_cur == S->B;
+  C->queue_ready = false;
+  if (!queue_ready && small_flat) hipLaunchKernelGGL(k_queue_init_iota, grid1(std::max(C->ring_cap, NCOUNTERS)), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, C->d_slots, n_cur, C->d_counters, NCOUNTERS);
+  else if (!queue_ready) HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
+  if (!queue_ready) HIPCHK(hipEventRecord(C->ev_k0, C->stream));
+  OrderUse use;
+  int rc = take_up_order(S, C, !small_flat && whole_set && X.list == C->d_slots && n == n_cur && one_per_wave(F.kind), true, n_cur, &use);
+  if (rc) return rc;
+  F.slice = flat_launch_slice(S, C, F.kind, F.mur, n, n_cur, use.ordered);
+  F.nw = F.ndec;
+  if (F.mur == 2) flat_table_window(S, F, n);
+  if (F.mur == 0) { F.ndec = X.ndec; F.kexp_lo = X.kexp_lo; F.nw = F.ndec; F.dw0 = 0; }   // (the range the handle's history asks for, as ever)
+  if (F.ndec > 0) {
+    const dim3 hgrid((unsigned)((n + X.ipw - 1) / X.ipw));
+    // [65][22] exchange rows (pass B's L columns, [NA + 1][64], live in them afterwards) + [65][6] S^w + the constraints' A^T A + the decades' mu
+    const size_t slds = (std::max((size_t)(WAVE + 1) * 22, (size_t)((F.small_na ? FLAT_NA_SMALL : FLAT_MAXA) + 1) * WAVE) + (size_t)(WAVE + 1) * 6 +
+                         (size_t)X.ipw * S->nc * 21 + 16) * sizeof(T);
+    auto* fslots = F.small_na ? k_fslots<T, FLAT_NA_SMALL> : k_fslots<T, FLAT_MAXA>;
+    hipLaunchKernelGGL(fslots, hgrid, dim3(WAVE), slds, C->stream, P, X.Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
+                       (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth, F.nanc, F.frows, S->flat.njmp, X.list, n,
+                       X.G, (T*)C->d_fslots, F.kexp_lo, F.ndec, F.dw0, F.nw, F.mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
+    HIPCHK(hipGetLastError());
+  }
+  // (no event between k_fslots and the engine in the short sequence: loikb_stats::hslots_ms reads 0 there -- an event costs a lone
+  //  problem's Solve() 2.5 us of 116: profiles/r06_o_small_finish_ab.jsonl)
+  if (!small_flat) HIPCHK(hipEventRecord(C->ev_k2, C->stream));
+  if (!small_flat) hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, X.list, n, C->d_counters);
+  if ((rc = launch_flat_kernel(X, F))) return rc;
+  P.mode = mode_keep;
+  int* next = (X.list == C->d_slots) ? C->d_slots2 : C->d_slots;
+  const bool small_finish = small_flat && S->tune.small_finish;
+  if (small_finish)   // (one workgroup: the list, the counts, and the launch's counters into the pinned host copy -- loik_lean.hpp)
+    hipLaunchKernelGGL(k_small_finish<T>, dim3(1), dim3(256), 0, C->stream, X.A.tiles, S->L, X.list, n, next, C->d_counters, NCOUNTERS, C->h_counters);
+  else
+    hipLaunchKernelGGL(k_list_unfinished<T>, grid1(n), dim3(256), 0, C->stream, X.A.tiles, S->L, X.list, n, next, C->d_counters + 3);
+  HIPCHK(hipGetLastError());
+  C->stats.launches++; C->stats.tail_launches++; C->stats.lean_launches++; C->stats.flat_launches++;
+  if (F.kind == FlatKind::Flat2) C->stats.flat_split_launches++;
+  HIPCHK(hipEventRecord(C->ev_k1, C->stream));
+  // (the order pass is skipped in the short sequence: every instance gets a wavefront at once, no order to leave)
+  const bool order_pass = !small_flat && S->tune.flat_order && whole_set && n == n_cur && one_per_wave(F.kind) && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
+  if (!order_pass && !small_finish) HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
+  if (order_pass && (rc = leave_order<T>(S, C, X.A, n_cur, true))) return rc;
+  HIPCHK(hipStreamSynchronize(C->stream));
+  return flat_read_back(X, F, use, order_pass, small_finish, queue_ready, next);
+}
+
+// ---- the lean engine: k_hslots + k_lean, two wavefronts per SIMD (loik_lean.hpp).  H_i / Dinv_i / UDinv_i of the listed instances are
+// precomputed for the decades mu0 * 10^(kexp_lo .. kexp_lo + ndec - 1) (k_hslots); instances whose mu leaves them come back unfinished
+// and go through k_tail.
+template <typename T>
+static int launch_lean(TailCtx<T>& X)
+{
+  loikb_solver_impl* S = X.S; Chunk* C = X.C;
+  Params<T>& P = X.P;
+  const Bufs<T>& Bf = X.Bf;
+  const int n = X.n, n_cur = X.n_cur, G = X.G, ipw = X.ipw, ndec = X.ndec, kexp_lo = X.kexp_lo;
+  const int* list = X.list;
+  const bool whole_set = X.whole_set, per_link = S->per_link;  // (UpdateReferences' table: the PERLINK instantiations of k_hslots / k_lean)
+  // decade slots are indexed by the instance's slot in the set (relaunches with shorter lists find them again);
+  // the buffer was sized for the chunk at SolveInit (ensure_hslots)
+  const size_t need = (size_t)n_cur * ndec * HSLOT_PAIRS * G * 2 * sizeof(T);
+  if (need > C->hslots_bytes) { g_last_error = "internal: decade-slot buffer smaller than the chunk"; return LOIKB_ERR_STATE; }
+  const int waves_cu = S->plan.lean_waves_cu;
+  const int ltw = S->plan.lean_wg_waves;  // wavefronts per workgroup
+  const size_t lds = ltw * lean_lds_bytes<T>(S->nc, G, S->a_shared);
+  if (lds > 64 * 1024) {
+    HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  const int wg_per_cu = S->tune.lean_wg_per_cu > 0 ? S->tune.lean_wg_per_cu : waves_cu / ltw;
+  const int wg_cap = wg_per_cu * std::max(1, (int)(S->ncu * ((double)C->B / (double)S->B) + 0.5));
+  HIPCHK(hipEventRecord(C->ev_k0, C->stream));
+  OrderUse use;
+  int rc = take_up_order(S, C, whole_set && list == C->d_slots && n == n_cur, whole_set, n_cur, &use);
+  if (rc) return rc;
+  P.max_launch_iters = S->opt.max_iter + 1;
+  const int wg_needed = (n + ipw * ltw - 1) / (ipw * ltw);
+  const dim3 grid((unsigned)std::min(wg_needed, wg_cap));
+  HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
+  const dim3 hgrid((unsigned)((n + ipw - 1) / ipw));
+  const size_t hlds = (size_t)(WAVE + 1) * 22 * sizeof(T);
+  auto* hslots = per_link ? k_hslots<T, false, true> : S->href_diag ? k_hslots<T, true> : k_hslots<T, false>;
+  hipLaunchKernelGGL(hslots, hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
+                     (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G, (T*)C->d_hslots, kexp_lo, ndec);
+  HIPCHK(hipEventRecord(C->ev_k2, C->stream));
+  hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, list, n, C->d_counters);
+  auto* lean = per_link ? k_lean<T, false, true> : S->href_diag ? k_lean<T, true> : k_lean<T, false>;
+  hipLaunchKernelGGL(lean, grid, dim3(WAVE * ltw), lds, C->stream, P, Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
+                     (const int*)S->d_child_list, S->maxdepth, S->maxchild, C->d_ring, n, G, (const T*)C->d_hslots, kexp_lo, ndec, S->multi_from);
+  HIPCHK(hipGetLastError());
+  // the instances that are still iterating: k_tail's list (ping-pong between the two list buffers)
+  int* next = (list == C->d_slots) ? C->d_slots2 : C->d_slots;
+  hipLaunchKernelGGL(k_list_unfinished<T>, grid1(n), dim3(256), 0, C->stream, X.A.tiles, S->L, list, n, next, C->d_counters + 3);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(C->ev_k1, C->stream));
+  HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
+  const bool lean_orders = S->tune.flat_order && whole_set && n == n_cur && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
+  if (lean_orders && (rc = leave_order<T>(S, C, X.A, n_cur, false))) return rc;
+  HIPCHK(hipStreamSynchronize(C->stream));
+  float ms = 0.f, t0 = 0.f, hms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, C->ev_k0, C->ev_k1));
+  if (lean_orders) judge_order(S, C, n_cur, use, (double)ms);
+  HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
+  X.iters += C->h_counters[1];
+  const unsigned int escaped = C->h_counters[2];
+  {
+    std::lock_guard<std::mutex> lock(S->alloc_mu);
+    record_decades(S, C->h_counters[LEAN_DECADES_SEEN], kexp_lo, escaped);
+  }
+  C->stats.lean_requeues += (int)C->h_counters[LEAN_Q_REQUEUES];
+  HIPCHK(hipEventElapsedTime(&hms, C->ev_k0, C->ev_k2));
+  C->stats.hslots_ms += hms;
+  if (S->tune.trace)
+    fprintf(stderr, "[loikb] lean engine: %6d instances on %u workgroups, done at %8.3f ms"
+                    "  inst-iters %9u  wave-iters %7u slot loads %7u  escaped %u  still iterating %u  requeued %u\n",
+            n, grid.x, ms, C->h_counters[1], C->h_counters[5], C->h_counters[6], escaped,
+            C->h_counters[3], C->h_counters[LEAN_Q_REQUEUES]);
+  C->stats.launches++; C->stats.tail_launches++; C->stats.lean_launches++;
+  X.total_ms = ms; X.n = (int)C->h_counters[3]; X.list = next;
+  C->tail_iv.emplace_back(t0, t0 + ms);
+  C->stats.lean_escaped += (int)escaped;
+  return LOIKB_OK;
+}
+
+// ---- k_tail: ONE launch of `tw` wavefronts per workgroup, as many workgroups as the chunk's share of the CUs holds (one wavefront per
+// SIMD: register budget); the lane groups pull the listed instances from an atomic queue head until the list is empty.
+template <typename T>
+static int launch_tail_kernel(TailCtx<T>& X, int tw, size_t lds)
+{
+  loikb_solver_impl* S = X.S; Chunk* C = X.C;
+  const int n = X.n, n_cur = X.n_cur;
+  const int cu_share = std::max(1, (int)(S->ncu * (TAIL_WAVES / tw) * ((double)C->B / (double)S->B) + 0.5));
+  X.P.max_launch_iters = S->opt.max_iter + 1;
+  const int wg_needed = (n + X.ipw * tw - 1) / (X.ipw * tw);
+  const dim3 grid((unsigned)std::min(wg_needed, cu_share));
+  HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
+  HIPCHK(hipEventRecord(C->ev_k0, C->stream));
+  // k_tail as the engine of a whole batch (OSQP rule, robots outside the on-chip engines' domain): longest first from the handle's
+  // previous solve, as in the flat and lean engines (its lane groups pull the list in order)
+  const bool tail_whole = X.whole_set && X.list == C->d_slots && n == n_cur && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS) && S->tune.flat_order;
+  OrderUse use;
+  int rc = take_up_order(S, C, tail_whole, tail_whole, n_cur, &use);
+  if (rc) return rc;
+  auto* kernel = S->href_diag ? k_tail<T, true> : k_tail<T, false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(WAVE * tw), lds, C->stream, X.P, X.Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
+                     (const int*)S->d_child_list, S->maxdepth, S->maxchild, X.list, n, X.G);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(C->ev_k1, C->stream));
+  HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
+  if (tail_whole && (rc = leave_order<T>(S, C, X.A, n_cur, false))) return rc;
+  HIPCHK(hipStreamSynchronize(C->stream));
+  float ms = 0.f, t0 = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, C->ev_k0, C->ev_k1));
+  HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
+  if (tail_whole) judge_order(S, C, n_cur, use, (double)ms);
+  C->tail_iv.emplace_back(t0, t0 + ms);
+  X.total_ms += ms;
+  X.iters += C->h_counters[1];
+  if (S->tune.trace)
+    fprintf(stderr, "[loikb] tail launch: %6d instances on %u workgroups  %8.3f ms  inst-iters %9u (%.1f M/s)"
+                    "  wave-iters %7u H-rebuild %3.0f%%\n",
+            n, grid.x, ms, C->h_counters[1], C->h_counters[1] / ms / 1e3,
+            C->h_counters[5], 100.0 * C->h_counters[6] / (C->h_counters[5] ? C->h_counters[5] : 1));
+  C->stats.launches++; C->stats.tail_launches++;
+  return LOIKB_OK;
+}
+
+// Every on-chip solve: the list of the set's live instances, then the flat engine or else the lean engine, then k_tail for what is left.
 template <typename T>
 int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, int n_live, double* ms_out,
              unsigned long long* iters_out, bool whole_set = false)
 {
   loikb_solver_impl::Set& A = C->set[cur];
   const int nw = (n_cur + WAVE - 1) / WAVE;
+  const bool flat_here = flat_applicable(S) && (P.mode & MODE_CACHE_H);
+  // (the builds with ONE instance per wavefront -- k_flat2, k_flat1 -- take any number of instances: a lone instance iterates in 2.3 us
+  //  there against k_tail's 10-12 us, and the reference's own call is one problem, tests/loik-loid.cpp:987-1032; k_flat, two instances
+  //  per wavefront, from 64 as ever)
+  const bool flat_1pw = one_per_wave(flat_kind(S));
   // Small batches on the one-instance-per-wavefront flat engines (every instance gets a wavefront at once: no schedule to prepare, no order
   // to leave for the next solve): the list, the ring and the counters come from ONE kernel, the order pass is skipped, and n_unfinished is
   // counted by k_list_unfinished -- 8 launches / copies and one synchronisation less per Solve() (B = 1: 0.168 -> see profiles/r06_*_small_batches)
-  int G0 = 8;
-  while (G0 < S->nb) G0 <<= 1;
-  const bool small_flat = whole_set && cur == 0 && S->chunks.size() == 1 && sizeof(T) == 8 && S->tune.flat_split && flat_applicable(S) && (P.mode & MODE_CACHE_H) &&
-                          ((G0 == F2G && S->flat.ok && S->flat.nanc <= FLAT_NA_SMALL) || G0 == WAVE) && n_cur <= S->tune.flat_small_batch &&
+  const bool small_flat = whole_set && cur == 0 && S->chunks.size() == 1 && flat_1pw && flat_here && n_cur <= S->tune.flat_small_batch &&
                           n_cur >= std::max(1, S->tune.flat_min_batch);
-  if (whole_set && small_flat) {
-    // (k_queue_init_iota below, once the ring's size is known to the flat path)
-  } else if (whole_set) {
-    // every slot of the set (finished instances, if any, stop at once inside the kernel)
+  if (whole_set && !small_flat) {
+    // every slot of the set (finished instances, if any, stop at once inside the kernel; the short sequence: k_queue_init_iota in launch_flat)
     hipLaunchKernelGGL(k_list_iota, grid1(n_cur), dim3(256), 0, C->stream, C->d_slots, n_cur);
-  } else {
+  } else if (!whole_set) {
     C->h_wave.resize(2 * (size_t)nw + 2);
     int* cnt = C->h_wave.data();
     int* off = cnt + nw + 1;
@@ -1917,12 +2430,10 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
     hipLaunchKernelGGL(k_list_live<T>, dim3(nw), dim3(WAVE), 0, C->stream, A.tiles, S->L, n_cur, A.wave_off, C->d_slots);
   }
   HIPCHK(hipGetLastError());
-  Bufs<T> Bf = make_bufs<T>(S, C, cur);
+  const int G = lanes_per_instance(S);
+  TailCtx<T> X{S, C, P, make_bufs<T>(S, C, cur), A, cur, n_cur, whole_set, small_flat, G, WAVE / G, S->plan.ndec, S->plan.kexp_lo, C->d_slots, n_live};
   P.B = n_cur;
-  int G = 8;  // lanes per instance: smallest power of two >= nb
-  while (G < S->nb) G <<= 1;
-  const int ipw = WAVE / G;
-  int tw = S->tune.tail_waves;  // wavefronts per workgroup
+  int tw = S->tune.tail_waves;  // k_tail's wavefronts per workgroup
   while (tw > 1 && tw * tail_lds_bytes<T>(S->nc, G) > 160 * 1024) --tw;
   const size_t lds = tw * tail_lds_bytes<T>(S->nc, G);
   if (lds > 160 * 1024) { g_last_error = "tail kernel: constraint data exceeds the LDS of a CU"; return LOIKB_ERR_ARG; }
@@ -1930,546 +2441,30 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
     HIPCHK(hipFuncSetAttribute((const void*)k_tail<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIPCHK(hipFuncSetAttribute((const void*)k_tail<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
-  // ONE launch: as many workgroups as the chunk's share of the CUs holds (one wavefront per SIMD: register budget);
-  // the lane groups pull the listed instances from an atomic queue head until the list is empty.
-  const int cu_share = std::max(1, (int)(S->ncu * (TAIL_WAVES / tw) * ((double)C->B / (double)S->B) + 0.5));
-  int n = n_live;
-  double total_ms = 0.0;
-  unsigned long long iters = 0;
-  const bool trace = S->tune.trace;
-  const int* list = C->d_slots;
-  // ---- lean tail kernel: two wavefronts per SIMD (loik_lean.hpp).  H_i / Dinv_i / UDinv_i of the listed instances are
-  // precomputed for the decades mu0 * 10^(0 .. ndec-1) (k_hslots); instances whose mu leaves them come back unfinished
-  // and go through k_tail below.
-  {
-    // decades of mu with precomputed slots: mu0 * 10^(kexp_lo .. kexp_lo + ndec - 1).  The DEFAULT rule moves mu up from
-    // mu0 in the first iterations and then mostly oscillates between two or three decades (Talos workload: 0..7 seen,
-    // < 0 never); an instance that leaves the range is finished by k_tail.
-    // (the table is built as a pipeline over the tree levels: a decade more costs one step)
-    // Every decade costs k_hslots a pipeline step and 176 B x joints per instance of HBM writes (0.14 ms per decade on the
-    // headline): after the first solve of a handle the table covers the decades its instances were seen in, plus one on
-    // each side (the headline workload lives in 0..6 of the configured -2..7: 21.8 -> 21.2 ms).  mu restarts at mu0 in every
-    // solve, batches of one application resemble each other; when they do not, the instance that leaves the table escapes
-    // to k_tail as always and the full range is back for the next solve.
-    int ndec = S->plan.ndec, kexp_lo = S->plan.kexp_lo;
-    // (a logged solve keeps the whole configured range: an instance that escaped to k_tail would stop writing its lists)
-    if (S->tune.lean_adapt && S->seen_hi >= S->seen_lo && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS) && !S->opt.logging) {
-      const int lo = std::max(kexp_lo, S->seen_lo - 1), hi = std::min(kexp_lo + ndec - 1, S->seen_hi + 1);
-      if (hi >= lo) { kexp_lo = lo; ndec = hi - lo + 1; }
-    }
-    const int ndec_hist = ndec, kexp_lo_hist = kexp_lo;
-    const size_t wave_lds = lean_lds_bytes<T>(S->nc, G, S->a_shared);
-    // ---- the flat engine (loik_flat.hpp: no loops over the tree levels) takes the place of k_hslots + k_lean when the solve's
-    // reference cost allows (H_ref = h I for all links)
-    // (the builds with ONE instance per wavefront -- k_flat2, k_flat1 -- take any number of instances: a lone instance iterates in 2.3 us
-    //  there against k_tail's 10-12 us, and the reference's own call is one problem, tests/loik-loid.cpp:987-1032; k_flat, two instances
-    //  per wavefront, from 64 as ever)
-    const bool flat_one_per_wave = S->tune.flat_split && sizeof(T) == 8 && ((G == F2G && S->flat.ok && S->flat.nanc <= FLAT_NA_SMALL) || G == WAVE);
-    const bool flat_ok = flat_applicable(S) && (P.mode & MODE_CACHE_H) && n >= (flat_one_per_wave ? std::max(1, S->tune.flat_min_batch) : 64);
-    if (flat_ok) {
-      const int nanc = S->flat.nanc;
-      const bool small_na = nanc <= FLAT_NA_SMALL;
-      const int frows = S->flat.fblk;  // (scalars per decade slot of an instance, packed columns: loik_flat.hpp)
-      // the rule that moves mu (k_flat2's MUR): 1 = OSQP's -- no table, every change of mu is an in-wave build --, 2 = decade steps with
-      // the in-wave builder for the decades the table lacks (LOIKB_FLAT_BUILD=1), 0 = decade steps, the table or k_tail
-      // (k_flat2 only: for k_flat1 -- 33..64 joints -- it was built and measured in round 6 and did not pay: loik_flat2.hpp)
-      const bool can_build2 = S->tune.flat_build && G == F2G && small_na && sizeof(T) == 8 && S->tune.flat_split && C->d_fmask != nullptr &&
-                              !S->opt.logging && !S->per_link && href_is_scalar(S);
-      int mur = flat_any_mu(S) ? 1 : (can_build2 ? 2 : 0);
-      if (mur == 1) { ndec = 1; kexp_lo = 0; }   // (the table holds mu0's slot: where every cold solve starts)
-      if (mur == 2) { ndec = S->plan.ndec; kexp_lo = S->plan.kexp_lo; }   // (the lazily populated table keeps its whole range: addresses, not work)
-      const size_t need = (size_t)n_cur * ndec * frows * sizeof(T);
-      if (need > C->fslots_bytes) { g_last_error = "internal: decade-slot buffer of the flat engine smaller than the chunk"; return LOIKB_ERR_STATE; }
-      const int has_hv = S->Hv_inf_norm != 0.0;
-      const size_t flds = small_na ? flat_lds_bytes<T, FLAT_NA_SMALL>(S->nc, G, S->a_shared, has_hv) : flat_lds_bytes<T, FLAT_MAXA>(S->nc, G, S->a_shared, has_hv);
-      int lgG = 3;
-      while ((1 << lgG) < G) ++lgG;
-      const double cu_sh = std::max(1.0, S->ncu * ((double)C->B / (double)S->B));
-      const int cap_lat = (int)std::min<size_t>(4, (160 * 1024) / flds) * (int)(cu_sh + 0.5);  // k_flat: one wavefront per SIMD
-      // two lanes per joint where the layout applies: 17..32 joints, few ancestors, fp64, no lists to write
-      const bool split = S->tune.flat_split && G == F2G && small_na && sizeof(T) == 8;
-      // one instance per wavefront anyway (33..64 joints): the build with nested loops, prefix-sum subtree sums, DPP fold
-      const bool one = S->tune.flat_split && G == WAVE && sizeof(T) == 8;
-      P.max_launch_iters = S->opt.max_iter + 1;
-      const int mode_keep = P.mode;
-      if (whole_set && S->zero_state && S->tune.flat_zero_state) P.mode |= MODE_ZERO_STATE;
-      // (queue_ready: this solve's reset launch left list, ring and counters -- nothing lies between the solve's first event and this point)
-      const bool queue_ready = small_flat && C->queue_ready && n_cur == S->B;
-      C->queue_ready = false;
-      if (queue_ready) {}
-      else if (small_flat) hipLaunchKernelGGL(k_queue_init_iota, grid1(std::max(C->ring_cap, NCOUNTERS)), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, C->d_slots, n_cur, C->d_counters, NCOUNTERS);
-      else HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
-      const hipEvent_t ev_first = queue_ready ? S->ev_t0 : C->ev_k0;
-      if (!queue_ready) HIPCHK(hipEventRecord(C->ev_k0, C->stream));
-      // longest first: the order the previous solve of this handle left (k_order_*, loik_lean.hpp) when this launch takes the same
-      // whole set; the decade slots are indexed by the INSTANCE slot (sidx / lidx), so k_fslots and the engine find them under any order of the list
-      const bool ordered = !small_flat && whole_set && list == C->d_slots && n == n_cur && (split || one) && order_usable(S, C, n_cur);
-      const bool order_was_stale = ordered && C->order_epoch != S->inputs_epoch;
-      if (C->order_holdoff > 0) --C->order_holdoff;
-      if (ordered) HIPCHK(hipMemcpyAsync(C->d_slots, C->d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, C->stream));
-      C->stats.flat_ordered += ordered ? 1 : 0;
-      // The decades k_fslots builds now: all of the table, or (MUR = 2) a window of it -- the rest is populated by the instances that get
-      // there (k_flat2<.., MUR = 2>, loik_flat2.hpp).  The window: LOIKB_FLAT_WINDOW=lo,n as given (any launch); else, for a time-sliced
-      // launch of a handle with a history, from the decade its previous solve's instances STARTED in (0 after a cold reset) to the one
-      // 97 % of them had ENDED in or below (k_order_count's histogram) -- the headline's instances end in decades 0..3 (8.7 / 23.8 / 60.6 /
-      // 6.9 %) of the 0..6 the handle's history says were visited by somebody: four decades built instead of nine, k_fslots 0.9 -> 0.55 ms,
-      // and the 0.2 % that go further build their slot once each (70 us).  Without a window the launch runs the build without the builder
-      // (MUR = 0: its iteration loop is 1-3 % shorter).
-      int dw0 = 0, nw = ndec;
-      if (mur == 2) {
-        int wlo = 0, whi = -1;
-        // (whether this launch is time-sliced, decided ONCE: the park buffer's size included -- ADVICE r05)
-        int q = (split && !S->opt.logging) ? flat_slice_for(S, n, ordered) : 0;
-        if (q > 0 && (C->d_park == nullptr || (size_t)n_cur * flat2_park_stride(S->nc, true) * sizeof(double) > C->park_bytes)) q = 0;
-        const bool win_ok = q > 0 && C->d_park != nullptr;   // (a window on time-sliced launches only: the builder beside the unsliced loop costs more than k_fslots saves)
-        if (S->tune.flat_win_n > 0) { wlo = S->tune.flat_win_lo; whi = wlo + S->tune.flat_win_n - 1; }
-        else if (S->tune.flat_build == 2 && win_ok && S->end_hist_n > 0) {
-          unsigned long long cum = 0;
-          int k03 = 99, k97 = 99;
-          for (int k = 0; k < 32; ++k) {
-            cum += S->end_hist[k];
-            if (k03 == 99 && cum * 100 >= 3ull * S->end_hist_n) k03 = k - 16;
-            if (k97 == 99 && cum * 100 >= 97ull * S->end_hist_n) k97 = k - 16;
-          }
-          wlo = std::min(0, k03); whi = std::max(0, k97);
-        }
-        else if (S->tune.flat_build == 2 && win_ok && n >= 49152) {
-          // No history (a handle's first solve): the five decades from mu0's upwards.  The rule moves mu up far more often than down, and
-          // rarely more than three decades; whoever leaves the window builds the slot once (results are bit-identical whatever the window:
-          // tests/test_engines.py::test_flat_lazy_table_*).  Measured, time-sliced headline launches, ms per solve incl. k_fslots, full
-          // table / this window: 65 536 instances 8.67 / 8.32, 131 072: 14.96 / 14.64, 262 144: 29.16 / 28.63; 32 768 and below no gain
-          // (5.45 / 5.49), nor on unsliced launches (the builder beside an unsliced loop costs it more than k_fslots saves:
-          // 65 536 ordered 7.44 / 7.59): profiles/r05_i_lazy_window_sizes.txt
-          wlo = 0; whi = 4;
-        }
-        const int lo = std::max(wlo, kexp_lo), hi = std::min(whi, kexp_lo + ndec - 1);
-        if (hi >= lo && (hi - lo + 1) < ndec) { dw0 = lo - kexp_lo; nw = hi - lo + 1; }
-        else if (S->tune.flat_build == 2) mur = 0;   // (auto: nothing to leave out -- the build without the builder)
-      }
-      if (mur == 0) {   // (the range the handle's history asks for, as ever)
-        ndec = ndec_hist; kexp_lo = kexp_lo_hist;
-        nw = ndec; dw0 = 0;
-      }
-      const int win_bits = (int)(((nw >= 16 ? 0xFFFFu : ((1u << nw) - 1u)) << dw0) & 0xFFFFu);
-      if (ndec > 0) {
-        const dim3 hgrid((unsigned)((n + ipw - 1) / ipw));
-        // [65][22] exchange rows (pass B's L columns, [NA + 1][64], live in them afterwards) + [65][6] S^w + the constraints' A^T A + the decades' mu
-        const size_t slds = (std::max((size_t)(WAVE + 1) * 22, (size_t)((small_na ? FLAT_NA_SMALL : FLAT_MAXA) + 1) * WAVE) + (size_t)(WAVE + 1) * 6 +
-                             (size_t)ipw * S->nc * 21 + 16) * sizeof(T);
-        if (small_na)
-          hipLaunchKernelGGL((k_fslots<T, FLAT_NA_SMALL>), hgrid, dim3(WAVE), slds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                             (const TailTopo*)S->d_topo, (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth,
-                             nanc, frows, S->flat.njmp, list, n, G, (T*)C->d_fslots, kexp_lo, ndec, dw0, nw,
-                             mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
-        else
-          hipLaunchKernelGGL((k_fslots<T, FLAT_MAXA>), hgrid, dim3(WAVE), slds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                             (const TailTopo*)S->d_topo, (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth,
-                             nanc, frows, S->flat.njmp, list, n, G, (T*)C->d_fslots, kexp_lo, ndec, dw0, nw,
-                             mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
-        HIPCHK(hipGetLastError());
-      }
-      // (no event between k_fslots and the engine in the short sequence: loikb_stats::hslots_ms reads 0 there -- an event costs a lone
-      //  problem's Solve() 2.5 us of 116: profiles/r06_o_small_finish_ab.jsonl)
-      if (!small_flat) HIPCHK(hipEventRecord(C->ev_k2, C->stream));
-      const int n_first = n;
-      bool small_finish = false;
-      dim3 grid((unsigned)std::min((n + ipw - 1) / ipw, cap_lat));
-      {
-        if (!small_flat) hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, list, n, C->d_counters);
-        if (split || one) {   // (what only the in-wave builder / the lazily populated table read, behind one kernel argument)
-          // (uploaded when one of the pointers changes -- synchronously, from the chunk's own copy: ADVICE r05)
-          if (C->d_aux == nullptr) HIPCHK(hipMalloc((void**)&C->d_aux, 4 * sizeof(void*)));
-          const void* auxh[4] = {S->d_topo, S->d_child_list, C->d_fmask, nullptr};
-          if (memcmp(auxh, C->aux_h, sizeof(auxh)) != 0) {
-            memcpy(C->aux_h, auxh, sizeof(auxh));
-            HIPCHK(hipStreamSynchronize(C->stream));
-            HIPCHK(hipMemcpy(C->d_aux, C->aux_h, sizeof(auxh), hipMemcpyHostToDevice));
-          }
-        }
-        if (split) {
-          // k_flat2: two lanes per joint, one instance per wavefront, two wavefronts per SIMD (loik_flat2.hpp)
-          const size_t lds2 = flat2_lds_bytes<FLAT_NA_SMALL>(S->nc, has_hv != 0, mur == 1);
-          int per_cu = (int)std::min<size_t>((size_t)8, (160 * 1024) / lds2);
-          if (S->tune.lean_wg_per_cu > 0) per_cu = std::min(per_cu, S->tune.lean_wg_per_cu);
-          grid = dim3((unsigned)std::min(n, per_cu * (int)(cu_sh + 0.5)));
-          // Round-robin time slicing inside the launch (k_flat2<.., SLICED>).  Iteration counts are heavy-tailed and unknown: run to
-          // completion in arrival order, the 999-iteration instances that are fetched late keep the launch alive ~3 ms after
-          // the queue ran dry.  With a slice of 160 iterations every long runner has done ~500 by then.  Measured (Talos-32,
-          // one GPU, ms per batch without / with): 8192: 4.23 / 4.39, 16 384: 5.46 / 5.61, 32 768: 8.13 / 7.80, 65 536: 13.28 /
-          // 12.29, 131 072: 23.13 / 22.24, 262 144: 44.19 / 44.48 -- a switch costs a store, an agent-scope reload and the set-up of
-          // an instance (~25 us), small batches are one straggler chain whatever the order, large ones hide it in their bulk:
-          // on by default between 12 and 96 instances per resident wavefront.  Slices of 32 / 64 / 96 / 128 / 192 / 256 / 384
-          // iterations on the headline: 19.6 / 13.7 / 12.40 / 12.36 / 12.33 / 12.45 / 12.76 ms.
-          const int resident = (int)grid.x;
-          // (an ordered launch runs to completion: its long runners start first and must not go to the back of the queue.  Time
-          //  slices for everything behind the predicted-long prefix were tried: the SLICED build's agent-scope loads / stores of
-          //  the records cost the short instances more than the slices bring -- 12.2 ms against 10.6)
-          // Round 4: OFF by default.  A sliced-out instance is now parked (its lane state and LDS blocks in a lane-contiguous record of
-          // its own, ~40 row accesses each way, the ticket for the next entry drawn with the stores, the decade slot fetched with the
-          // record: three round trips instead of ten through the tile records) -- and with the iteration at 2.9 instead of 3.6 us the
-          // slices still bring only 0..2.5 %: headline batch in arrival order, k_flat2 alone, ms: unsliced 9.47, slices of 192 / 128 /
-          // 96 / 64 / 48 / 32: 9.32 / 9.28 / 9.32 / 9.76 / 11.45 / 13.9; 131 072 instances 16.73 -> 16.31 (128); 32 768: 5.87 -> 5.82;
-          // 16 384 and below: slower (one straggler chain whatever the order).  A switch costs ~27 us of a wavefront under load (five
-          // dependent trips to the L2 / HBM at ~2.5 us each when 2048 wavefronts share them), a slice of 64 iterations 190 us.
-          // LOIKB_FLAT_SLICE=q switches it on.
-          // End of round 4: ON again for arrival-order launches of >= 32 768 instances (flat_slice_for has the numbers).
-          const size_t park_need = (size_t)n_cur * flat2_park_stride(S->nc, true) * sizeof(double);
-          (void)resident;
-          int quantum = flat_slice_for(S, n, ordered);
-          if (quantum > 0 && (C->d_park == nullptr || park_need > C->park_bytes)) quantum = 0;
-          // (not for a handle on a stream of its own: that is how batches are kept in flight side by side, and then the other
-          //  batch's bulk fills this one's ragged end -- slicing only adds its switches, and its wavefronts that wait for queue
-          //  entries hold slots the other launch could use: two headline batches in flight 21.5 ms per pair without, 24.9 with)
-#define LOIKB_LAUNCH_FLAT2(...)                                                                                                 \
-  hipLaunchKernelGGL((k_flat2<FLAT_NA_SMALL, ##__VA_ARGS__>), grid, dim3(WAVE), lds2, C->stream,                                 \
-                     *reinterpret_cast<const Params<double>*>(&P), *reinterpret_cast<const Bufs<double>*>(&Bf),                  \
-                     (const JointDesc*)S->d_jd, (const FlatLane*)S->flat.d_lanes, nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, \
-                     (const double*)C->d_fslots, frows, kexp_lo, ndec, (double)S->Href[0], (int)((unsigned int)has_hv | ((unsigned int)(S->maxdepth & 0xFF) << 8) | ((unsigned int)win_bits << 16)), C->ring_cap - 1, quantum,       \
-                     (double*)C->d_park, flat2_park_stride(S->nc, true), (const void* const*)C->d_aux)
-          const int hm = S->per_link ? 3 : href_is_scalar(S) ? 0 : href_is_diagonal(S) ? 1 : 2;
-          if (mur == 1) {
-            // (OSQP's rule runs unsliced unless LOIKB_FLAT_SLICE asks: a parked instance rebuilds its factors when it is taken up again --
-            //  headline batch, first solve: 12.7 ms with the default slices, 11.4 without: profiles/r05_d_mu_rules.jsonl)
-            if (S->tune.flat_slice < 0) quantum = 0;
-            if (hm == 3) { quantum = 0; LOIKB_LAUNCH_FLAT2(false, 3, false, 1); }
-            else if (hm == 2) { quantum = 0; LOIKB_LAUNCH_FLAT2(false, 2, false, 1); }
-            else if (hm == 1) { quantum = 0; LOIKB_LAUNCH_FLAT2(false, 1, false, 1); }
-            else if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 0, false, 1);
-            else LOIKB_LAUNCH_FLAT2(false, 0, false, 1);
-          }
-          else if (mur == 2) {
-            if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 0, false, 2); else LOIKB_LAUNCH_FLAT2(false, 0, false, 2);
-          }
-          else if (S->opt.logging) {   // (the SolverInfo lists: unsliced; a diagonal reference weight goes as a general one)
-            quantum = 0;
-            if (hm == 3) LOIKB_LAUNCH_FLAT2(false, 3, true);
-            else if (hm >= 1) LOIKB_LAUNCH_FLAT2(false, 2, true);
-            else LOIKB_LAUNCH_FLAT2(false, 0, true);
-          }
-          else if (hm == 3) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 3); else LOIKB_LAUNCH_FLAT2(false, 3); }
-          else if (hm == 2) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 2); else LOIKB_LAUNCH_FLAT2(false, 2); }
-          else if (hm == 1) { if (quantum > 0) LOIKB_LAUNCH_FLAT2(true, 1); else LOIKB_LAUNCH_FLAT2(false, 1); }
-          else if (quantum > 0) LOIKB_LAUNCH_FLAT2(true);
-          else LOIKB_LAUNCH_FLAT2();
-#undef LOIKB_LAUNCH_FLAT2
-        } else if (one) {
-          // one decade slot in LDS instead of two when that buys wavefronts per CU (whole body, four task constraints: 6 -> 8)
-          auto lds_of = [&](int bufs) { return small_na ? flat1_lds_bytes<FLAT_NA_SMALL>(S->nc, has_hv != 0, bufs) : flat1_lds_bytes<FLAT_MAXA>(S->nc, has_hv != 0, bufs); };
-          // (OSQP's rule: the in-wave builder's rows lie over both slots -- two it is)
-          const int one_buf = mur != 1 && std::min<size_t>(8, (160 * 1024) / lds_of(1)) > std::min<size_t>(8, (160 * 1024) / lds_of(2));
-          const size_t lds1 = lds_of(one_buf ? 1 : 2);
-          int per_cu1 = (int)std::min<size_t>(8, (160 * 1024) / lds1);
-          if (S->tune.lean_wg_per_cu > 0) per_cu1 = std::min(per_cu1, S->tune.lean_wg_per_cu);
-          grid = dim3((unsigned)std::min(n, per_cu1 * (int)(cu_sh + 0.5)));
-          // (time slicing as in k_flat2, same window: whole body, four tasks, B = 65 536: 34.7 ms without)
-          const int resident = (int)grid.x, full = per_cu1 * (int)(cu_sh + 0.5);
-          (void)resident; (void)full;
-          const int quantum = mur == 1 ? 0 : flat_slice_for(S, n, ordered);
-#define LOIKB_LAUNCH_FLAT1(NAV, ...)                                                                                            \
-  hipLaunchKernelGGL((k_flat1<NAV, ##__VA_ARGS__>), grid, dim3(WAVE), lds1, C->stream,                                          \
-                     *reinterpret_cast<const Params<double>*>(&P), *reinterpret_cast<const Bufs<double>*>(&Bf),                  \
-                     (const JointDesc*)S->d_jd, (const FlatLane*)S->flat.d_lanes, nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, \
-                     (const double*)C->d_fslots, frows, kexp_lo, ndec, (double)S->Href[0], has_hv | (one_buf ? 2 : 0) | ((S->maxdepth & 0xFF) << 8),  \
-                     C->ring_cap - 1, quantum, (const void* const*)C->d_aux)
-          const int hm = S->per_link ? 3 : href_is_scalar(S) ? 0 : href_is_diagonal(S) ? 1 : 2;
-          if (mur == 1) {   // (OSQP's rule: unsliced; a diagonal reference weight goes as a general one)
-            if (hm == 3) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 3, false, 1); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 3, false, 1); }
-            else if (hm >= 1) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 2, false, 1); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 2, false, 1); }
-            else if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 0, false, 1);
-            else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 0, false, 1);
-          }
-          else if (S->opt.logging) {   // (as k_flat2's)
-            const int quantum = 0;
-            if (hm == 3) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 3, true); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 3, true); }
-            else if (hm >= 1) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 2, true); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 2, true); }
-            else if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 0, true);
-            else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 0, true);
-          }
-          else if (hm == 3) {
-            if (quantum > 0) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, true, 3); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, true, 3); }
-            else if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 3);
-            else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 3);
-          } else if (hm == 2) {
-            if (quantum > 0) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, true, 2); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, true, 2); }
-            else if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 2);
-            else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 2);
-          } else if (hm == 1) {
-            if (quantum > 0) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, true, 1); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, true, 1); }
-            else if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, false, 1);
-            else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, false, 1);
-          } else if (quantum > 0) { if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL, true); else LOIKB_LAUNCH_FLAT1(FLAT_MAXA, true); }
-          else if (small_na) LOIKB_LAUNCH_FLAT1(FLAT_NA_SMALL);
-          else LOIKB_LAUNCH_FLAT1(FLAT_MAXA);
-#undef LOIKB_LAUNCH_FLAT1
-        } else {
-#define LOIKB_LAUNCH_FLAT(NAV, ...)                                                                                             \
-  hipLaunchKernelGGL((k_flat<T, NAV, ##__VA_ARGS__>), grid, dim3(WAVE), flds, C->stream, P, Bf, (const JointDesc*)S->d_jd,                \
-                     (const FlatLane*)S->flat.d_lanes, nanc, S->flat.nscan, S->flat.njmp, (const int*)C->d_ring, n, lgG,          \
-                     (const T*)C->d_fslots, frows, kexp_lo, ndec, (T)S->Href[0], has_hv)
-        if (S->opt.logging) { if (small_na) LOIKB_LAUNCH_FLAT(FLAT_NA_SMALL, true); else LOIKB_LAUNCH_FLAT(FLAT_MAXA, true); }
-        else if (small_na) LOIKB_LAUNCH_FLAT(FLAT_NA_SMALL);
-        else LOIKB_LAUNCH_FLAT(FLAT_MAXA);
-#undef LOIKB_LAUNCH_FLAT
-        }
-        HIPCHK(hipGetLastError());
-        P.mode = mode_keep;
-        int* nxt = (list == C->d_slots) ? C->d_slots2 : C->d_slots;
-        small_finish = small_flat && S->tune.small_finish;
-        if (small_finish)   // (one workgroup: the list, the counts, and the launch's counters into the pinned host copy -- loik_lean.hpp)
-          hipLaunchKernelGGL(k_small_finish<T>, dim3(1), dim3(256), 0, C->stream, A.tiles, S->L, list, n, nxt, C->d_counters, NCOUNTERS, C->h_counters);
-        else
-          hipLaunchKernelGGL(k_list_unfinished<T>, grid1(n), dim3(256), 0, C->stream, A.tiles, S->L, list, n, nxt, C->d_counters + 3);
-        HIPCHK(hipGetLastError());
-        C->stats.launches++;
-        C->stats.tail_launches++;
-        C->stats.lean_launches++;
-        C->stats.flat_launches++;
-        if (split) C->stats.flat_split_launches++;
-      }
-      int* next = (list == C->d_slots) ? C->d_slots2 : C->d_slots;
-      HIPCHK(hipEventRecord(C->ev_k1, C->stream));
-      const bool order_pass = !small_flat && S->tune.flat_order && whole_set && n_first == n_cur && (split || one) && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
-      if (!order_pass && !small_finish) HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
-      if (order_pass) {
-        // the order for the handle's next solve: longest first by the iteration counts of this one (an instance that escaped to
-        // k_tail counts with what it had when it left); and the decades the instances ended in (the next sliced launch's table window)
-        HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
-        hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins,
-                           C->d_counters + ORDER_DEC_HIST);
-        HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
-        hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_BINS), 0, C->stream, C->d_order_bins);
-        hipLaunchKernelGGL(k_order_scatter<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins, C->d_order);
-        HIPCHK(hipGetLastError());
-        C->order_n = n_cur;
-        C->order_epoch = S->inputs_epoch;
-      }
-      HIPCHK(hipStreamSynchronize(C->stream));
-      float ms = 0.f, t0 = 0.f, hms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, ev_first, C->ev_k1));
-      if (!queue_ready) HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
-      if (!small_flat) HIPCHK(hipEventElapsedTime(&hms, ev_first, C->ev_k2));
-      iters += C->h_counters[1];
-      if (C->h_counters[FLAT_COUNTERS_ERR]) {
-        g_last_error = (C->h_counters[FLAT_COUNTERS_ERR] & 4u) ? "internal: the flat engine's dynamic LDS does not start at LDS address 0 (lds_abs)"
-                                                               : "internal: a wavefront of the flat engine gave up waiting on its work queue";
-        return LOIKB_ERR_STATE;
-      }
-      C->stats.lean_requeues += (int)C->h_counters[LEAN_Q_REQUEUES];
-      const unsigned int escaped = C->h_counters[2];
-      C->stats.flat_built += (int)C->h_counters[FLAT_COUNTERS_BUILT];
-      {
-        std::lock_guard<std::mutex> lock(S->alloc_mu);
-        const unsigned int seen = C->h_counters[LEAN_DECADES_SEEN];
-        for (int d = 0; d < 16; ++d)
-          if (seen & (1u << d)) { S->seen_lo = std::min(S->seen_lo, kexp_lo + d); S->seen_hi = std::max(S->seen_hi, kexp_lo + d); }
-        if (escaped) { S->seen_lo = S->plan.kexp_lo; S->seen_hi = S->plan.kexp_lo + S->plan.ndec - 1; }
-        if (order_pass) {   // (summed over the chunks of one solve: the first chunk to report starts the histogram anew -- ADVICE r05)
-          if (S->end_hist_epoch != S->solve_serial) { S->end_hist_epoch = S->solve_serial; S->end_hist_n = 0; for (int k = 0; k < 32; ++k) S->end_hist[k] = 0; }
-          for (int k = 0; k < 32; ++k) { S->end_hist[k] += C->h_counters[ORDER_DEC_HIST + k]; S->end_hist_n += C->h_counters[ORDER_DEC_HIST + k]; }
-        }
-        if (mur == 2) {   // (the decades somebody took up, loaded or built: the handle's history as the table's range sees it)
-          for (int k = 0; k < 32; ++k)
-            if (C->h_counters[FLAT_COUNTERS_DEC + k]) { S->seen_lo = std::min(S->seen_lo, k - 16); S->seen_hi = std::max(S->seen_hi, k - 16); }
-        }
-        S->ud_stale = true;
-      }
-      C->stats.hslots_ms += hms;
-      if (C->h_counters[FLAT_COUNTERS_DRY])  // (100 MHz clock, low words: from the ring fill of the last stage to the first empty fetch)
-        C->stats.queue_dry_ms += (double)(unsigned int)(C->h_counters[FLAT_COUNTERS_TDRY] - C->h_counters[FLAT_COUNTERS_T0]) * 1e-5;
-      if ((split || one) && whole_set && n_first == n_cur) {
-        // did the order predict this solve?  The launch is compared with the handle's last launch in arrival order (+ time slices)
-        // of the same set: a batch that resembles the previous one runs 5..35 % shorter ordered (no ragged end); one that does
-        // not is arrival order without the slices that would have softened it, a few per cent LONGER -- then the next four solves
-        // go back to arrival order, which also refreshes the figure to compare with.  (What the launch leaves after its queue ran
-        // dry does not tell: a small batch's queue is empty long before its long runners are done, whatever the order.)
-        const double flat_ms = (double)ms - (double)hms;
-        if (C->arrival_n != n_cur) { C->arrival_n = n_cur; C->arrival_ms = 0.0; }
-        if (!ordered) C->arrival_ms = flat_ms;
-        else if (order_was_stale && C->arrival_ms > 0.0 && flat_ms > 0.985 * C->arrival_ms) C->order_holdoff = S->tune.flat_order_holdoff;
-      }
-      if (trace)
-        fprintf(stderr, "[loikb] flat engine: %6d instances on %u workgroups, done at %8.3f ms (slots %6.3f ms)  "
-                        "inst-iters %9u  wave-iters %7u  slot loads %7u (+ %u served from LDS)  escaped %u  still iterating %u\n",
-                n_first, grid.x, ms, hms, C->h_counters[1], C->h_counters[5], C->h_counters[6],
-                C->h_counters[FLAT_COUNTERS_SLOT_HITS], escaped, C->h_counters[3]);
-      C->stats.lean_escaped += (int)escaped;
-      C->tail_iv.emplace_back(t0, t0 + ms);
-      total_ms = ms;
-      n = (int)C->h_counters[3];
-      list = next;
-      // (the launch took the chunk's whole home set and nothing is still iterating: k_list_unfinished has counted loikb_stats::n_unfinished)
-      if (n == 0 && whole_set && cur == 0 && n_first == n_cur && S->chunks.size() == 1) { C->stats.n_unfinished = (int)C->h_counters[4]; C->unfinished_counted = true; C->small_finished = small_finish; }
-      if (n == 0) { *ms_out = total_ms; *iters_out = iters; return LOIKB_OK; }
-      // what is left escaped the precomputed decades: k_tail below finishes it
-    }
-    // (k_lean's lane groups need whole wavefronts of work to pay: below 64 instances k_tail's direct path is as good)
-    const bool lean_ok = !flat_ok && S->plan.lean && (P.mode & MODE_CACHE_H) && n >= 64;
-    const bool per_link = S->per_link;  // (UpdateReferences' table: the PERLINK instantiations of k_hslots / k_lean)
-    if (lean_ok) {
-      // decade slots are indexed by the instance's slot in the set (relaunches with shorter lists find them again);
-      // the buffer was sized for the chunk at SolveInit (ensure_hslots)
-      const size_t need = (size_t)n_cur * ndec * HSLOT_PAIRS * G * 2 * sizeof(T);
-      if (need > C->hslots_bytes) { g_last_error = "internal: decade-slot buffer smaller than the chunk"; return LOIKB_ERR_STATE; }
-    }
-    if (lean_ok) {
-      const int waves_cu = S->plan.lean_waves_cu;
-      const int ltw = S->plan.lean_wg_waves;  // wavefronts per workgroup
-      const size_t lds = ltw * wave_lds;
-      if (lds > 64 * 1024) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_lean<T, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      }
-      const int wg_per_cu = S->tune.lean_wg_per_cu > 0 ? S->tune.lean_wg_per_cu : waves_cu / ltw;
-      const int wg_cap = wg_per_cu * std::max(1, (int)(S->ncu * ((double)C->B / (double)S->B) + 0.5));
-      HIPCHK(hipEventRecord(C->ev_k0, C->stream));
-      // longest first, as in the flat engine: the order the handle's previous solve left, for a whole-set launch (the decade slots are
-      // indexed by the instance: k_hslots and k_lean see the same list)
-      const bool lean_ordered = whole_set && list == C->d_slots && n == n_cur && order_usable(S, C, n_cur);
-      const bool lean_order_was_stale = lean_ordered && C->order_epoch != S->inputs_epoch;
-      if (whole_set && C->order_holdoff > 0) --C->order_holdoff;
-      if (lean_ordered) HIPCHK(hipMemcpyAsync(C->d_slots, C->d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, C->stream));
-      C->stats.flat_ordered += lean_ordered ? 1 : 0;
-      P.max_launch_iters = S->opt.max_iter + 1;
-      const int wg_needed = (n + ipw * ltw - 1) / (ipw * ltw);
-      const dim3 grid((unsigned)std::min(wg_needed, wg_cap));
-      HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
-      const dim3 hgrid((unsigned)((n + ipw - 1) / ipw));
-      const size_t hlds = (size_t)(WAVE + 1) * 22 * sizeof(T);
-      if (per_link)
-        hipLaunchKernelGGL((k_hslots<T, false, true>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                           (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
-                           (T*)C->d_hslots, kexp_lo, ndec);
-      else if (S->href_diag)
-        hipLaunchKernelGGL((k_hslots<T, true>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                           (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
-                           (T*)C->d_hslots, kexp_lo, ndec);
-      else
-        hipLaunchKernelGGL((k_hslots<T, false>), hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                           (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G,
-                           (T*)C->d_hslots, kexp_lo, ndec);
-      HIPCHK(hipEventRecord(C->ev_k2, C->stream));
-      hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, list, n, C->d_counters);
-#define LOIKB_LAUNCH_LEAN(...)                                                                                                  \
-  hipLaunchKernelGGL((k_lean<T, ##__VA_ARGS__>), grid, dim3(WAVE * ltw), lds, C->stream, P, Bf, (const JointDesc*)S->d_jd,               \
-                     (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild, C->d_ring, n, G,            \
-                     (const T*)C->d_hslots, kexp_lo, ndec, S->multi_from)
-      if (per_link) LOIKB_LAUNCH_LEAN(false, true);
-      else if (S->href_diag) LOIKB_LAUNCH_LEAN(true);
-      else LOIKB_LAUNCH_LEAN(false);
-#undef LOIKB_LAUNCH_LEAN
-      HIPCHK(hipGetLastError());
-      // the instances that are still iterating: k_tail's list (ping-pong between the two list buffers)
-      int* next = (list == C->d_slots) ? C->d_slots2 : C->d_slots;
-      hipLaunchKernelGGL(k_list_unfinished<T>, grid1(n), dim3(256), 0, C->stream, A.tiles, S->L, list, n, next, C->d_counters + 3);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(C->ev_k1, C->stream));
-      HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
-      const bool lean_orders = S->tune.flat_order && whole_set && n == n_cur && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
-      if (lean_orders) {  // the order for the handle's next solve (k_order_*)
-        HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
-        hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins);
-        hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_BINS), 0, C->stream, C->d_order_bins);
-        hipLaunchKernelGGL(k_order_scatter<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins, C->d_order);
-        HIPCHK(hipGetLastError());
-        C->order_n = n_cur;
-        C->order_epoch = S->inputs_epoch;
-      }
-      HIPCHK(hipStreamSynchronize(C->stream));
-      float ms = 0.f, t0 = 0.f, hms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, C->ev_k0, C->ev_k1));
-      if (lean_orders) {  // (held off like the flat engine's: compared with the handle's last launch in arrival order)
-        if (C->arrival_n != n_cur) { C->arrival_n = n_cur; C->arrival_ms = 0.0; }
-        if (!lean_ordered) C->arrival_ms = (double)ms;
-        else if (lean_order_was_stale && C->arrival_ms > 0.0 && (double)ms > 0.985 * C->arrival_ms) C->order_holdoff = S->tune.flat_order_holdoff;
-      }
-      HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
-      iters += C->h_counters[1];
-      const unsigned int escaped = C->h_counters[2];
-      {
-        std::lock_guard<std::mutex> lock(S->alloc_mu);
-        const unsigned int seen = C->h_counters[LEAN_DECADES_SEEN];
-        for (int d = 0; d < 16; ++d)
-          if (seen & (1u << d)) { S->seen_lo = std::min(S->seen_lo, kexp_lo + d); S->seen_hi = std::max(S->seen_hi, kexp_lo + d); }
-        if (escaped) { S->seen_lo = S->plan.kexp_lo; S->seen_hi = S->plan.kexp_lo + S->plan.ndec - 1; }  // the table was too narrow
-      }
-      C->stats.lean_requeues += (int)C->h_counters[LEAN_Q_REQUEUES];
-      HIPCHK(hipEventElapsedTime(&hms, C->ev_k0, C->ev_k2));
-      C->stats.hslots_ms += hms;
-      if (trace)
-        fprintf(stderr, "[loikb] lean engine: %6d instances on %u workgroups, done at %8.3f ms"
-                        "  inst-iters %9u  wave-iters %7u slot loads %7u  escaped %u  still iterating %u  requeued %u\n",
-                n, grid.x, ms, C->h_counters[1], C->h_counters[5], C->h_counters[6], escaped,
-                C->h_counters[3], C->h_counters[LEAN_Q_REQUEUES]);
-      C->stats.launches++;
-      C->stats.tail_launches++;
-      C->stats.lean_launches++;
-      total_ms = ms;
-      n = (int)C->h_counters[3];
-      list = next;
-      C->tail_iv.emplace_back(t0, t0 + (float)total_ms);
-      C->stats.lean_escaped += (int)escaped;
-      if (n == 0) { *ms_out = total_ms; *iters_out = iters; return LOIKB_OK; }
-      // what is left escaped the precomputed decades: k_tail below finishes it
-    }
+  // decades of mu with precomputed slots: mu0 * 10^(kexp_lo .. kexp_lo + ndec - 1).  The DEFAULT rule moves mu up from
+  // mu0 in the first iterations and then mostly oscillates between two or three decades (Talos workload: 0..7 seen,
+  // < 0 never); an instance that leaves the range is finished by k_tail.
+  // (the table is built as a pipeline over the tree levels: a decade more costs one step)
+  // Every decade costs k_hslots a pipeline step and 176 B x joints per instance of HBM writes (0.14 ms per decade on the
+  // headline): after the first solve of a handle the table covers the decades its instances were seen in, plus one on
+  // each side (the headline workload lives in 0..6 of the configured -2..7: 21.8 -> 21.2 ms).  mu restarts at mu0 in every
+  // solve, batches of one application resemble each other; when they do not, the instance that leaves the table escapes
+  // to k_tail as always and the full range is back for the next solve.
+  // (a logged solve keeps the whole configured range: an instance that escaped to k_tail would stop writing its lists)
+  if (S->tune.lean_adapt && S->seen_hi >= S->seen_lo && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS) && !S->opt.logging) {
+    const int lo = std::max(X.kexp_lo, S->seen_lo - 1), hi = std::min(X.kexp_lo + X.ndec - 1, S->seen_hi + 1);
+    if (hi >= lo) { X.kexp_lo = lo; X.ndec = hi - lo + 1; }
   }
-  {
-    P.max_launch_iters = S->opt.max_iter + 1;
-    const int wg_needed = (n + ipw * tw - 1) / (ipw * tw);
-    const dim3 grid((unsigned)std::min(wg_needed, cu_share));
-    HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
-    HIPCHK(hipEventRecord(C->ev_k0, C->stream));
-    // k_tail as the engine of a whole batch (OSQP rule, robots outside the on-chip engines' domain): longest first from the handle's
-    // previous solve, as in the flat and lean engines (its lane groups pull the list in order)
-    const bool tail_whole = whole_set && list == C->d_slots && n == n_cur && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS) &&
-                            S->tune.flat_order;
-    const bool tail_ordered = tail_whole && order_usable(S, C, n_cur);
-    const bool tail_order_was_stale = tail_ordered && C->order_epoch != S->inputs_epoch;
-    if (tail_whole && C->order_holdoff > 0) --C->order_holdoff;
-    if (tail_ordered) HIPCHK(hipMemcpyAsync(C->d_slots, C->d_order, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, C->stream));
-    C->stats.flat_ordered += tail_ordered ? 1 : 0;
-    if (S->href_diag)
-      hipLaunchKernelGGL((k_tail<T, true>), grid, dim3(WAVE * tw), lds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                         (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild,
-                         list, n, G);
-    else
-      hipLaunchKernelGGL((k_tail<T, false>), grid, dim3(WAVE * tw), lds, C->stream, P, Bf, (const JointDesc*)S->d_jd,
-                         (const TailTopo*)S->d_topo, (const int*)S->d_child_list, S->maxdepth, S->maxchild,
-                         list, n, G);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(C->ev_k1, C->stream));
-    HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
-    if (tail_whole) {
-      HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
-      hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins);
-      hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_BINS), 0, C->stream, C->d_order_bins);
-      hipLaunchKernelGGL(k_order_scatter<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins, C->d_order);
-      HIPCHK(hipGetLastError());
-      C->order_n = n_cur;
-      C->order_epoch = S->inputs_epoch;
-    }
-    HIPCHK(hipStreamSynchronize(C->stream));
-    float ms = 0.f, t0 = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, C->ev_k0, C->ev_k1));
-    HIPCHK(hipEventElapsedTime(&t0, S->ev_t0, C->ev_k0));
-    if (tail_whole) {
-      if (C->arrival_n != n_cur) { C->arrival_n = n_cur; C->arrival_ms = 0.0; }
-      if (!tail_ordered) C->arrival_ms = (double)ms;
-      else if (tail_order_was_stale && C->arrival_ms > 0.0 && (double)ms > 0.985 * C->arrival_ms) C->order_holdoff = S->tune.flat_order_holdoff;
-    }
-    C->tail_iv.emplace_back(t0, t0 + ms);
-    total_ms += ms;
-    iters += C->h_counters[1];
-    if (trace)
-      fprintf(stderr, "[loikb] tail launch: %6d instances on %u workgroups  %8.3f ms  inst-iters %9u (%.1f M/s)"
-                      "  wave-iters %7u H-rebuild %3.0f%%\n",
-              n, grid.x, ms, C->h_counters[1], C->h_counters[1] / ms / 1e3,
-              C->h_counters[5], 100.0 * C->h_counters[6] / (C->h_counters[5] ? C->h_counters[5] : 1));
-    C->stats.launches++;
-    C->stats.tail_launches++;
-  }
-  *ms_out = total_ms;
-  *iters_out = iters;
+  int rc = LOIKB_OK;
+  bool engine_ran = true;
+  // (k_lean's lane groups need whole wavefronts of work to pay: below 64 instances k_tail's direct path is as good)
+  if (flat_here && X.n >= (flat_1pw ? std::max(1, S->tune.flat_min_batch) : 64)) rc = launch_flat(X);
+  else if (S->plan.lean && (P.mode & MODE_CACHE_H) && X.n >= 64) rc = launch_lean(X);
+  else engine_ran = false;
+  if (rc) return rc;
+  if (!(engine_ran && X.n == 0) && (rc = launch_tail_kernel(X, tw, lds))) return rc;
+  *ms_out = X.total_ms;
+  *iters_out = X.iters;
   return LOIKB_OK;
 }
 
@@ -2899,6 +2894,15 @@ int loikb_flat_schedule(const int* parents, int njoints, int* out, int cap, int*
   if (!out || cap < fs.G * W) return fs.G * W;
   memcpy(out, fs.lanes.data(), sizeof(FlatLane) * fs.lanes.size());
   for (int l = 0; l < fs.G; ++l) out[l * W + (int)(offsetof(FlatLane, helper) / sizeof(int))] &= 1;  // (the upper bits are internal)
+  return LOIKB_OK;
+}
+
+// the variant of k_flat2 (kind 2) / k_flat1 (kind 1) a launch would run (inspection / tests: flat_variant)
+int loikb_flat_variant(int kind, int hm, int sliced, int logging, int mur, int* out4)
+{
+  if ((kind != 1 && kind != 2) || hm < 0 || hm > 3 || mur < 0 || mur > 2 || !out4) return LOIKB_ERR_ARG;
+  const FlatVariant v = flat_variant(kind == 2 ? FlatKind::Flat2 : FlatKind::Flat1, hm, sliced != 0, logging != 0, mur);
+  out4[0] = v.sliced; out4[1] = v.hm; out4[2] = v.log; out4[3] = v.mur;
   return LOIKB_OK;
 }
 
@@ -3621,8 +3625,8 @@ const char* loikb_plan_string(loikb_solver* S)
   char buf[512];
   const EnginePlan& pl = S->plan;
   if (pl.flat && (flat_applicable(S) || !S->have_problem)) {
-    const bool split = S->tune.flat_split && S->flat.G == F2G && S->flat.nanc <= FLAT_NA_SMALL && !S->f32;
-    const bool one = S->tune.flat_split && S->flat.G == WAVE && !S->f32;
+    const FlatKind kind = flat_kind(S);
+    const bool split = kind == FlatKind::Flat2, one = kind == FlatKind::Flat1;
     snprintf(buf, sizeof(buf), "k_fslots + %s (no loops over the tree levels%s) for whole batches up to %d instances (%d wavefronts per "
              "CU, decades mu0*10^%d..%d, %d ancestors per joint, %d scan steps, %d jump rounds)%s; k_solve above that; %d chunk(s)",
              split ? "k_flat2" : one ? "k_flat1" : "k_flat",
