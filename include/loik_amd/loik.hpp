@@ -19,6 +19,7 @@
 #include "../loik_amd_pose.h"
 #include "../loik_amd_limits.h"
 #include "../loik_amd_tasks.h"
+#include "../loik_amd_multistart.h"
 
 #include <array>
 #include <map>
@@ -439,6 +440,61 @@ public:
     for (std::size_t i = 0; i < M.size(); ++i) std::copy(out.begin() + 12 * i, out.begin() + 12 * (i + 1), M[i].begin());
     return M;
   }
+  // ---- multi-start pose IK (include/loik_amd_multistart.h): batch = G goals * K seeds, instance g * K + k is seed k of goal g
+  // the ranges [nv] the seeds are drawn from (a DoF is sampled iff both ends are finite; both empty = the joint limits) and the
+  // weights [nv] of the nearest-seed metric (empty = 1)
+  void setSeedRanges(const DVec& s_lo = {}, const DVec& s_hi = {}, const DVec& weights = {})
+  {
+    if (s_lo.size() != s_hi.size() || (!weights.empty() && !s_lo.empty() && weights.size() != s_lo.size()))
+      throw std::runtime_error("loik_amd: s_lo, s_hi and weights differ in size");
+    check(loikb_multistart_set_ranges(h_, s_lo.empty() ? nullptr : s_lo.data(), s_hi.empty() ? nullptr : s_hi.data(),
+                                      weights.empty() ? nullptr : weights.data(), (int)(s_lo.empty() ? weights.size() : s_lo.size())));
+  }
+  // writes the seeds of `round` into the resident q of all instances and nothing else.  q0: [G][nq], [nq] = one row for every
+  // goal, nullptr = the resident q of each goal's instance g * K
+  void SampleSeeds(int seeds_per_goal, unsigned long long seed = 0, int round = 0, const DVec* q0 = nullptr)
+  {
+    check(loikb_multistart_sample(h_, q0 ? q0->data() : nullptr, q0_flags(q0, seeds_per_goal), seed, seeds_per_goal, round));
+  }
+  struct MultiStartResult {
+    std::vector<int> winner, goal_status, nreached;  // [G]; goal_status: LOIKB_MS_GOAL_* bits
+    std::vector<int> round;                          // [batch]
+    DVec q, err, cost;                               // [G][nq], [G][nc][6], [G]
+    int rounds_run = 0;
+    std::array<double, 6> timing{};                  // LOIKB_MS_F_TIMING
+  };
+  // targets: one per goal and active constraint (G * nc, goal-major), or nc shared by the goals; q0 as SampleSeeds takes it
+  MultiStartResult SolvePoseMultiStart(const std::vector<SE3>& targets, int seeds_per_goal, int rounds = 1, unsigned long long seed = 0,
+                                       int pick = LOIKB_MS_PICK_NEAREST, const DVec* q0 = nullptr, double dt = 1.0, double gain = 1.0,
+                                       double tol_pose = 1e-6, int max_steps = 100)
+  {
+    const std::size_t nc = (std::size_t)loikb_num_eq_c(h_);
+    const bool k_ok = seeds_per_goal >= 1 && batch_ % seeds_per_goal == 0;   // (else the library says what is wrong with it)
+    const std::size_t G = k_ok ? (std::size_t)(batch_ / seeds_per_goal) : 1;
+    int flags = q0_flags(q0, seeds_per_goal);
+    if (targets.size() == nc && G > 1) flags |= LOIKB_POSE_TARGET_SHARED;
+    else if (targets.size() != G * nc)
+      throw std::runtime_error("loik_amd: SolvePoseMultiStart needs one target per active constraint, shared or per goal");
+    DVec t(targets.size() * 12);
+    for (std::size_t i = 0; i < targets.size(); ++i) std::copy(targets[i].begin(), targets[i].end(), t.begin() + 12 * i);
+    const loikb_pose_params p{dt, gain, tol_pose, max_steps, 0};
+    const loikb_multistart_params m{seeds_per_goal, rounds, seed, pick, 0};
+    check(loikb_solve_pose_multistart(h_, q0 ? q0->data() : nullptr, t.data(), flags, &p, &m));
+    solved();
+    MultiStartResult r;
+    r.winner.resize(G); r.goal_status.resize(G); r.nreached.resize(G); r.round.resize(batch_);
+    r.q.resize(G * model_.nq); r.err.resize(G * nc * 6); r.cost.resize(G);
+    check(loikb_multistart_get(h_, LOIKB_MS_F_WINNER, r.winner.data(), 0));
+    check(loikb_multistart_get(h_, LOIKB_MS_F_GOAL_STATUS, r.goal_status.data(), 0));
+    check(loikb_multistart_get(h_, LOIKB_MS_F_NREACHED, r.nreached.data(), 0));
+    check(loikb_multistart_get(h_, LOIKB_MS_F_ROUND, r.round.data(), 0));
+    check(loikb_multistart_get(h_, LOIKB_MS_F_Q, r.q.data(), 0));
+    check(loikb_multistart_get(h_, LOIKB_MS_F_ERR, r.err.data(), 0));
+    check(loikb_multistart_get(h_, LOIKB_MS_F_COST, r.cost.data(), 0));
+    check(loikb_multistart_get(h_, LOIKB_MS_F_TIMING, r.timing.data(), 0));
+    r.rounds_run = (int)r.timing[0];
+    return r;
+  }
   // the resident configurations, [batch][nq]
   DVec q_resident() const
   {
@@ -686,6 +742,16 @@ private:
 
   Model model_;             // by value, as upstream (loik-loid-optimized.hpp:762)
   IkIdData& ik_id_data_;    // caller-owned, must outlive the solver (loik-loid-optimized.hpp:763)
+  // q0 of the multi-start entry points: [nq] = one shared row, [G][nq] = one per goal (G = 1: per goal)
+  int q0_flags(const DVec* q0, int seeds_per_goal) const
+  {
+    if (!q0) return 0;
+    const bool k_ok = seeds_per_goal >= 1 && batch_ % seeds_per_goal == 0;
+    const std::size_t G = k_ok ? (std::size_t)(batch_ / seeds_per_goal) : 1;
+    if (q0->size() == G * (std::size_t)model_.nq) return 0;
+    if (q0->size() == (std::size_t)model_.nq) return LOIKB_Q_SHARED;
+    throw std::runtime_error("loik_amd: q0 must hold model.nq values (shared by the goals) or goals * model.nq");
+  }
   loikb_solver* h_ = nullptr;
   int batch_, nc_;
   int max_iter_ = 0;

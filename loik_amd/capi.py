@@ -109,8 +109,22 @@ TASK_POSE, TASK_POSITION, TASK_ORIENTATION = 0, 1, 2
 TASK_KINDS = {"pose": TASK_POSE, "position": TASK_POSITION, "orientation": TASK_ORIENTATION}
 
 
+# include/loik_amd_multistart.h: device-sampled seeds, restarts and the best seed per goal around the pose loop; its own header and version again
+MULTISTART_ABI_VERSION = 1
+MULTISTART_SYMBOLS = ["loikb_multistart_version", "loikb_multistart_set_ranges", "loikb_multistart_sample", "loikb_solve_pose_multistart",
+                      "loikb_multistart_get"]
+MS_PICK_NEAREST, MS_PICK_FIRST = 0, 1
+MS_PICKS = {"nearest": MS_PICK_NEAREST, "first": MS_PICK_FIRST}
+MS_F_WINNER, MS_F_GOAL_STATUS, MS_F_Q, MS_F_ERR, MS_F_COST, MS_F_NREACHED, MS_F_ROUND, MS_F_TIMING = range(8)
+MS_GOAL_REACHED, MS_GOAL_BEST_EFFORT, MS_GOAL_FAILED = 1, 2, 4
+
+
 class PoseParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
+
+
+class MultiStartParams(C.Structure):
+    _fields_ = [("seeds_per_goal", C.c_int), ("rounds", C.c_int), ("seed", C.c_ulonglong), ("pick", C.c_int), ("flags", C.c_int)]
 
 
 _lib = None
@@ -180,6 +194,10 @@ def lib():
     L.loikb_pose_clear_tasks.argtypes = [C.c_void_p]
     L.loikb_pose_get_tasks.argtypes = [C.c_void_p, _ip, _dp, C.c_int]
     L.loikb_frame_placements.argtypes = [C.c_void_p, _ip, _dp, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_multistart_set_ranges.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
+    L.loikb_multistart_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.c_int, C.c_int]
+    L.loikb_solve_pose_multistart.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseParams), C.POINTER(MultiStartParams)]
+    L.loikb_multistart_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -445,6 +463,7 @@ class BatchedLoik:
         _check(self.L.loikb_create(C.byref(self._desc), C.byref(self.opts), C.byref(h)))
         self.h = h
         self._limits = False   # set_joint_limits left a finite limit on the handle: SolvePose returns limit_flags
+        self._ms_goals = 0     # goals of the last SolvePoseMultiStart: the shapes of multistart_get
 
     def close(self):
         if getattr(self, "h", None):
@@ -802,6 +821,110 @@ class BatchedLoik:
         out = np.empty((self.batch, n, 12))
         _check(self.L.loikb_frame_placements(self.h, links.ctypes.data_as(_ip), fp, n, out.ctypes.data_as(C.c_void_p), 0))
         return self._to44(out)
+
+    # ---- multi-start pose IK (include/loik_amd_multistart.h) ------------------------------------------------
+    def set_seed_ranges(self, s_lo=None, s_hi=None, weights=None):
+        """the ranges [nv] (idx_v order) the seeds are drawn from (loikb_multistart_set_ranges): a DoF is sampled iff both ends are
+        finite; None, None = the handle's joint limits.  weights [nv] >= 0 (None = 1): the metric of pick="nearest"."""
+        arrs = [None if a is None else _f64(a).reshape(-1) for a in (s_lo, s_hi, weights)]
+        sizes = {a.size for a in arrs if a is not None}
+        if len(sizes) > 1:
+            raise ValueError("s_lo, s_hi and weights differ in size")
+        _check(self.L.loikb_multistart_set_ranges(self.h, *[None if a is None else a.ctypes.data_as(_dp) for a in arrs],
+                                                  sizes.pop() if sizes else 0))
+
+    def _goal_q0(self, q0, G, device_ok):
+        """q0 of the multi-start entry points -> (void*, flags, keep-alive): None, [nq] (shared), [G][nq], or a device [G][nq]"""
+        if q0 is None:
+            return None, 0, None
+        if isinstance(q0, int) or (hasattr(q0, "data_ptr") and getattr(q0, "is_cuda", False)):
+            if not device_ok:
+                raise ValueError("q0 and targets must both be host arrays or both device pointers (a shared q0 row is a host array)")
+            return C.c_void_p(q0 if isinstance(q0, int) else q0.data_ptr()), IN_DEVICE, q0
+        a = _f64(q0.numpy() if hasattr(q0, "numpy") else q0)
+        nq = self.model.nq
+        if a.size == G * nq and not (a.ndim == 1 and G == 1):
+            return a.ctypes.data_as(C.c_void_p), 0, a
+        if a.size == nq:
+            return a.ctypes.data_as(C.c_void_p), Q_SHARED, a
+        raise ValueError("q0 has %d elements: expected nq = %d (shared by the goals) or goals * nq = %d" % (a.size, nq, G * nq))
+
+    def sample_seeds(self, seeds_per_goal, seed=0, round=0, q0=None):
+        """writes the seeds of `round` into the resident q of all instances (loikb_multistart_sample) and nothing else; q0 as in
+        SolvePoseMultiStart"""
+        K = int(seeds_per_goal)
+        qp, qf, keep = self._goal_q0(q0, self.batch // K if K >= 1 and self.batch % K == 0 else 1, True)
+        _check(self.L.loikb_multistart_sample(self.h, qp, qf, int(seed), K, int(round)))
+
+    def SolvePoseMultiStart(self, targets, seeds_per_goal, rounds=1, seed=0, pick="nearest", q0=None, dt=1.0, gain=1.0, tol_pose=1e-6,
+                            max_steps=100):
+        """G = batch / seeds_per_goal goals, K = seeds_per_goal seeds each (loikb_solve_pose_multistart): instance g * K + k is seed k
+        of goal g.  Seeds are drawn on the device inside the seed ranges (set_seed_ranges; default the joint limits), SolvePose
+        runs on the whole batch, instances without REACHED are re-seeded for up to rounds - 1 restarts while a goal is
+        unanswered, and one winner per goal is selected on the device.
+        targets: [G][nc][4][4] / [G][nc][12], or [nc][..] shared by the goals (a device tensor by its numel).  q0: [G][nq], [nq]
+        shared, None = the resident q of each goal's instance g * K; seed 0 of round 0 is q0 itself.
+        Returns dict(winner [G], goal_status [G] MS_GOAL_* bits, q [G][nq], err [G][nc][6], cost [G], nreached [G], round [B],
+        rounds_run, timing)."""
+        B, nc, K = self.batch, int(self.L.loikb_num_eq_c(self.h)), int(seeds_per_goal)
+        G = B // K if K >= 1 and B % K == 0 else 1   # (a K the library rejects: it says so)
+        flags, keep = 0, []
+        if isinstance(targets, int) or (hasattr(targets, "data_ptr") and getattr(targets, "is_cuda", False)):
+            n = None if isinstance(targets, int) else int(targets.numel())
+            if n is not None and n not in (G * nc * 12, nc * 12):
+                raise ValueError("targets: device tensor has %d elements, expected goals * nc * 12 or nc * 12" % n)
+            tp = C.c_void_p(targets if isinstance(targets, int) else targets.data_ptr())
+            flags |= IN_DEVICE
+            if n == nc * 12 and G > 1:
+                flags |= POSE_TARGET_SHARED
+        else:
+            t = self._placements12(targets.numpy() if hasattr(targets, "numpy") else targets, "targets")
+            if t.size == G * nc * 12:
+                pass
+            elif t.size == nc * 12:
+                flags |= POSE_TARGET_SHARED
+            else:
+                raise ValueError("targets: %d placements, expected goals * nc = %d or nc = %d" % (t.size // 12, G * nc, nc))
+            keep.append(t)
+            tp = t.ctypes.data_as(C.c_void_p)
+        qp, qf, k0 = self._goal_q0(q0, G, bool(flags & IN_DEVICE))
+        if q0 is not None and not qf & Q_SHARED and bool(qf & IN_DEVICE) != bool(flags & IN_DEVICE):
+            raise ValueError("q0 and targets must both be host arrays or both device pointers (a shared q0 row is a host array)")
+        if isinstance(pick, str):
+            if pick not in MS_PICKS:
+                raise ValueError("pick %r: expected one of %s" % (pick, sorted(MS_PICKS)))
+            pick = MS_PICKS[pick]
+        prm = PoseParams(float(dt), float(gain), float(tol_pose), int(max_steps), 0)
+        msp = MultiStartParams(K, int(rounds), int(seed), int(pick), 0)
+        _check(self.L.loikb_solve_pose_multistart(self.h, qp, tp, flags | qf, C.byref(prm), C.byref(msp)))
+        self._ms_goals = G
+        out = {name: self.multistart_get(name) for name in ("winner", "goal_status", "q", "err", "cost", "nreached", "round", "timing")}
+        out["rounds_run"] = out["timing"]["rounds"]
+        return out
+
+    def multistart_get(self, name):
+        """one result of the last SolvePoseMultiStart (loikb_multistart_get): winner / goal_status / q / err / cost / nreached /
+        round / timing (a dict: rounds, total_ms, solve_ms, sample_ms, select_ms, other_ms)"""
+        fields = {"winner": (MS_F_WINNER, np.int32), "goal_status": (MS_F_GOAL_STATUS, np.int32), "q": (MS_F_Q, np.float64),
+                  "err": (MS_F_ERR, np.float64), "cost": (MS_F_COST, np.float64), "nreached": (MS_F_NREACHED, np.int32),
+                  "round": (MS_F_ROUND, np.int32), "timing": (MS_F_TIMING, np.float64)}
+        fid, dtype = fields[name]
+        if name == "timing":
+            t = np.zeros(6)
+            _check(self.L.loikb_multistart_get(self.h, fid, t.ctypes.data_as(C.c_void_p), 0))
+            return dict(rounds=int(t[0]), total_ms=float(t[1]), solve_ms=float(t[2]), sample_ms=float(t[3]), select_ms=float(t[4]),
+                        other_ms=float(t[5]))
+        if name == "round":
+            arr = np.empty(self.batch, dtype=dtype)
+            _check(self.L.loikb_multistart_get(self.h, fid, arr.ctypes.data_as(C.c_void_p), 0))
+            return arr
+        # (the goal count is the library's: the winners come first, their number sizes the rest)
+        nc = int(self.L.loikb_num_eq_c(self.h))
+        big = np.empty(self.batch * {"q": self.model.nq, "err": nc * 6}.get(name, 1), dtype=dtype)
+        _check(self.L.loikb_multistart_get(self.h, fid, big.ctypes.data_as(C.c_void_p), 0))
+        G = self._ms_goals
+        shape = {"q": (G, self.model.nq), "err": (G, nc, 6)}.get(name, (G,))
+        return big[:int(np.prod(shape))].reshape(shape).copy()
 
     # ------------------------------------------------------------------------------------------------------
     def set_max_iter(self, n):

@@ -20,6 +20,7 @@
 #include "loik_passes.hpp"
 #include "loik_pose.hpp"
 #include "loik_pose_tasks.hpp"
+#include "loik_pose_multistart.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -34,6 +35,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_pose.h"
 #include "../../include/loik_amd_limits.h"
 #include "../../include/loik_amd_tasks.h"
+#include "../../include/loik_amd_multistart.h"
 
 #include <algorithm>
 #include <chrono>
@@ -41,6 +43,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -364,6 +367,26 @@ struct loikb_solver_impl {
     std::vector<PoseTask> tasks;       // [nc_active] host copy of d_tasks
     PoseTask* d_tasks = nullptr;       // [nc] (slot capacity), allocated by the first loikb_pose_set_tasks
   } pose;
+  // multi-start pose IK (loik_pose_multistart.hpp): buffers of loikb_multistart_sample / loikb_solve_pose_multistart, allocated by
+  // the first call of either (sizes: batch and slot capacity; a goal count G <= B fits whatever K is)
+  struct MultiStartState {
+    bool have_ranges = false;          // loikb_multistart_set_ranges gave ranges of its own (else: the joint limits of the handle)
+    std::vector<double> lo, hi, w;     // [nv] those ranges; the weights of the nearest-seed metric (empty: 1)
+    std::vector<double> up_lo, up_hi;  // [nv] what the last call sent to d_lo / d_hi (host staging: outlives the copy)
+    std::vector<int> up_table;         // [nq] likewise, d_table
+    double* d_tgt_in = nullptr;        // [G][nc][12] the caller's targets (shared: the first nc rows)
+    double* d_tgt = nullptr;           // [B][nc][12] the same per instance: what loikb_solve_pose is given
+    double* d_q0 = nullptr;            // [G][nq] the goals' q0 rows
+    int* d_table = nullptr;            // [nq] per coordinate: the sampled DoF, or -1 = copy from q0
+    int* d_dofq = nullptr;             // [nv] lim_q on the device
+    double *d_lo = nullptr, *d_hi = nullptr, *d_w = nullptr;   // [nv]
+    int* d_round = nullptr;            // [B] LOIKB_MS_F_ROUND
+    int *d_winner = nullptr, *d_gstatus = nullptr, *d_nreached = nullptr;   // [G]
+    double *d_cost = nullptr, *d_wq = nullptr, *d_werr = nullptr;           // [G], [G][nq], [G][nc][6]
+    unsigned int* d_count = nullptr;   // [2] goals with a reached seed, target rotations rejected
+    int G = 0, nc = 0;                 // of the last loikb_solve_pose_multistart (G = 0: none yet)
+    double timing[6] = {0, 0, 0, 0, 0, 0};   // LOIKB_MS_F_TIMING
+  } ms;
 };
 using Chunk = loikb_solver_impl::Chunk;
 
@@ -4149,16 +4172,24 @@ int loikb_forward_kinematics(loikb_solver* S, const int* links, int n, double* o
   return LOIKB_OK;
 }
 
-int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, int in_flags, const loikb_pose_params* p)
+// what loikb_solve_pose asks of its parameters and of the handle before it looks at the targets (loikb_solve_pose_multistart asks
+// the same before it changes anything)
+static int pose_preconditions(const loikb_solver_impl* S, const loikb_pose_params* p, bool need_resident_q)
 {
-  if (!S || !targets || !p) return LOIKB_ERR_ARG;
   if (!(p->dt > 0.0) || !(p->gain > 0.0) || !(p->tol_pose >= 0.0) || p->max_steps < 0 || std::isinf(p->dt) || std::isinf(p->gain)) {
     g_last_error = "solve_pose: need dt > 0, gain > 0, tol_pose >= 0, max_steps >= 0";
     return LOIKB_ERR_ARG;
   }
   if (!S->have_problem) { g_last_error = "solve_pose before SolveInit()"; return LOIKB_ERR_STATE; }
   if (S->nc_active < 1) { g_last_error = "solve_pose: no active task constraint"; return LOIKB_ERR_STATE; }
-  if (!q && !S->have_q) { g_last_error = "solve_pose: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (need_resident_q && !S->have_q) { g_last_error = "solve_pose: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  return LOIKB_OK;
+}
+
+int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, int in_flags, const loikb_pose_params* p)
+{
+  if (!S || !targets || !p) return LOIKB_ERR_ARG;
+  if (int pre = pose_preconditions(S, p, !q)) return pre;
   const auto t_call = std::chrono::steady_clock::now();
   HIPCHK(hipSetDevice(S->device));
   int rc;
@@ -4292,27 +4323,41 @@ int loikb_pose_get(loikb_solver* S, int field, void* out, int out_flags)
 // ---- include/loik_amd_limits.h ----------------------------------------------------------------------------------------------
 int loikb_limits_version(void) { return LOIKB_LIMITS_VERSION; }
 
-int loikb_set_joint_limits(loikb_solver* S, const double* q_lo, const double* q_hi, int n)
+// The rule of a per-DoF pair (lo, hi) [nv] in idx_v order, shared by loikb_set_joint_limits and loikb_multistart_set_ranges
+// (loik_amd_multistart.h): both pointers given, n == nv, no NaN, lo <= hi, and a finite entry only on a DoF whose coordinate a
+// plain sum advances (S->lim_q).  `fn`, `lo_name`, `hi_name` go into loikb_last_error().
+static int check_dof_pairs(const loikb_solver_impl* S, const char* fn, const char* lo_name, const char* hi_name, const double* lo, const double* hi, int n)
 {
-  if (!S) return LOIKB_ERR_ARG;
-  loikb_solver_impl::PoseState& P = S->pose;
-  if (!q_lo && !q_hi) { P.have_limits = false; return LOIKB_OK; }
-  if (!q_lo || !q_hi) { g_last_error = "set_joint_limits: q_lo and q_hi must both be given, or both be NULL (clear)"; return LOIKB_ERR_ARG; }
-  if (n != S->nv) { g_last_error = "set_joint_limits: need one (q_lo, q_hi) pair per DoF, n == model.nv"; return LOIKB_ERR_ARG; }
-  std::vector<PoseLimit> lim(S->nb);
-  bool any = false;
+  const std::string f(fn), ln(lo_name), hn(hi_name);
+  if (!lo || !hi) { g_last_error = f + ": " + ln + " and " + hn + " must both be given, or both be NULL (clear)"; return LOIKB_ERR_ARG; }
+  if (n != S->nv) { g_last_error = f + ": need one (" + ln + ", " + hn + ") pair per DoF, n == model.nv"; return LOIKB_ERR_ARG; }
   for (int j = 0; j < n; ++j) {
     char what[96];
-    snprintf(what, sizeof(what), "set_joint_limits: DoF %d (joint %d)", j, S->dof_ext[j]);
-    if (std::isnan(q_lo[j]) || std::isnan(q_hi[j])) { g_last_error = std::string(what) + ": a limit is NaN"; return LOIKB_ERR_ARG; }
-    if (q_lo[j] > q_hi[j]) { g_last_error = std::string(what) + ": q_lo > q_hi"; return LOIKB_ERR_ARG; }
-    const bool finite = std::isfinite(q_lo[j]) || std::isfinite(q_hi[j]);
+    snprintf(what, sizeof(what), "%s: DoF %d (joint %d)", fn, j, S->dof_ext[j]);
+    if (std::isnan(lo[j]) || std::isnan(hi[j])) { g_last_error = std::string(what) + ": a limit is NaN"; return LOIKB_ERR_ARG; }
+    if (lo[j] > hi[j]) { g_last_error = std::string(what) + ": " + ln + " > " + hn; return LOIKB_ERR_ARG; }
+    const bool finite = std::isfinite(lo[j]) || std::isfinite(hi[j]);
     if (finite && S->lim_q[j] < 0) {
       const int jt = S->dof_jt[j];
       const char* kind = jt == LOIKB_J_FREEFLYER ? "free-flyer" : jt == LOIKB_J_SPHERICAL ? "spherical" : jt == LOIKB_J_PLANAR ? "planar" : "unbounded (cos, sin) revolute";
       g_last_error = std::string(what) + " belongs to a " + kind + " joint: its configuration is not a scalar that a plain sum advances, it cannot carry a position limit";
       return LOIKB_ERR_ARG;
     }
+  }
+  return LOIKB_OK;
+}
+
+int loikb_set_joint_limits(loikb_solver* S, const double* q_lo, const double* q_hi, int n)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!q_lo && !q_hi) { P.have_limits = false; return LOIKB_OK; }
+  int rc;
+  if ((rc = check_dof_pairs(S, "set_joint_limits", "q_lo", "q_hi", q_lo, q_hi, n))) return rc;
+  std::vector<PoseLimit> lim(S->nb);
+  bool any = false;
+  for (int j = 0; j < n; ++j) {
+    const bool finite = std::isfinite(q_lo[j]) || std::isfinite(q_hi[j]);
     lim[j].qi = finite ? S->lim_q[j] : -1;
     lim[j].pad = 0;
     lim[j].lo = q_lo[j];
@@ -4321,7 +4366,6 @@ int loikb_set_joint_limits(loikb_solver* S, const double* q_lo, const double* q_
   }
   if (!any) { P.have_limits = false; return LOIKB_OK; }   // (no finite limit anywhere: the handle runs what it runs without limits)
   HIPCHK(hipSetDevice(S->device));
-  int rc;
   if (!P.d_lim && (rc = alloc_dev(S, (void**)&P.d_lim, sizeof(PoseLimit) * S->nb))) return rc;
   P.lim.swap(lim);
   HIPCHK(hipMemcpyAsync(P.d_lim, P.lim.data(), sizeof(PoseLimit) * S->nb, hipMemcpyHostToDevice, S->stream));
@@ -4469,6 +4513,251 @@ int loikb_frame_placements(loikb_solver* S, const int* links, const double* fram
   HIPCHK(hipGetLastError());
   if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));   // (dl and the caller's frames have been read)
+  return LOIKB_OK;
+}
+
+// ---- include/loik_amd_multistart.h (kernels in loik_pose_multistart.hpp) ------------------------------------------------------
+int loikb_multistart_version(void) { return LOIKB_MULTISTART_VERSION; }
+
+static int ms_alloc(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  if (M.d_count) return LOIKB_OK;
+  const size_t B = (size_t)S->B, nc = (size_t)std::max(S->nc, 1), nq = (size_t)S->nq, nv = (size_t)S->nb;
+  int rc;
+  if ((rc = alloc_dev(S, (void**)&M.d_tgt_in, sizeof(double) * B * nc * 12)) || (rc = alloc_dev(S, (void**)&M.d_tgt, sizeof(double) * B * nc * 12)) ||
+      (rc = alloc_dev(S, (void**)&M.d_q0, sizeof(double) * B * nq)) || (rc = alloc_dev(S, (void**)&M.d_table, sizeof(int) * nq)) ||
+      (rc = alloc_dev(S, (void**)&M.d_dofq, sizeof(int) * nv)) || (rc = alloc_dev(S, (void**)&M.d_lo, sizeof(double) * nv)) ||
+      (rc = alloc_dev(S, (void**)&M.d_hi, sizeof(double) * nv)) || (rc = alloc_dev(S, (void**)&M.d_w, sizeof(double) * nv)) ||
+      (rc = alloc_dev(S, (void**)&M.d_round, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&M.d_winner, sizeof(int) * B)) ||
+      (rc = alloc_dev(S, (void**)&M.d_gstatus, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&M.d_nreached, sizeof(int) * B)) ||
+      (rc = alloc_dev(S, (void**)&M.d_cost, sizeof(double) * B)) || (rc = alloc_dev(S, (void**)&M.d_wq, sizeof(double) * B * nq)) ||
+      (rc = alloc_dev(S, (void**)&M.d_werr, sizeof(double) * B * nc * 6)) || (rc = alloc_dev(S, (void**)&M.d_count, sizeof(unsigned int) * 2))) {
+    M.d_count = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+    return rc;
+  }
+  return LOIKB_OK;
+}
+
+// The ranges in force into M.up_lo / up_hi / up_table: those of loikb_multistart_set_ranges, else the joint limits of the handle.
+// A DoF is sampled iff both ends are finite.  Returns the number of sampled DoFs; touches nothing on the device.
+static int ms_resolve_ranges(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const loikb_solver_impl::PoseState& P = S->pose;
+  const double inf = std::numeric_limits<double>::infinity();
+  M.up_lo.assign(S->nv, -inf);
+  M.up_hi.assign(S->nv, inf);
+  M.up_table.assign(S->nq, -1);
+  int sampled = 0;
+  for (int j = 0; j < S->nv; ++j) {
+    if (M.have_ranges) { M.up_lo[j] = M.lo[j]; M.up_hi[j] = M.hi[j]; }
+    else if (P.have_limits) { M.up_lo[j] = P.lim[j].lo; M.up_hi[j] = P.lim[j].hi; }
+    if (std::isfinite(M.up_lo[j]) && std::isfinite(M.up_hi[j]) && S->lim_q[j] >= 0) { M.up_table[S->lim_q[j]] = j; ++sampled; }
+  }
+  return sampled;
+}
+
+// the tables of the sampler and of the selection onto the device (queued; the sources are members of the handle)
+static int ms_upload_tables(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  HIPCHK(hipMemcpyAsync(M.d_lo, M.up_lo.data(), sizeof(double) * S->nv, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(M.d_hi, M.up_hi.data(), sizeof(double) * S->nv, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(M.d_table, M.up_table.data(), sizeof(int) * S->nq, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(M.d_dofq, S->lim_q.data(), sizeof(int) * S->nv, hipMemcpyHostToDevice, S->stream));
+  if (!M.w.empty()) HIPCHK(hipMemcpyAsync(M.d_w, M.w.data(), sizeof(double) * S->nv, hipMemcpyHostToDevice, S->stream));
+  return LOIKB_OK;
+}
+
+// the goals' q0 rows into M.d_q0: the caller's [G][nq] (host / device), one shared host row, or the resident row g * K
+static int ms_set_q0(loikb_solver_impl* S, const double* q0, int flags, int G, int K)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const bool shared = q0 && (flags & LOIKB_Q_SHARED), dev = q0 && (flags & LOIKB_IN_DEVICE) && !shared;
+  const void* src = S->d_q;
+  size_t stride = (size_t)K * S->nq;
+  int rc;
+  if (q0) {
+    if ((rc = to_device(S, q0, sizeof(double) * (shared ? (size_t)S->nq : (size_t)G * S->nq), dev, &src))) return rc;
+    stride = shared ? 0 : (size_t)S->nq;
+  }
+  hipLaunchKernelGGL(k_ms_set_q0, grid1((size_t)G * S->nq), dim3(256), 0, S->stream, (const double*)src, stride, S->nq, G, M.d_q0);
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+static unsigned long long ms_mix_host(unsigned long long x)
+{
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+// the seeds of `round` into the resident q (status == nullptr: every row; else the rows without REACHED).  The handle is left as
+// loikb_solve_pose(q != NULL) leaves it after its copy: q resident, the inputs changed.
+static int ms_sample(loikb_solver_impl* S, unsigned long long seed, int K, int round, const int* status)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const unsigned long long key = ms_mix_host(seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)round + 1ull));
+  hipLaunchKernelGGL(k_ms_sample, grid1((size_t)S->B * S->nq), dim3(256), 0, S->stream, S->d_q, (const double*)M.d_q0, S->nq, S->B, K,
+                     (const int*)M.d_table, (const double*)M.d_lo, (const double*)M.d_hi, key, round, status, M.d_round);
+  HIPCHK(hipGetLastError());
+  S->have_q = true;
+  ++S->inputs_epoch;
+  return LOIKB_OK;
+}
+
+int loikb_multistart_set_ranges(loikb_solver* S, const double* s_lo, const double* s_hi, const double* weights, int n)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  int rc;
+  if ((s_lo || s_hi) && (rc = check_dof_pairs(S, "multistart_set_ranges", "s_lo", "s_hi", s_lo, s_hi, n))) return rc;
+  if (weights) {
+    if (n != S->nv) { g_last_error = "multistart_set_ranges: need one weight per DoF, n == model.nv"; return LOIKB_ERR_ARG; }
+    for (int j = 0; j < n; ++j)
+      if (!(weights[j] >= 0.0) || !std::isfinite(weights[j])) { g_last_error = "multistart_set_ranges: a weight is negative or not finite"; return LOIKB_ERR_ARG; }
+  }
+  M.have_ranges = s_lo != nullptr;
+  if (s_lo) { M.lo.assign(s_lo, s_lo + n); M.hi.assign(s_hi, s_hi + n); }
+  if (weights) M.w.assign(weights, weights + n);
+  else M.w.clear();
+  return LOIKB_OK;
+}
+
+int loikb_multistart_sample(loikb_solver* S, const double* q0, int q0_flags, unsigned long long seed, int seeds_per_goal, int round)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  const int K = seeds_per_goal;
+  if (K < 1 || S->B % K != 0 || round < 0) { g_last_error = "multistart_sample: need seeds_per_goal >= 1 that divides the batch, round >= 0"; return LOIKB_ERR_ARG; }
+  if (!S->have_problem) { g_last_error = "multistart_sample before SolveInit()"; return LOIKB_ERR_STATE; }
+  if (!q0 && !S->have_q) { g_last_error = "multistart_sample: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (ms_resolve_ranges(S) == 0 && (K > 1 || round > 0)) {
+    g_last_error = "multistart_sample: no DoF to sample (set ranges with loikb_multistart_set_ranges or joint limits with a finite pair)";
+    return LOIKB_ERR_STATE;
+  }
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if ((rc = ms_alloc(S)) || (rc = ms_upload_tables(S)) || (rc = ms_set_q0(S, q0, q0_flags, S->B / K, K)) || (rc = ms_sample(S, seed, K, round, nullptr))) {
+    (void)hipStreamSynchronize(S->stream);
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q0 has been read)
+  return LOIKB_OK;
+}
+
+int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double* targets, int in_flags, const loikb_pose_params* pose,
+                                const loikb_multistart_params* ms)
+{
+  if (!S || !targets || !pose || !ms) return LOIKB_ERR_ARG;
+  const int K = ms->seeds_per_goal, R = ms->rounds;
+  if (K < 1 || S->B % K != 0 || R < 1 || ms->pick < LOIKB_MS_PICK_NEAREST || ms->pick > LOIKB_MS_PICK_FIRST || ms->flags != 0) {
+    g_last_error = "solve_pose_multistart: need seeds_per_goal >= 1 that divides the batch, rounds >= 1, pick 0 or 1, flags 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (int pre = pose_preconditions(S, pose, !q0)) return pre;
+  if (ms_resolve_ranges(S) == 0 && (K > 1 || R > 1)) {
+    g_last_error = "solve_pose_multistart: no DoF to sample (set ranges with loikb_multistart_set_ranges or joint limits with a finite pair)";
+    return LOIKB_ERR_STATE;
+  }
+  const auto t_call = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if ((rc = ms_alloc(S))) return rc;
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const int B = S->B, G = B / K, nc = S->nc_active;
+  const bool dev = in_flags & LOIKB_IN_DEVICE, tgt_shared = in_flags & LOIKB_POSE_TARGET_SHARED;
+  // the targets, checked as loikb_solve_pose checks them, before anything of the handle changes
+  const size_t ntgt = (size_t)(tgt_shared ? 1 : G) * nc;
+  HIPCHK(hipMemcpyAsync(M.d_tgt_in, targets, sizeof(double) * 12 * ntgt, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemsetAsync(M.d_count, 0, 2 * sizeof(unsigned int), S->stream));
+  hipLaunchKernelGGL(k_pose_check_targets, grid1(ntgt), dim3(256), 0, S->stream, (const double*)M.d_tgt_in, (int)ntgt, 1e-9, M.d_count + 1);
+  HIPCHK(hipGetLastError());
+  unsigned int counts[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(counts, M.d_count, sizeof(counts), hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  if (counts[1]) { g_last_error = "solve_pose: a target rotation is not orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+  const auto t_sample = std::chrono::steady_clock::now();
+  double sample_ms = 0.0, solve_ms = 0.0, select_ms = 0.0;
+  hipLaunchKernelGGL(k_ms_expand_targets, grid1((size_t)B * nc * 12), dim3(256), 0, S->stream, (const double*)M.d_tgt_in, (int)tgt_shared, nc, K, B, M.d_tgt);
+  HIPCHK(hipGetLastError());
+  if ((rc = ms_upload_tables(S)) || (rc = ms_set_q0(S, q0, in_flags, G, K)) || (rc = ms_sample(S, ms->seed, K, 0, nullptr))) {
+    (void)hipStreamSynchronize(S->stream);
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q0 has been read)
+  sample_ms += ms_since(t_sample);
+  M.G = 0;
+  const loikb_solver_impl::PoseState& P = S->pose;
+  auto select = [&](int count_only) -> int {
+    HIPCHK(hipMemsetAsync(M.d_count, 0, sizeof(unsigned int), S->stream));
+    hipLaunchKernelGGL(k_ms_select, dim3((unsigned)G), dim3(MS_SELECT_THREADS), 0, S->stream, (const int*)P.d_status, (const double*)P.d_err,
+                       (const double*)S->d_q, (const double*)M.d_q0, (const int*)M.d_dofq, M.w.empty() ? (const double*)nullptr : (const double*)M.d_w,
+                       S->nv, S->nq, nc, K, (int)(ms->pick == LOIKB_MS_PICK_FIRST), count_only, M.d_count, M.d_winner, M.d_gstatus, M.d_cost,
+                       M.d_nreached, M.d_wq, M.d_werr);
+    HIPCHK(hipGetLastError());
+    return LOIKB_OK;
+  };
+  int rounds_run = 0;
+  for (int r = 0; r < R; ++r) {
+    const auto t_solve = std::chrono::steady_clock::now();
+    if ((rc = loikb_solve_pose(S, nullptr, M.d_tgt, LOIKB_IN_DEVICE, pose))) return rc;
+    solve_ms += ms_since(t_solve);
+    ++rounds_run;
+    if (r == R - 1) break;
+    // goals that own a reached seed: one counter back to the host
+    const auto t_count = std::chrono::steady_clock::now();
+    if ((rc = select(1))) return rc;
+    unsigned int answered = 0;
+    HIPCHK(hipMemcpyAsync(&answered, M.d_count, sizeof(answered), hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    select_ms += ms_since(t_count);
+    if (answered == (unsigned int)G) break;
+    const auto t_again = std::chrono::steady_clock::now();
+    if ((rc = ms_sample(S, ms->seed, K, r + 1, P.d_status))) return rc;
+    HIPCHK(hipStreamSynchronize(S->stream));
+    sample_ms += ms_since(t_again);
+  }
+  const auto t_select = std::chrono::steady_clock::now();
+  if ((rc = select(0))) return rc;
+  HIPCHK(hipStreamSynchronize(S->stream));
+  select_ms += ms_since(t_select);
+  M.G = G;
+  M.nc = nc;
+  const double total = ms_since(t_call);
+  M.timing[0] = rounds_run; M.timing[1] = total; M.timing[2] = solve_ms; M.timing[3] = sample_ms; M.timing[4] = select_ms;
+  M.timing[5] = total - solve_ms - sample_ms - select_ms;
+  return LOIKB_OK;
+}
+
+int loikb_multistart_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  const loikb_solver_impl::MultiStartState& M = S->ms;
+  if (M.G == 0) { g_last_error = "multistart_get before solve_pose_multistart"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const size_t G = (size_t)M.G;
+  switch (field) {
+  case LOIKB_MS_F_WINNER: src = M.d_winner; bytes = sizeof(int) * G; break;
+  case LOIKB_MS_F_GOAL_STATUS: src = M.d_gstatus; bytes = sizeof(int) * G; break;
+  case LOIKB_MS_F_Q: src = M.d_wq; bytes = sizeof(double) * G * S->nq; break;
+  case LOIKB_MS_F_ERR: src = M.d_werr; bytes = sizeof(double) * G * M.nc * 6; break;
+  case LOIKB_MS_F_COST: src = M.d_cost; bytes = sizeof(double) * G; break;
+  case LOIKB_MS_F_NREACHED: src = M.d_nreached; bytes = sizeof(int) * G; break;
+  case LOIKB_MS_F_ROUND: src = M.d_round; bytes = sizeof(int) * (size_t)S->B; break;
+  case LOIKB_MS_F_TIMING:
+    if (!to_dev) { memcpy(out, M.timing, sizeof(M.timing)); return LOIKB_OK; }
+    HIPCHK(hipMemcpy(out, M.timing, sizeof(M.timing), hipMemcpyHostToDevice));
+    return LOIKB_OK;
+  default: g_last_error = "multistart_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  HIPCHK(hipMemcpyAsync(out, src, bytes, to_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
   return LOIKB_OK;
 }
 
