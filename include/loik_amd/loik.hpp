@@ -20,6 +20,7 @@
 #include "../loik_amd_limits.h"
 #include "../loik_amd_tasks.h"
 #include "../loik_amd_multistart.h"
+#include "../loik_amd_path.h"
 
 #include <array>
 #include <map>
@@ -493,6 +494,50 @@ public:
     check(loikb_multistart_get(h_, LOIKB_MS_F_COST, r.cost.data(), 0));
     check(loikb_multistart_get(h_, LOIKB_MS_F_TIMING, r.timing.data(), 0));
     r.rounds_run = (int)r.timing[0];
+    return r;
+  }
+  // ---- waypoint paths (include/loik_amd_path.h): SolvePose along T waypoints per instance, each instance at its own pace
+  struct PathResult {
+    std::vector<int> reached, cursor, steps, status, path_status;  // [batch]; status: LOIKB_POSE_ST_*, path_status: LOIKB_PATH_ST_* bits
+    std::vector<int> wsteps;                                       // [batch][T]: steps spent on each waypoint
+    DVec err;                                                      // [batch][nc][6]: against waypoint min(cursor, T - 1)
+    DVec q_path;                                                   // [batch][T][nq], NaN rows from the cursor on; empty without record
+    int n_waypoints = 0;
+    std::array<double, 4> timing{};                                // LOIKB_PATH_F_TIMING
+  };
+  // waypoints: T * nc (waypoint-major) for the whole batch, or batch * T * nc instance-major; max_steps bounds the whole path,
+  // max_steps_per_waypoint (0: no bound) one waypoint; q as SolvePose takes it
+  PathResult SolvePosePath(const std::vector<SE3>& waypoints, int n_waypoints, double dt = 1.0, double gain = 1.0, double tol_pose = 1e-6,
+                           int max_steps = 100, int max_steps_per_waypoint = 0, bool record = true, const DVec* q = nullptr)
+  {
+    const std::size_t nc = (std::size_t)loikb_num_eq_c(h_), T = (std::size_t)(n_waypoints > 0 ? n_waypoints : 1);
+    int flags = 0;
+    if (waypoints.size() == T * nc && batch_ > 1) flags |= LOIKB_POSE_TARGET_SHARED;
+    else if (waypoints.size() != (std::size_t)batch_ * T * nc)
+      throw std::runtime_error("loik_amd: SolvePosePath needs n_waypoints placements per active constraint, shared or per instance");
+    if (q && q->size() != (std::size_t)batch_ * model_.nq) throw std::runtime_error("loik_amd: q must hold batch * model.nq values");
+    DVec t(waypoints.size() * 12);
+    for (std::size_t i = 0; i < waypoints.size(); ++i) std::copy(waypoints[i].begin(), waypoints[i].end(), t.begin() + 12 * i);
+    const loikb_pose_params p{dt, gain, tol_pose, max_steps, 0};
+    const loikb_path_params w{n_waypoints, max_steps_per_waypoint, record ? 1 : 0, 0};
+    check(loikb_solve_pose_path(h_, q ? q->data() : nullptr, t.data(), flags, &p, &w));
+    solved();
+    PathResult r;
+    r.n_waypoints = n_waypoints;
+    r.steps.resize(batch_); r.status.resize(batch_); r.reached.resize(batch_); r.cursor.resize(batch_); r.path_status.resize(batch_);
+    r.wsteps.resize((std::size_t)batch_ * T); r.err.resize((std::size_t)batch_ * nc * 6);
+    check(loikb_pose_get(h_, LOIKB_POSE_F_STEPS, r.steps.data(), 0));
+    check(loikb_pose_get(h_, LOIKB_POSE_F_STATUS, r.status.data(), 0));
+    check(loikb_pose_get(h_, LOIKB_POSE_F_ERR, r.err.data(), 0));
+    check(loikb_path_get(h_, LOIKB_PATH_F_CURSOR, r.cursor.data(), 0));
+    check(loikb_path_get(h_, LOIKB_PATH_F_STATUS, r.path_status.data(), 0));
+    check(loikb_path_get(h_, LOIKB_PATH_F_WSTEPS, r.wsteps.data(), 0));
+    check(loikb_path_get(h_, LOIKB_PATH_F_TIMING, r.timing.data(), 0));
+    if (record) {
+      r.q_path.resize((std::size_t)batch_ * T * model_.nq);
+      check(loikb_path_get(h_, LOIKB_PATH_F_Q, r.q_path.data(), 0));
+    }
+    for (int b = 0; b < batch_; ++b) r.reached[b] = (r.status[b] & LOIKB_POSE_ST_REACHED) ? 1 : 0;
     return r;
   }
   // the resident configurations, [batch][nq]

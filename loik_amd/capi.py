@@ -119,12 +119,23 @@ MS_F_WINNER, MS_F_GOAL_STATUS, MS_F_Q, MS_F_ERR, MS_F_COST, MS_F_NREACHED, MS_F_
 MS_GOAL_REACHED, MS_GOAL_BEST_EFFORT, MS_GOAL_FAILED = 1, 2, 4
 
 
+# include/loik_amd_path.h: per-instance waypoint paths in the pose loop; its own header and version again
+PATH_ABI_VERSION = 1
+PATH_SYMBOLS = ["loikb_path_version", "loikb_solve_pose_path", "loikb_path_get"]
+PATH_F_CURSOR, PATH_F_STATUS, PATH_F_WSTEPS, PATH_F_Q, PATH_F_TIMING = range(5)
+PATH_ST_COMPLETE, PATH_ST_STALLED = 1, 2
+
+
 class PoseParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
     _fields_ = [("seeds_per_goal", C.c_int), ("rounds", C.c_int), ("seed", C.c_ulonglong), ("pick", C.c_int), ("flags", C.c_int)]
+
+
+class PathParams(C.Structure):
+    _fields_ = [("n_waypoints", C.c_int), ("max_steps_per_waypoint", C.c_int), ("record", C.c_int), ("flags", C.c_int)]
 
 
 _lib = None
@@ -198,6 +209,8 @@ def lib():
     L.loikb_multistart_sample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.c_int, C.c_int]
     L.loikb_solve_pose_multistart.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseParams), C.POINTER(MultiStartParams)]
     L.loikb_multistart_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_solve_pose_path.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseParams), C.POINTER(PathParams)]
+    L.loikb_path_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -925,6 +938,92 @@ class BatchedLoik:
         G = self._ms_goals
         shape = {"q": (G, self.model.nq), "err": (G, nc, 6)}.get(name, (G,))
         return big[:int(np.prod(shape))].reshape(shape).copy()
+
+    # ---- waypoint paths (include/loik_amd_path.h) ------------------------------------------------------------
+    def SolvePosePath(self, waypoints, dt=1.0, gain=1.0, tol_pose=1e-6, max_steps=100, max_steps_per_waypoint=0, record=True, q=None):
+        """SolvePose along a path of T waypoints per instance, each instance at its own pace (loikb_solve_pose_path): an instance that
+        reaches its waypoint heads for the next in the same step, whatever the rest of the batch does.  max_steps bounds the steps
+        of the WHOLE path, max_steps_per_waypoint (0: no bound) those spent on one waypoint: an instance that exhausts it is
+        STALLED and stays where it is.
+        waypoints: [B][T][nc][4][4] / [B][T][nc][12], or [T][nc][4][4] / [T][nc][12] shared by the batch.  A device tensor of these
+        shapes likewise; a flat one goes by its numel: [B][T][nc][12] when that is a multiple of batch * nc * 12, else [T][nc][12].
+        q as in SolvePose.
+        Returns dict(reached [B] bool (the whole path), cursor [B] waypoints reached, steps [B] in total, wsteps [B][T] steps per
+        waypoint, status [B] POSE_ST_* bits, path_status [B] PATH_ST_* bits, err [B][nc][6] against waypoint min(cursor, T - 1),
+        q_path [B][T][nq] = q at each reached waypoint, NaN rows from the cursor on (None with record=False)), and with joint
+        position limits on the handle limit_flags [B][nv]."""
+        B, nc = self.batch, int(self.L.loikb_num_eq_c(self.h))
+        flags, keep = 0, []
+        if hasattr(waypoints, "data_ptr") and getattr(waypoints, "is_cuda", False):
+            n, shape = int(waypoints.numel()), tuple(getattr(waypoints, "shape", ()))
+            if len(shape) == 4 and shape[0] == B and shape[2] == nc:
+                T, shared = shape[1], False
+            elif len(shape) == 3 and shape[1] == nc:
+                T, shared = shape[0], True
+            elif n and n % (B * nc * 12) == 0:
+                T, shared = n // (B * nc * 12), False
+            elif n and n % (nc * 12) == 0:
+                T, shared = n // (nc * 12), True
+            else:
+                raise ValueError("waypoints: device tensor has %d elements, expected batch * T * nc * 12 or T * nc * 12" % n)
+            if n != (1 if shared else B) * T * nc * 12:
+                raise ValueError("waypoints: device tensor of shape %s is neither [B][T][nc][12] nor [T][nc][12]" % (shape,))
+            wp = C.c_void_p(waypoints.data_ptr())
+            flags |= IN_DEVICE
+        else:
+            t = self._placements12(waypoints.numpy() if hasattr(waypoints, "numpy") else waypoints, "waypoints")
+            if t.ndim == 4 and t.shape[0] == B and t.shape[2] == nc:
+                T, shared = t.shape[1], False
+            elif t.ndim == 3 and t.shape[1] == nc:
+                T, shared = t.shape[0], True
+            else:
+                raise ValueError("waypoints: shape %s, expected [batch = %d][T][nc = %d][12] or [T][nc][12]" % (t.shape, B, nc))
+            keep.append(t)
+            wp = t.ctypes.data_as(C.c_void_p)
+        if shared and B > 1:
+            flags |= POSE_TARGET_SHARED
+        qp = None
+        if q is not None:
+            if isinstance(q, int) or (hasattr(q, "data_ptr") and getattr(q, "is_cuda", False)):
+                if not flags & IN_DEVICE:
+                    raise ValueError("q and waypoints must both be host arrays or both device pointers")
+                qp = C.c_void_p(q if isinstance(q, int) else q.data_ptr())
+            else:
+                if flags & IN_DEVICE:
+                    raise ValueError("q and waypoints must both be host arrays or both device pointers")
+                qa = _f64(q)
+                if qa.size != B * self.model.nq:
+                    raise ValueError("q has %d elements, expected batch * nq = %d" % (qa.size, B * self.model.nq))
+                keep.append(qa)
+                qp = qa.ctypes.data_as(C.c_void_p)
+        prm = PoseParams(float(dt), float(gain), float(tol_pose), int(max_steps), 0)
+        pth = PathParams(int(T), int(max_steps_per_waypoint), int(record), 0)
+        _check(self.L.loikb_solve_pose_path(self.h, qp, wp, flags, C.byref(prm), C.byref(pth)))
+        self._path_T = int(T)
+        status = np.empty(B, dtype=np.int32)
+        steps = np.empty(B, dtype=np.int32)
+        err = np.empty((B, nc, 6))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_STATUS, status.ctypes.data_as(C.c_void_p), 0))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_STEPS, steps.ctypes.data_as(C.c_void_p), 0))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_ERR, err.ctypes.data_as(C.c_void_p), 0))
+        out = dict(reached=(status & POSE_ST_REACHED) != 0, cursor=self.path_get("cursor"), steps=steps, wsteps=self.path_get("wsteps"),
+                   status=status, path_status=self.path_get("path_status"), err=err, q_path=self.path_get("q_path") if int(record) == 1 else None)
+        if self._limits:
+            out["limit_flags"] = self.pose_limit_flags()
+        return out
+
+    def path_get(self, name):
+        """one result of the last SolvePosePath (loikb_path_get): cursor / path_status / wsteps / q_path / timing (a dict as pose_timing)"""
+        B, T = self.batch, getattr(self, "_path_T", 1)
+        if name == "timing":
+            t = np.zeros(4)
+            _check(self.L.loikb_path_get(self.h, PATH_F_TIMING, t.ctypes.data_as(C.c_void_p), 0))
+            return dict(steps=int(t[0]), total_ms=float(t[1]), solve_ms=float(t[2]), other_ms=float(t[3]))
+        fid, dtype, shape = {"cursor": (PATH_F_CURSOR, np.int32, (B,)), "path_status": (PATH_F_STATUS, np.int32, (B,)),
+                             "wsteps": (PATH_F_WSTEPS, np.int32, (B, T)), "q_path": (PATH_F_Q, np.float64, (B, T, self.model.nq))}[name]
+        arr = np.empty(shape, dtype=dtype)
+        _check(self.L.loikb_path_get(self.h, fid, arr.ctypes.data_as(C.c_void_p), 0))
+        return arr
 
     # ------------------------------------------------------------------------------------------------------
     def set_max_iter(self, n):

@@ -21,6 +21,7 @@
 #include "loik_pose.hpp"
 #include "loik_pose_tasks.hpp"
 #include "loik_pose_multistart.hpp"
+#include "loik_pose_path.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -36,6 +37,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_limits.h"
 #include "../../include/loik_amd_tasks.h"
 #include "../../include/loik_amd_multistart.h"
+#include "../../include/loik_amd_path.h"
 
 #include <algorithm>
 #include <chrono>
@@ -387,6 +389,22 @@ struct loikb_solver_impl {
     int G = 0, nc = 0;                 // of the last loikb_solve_pose_multistart (G = 0: none yet)
     double timing[6] = {0, 0, 0, 0, 0, 0};   // LOIKB_MS_F_TIMING
   } ms;
+  // waypoint paths (loik_pose_path.hpp): buffers of loikb_solve_pose_path, allocated by its first call.  The [B] arrays go with the
+  // handle's `allocs`; the three sized by the waypoint count are the path's own and grow with it (path_alloc)
+  struct PathState {
+    int* d_cursor = nullptr;           // [B] waypoints reached
+    int* d_ws = nullptr;               // [B] steps spent on the waypoint at the cursor
+    int* d_wfrom = nullptr;            // [B] the cursor before the last re-target (k_path_record stores the rows [wfrom, cursor))
+    int* d_lstatus = nullptr;          // [B] the loop-private status word handed to k_pose_integrate / k_pose_limit_box
+    int* d_pstatus = nullptr;          // [B] LOIKB_PATH_ST_* bits
+    double* d_wp = nullptr;            // [B][T][nc][12] waypoints (shared: the first T * nc rows)
+    int* d_wsteps = nullptr;           // [B][T]
+    double* d_Q = nullptr;             // [B][T][nq], allocated by the first call with record
+    int cap_wp = 0, cap_T = 0, cap_TQ = 0;   // waypoint counts d_wp, d_wsteps and d_Q have room for
+    int T = 0;                         // of the last loikb_solve_pose_path (0: none yet)
+    bool recorded = false;             // it ran with record: d_Q is its result
+    double timing[4] = {0, 0, 0, 0};   // LOIKB_PATH_F_TIMING
+  } path;
 };
 using Chunk = loikb_solver_impl::Chunk;
 
@@ -3069,6 +3087,9 @@ int loikb_destroy(loikb_solver* S)
   if (S->d_pass_cslot) (void)hipFree(S->d_pass_cslot);
   if (S->d_log) (void)hipFree(S->d_log);
   if (S->d_log_rows) (void)hipFree(S->d_log_rows);
+  if (S->path.d_wp) (void)hipFree(S->path.d_wp);
+  if (S->path.d_wsteps) (void)hipFree(S->path.d_wsteps);
+  if (S->path.d_Q) (void)hipFree(S->path.d_Q);
   (void)hipGetLastError();  // a failed free must not surface in the next solver's first launch check
   if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
   if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
@@ -4186,6 +4207,78 @@ static int pose_preconditions(const loikb_solver_impl* S, const loikb_pose_param
   return LOIKB_OK;
 }
 
+// The head of a pose loop once its targets are accepted (loikb_solve_pose, loikb_solve_pose_path): q replaces the resident
+// configurations, the constraint links and the shared A go to the device, status and steps start at 0.
+static int pose_begin(loikb_solver_impl* S, const double* q, bool dev)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  const int B = S->B, nc = S->nc_active;
+  int rc;
+  if (q) {   // (the copy path of k_advance_q: the resident configurations are replaced; FwdPassInit runs in the first solve)
+    const void* dq = nullptr;
+    if ((rc = to_device(S, q, sizeof(double) * (size_t)B * S->nq, dev, &dq))) return rc;
+    if (S->f32) hipLaunchKernelGGL(k_advance_q<float>, grid1(B), dim3(256), 0, S->stream, S->d_q, (const double*)dq, 0, S->nq, S->d_jd, S->d_idx_q, S->L, B, S->home.tiles, 0.0);
+    else hipLaunchKernelGGL(k_advance_q<double>, grid1(B), dim3(256), 0, S->stream, S->d_q, (const double*)dq, 0, S->nq, S->d_jd, S->d_idx_q, S->L, B, S->home.tiles, 0.0);
+    HIPCHK(hipGetLastError());
+    S->have_q = true;
+  }
+  std::vector<int> cl(nc);
+  for (int c = 0; c < nc; ++c) cl[c] = S->link_of[S->active_ids[c]];
+  HIPCHK(hipMemcpyAsync(P.d_clink, cl.data(), sizeof(int) * nc, hipMemcpyHostToDevice, S->stream));
+  if (S->a_shared) HIPCHK(hipMemcpyAsync(P.d_A, S->A_host.data(), sizeof(double) * 36 * nc, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_status, 0, sizeof(int) * B, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_steps, 0, sizeof(int) * B, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (q, cl are the caller's / locals)
+  P.nc = nc;
+  P.flags_valid = P.have_limits;
+  return LOIKB_OK;
+}
+
+// One step of a pose loop after its re-target left b_c in P.d_b: the step's box (limits), the b edits, the tailored Solve, the
+// integrate and the clamp.  `d_status`: the word whose POSE_REACHED / POSE_STOPPED bits say which instances run (P.d_status for
+// loikb_solve_pose, the loop-private word for loikb_solve_pose_path).
+static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxScope& box, int* d_status, double* solve_ms)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  const int B = S->B, nc = S->nc_active;
+  int rc = LOIKB_OK;
+  if (box.active) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
+    if (S->f32)
+      hipLaunchKernelGGL(k_pose_limit_box<float>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                         p->dt, (const int*)d_status, box.was_shared ? (const float*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
+                         S->home.tiles, S->L, P.d_lflags, P.d_inrange);
+    else
+      hipLaunchKernelGGL(k_pose_limit_box<double>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                         p->dt, (const int*)d_status, box.was_shared ? (const double*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
+                         S->home.tiles, S->L, P.d_lflags, P.d_inrange);
+    HIPCHK(hipGetLastError());
+  }
+  // UpdateEqConstraint(c, NULL, b_c, LOIKB_IN_DEVICE) for every active constraint, queued behind each other (the solve below
+  // synchronises), then the tailored Solve on the resident q without a constraint rewrite
+  S->defer_sync = true;
+  for (int c = 0; c < nc && rc == LOIKB_OK; ++c) rc = update_eq_single(S, S->active_ids[c], nullptr, P.d_b + (size_t)c * B * 6, LOIKB_IN_DEVICE);
+  S->defer_sync = false;
+  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
+  S->pass_active = false;
+  const auto t_solve = std::chrono::steady_clock::now();
+  if ((rc = loikb_solve_tailored(S, nullptr, -1, nullptr, nullptr, 0))) return rc;
+  *solve_ms += ms_since(t_solve);
+  if (S->f32)
+    hipLaunchKernelGGL(k_pose_integrate<float>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
+                       (const char*)S->home.tiles, p->dt, d_status);
+  else
+    hipLaunchKernelGGL(k_pose_integrate<double>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
+                       (const char*)S->home.tiles, p->dt, d_status);
+  HIPCHK(hipGetLastError());
+  if (box.active) {
+    hipLaunchKernelGGL(k_pose_limit_clamp, grid_dof(S), dim3(256), 0, S->stream, S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                       (const unsigned char*)P.d_inrange);
+    HIPCHK(hipGetLastError());
+  }
+  ++S->inputs_epoch;
+  return LOIKB_OK;
+}
+
 int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, int in_flags, const loikb_pose_params* p)
 {
   if (!S || !targets || !p) return LOIKB_ERR_ARG;
@@ -4208,23 +4301,7 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
   HIPCHK(hipStreamSynchronize(S->stream));
   if (counts[1]) { g_last_error = "solve_pose: a target rotation is not orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
   ++S->inputs_epoch;
-  if (q) {   // (the copy path of k_advance_q: the resident configurations are replaced; FwdPassInit runs in the first solve)
-    const void* dq = nullptr;
-    if ((rc = to_device(S, q, sizeof(double) * (size_t)B * S->nq, dev, &dq))) return rc;
-    if (S->f32) hipLaunchKernelGGL(k_advance_q<float>, grid1(B), dim3(256), 0, S->stream, S->d_q, (const double*)dq, 0, S->nq, S->d_jd, S->d_idx_q, S->L, B, S->home.tiles, 0.0);
-    else hipLaunchKernelGGL(k_advance_q<double>, grid1(B), dim3(256), 0, S->stream, S->d_q, (const double*)dq, 0, S->nq, S->d_jd, S->d_idx_q, S->L, B, S->home.tiles, 0.0);
-    HIPCHK(hipGetLastError());
-    S->have_q = true;
-  }
-  std::vector<int> cl(nc);
-  for (int c = 0; c < nc; ++c) cl[c] = S->link_of[S->active_ids[c]];
-  HIPCHK(hipMemcpyAsync(P.d_clink, cl.data(), sizeof(int) * nc, hipMemcpyHostToDevice, S->stream));
-  if (S->a_shared) HIPCHK(hipMemcpyAsync(P.d_A, S->A_host.data(), sizeof(double) * 36 * nc, hipMemcpyHostToDevice, S->stream));
-  HIPCHK(hipMemsetAsync(P.d_status, 0, sizeof(int) * B, S->stream));
-  HIPCHK(hipMemsetAsync(P.d_steps, 0, sizeof(int) * B, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));   // (q, cl are the caller's / locals)
-  P.nc = nc;
-  P.flags_valid = P.have_limits;
+  if ((rc = pose_begin(S, q, dev))) return rc;
   PoseBoxScope box{S};
   if (P.have_limits) {
     if ((rc = box.enter())) return rc;
@@ -4254,40 +4331,7 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
     HIPCHK(hipMemcpyAsync(&running, P.d_count, sizeof(running), hipMemcpyDeviceToHost, S->stream));
     HIPCHK(hipStreamSynchronize(S->stream));
     if (running == 0) break;
-    if (box.active) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
-      if (S->f32)
-        hipLaunchKernelGGL(k_pose_limit_box<float>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
-                           p->dt, (const int*)P.d_status, box.was_shared ? (const float*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
-                           S->home.tiles, S->L, P.d_lflags, P.d_inrange);
-      else
-        hipLaunchKernelGGL(k_pose_limit_box<double>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
-                           p->dt, (const int*)P.d_status, box.was_shared ? (const double*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
-                           S->home.tiles, S->L, P.d_lflags, P.d_inrange);
-      HIPCHK(hipGetLastError());
-    }
-    // UpdateEqConstraint(c, NULL, b_c, LOIKB_IN_DEVICE) for every active constraint, queued behind each other (the solve below
-    // synchronises), then the tailored Solve on the resident q without a constraint rewrite
-    S->defer_sync = true;
-    for (int c = 0; c < nc && rc == LOIKB_OK; ++c) rc = update_eq_single(S, S->active_ids[c], nullptr, P.d_b + (size_t)c * B * 6, LOIKB_IN_DEVICE);
-    S->defer_sync = false;
-    if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
-    S->pass_active = false;
-    const auto t_solve = std::chrono::steady_clock::now();
-    if ((rc = loikb_solve_tailored(S, nullptr, -1, nullptr, nullptr, 0))) return rc;
-    solve_ms += ms_since(t_solve);
-    if (S->f32)
-      hipLaunchKernelGGL(k_pose_integrate<float>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
-                         (const char*)S->home.tiles, p->dt, P.d_status);
-    else
-      hipLaunchKernelGGL(k_pose_integrate<double>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
-                         (const char*)S->home.tiles, p->dt, P.d_status);
-    HIPCHK(hipGetLastError());
-    if (box.active) {
-      hipLaunchKernelGGL(k_pose_limit_clamp, grid_dof(S), dim3(256), 0, S->stream, S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
-                         (const unsigned char*)P.d_inrange);
-      HIPCHK(hipGetLastError());
-    }
-    ++S->inputs_epoch;
+    if ((rc = pose_step(S, p, box, P.d_status, &solve_ms))) return rc;
     ++steps_run;
   }
   if ((rc = box.leave())) return rc;
@@ -4755,6 +4799,170 @@ int loikb_multistart_get(loikb_solver* S, int field, void* out, int out_flags)
     HIPCHK(hipMemcpy(out, M.timing, sizeof(M.timing), hipMemcpyHostToDevice));
     return LOIKB_OK;
   default: g_last_error = "multistart_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  HIPCHK(hipMemcpyAsync(out, src, bytes, to_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
+}
+
+// ---- include/loik_amd_path.h (kernels in loik_pose_path.hpp) ------------------------------------------------------------------
+int loikb_path_version(void) { return LOIKB_PATH_VERSION; }
+
+// a buffer of the path state that is sized by the waypoint count: grown (never shrunk) to `bytes`, its contents are not kept
+static int path_grow(void** buf, size_t bytes)
+{
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
+  if (*buf) HIPCHK(hipFree(*buf));
+  *buf = p;
+  return LOIKB_OK;
+}
+
+// the [B] arrays on first use, and room for T waypoints in the staging buffer.  Holds no result of an earlier call.
+static int path_alloc_inputs(loikb_solver_impl* S, int T)
+{
+  loikb_solver_impl::PathState& W = S->path;
+  const size_t B = (size_t)S->B, nc = (size_t)std::max(S->nc, 1);
+  int rc;
+  if (!W.d_cursor) {
+    if ((rc = alloc_dev(S, (void**)&W.d_ws, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&W.d_wfrom, sizeof(int) * B)) ||
+        (rc = alloc_dev(S, (void**)&W.d_lstatus, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&W.d_pstatus, sizeof(int) * B)) ||
+        (rc = alloc_dev(S, (void**)&W.d_cursor, sizeof(int) * B))) {
+      W.d_cursor = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+      return rc;
+    }
+  }
+  if (T > W.cap_wp) {
+    if ((rc = path_grow((void**)&W.d_wp, sizeof(double) * B * (size_t)T * nc * 12))) return rc;
+    W.cap_wp = T;
+  }
+  return LOIKB_OK;
+}
+
+// WSTEPS and, with record, Q for T waypoints: they hold the results of the last call, so they are regrown only by a call that
+// has passed every check
+static int path_alloc_results(loikb_solver_impl* S, int T, bool record)
+{
+  loikb_solver_impl::PathState& W = S->path;
+  const size_t B = (size_t)S->B;
+  int rc;
+  if (T > W.cap_T) {
+    if ((rc = path_grow((void**)&W.d_wsteps, sizeof(int) * B * (size_t)T))) return rc;
+    W.cap_T = T;
+  }
+  if (record && T > W.cap_TQ) {
+    if ((rc = path_grow((void**)&W.d_Q, sizeof(double) * B * (size_t)T * S->nq))) return rc;
+    W.cap_TQ = T;
+  }
+  return LOIKB_OK;
+}
+
+int loikb_solve_pose_path(loikb_solver* S, const double* q, const double* waypoints, int in_flags, const loikb_pose_params* p,
+                          const loikb_path_params* path)
+{
+  if (!S || !waypoints || !p || !path) return LOIKB_ERR_ARG;
+  if (path->n_waypoints < 1 || path->max_steps_per_waypoint < 0 || path->record < 0 || path->record > 1 || path->flags != 0) {
+    g_last_error = "solve_pose_path: need n_waypoints >= 1, max_steps_per_waypoint >= 0, record 0 or 1, flags 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (int pre = pose_preconditions(S, p, !q)) return pre;
+  const auto t_call = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(S->device));
+  const int B = S->B, nc = S->nc_active, T = path->n_waypoints, budget = path->max_steps_per_waypoint;
+  const bool dev = in_flags & LOIKB_IN_DEVICE, wp_shared = in_flags & LOIKB_POSE_TARGET_SHARED, record = path->record != 0;
+  if ((size_t)(wp_shared ? 1 : B) * T * nc > (size_t)0x7fffffff) { g_last_error = "solve_pose_path: too many waypoints"; return LOIKB_ERR_ARG; }
+  int rc;
+  if ((rc = pose_alloc(S)) || (rc = path_alloc_inputs(S, T))) return rc;
+  loikb_solver_impl::PoseState& P = S->pose;
+  loikb_solver_impl::PathState& W = S->path;
+  // the waypoints, all of them, checked before anything of the handle changes
+  const size_t nwp = (size_t)(wp_shared ? 1 : B) * T * nc;
+  HIPCHK(hipMemcpyAsync(W.d_wp, waypoints, sizeof(double) * 12 * nwp, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_count, 0, 2 * sizeof(unsigned int), S->stream));
+  hipLaunchKernelGGL(k_pose_check_targets, grid1(nwp), dim3(256), 0, S->stream, (const double*)W.d_wp, (int)nwp, 1e-9, P.d_count + 1);
+  HIPCHK(hipGetLastError());
+  unsigned int counts[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(counts, P.d_count, sizeof(counts), hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  if (counts[1]) { g_last_error = "solve_pose_path: a waypoint rotation is not orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+  if ((rc = path_alloc_results(S, T, record))) return rc;
+  ++S->inputs_epoch;
+  if ((rc = pose_begin(S, q, dev))) return rc;
+  W.T = T;
+  W.recorded = record;
+  const size_t nBT = (size_t)B * T, nQ = record ? nBT * S->nq : 0;
+  hipLaunchKernelGGL(k_path_setup, grid1(std::max(std::max(nBT, nQ), (size_t)B)), dim3(256), 0, S->stream, B, nBT, nQ, W.d_cursor, W.d_ws,
+                     W.d_wfrom, W.d_lstatus, W.d_pstatus, W.d_wsteps, W.d_Q);
+  HIPCHK(hipGetLastError());
+  PoseBoxScope box{S};
+  if (P.have_limits) {
+    if ((rc = box.enter())) return rc;
+    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
+  }
+  const double k = p->gain / p->dt;
+  const PoseTask* tasks = P.have_tasks ? (const PoseTask*)P.d_tasks : nullptr;
+  const double* A_sh = S->a_shared ? (const double*)P.d_A : nullptr;
+  double solve_ms = 0.0;
+  int steps_run = 0;
+  for (int step = 0;; ++step) {
+    const int go = step < p->max_steps;
+    HIPCHK(hipMemsetAsync(P.d_count, 0, sizeof(unsigned int), S->stream));
+    if (S->f32)
+      hipLaunchKernelGGL(k_path_retarget<float>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                         (const int*)P.d_clink, nc, tasks, (const double*)W.d_wp, (int)wp_shared, T, A_sh, (const char*)S->home.tiles, S->L, B,
+                         k, p->tol_pose, go, budget, P.d_b, P.d_err, W.d_lstatus, P.d_status, W.d_pstatus, P.d_steps, W.d_cursor, W.d_ws,
+                         W.d_wfrom, W.d_wsteps, P.d_count);
+    else
+      hipLaunchKernelGGL(k_path_retarget<double>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                         (const int*)P.d_clink, nc, tasks, (const double*)W.d_wp, (int)wp_shared, T, A_sh, (const char*)S->home.tiles, S->L, B,
+                         k, p->tol_pose, go, budget, P.d_b, P.d_err, W.d_lstatus, P.d_status, W.d_pstatus, P.d_steps, W.d_cursor, W.d_ws,
+                         W.d_wfrom, W.d_wsteps, P.d_count);
+    HIPCHK(hipGetLastError());
+    if (record) {   // (q is the one the re-target saw: the step's integrate is queued behind)
+      hipLaunchKernelGGL(k_path_record, grid1((size_t)B * S->nq), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, B, T,
+                         (const int*)W.d_wfrom, (const int*)W.d_cursor, W.d_Q);
+      HIPCHK(hipGetLastError());
+    }
+    if (!go) break;
+    unsigned int running = 0;
+    HIPCHK(hipMemcpyAsync(&running, P.d_count, sizeof(running), hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    if (running == 0) break;
+    // (the loop-private word: a stalled instance is "stopped" to the integrate and the limit box, and to them alone)
+    if ((rc = pose_step(S, p, box, W.d_lstatus, &solve_ms))) return rc;
+    ++steps_run;
+  }
+  if ((rc = box.leave())) return rc;
+  HIPCHK(hipStreamSynchronize(S->stream));
+  const double total = ms_since(t_call);
+  P.timing[0] = steps_run; P.timing[1] = total; P.timing[2] = solve_ms; P.timing[3] = total - solve_ms;
+  memcpy(W.timing, P.timing, sizeof(W.timing));
+  return LOIKB_OK;
+}
+
+int loikb_path_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  const loikb_solver_impl::PathState& W = S->path;
+  if (W.T == 0) { g_last_error = "path_get before solve_pose_path"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const size_t B = (size_t)S->B;
+  switch (field) {
+  case LOIKB_PATH_F_CURSOR: src = W.d_cursor; bytes = sizeof(int) * B; break;
+  case LOIKB_PATH_F_STATUS: src = W.d_pstatus; bytes = sizeof(int) * B; break;
+  case LOIKB_PATH_F_WSTEPS: src = W.d_wsteps; bytes = sizeof(int) * B * W.T; break;
+  case LOIKB_PATH_F_Q:
+    if (!W.recorded) { g_last_error = "path_get: the last solve_pose_path ran with record = 0"; return LOIKB_ERR_STATE; }
+    src = W.d_Q; bytes = sizeof(double) * B * W.T * S->nq;
+    break;
+  case LOIKB_PATH_F_TIMING:
+    if (!to_dev) { memcpy(out, W.timing, sizeof(W.timing)); return LOIKB_OK; }
+    HIPCHK(hipMemcpy(out, W.timing, sizeof(W.timing), hipMemcpyHostToDevice));
+    return LOIKB_OK;
+  default: g_last_error = "path_get: unknown field"; return LOIKB_ERR_ARG;
   }
   HIPCHK(hipMemcpyAsync(out, src, bytes, to_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
