@@ -1,0 +1,863 @@
+// loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
+// (loik_amd_limits.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h) and waypoint paths
+// (loik_amd_path.h).  Included at the end of loik_host.hip, whose translation unit it belongs to: it is no header of its own.
+//
+// What the three solves share is here once: pose_check_targets (the check before anything of the handle changes), pose_begin,
+// pose_loop (the step loop around the caller's re-target) with pose_step, and get_copy_out / get_timing_out for the getters.
+
+// ---- batched pose IK (include/loik_amd_pose.h, kernels in loik_pose.hpp) ---------------------------------------------------
+static int pose_alloc(loikb_solver_impl* S)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (P.d_tgt) return LOIKB_OK;
+  const size_t B = (size_t)S->B, nc = (size_t)std::max(S->nc, 1);
+  int rc;
+  if ((rc = alloc_dev(S, (void**)&P.d_tgt, sizeof(double) * B * nc * 12)) || (rc = alloc_dev(S, (void**)&P.d_b, sizeof(double) * B * nc * 6)) ||
+      (rc = alloc_dev(S, (void**)&P.d_err, sizeof(double) * B * nc * 6)) || (rc = alloc_dev(S, (void**)&P.d_A, sizeof(double) * nc * 36)) ||
+      (rc = alloc_dev(S, (void**)&P.d_status, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&P.d_steps, sizeof(int) * B)) ||
+      (rc = alloc_dev(S, (void**)&P.d_clink, sizeof(int) * nc)) || (rc = alloc_dev(S, (void**)&P.d_count, sizeof(unsigned int) * 2))) {
+    P.d_tgt = nullptr;   // (what was allocated stays in `allocs` and goes with the handle; the next call allocates afresh)
+    return rc;
+  }
+  return LOIKB_OK;
+}
+
+// ---- joint position limits (include/loik_amd_limits.h) --------------------------------------------------------------------
+// buffers of a pose solve with limits; the [nb][B] copy of the base box only for a handle whose box is per instance
+static int pose_limits_alloc(loikb_solver_impl* S, bool need_box)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  const size_t n = (size_t)S->B * S->nb;
+  int rc;
+  if (!P.d_lflags && (rc = alloc_dev(S, (void**)&P.d_lflags, sizeof(int) * n))) return rc;
+  if (!P.d_inrange && (rc = alloc_dev(S, (void**)&P.d_inrange, n))) return rc;
+  if (need_box && !P.d_box && (rc = alloc_dev(S, (void**)&P.d_box, sizeof(double2) * n))) return rc;
+  return LOIKB_OK;
+}
+
+static dim3 grid_dof(const loikb_solver_impl* S) { return dim3((unsigned)((S->B + 255) / 256), (unsigned)S->nb); }
+
+// JP_LBUB of the home tiles <-> PoseState::d_box
+static int pose_box_copy(loikb_solver_impl* S, int restore)
+{
+  with_real(S, [&](auto t) {
+    hipLaunchKernelGGL(k_box_copy<decltype(t)>, grid_dof(S), dim3(256), 0, S->stream, S->home.tiles, S->L, S->B, S->pose.d_box, restore);
+  });
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+// The handle while a pose solve with limits runs: per-instance-box mode (every engine, the compaction's move_bounds and the
+// pass-level path read S->bnd_shared when a solve is launched: make_params in run_chunk, compact, pass_params), the base box
+// kept in the uniform buffer (shared) or in d_box (per instance).  Leaving the scope puts the base box back in force in the
+// mode it had, on every return path.
+struct PoseBoxScope {
+  loikb_solver_impl* S;
+  bool active = false, was_shared = false;
+  int enter()
+  {
+    was_shared = S->bnd_shared;
+    int rc;
+    if ((rc = pose_limits_alloc(S, !was_shared))) return rc;
+    if (!was_shared && (rc = pose_box_copy(S, 0))) return rc;
+    S->bnd_shared = false;
+    active = true;
+    return LOIKB_OK;
+  }
+  int leave()
+  {
+    if (!active) return LOIKB_OK;
+    active = false;
+    S->bnd_shared = was_shared;
+    S->pass_active = false;
+    ++S->inputs_epoch;
+    return was_shared ? LOIKB_OK : pose_box_copy(S, 1);
+  }
+  ~PoseBoxScope() { if (active) { (void)leave(); (void)hipStreamSynchronize(S->stream); } }
+};
+
+static double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// `n` placements [12] of the caller (`dev`: on the device) into `staging`, and the check every pose solve makes before anything
+// of the handle changes: `message` and LOIKB_ERR_ARG if one of them is not finite or its rotation not orthonormal with
+// determinant 1.  `d_count`: two counters of the caller's state.
+static int pose_check_targets(loikb_solver_impl* S, double* staging, const double* src, size_t n, bool dev, unsigned int* d_count,
+                              const char* message)
+{
+  HIPCHK(hipMemcpyAsync(staging, src, sizeof(double) * 12 * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemsetAsync(d_count, 0, 2 * sizeof(unsigned int), S->stream));
+  hipLaunchKernelGGL(k_pose_check_targets, grid1(n), dim3(256), 0, S->stream, (const double*)staging, (int)n, 1e-9, d_count + 1);
+  HIPCHK(hipGetLastError());
+  unsigned int counts[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(counts, d_count, sizeof(counts), hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  if (counts[1]) { g_last_error = message; return LOIKB_ERR_ARG; }
+  return LOIKB_OK;
+}
+
+// The tail of a getter: `bytes` from the device buffer `src` to `out` (host, or device with LOIKB_OUT_DEVICE), complete on return
+static int get_copy_out(loikb_solver_impl* S, const void* src, size_t bytes, void* out, int out_flags)
+{
+  HIPCHK(hipMemcpyAsync(out, src, bytes, (out_flags & LOIKB_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
+}
+
+// ... and of a TIMING field, which lives on the host
+static int get_timing_out(const double* timing, size_t nbytes, void* out, bool to_dev)
+{
+  if (!to_dev) { memcpy(out, timing, nbytes); return LOIKB_OK; }
+  HIPCHK(hipMemcpy(out, timing, nbytes, hipMemcpyHostToDevice));
+  return LOIKB_OK;
+}
+
+// what loikb_solve_pose asks of its parameters and of the handle before it looks at the targets (loikb_solve_pose_multistart asks
+// the same before it changes anything)
+static int pose_preconditions(const loikb_solver_impl* S, const loikb_pose_params* p, bool need_resident_q)
+{
+  if (!(p->dt > 0.0) || !(p->gain > 0.0) || !(p->tol_pose >= 0.0) || p->max_steps < 0 || std::isinf(p->dt) || std::isinf(p->gain)) {
+    g_last_error = "solve_pose: need dt > 0, gain > 0, tol_pose >= 0, max_steps >= 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (!S->have_problem) { g_last_error = "solve_pose before SolveInit()"; return LOIKB_ERR_STATE; }
+  if (S->nc_active < 1) { g_last_error = "solve_pose: no active task constraint"; return LOIKB_ERR_STATE; }
+  if (need_resident_q && !S->have_q) { g_last_error = "solve_pose: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  return LOIKB_OK;
+}
+
+// The head of a pose loop once its targets are accepted (loikb_solve_pose, loikb_solve_pose_path): q replaces the resident
+// configurations, the constraint links and the shared A go to the device, status and steps start at 0.
+static int pose_begin(loikb_solver_impl* S, const double* q, bool dev)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  const int B = S->B, nc = S->nc_active;
+  int rc;
+  if (q) {   // (the copy path of k_advance_q: the resident configurations are replaced; FwdPassInit runs in the first solve)
+    const void* dq = nullptr;
+    if ((rc = to_device(S, q, sizeof(double) * (size_t)B * S->nq, dev, &dq))) return rc;
+    with_real(S, [&](auto t) {
+      hipLaunchKernelGGL(k_advance_q<decltype(t)>, grid1(B), dim3(256), 0, S->stream, S->d_q, (const double*)dq, 0, S->nq, S->d_jd, S->d_idx_q, S->L, B, S->home.tiles, 0.0);
+    });
+    HIPCHK(hipGetLastError());
+    S->have_q = true;
+  }
+  std::vector<int> cl(nc);
+  for (int c = 0; c < nc; ++c) cl[c] = S->link_of[S->active_ids[c]];
+  HIPCHK(hipMemcpyAsync(P.d_clink, cl.data(), sizeof(int) * nc, hipMemcpyHostToDevice, S->stream));
+  if (S->a_shared) HIPCHK(hipMemcpyAsync(P.d_A, S->A_host.data(), sizeof(double) * 36 * nc, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_status, 0, sizeof(int) * B, S->stream));
+  HIPCHK(hipMemsetAsync(P.d_steps, 0, sizeof(int) * B, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (q, cl are the caller's / locals)
+  P.nc = nc;
+  P.flags_valid = P.have_limits;
+  return LOIKB_OK;
+}
+
+// One step of a pose loop after its re-target left b_c in P.d_b: the step's box (limits), the b edits, the tailored Solve, the
+// integrate and the clamp.  `d_status`: the word whose POSE_REACHED / POSE_STOPPED bits say which instances run (P.d_status for
+// loikb_solve_pose, the loop-private word for loikb_solve_pose_path).
+static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxScope& box, int* d_status, double* solve_ms)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  const int B = S->B, nc = S->nc_active;
+  int rc = LOIKB_OK;
+  if (box.active) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
+    with_real(S, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_pose_limit_box<T>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                         p->dt, (const int*)d_status, box.was_shared ? (const T*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
+                         S->home.tiles, S->L, P.d_lflags, P.d_inrange);
+    });
+    HIPCHK(hipGetLastError());
+  }
+  // UpdateEqConstraint(c, NULL, b_c, LOIKB_IN_DEVICE) for every active constraint, queued behind each other (the solve below
+  // synchronises), then the tailored Solve on the resident q without a constraint rewrite
+  S->defer_sync = true;
+  for (int c = 0; c < nc && rc == LOIKB_OK; ++c) rc = update_eq_single(S, S->active_ids[c], nullptr, P.d_b + (size_t)c * B * 6, LOIKB_IN_DEVICE);
+  S->defer_sync = false;
+  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
+  S->pass_active = false;
+  const auto t_solve = std::chrono::steady_clock::now();
+  if ((rc = loikb_solve_tailored(S, nullptr, -1, nullptr, nullptr, 0))) return rc;
+  *solve_ms += ms_since(t_solve);
+  with_real(S, [&](auto t) {
+    hipLaunchKernelGGL(k_pose_integrate<decltype(t)>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
+                       (const char*)S->home.tiles, p->dt, d_status);
+  });
+  HIPCHK(hipGetLastError());
+  if (box.active) {
+    hipLaunchKernelGGL(k_pose_limit_clamp, grid_dof(S), dim3(256), 0, S->stream, S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
+                       (const unsigned char*)P.d_inrange);
+    HIPCHK(hipGetLastError());
+  }
+  ++S->inputs_epoch;
+  return LOIKB_OK;
+}
+
+// The step loop of a pose solve after pose_begin, and its end.  retarget(go) queues the caller's re-target of the resident q
+// (go = 0: the last one, which only judges), which leaves b_c in P.d_b and the count of running instances in P.d_count[0];
+// the loop reads that count back, stops at 0 and otherwise runs pose_step on `d_status`.  Then the base box is back in force,
+// the stream is drained and P.timing holds {steps, total since t_call, inner solves, the rest} in ms.
+template <class Retarget>
+static int pose_loop(loikb_solver* S, const loikb_pose_params* p, PoseBoxScope& box, int* d_status,
+                     std::chrono::steady_clock::time_point t_call, Retarget&& retarget)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  double solve_ms = 0.0;
+  int steps_run = 0, rc;
+  for (int step = 0;; ++step) {
+    const int go = step < p->max_steps;
+    HIPCHK(hipMemsetAsync(P.d_count, 0, sizeof(unsigned int), S->stream));
+    if ((rc = retarget(go))) return rc;
+    if (!go) break;
+    unsigned int running = 0;
+    HIPCHK(hipMemcpyAsync(&running, P.d_count, sizeof(running), hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    if (running == 0) break;
+    if ((rc = pose_step(S, p, box, d_status, &solve_ms))) return rc;
+    ++steps_run;
+  }
+  if ((rc = box.leave())) return rc;
+  HIPCHK(hipStreamSynchronize(S->stream));
+  const double total = ms_since(t_call);
+  P.timing[0] = steps_run; P.timing[1] = total; P.timing[2] = solve_ms; P.timing[3] = total - solve_ms;
+  return LOIKB_OK;
+}
+
+extern "C" {
+
+int loikb_pose_version(void) { return LOIKB_POSE_VERSION; }
+
+int loikb_forward_kinematics(loikb_solver* S, const int* links, int n, double* out, int out_flags)
+{
+  if (!S || n < 0 || (n > 0 && (!links || !out))) return LOIKB_ERR_ARG;
+  for (int e = 0; e < n; ++e)
+    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = "forward_kinematics: link id out of range"; return LOIKB_ERR_ARG; }
+  if (!S->have_q) { g_last_error = "forward_kinematics: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  std::vector<int> dl(n);
+  for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
+  const size_t bytes = sizeof(double) * (size_t)S->B * n * 12;
+  int rc;
+  if ((rc = ensure_getscr(S, 1, sizeof(int) * (size_t)n))) return rc;
+  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) return rc;
+  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  HIPCHK(hipMemcpyAsync(S->d_getscr[1], dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
+  hipLaunchKernelGGL(k_link_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
+                     S->d_idx_q, (const int*)S->d_getscr[1], n, S->B, dst);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (dl is a local)
+  return LOIKB_OK;
+}
+
+int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, int in_flags, const loikb_pose_params* p)
+{
+  if (!S || !targets || !p) return LOIKB_ERR_ARG;
+  if (int pre = pose_preconditions(S, p, !q)) return pre;
+  const auto t_call = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if ((rc = pose_alloc(S))) return rc;
+  loikb_solver_impl::PoseState& P = S->pose;
+  const int B = S->B, nc = S->nc_active;
+  const bool dev = in_flags & LOIKB_IN_DEVICE, tgt_shared = in_flags & LOIKB_POSE_TARGET_SHARED;
+  // the targets, checked before anything of the handle changes
+  if ((rc = pose_check_targets(S, P.d_tgt, targets, (size_t)(tgt_shared ? 1 : B) * nc, dev, P.d_count,
+                               "solve_pose: a target rotation is not orthonormal with determinant 1 (tolerance 1e-9)")))
+    return rc;
+  ++S->inputs_epoch;
+  if ((rc = pose_begin(S, q, dev))) return rc;
+  PoseBoxScope box{S};
+  if (P.have_limits) {
+    if ((rc = box.enter())) return rc;
+    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
+  }
+  const double k = p->gain / p->dt;
+  return pose_loop(S, p, box, P.d_status, t_call, [&](int go) -> int {
+    if (P.have_tasks)   // (loik_amd_tasks.h: the task-frame error by kind, b = k S e; needs neither the tiles nor A)
+      hipLaunchKernelGGL(k_pose_retarget_tasks, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                         (const int*)P.d_clink, nc, (const PoseTask*)P.d_tasks, (const double*)P.d_tgt, (int)tgt_shared, B, k,
+                         p->tol_pose, go, P.d_b, P.d_err, P.d_status, P.d_steps, P.d_count);
+    else
+      with_real(S, [&](auto t) {
+        hipLaunchKernelGGL(k_pose_retarget<decltype(t)>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                           (const int*)P.d_clink, nc, (const double*)P.d_tgt, (int)tgt_shared, S->a_shared ? (const double*)P.d_A : nullptr,
+                           (const char*)S->home.tiles, S->L, B, k, p->tol_pose, go, P.d_b, P.d_err, P.d_status, P.d_steps, P.d_count);
+      });
+    HIPCHK(hipGetLastError());
+    return LOIKB_OK;
+  });
+}
+
+int loikb_pose_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  if (S->pose.nc == 0) { g_last_error = "pose_get before solve_pose"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (field) {
+  case LOIKB_POSE_F_STEPS: src = S->pose.d_steps; bytes = sizeof(int) * (size_t)S->B; break;
+  case LOIKB_POSE_F_STATUS: src = S->pose.d_status; bytes = sizeof(int) * (size_t)S->B; break;
+  case LOIKB_POSE_F_ERR: src = S->pose.d_err; bytes = sizeof(double) * (size_t)S->B * S->pose.nc * 6; break;
+  case LOIKB_POSE_F_TIMING: return get_timing_out(S->pose.timing, sizeof(S->pose.timing), out, out_flags & LOIKB_OUT_DEVICE);
+  default: g_last_error = "pose_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  return get_copy_out(S, src, bytes, out, out_flags);
+}
+
+// ---- include/loik_amd_limits.h ----------------------------------------------------------------------------------------------
+int loikb_limits_version(void) { return LOIKB_LIMITS_VERSION; }
+
+// The rule of a per-DoF pair (lo, hi) [nv] in idx_v order, shared by loikb_set_joint_limits and loikb_multistart_set_ranges
+// (loik_amd_multistart.h): both pointers given, n == nv, no NaN, lo <= hi, and a finite entry only on a DoF whose coordinate a
+// plain sum advances (S->lim_q).  `fn`, `lo_name`, `hi_name` go into loikb_last_error().
+static int check_dof_pairs(const loikb_solver_impl* S, const char* fn, const char* lo_name, const char* hi_name, const double* lo, const double* hi, int n)
+{
+  const std::string f(fn), ln(lo_name), hn(hi_name);
+  if (!lo || !hi) { g_last_error = f + ": " + ln + " and " + hn + " must both be given, or both be NULL (clear)"; return LOIKB_ERR_ARG; }
+  if (n != S->nv) { g_last_error = f + ": need one (" + ln + ", " + hn + ") pair per DoF, n == model.nv"; return LOIKB_ERR_ARG; }
+  for (int j = 0; j < n; ++j) {
+    char what[96];
+    snprintf(what, sizeof(what), "%s: DoF %d (joint %d)", fn, j, S->dof_ext[j]);
+    if (std::isnan(lo[j]) || std::isnan(hi[j])) { g_last_error = std::string(what) + ": a limit is NaN"; return LOIKB_ERR_ARG; }
+    if (lo[j] > hi[j]) { g_last_error = std::string(what) + ": " + ln + " > " + hn; return LOIKB_ERR_ARG; }
+    const bool finite = std::isfinite(lo[j]) || std::isfinite(hi[j]);
+    if (finite && S->lim_q[j] < 0) {
+      const int jt = S->dof_jt[j];
+      const char* kind = jt == LOIKB_J_FREEFLYER ? "free-flyer" : jt == LOIKB_J_SPHERICAL ? "spherical" : jt == LOIKB_J_PLANAR ? "planar" : "unbounded (cos, sin) revolute";
+      g_last_error = std::string(what) + " belongs to a " + kind + " joint: its configuration is not a scalar that a plain sum advances, it cannot carry a position limit";
+      return LOIKB_ERR_ARG;
+    }
+  }
+  return LOIKB_OK;
+}
+
+int loikb_set_joint_limits(loikb_solver* S, const double* q_lo, const double* q_hi, int n)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!q_lo && !q_hi) { P.have_limits = false; return LOIKB_OK; }
+  int rc;
+  if ((rc = check_dof_pairs(S, "set_joint_limits", "q_lo", "q_hi", q_lo, q_hi, n))) return rc;
+  std::vector<PoseLimit> lim(S->nb);
+  bool any = false;
+  for (int j = 0; j < n; ++j) {
+    const bool finite = std::isfinite(q_lo[j]) || std::isfinite(q_hi[j]);
+    lim[j].qi = finite ? S->lim_q[j] : -1;
+    lim[j].pad = 0;
+    lim[j].lo = q_lo[j];
+    lim[j].hi = q_hi[j];
+    any = any || finite;
+  }
+  if (!any) { P.have_limits = false; return LOIKB_OK; }   // (no finite limit anywhere: the handle runs what it runs without limits)
+  HIPCHK(hipSetDevice(S->device));
+  if (!P.d_lim && (rc = alloc_dev(S, (void**)&P.d_lim, sizeof(PoseLimit) * S->nb))) return rc;
+  P.lim.swap(lim);
+  HIPCHK(hipMemcpyAsync(P.d_lim, P.lim.data(), sizeof(PoseLimit) * S->nb, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  P.have_limits = true;
+  return LOIKB_OK;
+}
+
+int loikb_pose_get_limit_flags(loikb_solver* S, int* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  if (S->pose.nc == 0 || !S->pose.flags_valid) { g_last_error = "pose_get_limit_flags: the last solve_pose ran without joint limits (or there was none)"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  return get_copy_out(S, S->pose.d_lflags, sizeof(int) * (size_t)S->B * S->nb, out, out_flags);
+}
+
+// ---- include/loik_amd_tasks.h -----------------------------------------------------------------------------------------------
+int loikb_tasks_version(void) { return LOIKB_TASKS_VERSION; }
+
+// iMf [12] = (R row-major, p): finite, R orthonormal with determinant 1 within 1e-9 per entry (k_pose_check_targets' rule)
+static bool frame_ok(const double* F)
+{
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(F[k])) return false;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double g = F[a] * F[b] + F[3 + a] * F[3 + b] + F[6 + a] * F[6 + b] - (a == b ? 1.0 : 0.0);
+      if (!(std::fabs(g) <= 1e-9)) return false;
+    }
+  const double det = F[0] * (F[4] * F[8] - F[5] * F[7]) - F[1] * (F[3] * F[8] - F[5] * F[6]) + F[2] * (F[3] * F[7] - F[4] * F[6]);
+  return std::fabs(det - 1.0) <= 1e-9;
+}
+
+int loikb_pose_set_tasks(loikb_solver* S, int nc, const int* kinds, const double* frames)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (!S->have_problem) { g_last_error = "pose_set_tasks before SolveInit()"; return LOIKB_ERR_STATE; }
+  if (!S->a_shared) { g_last_error = "pose_set_tasks: the handle's A is per instance; a task matrix is one per constraint for the whole batch (SolveInit with a shared A)"; return LOIKB_ERR_STATE; }
+  if (nc != S->nc_active) { g_last_error = "pose_set_tasks: need one task per active constraint, nc == loikb_num_eq_c()"; return LOIKB_ERR_ARG; }
+  if (!kinds) { g_last_error = "pose_set_tasks: kinds is NULL"; return LOIKB_ERR_ARG; }
+  static const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+  std::vector<PoseTask> tasks(nc);
+  for (int c = 0; c < nc; ++c) {
+    char what[64];
+    snprintf(what, sizeof(what), "pose_set_tasks: task %d", c);
+    if (kinds[c] < LOIKB_TASK_POSE || kinds[c] > LOIKB_TASK_ORIENTATION) { g_last_error = std::string(what) + ": unknown kind (LOIKB_TASK_POSE / POSITION / ORIENTATION)"; return LOIKB_ERR_ARG; }
+    const double* F = frames ? frames + 12 * c : ident;
+    if (!frame_ok(F)) { g_last_error = std::string(what) + ": the frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+    tasks[c].kind = kinds[c];
+    tasks[c].pad = 0;
+    memcpy(tasks[c].Rf, F, 9 * sizeof(double));
+    memcpy(tasks[c].pf, F + 9, 3 * sizeof(double));
+  }
+  HIPCHK(hipSetDevice(S->device));
+  loikb_solver_impl::PoseState& P = S->pose;
+  int rc;
+  if (!P.d_tasks && (rc = alloc_dev(S, (void**)&P.d_tasks, sizeof(PoseTask) * std::max(S->nc, 1)))) return rc;
+  // A_c = S_c X_c^-1, X^-1 = [[Rf^T, -Rf^T [pf]x], [0, Rf^T]], b_c = 0: UpdateEqConstraint(c, A_c, 0) for every active constraint
+  const double zero[6] = {0, 0, 0, 0, 0, 0};
+  for (int c = 0; c < nc; ++c) {
+    const double *Rf = tasks[c].Rf, *pf = tasks[c].pf;
+    const double px[9] = {0, -pf[2], pf[1], pf[2], 0, -pf[0], -pf[1], pf[0], 0};
+    double A[36] = {0};
+    for (int r = 0; r < 3; ++r)
+      for (int m = 0; m < 3; ++m) {
+        const double rt = Rf[3 * m + r];   // Rf^T
+        A[6 * r + m] = rt;
+        A[6 * (3 + r) + 3 + m] = rt;
+        A[6 * r + 3 + m] = -(Rf[r] * px[m] + Rf[3 + r] * px[3 + m] + Rf[6 + r] * px[6 + m]);
+      }
+    const int r0 = tasks[c].kind == LOIKB_TASK_ORIENTATION ? 0 : 3, r1 = tasks[c].kind == LOIKB_TASK_POSE ? 0 : r0 + 3;
+    for (int x = 6 * r0; x < 6 * r1; ++x) A[x] = 0.0;   // S_c: the masked-out rows
+    if ((rc = update_eq_single(S, S->active_ids[c], A, zero, LOIKB_A_SHARED | LOIKB_B_SHARED))) return rc;
+  }
+  S->pass_active = false;
+  if ((rc = reset_home(S, RS_HCACHE))) return rc;
+  P.tasks.swap(tasks);
+  HIPCHK(hipMemcpyAsync(P.d_tasks, P.tasks.data(), sizeof(PoseTask) * nc, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  P.have_tasks = true;   // (last: update_eq_single drops the specification it is given an A under)
+  return LOIKB_OK;
+}
+
+int loikb_pose_clear_tasks(loikb_solver* S)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  S->pose.have_tasks = false;
+  return LOIKB_OK;
+}
+
+int loikb_pose_get_tasks(const loikb_solver* S, int* kinds, double* frames, int cap)
+{
+  if (!S || !S->pose.have_tasks) return 0;
+  const int n = (int)S->pose.tasks.size();
+  for (int c = 0; c < std::min(n, cap); ++c) {
+    const PoseTask& t = S->pose.tasks[c];
+    if (kinds) kinds[c] = t.kind;
+    if (frames) { memcpy(frames + 12 * c, t.Rf, 9 * sizeof(double)); memcpy(frames + 12 * c + 9, t.pf, 3 * sizeof(double)); }
+  }
+  return n;
+}
+
+int loikb_frame_placements(loikb_solver* S, const int* links, const double* frames, int n, double* out, int out_flags)
+{
+  if (!frames) return loikb_forward_kinematics(S, links, n, out, out_flags);
+  if (!S || n < 0 || (n > 0 && (!links || !out))) return LOIKB_ERR_ARG;
+  for (int e = 0; e < n; ++e) {
+    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = "frame_placements: link id out of range"; return LOIKB_ERR_ARG; }
+    if (!frame_ok(frames + 12 * e)) { g_last_error = "frame_placements: a frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+  }
+  if (!S->have_q) { g_last_error = "frame_placements: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  // scratch 1: the frames [n][12], then the device joints [n]
+  std::vector<int> dl(n);
+  for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
+  const size_t bytes = sizeof(double) * (size_t)S->B * n * 12, fbytes = sizeof(double) * (size_t)n * 12;
+  int rc;
+  if ((rc = ensure_getscr(S, 1, fbytes + sizeof(int) * (size_t)n))) return rc;
+  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) return rc;
+  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  double* d_fr = (double*)S->d_getscr[1];
+  int* d_dl = (int*)((char*)S->d_getscr[1] + fbytes);
+  HIPCHK(hipMemcpyAsync(d_fr, frames, fbytes, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(d_dl, dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
+  hipLaunchKernelGGL(k_frame_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
+                     S->d_idx_q, (const int*)d_dl, (const double*)d_fr, n, S->B, dst);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (dl and the caller's frames have been read)
+  return LOIKB_OK;
+}
+
+// ---- include/loik_amd_multistart.h (kernels in loik_pose_multistart.hpp) ------------------------------------------------------
+int loikb_multistart_version(void) { return LOIKB_MULTISTART_VERSION; }
+
+static int ms_alloc(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  if (M.d_count) return LOIKB_OK;
+  const size_t B = (size_t)S->B, nc = (size_t)std::max(S->nc, 1), nq = (size_t)S->nq, nv = (size_t)S->nb;
+  int rc;
+  if ((rc = alloc_dev(S, (void**)&M.d_tgt_in, sizeof(double) * B * nc * 12)) || (rc = alloc_dev(S, (void**)&M.d_tgt, sizeof(double) * B * nc * 12)) ||
+      (rc = alloc_dev(S, (void**)&M.d_q0, sizeof(double) * B * nq)) || (rc = alloc_dev(S, (void**)&M.d_table, sizeof(int) * nq)) ||
+      (rc = alloc_dev(S, (void**)&M.d_dofq, sizeof(int) * nv)) || (rc = alloc_dev(S, (void**)&M.d_lo, sizeof(double) * nv)) ||
+      (rc = alloc_dev(S, (void**)&M.d_hi, sizeof(double) * nv)) || (rc = alloc_dev(S, (void**)&M.d_w, sizeof(double) * nv)) ||
+      (rc = alloc_dev(S, (void**)&M.d_round, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&M.d_winner, sizeof(int) * B)) ||
+      (rc = alloc_dev(S, (void**)&M.d_gstatus, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&M.d_nreached, sizeof(int) * B)) ||
+      (rc = alloc_dev(S, (void**)&M.d_cost, sizeof(double) * B)) || (rc = alloc_dev(S, (void**)&M.d_wq, sizeof(double) * B * nq)) ||
+      (rc = alloc_dev(S, (void**)&M.d_werr, sizeof(double) * B * nc * 6)) || (rc = alloc_dev(S, (void**)&M.d_count, sizeof(unsigned int) * 2))) {
+    M.d_count = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+    return rc;
+  }
+  return LOIKB_OK;
+}
+
+// The ranges in force into M.up_lo / up_hi / up_table: those of loikb_multistart_set_ranges, else the joint limits of the handle.
+// A DoF is sampled iff both ends are finite.  Returns the number of sampled DoFs; touches nothing on the device.
+static int ms_resolve_ranges(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const loikb_solver_impl::PoseState& P = S->pose;
+  const double inf = std::numeric_limits<double>::infinity();
+  M.up_lo.assign(S->nv, -inf);
+  M.up_hi.assign(S->nv, inf);
+  M.up_table.assign(S->nq, -1);
+  int sampled = 0;
+  for (int j = 0; j < S->nv; ++j) {
+    if (M.have_ranges) { M.up_lo[j] = M.lo[j]; M.up_hi[j] = M.hi[j]; }
+    else if (P.have_limits) { M.up_lo[j] = P.lim[j].lo; M.up_hi[j] = P.lim[j].hi; }
+    if (std::isfinite(M.up_lo[j]) && std::isfinite(M.up_hi[j]) && S->lim_q[j] >= 0) { M.up_table[S->lim_q[j]] = j; ++sampled; }
+  }
+  return sampled;
+}
+
+// the tables of the sampler and of the selection onto the device (queued; the sources are members of the handle)
+static int ms_upload_tables(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  HIPCHK(hipMemcpyAsync(M.d_lo, M.up_lo.data(), sizeof(double) * S->nv, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(M.d_hi, M.up_hi.data(), sizeof(double) * S->nv, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(M.d_table, M.up_table.data(), sizeof(int) * S->nq, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(M.d_dofq, S->lim_q.data(), sizeof(int) * S->nv, hipMemcpyHostToDevice, S->stream));
+  if (!M.w.empty()) HIPCHK(hipMemcpyAsync(M.d_w, M.w.data(), sizeof(double) * S->nv, hipMemcpyHostToDevice, S->stream));
+  return LOIKB_OK;
+}
+
+// the goals' q0 rows into M.d_q0: the caller's [G][nq] (host / device), one shared host row, or the resident row g * K
+static int ms_set_q0(loikb_solver_impl* S, const double* q0, int flags, int G, int K)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const bool shared = q0 && (flags & LOIKB_Q_SHARED), dev = q0 && (flags & LOIKB_IN_DEVICE) && !shared;
+  const void* src = S->d_q;
+  size_t stride = (size_t)K * S->nq;
+  int rc;
+  if (q0) {
+    if ((rc = to_device(S, q0, sizeof(double) * (shared ? (size_t)S->nq : (size_t)G * S->nq), dev, &src))) return rc;
+    stride = shared ? 0 : (size_t)S->nq;
+  }
+  hipLaunchKernelGGL(k_ms_set_q0, grid1((size_t)G * S->nq), dim3(256), 0, S->stream, (const double*)src, stride, S->nq, G, M.d_q0);
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+static unsigned long long ms_mix_host(unsigned long long x)
+{
+  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27; x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+// the seeds of `round` into the resident q (status == nullptr: every row; else the rows without REACHED).  The handle is left as
+// loikb_solve_pose(q != NULL) leaves it after its copy: q resident, the inputs changed.
+static int ms_sample(loikb_solver_impl* S, unsigned long long seed, int K, int round, const int* status)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const unsigned long long key = ms_mix_host(seed + 0x9E3779B97F4A7C15ull * ((unsigned long long)round + 1ull));
+  hipLaunchKernelGGL(k_ms_sample, grid1((size_t)S->B * S->nq), dim3(256), 0, S->stream, S->d_q, (const double*)M.d_q0, S->nq, S->B, K,
+                     (const int*)M.d_table, (const double*)M.d_lo, (const double*)M.d_hi, key, round, status, M.d_round);
+  HIPCHK(hipGetLastError());
+  S->have_q = true;
+  ++S->inputs_epoch;
+  return LOIKB_OK;
+}
+
+int loikb_multistart_set_ranges(loikb_solver* S, const double* s_lo, const double* s_hi, const double* weights, int n)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  int rc;
+  if ((s_lo || s_hi) && (rc = check_dof_pairs(S, "multistart_set_ranges", "s_lo", "s_hi", s_lo, s_hi, n))) return rc;
+  if (weights) {
+    if (n != S->nv) { g_last_error = "multistart_set_ranges: need one weight per DoF, n == model.nv"; return LOIKB_ERR_ARG; }
+    for (int j = 0; j < n; ++j)
+      if (!(weights[j] >= 0.0) || !std::isfinite(weights[j])) { g_last_error = "multistart_set_ranges: a weight is negative or not finite"; return LOIKB_ERR_ARG; }
+  }
+  M.have_ranges = s_lo != nullptr;
+  if (s_lo) { M.lo.assign(s_lo, s_lo + n); M.hi.assign(s_hi, s_hi + n); }
+  if (weights) M.w.assign(weights, weights + n);
+  else M.w.clear();
+  return LOIKB_OK;
+}
+
+int loikb_multistart_sample(loikb_solver* S, const double* q0, int q0_flags, unsigned long long seed, int seeds_per_goal, int round)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  const int K = seeds_per_goal;
+  if (K < 1 || S->B % K != 0 || round < 0) { g_last_error = "multistart_sample: need seeds_per_goal >= 1 that divides the batch, round >= 0"; return LOIKB_ERR_ARG; }
+  if (!S->have_problem) { g_last_error = "multistart_sample before SolveInit()"; return LOIKB_ERR_STATE; }
+  if (!q0 && !S->have_q) { g_last_error = "multistart_sample: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (ms_resolve_ranges(S) == 0 && (K > 1 || round > 0)) {
+    g_last_error = "multistart_sample: no DoF to sample (set ranges with loikb_multistart_set_ranges or joint limits with a finite pair)";
+    return LOIKB_ERR_STATE;
+  }
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if ((rc = ms_alloc(S)) || (rc = ms_upload_tables(S)) || (rc = ms_set_q0(S, q0, q0_flags, S->B / K, K)) || (rc = ms_sample(S, seed, K, round, nullptr))) {
+    (void)hipStreamSynchronize(S->stream);
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q0 has been read)
+  return LOIKB_OK;
+}
+
+int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double* targets, int in_flags, const loikb_pose_params* pose,
+                                const loikb_multistart_params* ms)
+{
+  if (!S || !targets || !pose || !ms) return LOIKB_ERR_ARG;
+  const int K = ms->seeds_per_goal, R = ms->rounds;
+  if (K < 1 || S->B % K != 0 || R < 1 || ms->pick < LOIKB_MS_PICK_NEAREST || ms->pick > LOIKB_MS_PICK_FIRST || ms->flags != 0) {
+    g_last_error = "solve_pose_multistart: need seeds_per_goal >= 1 that divides the batch, rounds >= 1, pick 0 or 1, flags 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (int pre = pose_preconditions(S, pose, !q0)) return pre;
+  if (ms_resolve_ranges(S) == 0 && (K > 1 || R > 1)) {
+    g_last_error = "solve_pose_multistart: no DoF to sample (set ranges with loikb_multistart_set_ranges or joint limits with a finite pair)";
+    return LOIKB_ERR_STATE;
+  }
+  const auto t_call = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if ((rc = ms_alloc(S))) return rc;
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const int B = S->B, G = B / K, nc = S->nc_active;
+  const bool dev = in_flags & LOIKB_IN_DEVICE, tgt_shared = in_flags & LOIKB_POSE_TARGET_SHARED;
+  // the targets, checked as loikb_solve_pose checks them, before anything of the handle changes
+  if ((rc = pose_check_targets(S, M.d_tgt_in, targets, (size_t)(tgt_shared ? 1 : G) * nc, dev, M.d_count,
+                               "solve_pose: a target rotation is not orthonormal with determinant 1 (tolerance 1e-9)")))
+    return rc;
+  const auto t_sample = std::chrono::steady_clock::now();
+  double sample_ms = 0.0, solve_ms = 0.0, select_ms = 0.0;
+  hipLaunchKernelGGL(k_ms_expand_targets, grid1((size_t)B * nc * 12), dim3(256), 0, S->stream, (const double*)M.d_tgt_in, (int)tgt_shared, nc, K, B, M.d_tgt);
+  HIPCHK(hipGetLastError());
+  if ((rc = ms_upload_tables(S)) || (rc = ms_set_q0(S, q0, in_flags, G, K)) || (rc = ms_sample(S, ms->seed, K, 0, nullptr))) {
+    (void)hipStreamSynchronize(S->stream);
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q0 has been read)
+  sample_ms += ms_since(t_sample);
+  M.G = 0;
+  const loikb_solver_impl::PoseState& P = S->pose;
+  auto select = [&](int count_only) -> int {
+    HIPCHK(hipMemsetAsync(M.d_count, 0, sizeof(unsigned int), S->stream));
+    hipLaunchKernelGGL(k_ms_select, dim3((unsigned)G), dim3(MS_SELECT_THREADS), 0, S->stream, (const int*)P.d_status, (const double*)P.d_err,
+                       (const double*)S->d_q, (const double*)M.d_q0, (const int*)M.d_dofq, M.w.empty() ? (const double*)nullptr : (const double*)M.d_w,
+                       S->nv, S->nq, nc, K, (int)(ms->pick == LOIKB_MS_PICK_FIRST), count_only, M.d_count, M.d_winner, M.d_gstatus, M.d_cost,
+                       M.d_nreached, M.d_wq, M.d_werr);
+    HIPCHK(hipGetLastError());
+    return LOIKB_OK;
+  };
+  int rounds_run = 0;
+  for (int r = 0; r < R; ++r) {
+    const auto t_solve = std::chrono::steady_clock::now();
+    if ((rc = loikb_solve_pose(S, nullptr, M.d_tgt, LOIKB_IN_DEVICE, pose))) return rc;
+    solve_ms += ms_since(t_solve);
+    ++rounds_run;
+    if (r == R - 1) break;
+    // goals that own a reached seed: one counter back to the host
+    const auto t_count = std::chrono::steady_clock::now();
+    if ((rc = select(1))) return rc;
+    unsigned int answered = 0;
+    HIPCHK(hipMemcpyAsync(&answered, M.d_count, sizeof(answered), hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    select_ms += ms_since(t_count);
+    if (answered == (unsigned int)G) break;
+    const auto t_again = std::chrono::steady_clock::now();
+    if ((rc = ms_sample(S, ms->seed, K, r + 1, P.d_status))) return rc;
+    HIPCHK(hipStreamSynchronize(S->stream));
+    sample_ms += ms_since(t_again);
+  }
+  const auto t_select = std::chrono::steady_clock::now();
+  if ((rc = select(0))) return rc;
+  HIPCHK(hipStreamSynchronize(S->stream));
+  select_ms += ms_since(t_select);
+  M.G = G;
+  M.nc = nc;
+  const double total = ms_since(t_call);
+  M.timing[0] = rounds_run; M.timing[1] = total; M.timing[2] = solve_ms; M.timing[3] = sample_ms; M.timing[4] = select_ms;
+  M.timing[5] = total - solve_ms - sample_ms - select_ms;
+  return LOIKB_OK;
+}
+
+int loikb_multistart_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  const loikb_solver_impl::MultiStartState& M = S->ms;
+  if (M.G == 0) { g_last_error = "multistart_get before solve_pose_multistart"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const size_t G = (size_t)M.G;
+  switch (field) {
+  case LOIKB_MS_F_WINNER: src = M.d_winner; bytes = sizeof(int) * G; break;
+  case LOIKB_MS_F_GOAL_STATUS: src = M.d_gstatus; bytes = sizeof(int) * G; break;
+  case LOIKB_MS_F_Q: src = M.d_wq; bytes = sizeof(double) * G * S->nq; break;
+  case LOIKB_MS_F_ERR: src = M.d_werr; bytes = sizeof(double) * G * M.nc * 6; break;
+  case LOIKB_MS_F_COST: src = M.d_cost; bytes = sizeof(double) * G; break;
+  case LOIKB_MS_F_NREACHED: src = M.d_nreached; bytes = sizeof(int) * G; break;
+  case LOIKB_MS_F_ROUND: src = M.d_round; bytes = sizeof(int) * (size_t)S->B; break;
+  case LOIKB_MS_F_TIMING: return get_timing_out(M.timing, sizeof(M.timing), out, out_flags & LOIKB_OUT_DEVICE);
+  default: g_last_error = "multistart_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  return get_copy_out(S, src, bytes, out, out_flags);
+}
+
+// ---- include/loik_amd_path.h (kernels in loik_pose_path.hpp) ------------------------------------------------------------------
+int loikb_path_version(void) { return LOIKB_PATH_VERSION; }
+
+// a buffer of the path state that is sized by the waypoint count: grown (never shrunk) to `bytes`, its contents are not kept
+static int path_grow(void** buf, size_t bytes)
+{
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
+  if (*buf) HIPCHK(hipFree(*buf));
+  *buf = p;
+  return LOIKB_OK;
+}
+
+// the [B] arrays on first use, and room for T waypoints in the staging buffer.  Holds no result of an earlier call.
+static int path_alloc_inputs(loikb_solver_impl* S, int T)
+{
+  loikb_solver_impl::PathState& W = S->path;
+  const size_t B = (size_t)S->B, nc = (size_t)std::max(S->nc, 1);
+  int rc;
+  if (!W.d_cursor) {
+    if ((rc = alloc_dev(S, (void**)&W.d_ws, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&W.d_wfrom, sizeof(int) * B)) ||
+        (rc = alloc_dev(S, (void**)&W.d_lstatus, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&W.d_pstatus, sizeof(int) * B)) ||
+        (rc = alloc_dev(S, (void**)&W.d_cursor, sizeof(int) * B))) {
+      W.d_cursor = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+      return rc;
+    }
+  }
+  if (T > W.cap_wp) {
+    if ((rc = path_grow((void**)&W.d_wp, sizeof(double) * B * (size_t)T * nc * 12))) return rc;
+    W.cap_wp = T;
+  }
+  return LOIKB_OK;
+}
+
+// WSTEPS and, with record, Q for T waypoints: they hold the results of the last call, so they are regrown only by a call that
+// has passed every check
+static int path_alloc_results(loikb_solver_impl* S, int T, bool record)
+{
+  loikb_solver_impl::PathState& W = S->path;
+  const size_t B = (size_t)S->B;
+  int rc;
+  if (T > W.cap_T) {
+    if ((rc = path_grow((void**)&W.d_wsteps, sizeof(int) * B * (size_t)T))) return rc;
+    W.cap_T = T;
+  }
+  if (record && T > W.cap_TQ) {
+    if ((rc = path_grow((void**)&W.d_Q, sizeof(double) * B * (size_t)T * S->nq))) return rc;
+    W.cap_TQ = T;
+  }
+  return LOIKB_OK;
+}
+
+int loikb_solve_pose_path(loikb_solver* S, const double* q, const double* waypoints, int in_flags, const loikb_pose_params* p,
+                          const loikb_path_params* path)
+{
+  if (!S || !waypoints || !p || !path) return LOIKB_ERR_ARG;
+  if (path->n_waypoints < 1 || path->max_steps_per_waypoint < 0 || path->record < 0 || path->record > 1 || path->flags != 0) {
+    g_last_error = "solve_pose_path: need n_waypoints >= 1, max_steps_per_waypoint >= 0, record 0 or 1, flags 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (int pre = pose_preconditions(S, p, !q)) return pre;
+  const auto t_call = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(S->device));
+  const int B = S->B, nc = S->nc_active, T = path->n_waypoints, budget = path->max_steps_per_waypoint;
+  const bool dev = in_flags & LOIKB_IN_DEVICE, wp_shared = in_flags & LOIKB_POSE_TARGET_SHARED, record = path->record != 0;
+  if ((size_t)(wp_shared ? 1 : B) * T * nc > (size_t)0x7fffffff) { g_last_error = "solve_pose_path: too many waypoints"; return LOIKB_ERR_ARG; }
+  int rc;
+  if ((rc = pose_alloc(S)) || (rc = path_alloc_inputs(S, T))) return rc;
+  loikb_solver_impl::PoseState& P = S->pose;
+  loikb_solver_impl::PathState& W = S->path;
+  // the waypoints, all of them, checked before anything of the handle changes
+  if ((rc = pose_check_targets(S, W.d_wp, waypoints, (size_t)(wp_shared ? 1 : B) * T * nc, dev, P.d_count,
+                               "solve_pose_path: a waypoint rotation is not orthonormal with determinant 1 (tolerance 1e-9)")))
+    return rc;
+  if ((rc = path_alloc_results(S, T, record))) return rc;
+  ++S->inputs_epoch;
+  if ((rc = pose_begin(S, q, dev))) return rc;
+  W.T = T;
+  W.recorded = record;
+  const size_t nBT = (size_t)B * T, nQ = record ? nBT * S->nq : 0;
+  hipLaunchKernelGGL(k_path_setup, grid1(std::max(std::max(nBT, nQ), (size_t)B)), dim3(256), 0, S->stream, B, nBT, nQ, W.d_cursor, W.d_ws,
+                     W.d_wfrom, W.d_lstatus, W.d_pstatus, W.d_wsteps, W.d_Q);
+  HIPCHK(hipGetLastError());
+  PoseBoxScope box{S};
+  if (P.have_limits) {
+    if ((rc = box.enter())) return rc;
+    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
+  }
+  const double k = p->gain / p->dt;
+  const PoseTask* tasks = P.have_tasks ? (const PoseTask*)P.d_tasks : nullptr;
+  const double* A_sh = S->a_shared ? (const double*)P.d_A : nullptr;
+  // (the loop-private word: a stalled instance is "stopped" to the integrate and the limit box, and to them alone)
+  rc = pose_loop(S, p, box, W.d_lstatus, t_call, [&](int go) -> int {
+    with_real(S, [&](auto t) {
+      hipLaunchKernelGGL(k_path_retarget<decltype(t)>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
+                         (const int*)P.d_clink, nc, tasks, (const double*)W.d_wp, (int)wp_shared, T, A_sh, (const char*)S->home.tiles, S->L, B,
+                         k, p->tol_pose, go, budget, P.d_b, P.d_err, W.d_lstatus, P.d_status, W.d_pstatus, P.d_steps, W.d_cursor, W.d_ws,
+                         W.d_wfrom, W.d_wsteps, P.d_count);
+    });
+    HIPCHK(hipGetLastError());
+    if (record) {   // (q is the one the re-target saw: the step's integrate is queued behind)
+      hipLaunchKernelGGL(k_path_record, grid1((size_t)B * S->nq), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, B, T,
+                         (const int*)W.d_wfrom, (const int*)W.d_cursor, W.d_Q);
+      HIPCHK(hipGetLastError());
+    }
+    return LOIKB_OK;
+  });
+  if (rc) return rc;
+  memcpy(W.timing, P.timing, sizeof(W.timing));
+  return LOIKB_OK;
+}
+
+int loikb_path_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  const loikb_solver_impl::PathState& W = S->path;
+  if (W.T == 0) { g_last_error = "path_get before solve_pose_path"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const size_t B = (size_t)S->B;
+  switch (field) {
+  case LOIKB_PATH_F_CURSOR: src = W.d_cursor; bytes = sizeof(int) * B; break;
+  case LOIKB_PATH_F_STATUS: src = W.d_pstatus; bytes = sizeof(int) * B; break;
+  case LOIKB_PATH_F_WSTEPS: src = W.d_wsteps; bytes = sizeof(int) * B * W.T; break;
+  case LOIKB_PATH_F_Q:
+    if (!W.recorded) { g_last_error = "path_get: the last solve_pose_path ran with record = 0"; return LOIKB_ERR_STATE; }
+    src = W.d_Q; bytes = sizeof(double) * B * W.T * S->nq;
+    break;
+  case LOIKB_PATH_F_TIMING: return get_timing_out(W.timing, sizeof(W.timing), out, out_flags & LOIKB_OUT_DEVICE);
+  default: g_last_error = "path_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  return get_copy_out(S, src, bytes, out, out_flags);
+}
+
+}  // extern "C"

@@ -4,12 +4,14 @@
 //   k_link_placements : oMi of requested links from the RESIDENT q (not the tiles' JP_CS pairs, which belong to the q of the
 //                       last FwdPassInit), one thread per (instance, link)
 //   k_pose_retarget   : e_c = log6(oMi_c^-1 oMdes_c) per active constraint, b_c = A_c (gain / dt) e_c, the reached / stopped
-//                       bookkeeping and the count of instances still running, one thread per instance
+//                       bookkeeping and the count of instances still running, one thread per instance.  Its rule -- the error, the
+//                       err store, the two control laws, the tail -- is the `retarget rule` section below, the one definition
+//                       that k_pose_retarget_tasks (loik_pose_tasks.hpp) and k_path_retarget (loik_pose_path.hpp) are written over too
 //   k_pose_integrate  : q <- q (+) dt z for the running instances only (advance_q_instance: the arithmetic of loikb_integrate)
 // and, on a handle with joint position limits (include/loik_amd_limits.h), around the same solve:
 //   k_pose_limit_box  : the step's velocity box [lo, hi] = the base box cut to the velocities that keep q (+) dt z in range, into
 //                       JP_LBUB of the home tiles, one thread per (instance, DoF)
-//   k_pose_limit_clamp: after k_pose_integrate (a kernel of its own: the integrate a handle without limits runs is untouched), a
+//   k_pose_limit_clamp: after k_pose_integrate (a kernel of its own: a handle without limits runs the integrate alone), a
 //                       limited coordinate that was in range before the step is clamped to its range
 //   k_box_copy        : JP_LBUB of every joint of every instance <-> a [nb][B] scratch: a per-instance base box is saved before
 //                       the first step and restored after the last
@@ -172,11 +174,108 @@ __global__ void k_pose_check_targets(const double* __restrict__ tgt, int n, doub
   if (!ok) atomicAdd(bad, 1u);
 }
 
+// ---- the retarget rule: what one re-target does for one instance, stated once.  k_pose_retarget, k_pose_retarget_tasks and
+// k_path_retarget are loops over these functions; a new control law goes here, beside pose_b_joint and pose_b_task.  The library
+// is built with -ffp-contract=on, which contracts within a statement only: a statement split or merged here changes bits.
+
+// task kinds (loik_amd_tasks.h)
+enum : int { TASK_POSE = 0, TASK_POSITION = 1, TASK_ORIENTATION = 2 };
+
+// one entry per active constraint, built by loikb_pose_set_tasks: iMf = (Rf row-major, pf)
+struct PoseTask {
+  int kind, pad;
+  double Rf[9], pf[3];
+};
+
+// (Rw, tw) = (R, t) * (Rf, pf); with the identity frame this returns (R, t) bit for bit (finite entries)
+__device__ __forceinline__ void frame_compose(const double* R, const double* t, const double* Rf, const double* pf, double* Rw,
+                                              double* tw)
+{
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) Rw[3 * r + c] = R[3 * r] * Rf[c] + R[3 * r + 1] * Rf[3 + c] + R[3 * r + 2] * Rf[6 + c];
+    tw[r] = t[r] + (R[3 * r] * pf[0] + R[3 * r + 1] * pf[1] + R[3 * r + 2] * pf[2]);
+  }
+}
+
+// e of the constraint on `link` against the desired placement D [12], in the task frame oMf = oMi iMf and by the task's kind;
+// tk = nullptr: the joint frame, the full pose (e = log6(oMi^-1 oMdes))
+__device__ __forceinline__ void pose_error(const double* q_row, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q, int link,
+                                           const PoseTask* tk, const double* D, double* e)
+{
+  double Ri[9], ti[3], Rw[9], tw[3], Re[9], pe[3];
+  link_placement(q_row, jd, idx_q, link, Ri, ti);
+  const double *R = Ri, *t = ti;
+  if (tk) {
+    frame_compose(Ri, ti, tk->Rf, tk->pf, Rw, tw);
+    R = Rw; t = tw;
+  }
+  for (int r = 0; r < 3; ++r) {   // oMf^-1 oMdes = (R^T Rd, R^T (td - t))
+    for (int cc = 0; cc < 3; ++cc) Re[3 * r + cc] = R[r] * D[cc] + R[3 + r] * D[3 + cc] + R[6 + r] * D[6 + cc];
+    pe[r] = R[r] * (D[9] - t[0]) + R[3 + r] * (D[10] - t[1]) + R[6 + r] * (D[11] - t[2]);
+  }
+  const int kind = tk ? tk->kind : TASK_POSE;
+  if (kind == TASK_POSITION) {
+    for (int r = 0; r < 3; ++r) { e[r] = pe[r]; e[3 + r] = 0.0; }
+  } else if (kind == TASK_ORIENTATION) {
+    pose_log3(Re, e + 3);
+    for (int r = 0; r < 3; ++r) e[r] = 0.0;
+  } else {
+    pose_log6(Re, pe, e);
+  }
+}
+
+// e into its err row eo, folded into the instance's `finite` and `emax`
+__device__ __forceinline__ void pose_store_err(const double* e, double* __restrict__ eo, bool& finite, double& emax)
+{
+  for (int r = 0; r < 6; ++r) {
+    eo[r] = e[r];
+    finite = finite && isfinite(e[r]);
+    emax = fmax(emax, fabs(e[r]));
+  }
+}
+
+// the joint-frame law bo = A_c (k e): A from `A_sh` [nc][36] (shared A), else the per-instance A of constraint c's record in the
+// tiles of instance b (hence the template on the handle's precision)
+template <typename T>
+__device__ __forceinline__ void pose_b_joint(const double* e, double k, const double* __restrict__ A_sh, const char* tiles, const Layout& L,
+                                             int b, int c, double* __restrict__ bo)
+{
+  const char* crec = lane_ptr<T>(const_cast<char*>(tiles), L, b) + (size_t)(L.off_c + c * L.crec) * pair_bytes<T>();
+  for (int r = 0; r < 6; ++r) {
+    double a = 0.0;
+    for (int m = 0; m < 6; ++m) {
+      const int x = 6 * r + m;
+      const double A = A_sh ? A_sh[c * 36 + x] : (double)*elem_ptr<T>(const_cast<char*>(crec), CP_A + x / 2, x & 1);
+      a += A * (k * e[m]);
+    }
+    bo[r] = a;
+  }
+}
+
+// the task law bo = k e (loik_amd_tasks.h: A_c v = S_c v_f by construction, so b_c is the masked error itself)
+__device__ __forceinline__ void pose_b_task(const double* e, double k, double* __restrict__ bo)
+{
+  for (int r = 0; r < 6; ++r) bo[r] = k * e[r];
+}
+
+// the tail of a re-target with `step` set: an instance that runs counts the step and itself, one that does not gets b_c = 0
+// (its inner solve is idle work: its q does not move)
+__device__ __forceinline__ void pose_count_or_idle(bool run, int b, int nc, int B, double* __restrict__ b_out, int* __restrict__ steps,
+                                                   unsigned int* __restrict__ running)
+{
+  if (run) {
+    steps[b] += 1;
+    atomicAdd(running, 1u);
+  } else {
+    for (int c = 0; c < nc; ++c)
+      for (int r = 0; r < 6; ++r) b_out[((size_t)c * B + b) * 6 + r] = 0.0;
+  }
+}
+
 // One step of the pose loop for instance b.  Instances already reached or stopped keep their status; the others get
 // err = e_c of the resident q, are marked reached (max_c |e_c|_inf <= tol) or stopped (e or q not finite), and otherwise stay
 // running: with `step` set, b_c = A_c k e_c (k = gain / dt) goes to b_out, steps[b] counts the step and `running` the instance.
-// Instances that do not run get b_c = 0 (their inner solve is idle work: their q does not move).
-// A: `A_sh` [nc][36] (shared A), else the per-instance A of the constraint record in the tiles.
+// Instances that do not run get b_c = 0.
 template <typename T>
 __global__ void k_pose_retarget(const double* __restrict__ q, int nq, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q,
                                 const int* __restrict__ c_link, int nc, const double* __restrict__ tgt, int tgt_shared,
@@ -194,47 +293,17 @@ __global__ void k_pose_retarget(const double* __restrict__ q, int nq, const Join
     for (int i = 0; i < nq; ++i) finite = finite && isfinite(q_row[i]);
     double emax = 0.0;
     for (int c = 0; c < nc; ++c) {
-      double R[9], t[3], Re[9], pe[3], e[6];
-      link_placement(q_row, jd, idx_q, c_link[c], R, t);
-      const double* D = tgt + ((tgt_shared ? 0 : (size_t)b * nc) + c) * 12;
-      for (int r = 0; r < 3; ++r) {   // oMi^-1 oMdes = (R^T Rd, R^T (td - t))
-        for (int cc = 0; cc < 3; ++cc) Re[3 * r + cc] = R[r] * D[cc] + R[3 + r] * D[3 + cc] + R[6 + r] * D[6 + cc];
-        pe[r] = R[r] * (D[9] - t[0]) + R[3 + r] * (D[10] - t[1]) + R[6 + r] * (D[11] - t[2]);
-      }
-      pose_log6(Re, pe, e);
-      double* eo = err + ((size_t)b * nc + c) * 6;
-      for (int r = 0; r < 6; ++r) {
-        eo[r] = e[r];
-        finite = finite && isfinite(e[r]);
-        emax = fmax(emax, fabs(e[r]));
-      }
-      if (step) {
-        const char* crec = lane_ptr<T>(const_cast<char*>(tiles), L, b) + (size_t)(L.off_c + c * L.crec) * pair_bytes<T>();
-        double* bo = b_out + ((size_t)c * B + b) * 6;
-        for (int r = 0; r < 6; ++r) {
-          double a = 0.0;
-          for (int m = 0; m < 6; ++m) {
-            const int x = 6 * r + m;
-            const double A = A_sh ? A_sh[c * 36 + x] : (double)*elem_ptr<T>(const_cast<char*>(crec), CP_A + x / 2, x & 1);
-            a += A * (k * e[m]);
-          }
-          bo[r] = a;
-        }
-      }
+      double e[6];
+      pose_error(q_row, jd, idx_q, c_link[c], nullptr, tgt + ((tgt_shared ? 0 : (size_t)b * nc) + c) * 12, e);
+      pose_store_err(e, err + ((size_t)b * nc + c) * 6, finite, emax);
+      if (step) pose_b_joint<T>(e, k, A_sh, tiles, L, b, c, b_out + ((size_t)c * B + b) * 6);
     }
     if (!finite) st |= POSE_STOPPED;
     else if (emax <= tol) st |= POSE_REACHED;
     run = !(st & (POSE_REACHED | POSE_STOPPED));
     status[b] = st;
   }
-  if (!step) return;
-  if (run) {
-    steps[b] += 1;
-    atomicAdd(running, 1u);
-  } else {
-    for (int c = 0; c < nc; ++c)
-      for (int r = 0; r < 6; ++r) b_out[((size_t)c * B + b) * 6 + r] = 0.0;
-  }
+  if (step) pose_count_or_idle(run, b, nc, B, b_out, steps, running);
 }
 
 // q <- q (+) dt z for the instances still running, and the inner solve's outcome into their pose status

@@ -8,14 +8,14 @@
 //                     handle's precision) and, with `tasks`, the task law of k_pose_retarget_tasks
 //   k_path_record   : q of instance b into the Q rows of the waypoints the last re-target crossed, one thread per coordinate
 //
-// k_pose_retarget, k_pose_retarget_tasks, k_pose_integrate and the limit kernels are not touched.  The latter two are reused as
-// they are: they take "does this instance run" from a status word with the POSE_* bits, and the path loop hands them its own,
-// LOOP-PRIVATE word, in which a stalled instance carries POSE_STOPPED | PATH_L_STALLED -- so it is not integrated, gets the base
-// box and keeps its limit flags, exactly like an instance that stopped.  The re-target folds the private word into the public
-// pose status (stalled: neither REACHED nor STOPPED) and the path status every time it handles the instance.
+// k_pose_integrate and the limit kernels are reused as they are: they take "does this instance run" from a status word with the
+// POSE_* bits, and the path loop hands them its own, LOOP-PRIVATE word, in which a stalled instance carries
+// POSE_STOPPED | PATH_L_STALLED -- so it is not integrated, gets the base box and keeps its limit flags, exactly like an instance
+// that stopped.  The re-target folds the private word into the public pose status (stalled: neither REACHED nor STOPPED) and the
+// path status every time it handles the instance.
 //
-// The arithmetic of the error and of b is that of the two pose kernels, statement for statement (-ffp-contract=on contracts
-// within a statement only), so a path of one waypoint is loikb_solve_pose bit for bit.  fp64 and untuned, as loik_pose.hpp says.
+// The error, the err store and b are the retarget rule of loik_pose.hpp, the one definition the two pose kernels run too, so a
+// path of one waypoint is loikb_solve_pose bit for bit.  fp64 and untuned, as loik_pose.hpp says.
 #pragma once
 
 #include "loik_pose_tasks.hpp"
@@ -34,32 +34,6 @@ __global__ void k_path_setup(int B, size_t nBT, size_t nQ, int* __restrict__ cur
   if (i < (size_t)B) { cursor[i] = 0; ws[i] = 0; wfrom[i] = 0; lstatus[i] = 0; pstatus[i] = 0; }
   if (i < nBT) wsteps[i] = 0;
   if (i < nQ) Q[i] = __longlong_as_double(0x7ff8000000000000ll);
-}
-
-// e of constraint c against the placement D: k_pose_retarget's (tk = nullptr) or k_pose_retarget_tasks'
-__device__ __forceinline__ void path_error(const double* q_row, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q, int link,
-                                           const PoseTask* tk, const double* D, double* e)
-{
-  double Ri[9], ti[3], Rw[9], tw[3], Re[9], pe[3];
-  link_placement(q_row, jd, idx_q, link, Ri, ti);
-  const double *R = Ri, *t = ti;
-  if (tk) {
-    frame_compose(Ri, ti, tk->Rf, tk->pf, Rw, tw);
-    R = Rw; t = tw;
-  }
-  for (int r = 0; r < 3; ++r) {   // oMf^-1 oMdes = (R^T Rd, R^T (td - t))
-    for (int cc = 0; cc < 3; ++cc) Re[3 * r + cc] = R[r] * D[cc] + R[3 + r] * D[3 + cc] + R[6 + r] * D[6 + cc];
-    pe[r] = R[r] * (D[9] - t[0]) + R[3 + r] * (D[10] - t[1]) + R[6 + r] * (D[11] - t[2]);
-  }
-  const int kind = tk ? tk->kind : TASK_POSE;
-  if (kind == TASK_POSITION) {
-    for (int r = 0; r < 3; ++r) { e[r] = pe[r]; e[3 + r] = 0.0; }
-  } else if (kind == TASK_ORIENTATION) {
-    pose_log3(Re, e + 3);
-    for (int r = 0; r < 3; ++r) e[r] = 0.0;
-  } else {
-    pose_log6(Re, pe, e);
-  }
 }
 
 // One re-target of the path loop for instance b (the numbered rule of loik_amd_path.h).  wp: [B][Tn][nc][12] or, shared,
@@ -92,30 +66,12 @@ __global__ void k_path_retarget(const double* __restrict__ q, int nq, const Join
       double emax = 0.0;
       for (int c = 0; c < nc; ++c) {
         double e[6];
-        const double* D = wp + (((wp_shared ? 0 : (size_t)b * Tn) + w) * nc + c) * 12;
-        path_error(q_row, jd, idx_q, c_link[c], tasks ? tasks + c : nullptr, D, e);
-        double* eo = err + ((size_t)b * nc + c) * 6;
-        for (int r = 0; r < 6; ++r) {
-          eo[r] = e[r];
-          finite = finite && isfinite(e[r]);
-          emax = fmax(emax, fabs(e[r]));
-        }
+        pose_error(q_row, jd, idx_q, c_link[c], tasks ? tasks + c : nullptr, wp + (((wp_shared ? 0 : (size_t)b * Tn) + w) * nc + c) * 12, e);
+        pose_store_err(e, err + ((size_t)b * nc + c) * 6, finite, emax);
         if (step) {
           double* bo = b_out + ((size_t)c * B + b) * 6;
-          if (tasks) {
-            for (int r = 0; r < 6; ++r) bo[r] = k * e[r];
-          } else {
-            const char* crec = lane_ptr<T>(const_cast<char*>(tiles), L, b) + (size_t)(L.off_c + c * L.crec) * pair_bytes<T>();
-            for (int r = 0; r < 6; ++r) {
-              double a = 0.0;
-              for (int m = 0; m < 6; ++m) {
-                const int x = 6 * r + m;
-                const double A = A_sh ? A_sh[c * 36 + x] : (double)*elem_ptr<T>(const_cast<char*>(crec), CP_A + x / 2, x & 1);
-                a += A * (k * e[m]);
-              }
-              bo[r] = a;
-            }
-          }
+          if (tasks) pose_b_task(e, k, bo);
+          else pose_b_joint<T>(e, k, A_sh, tiles, L, b, c, bo);
         }
       }
       if (!finite) { ls |= POSE_STOPPED; break; }
@@ -138,14 +94,7 @@ __global__ void k_path_retarget(const double* __restrict__ q, int nq, const Join
     status[b] = (ls & PATH_L_STALLED) ? (ls & ~(POSE_STOPPED | PATH_L_STALLED)) : ls;
     pstatus[b] = ((ls & POSE_REACHED) ? PATH_COMPLETE : 0) | ((ls & PATH_L_STALLED) ? PATH_STALLED : 0);
   }
-  if (!step) return;
-  if (run) {
-    steps[b] += 1;
-    atomicAdd(running, 1u);
-  } else {
-    for (int c = 0; c < nc; ++c)
-      for (int r = 0; r < 6; ++r) b_out[((size_t)c * B + b) * 6 + r] = 0.0;
-  }
+  if (step) pose_count_or_idle(run, b, nc, B, b_out, steps, running);
 }
 
 // Q[b][w] = q[b] for the waypoints w in [wfrom[b], cursor[b]) the last re-target crossed: thread (b, i) carries coordinate i, so

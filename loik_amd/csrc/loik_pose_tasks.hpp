@@ -6,33 +6,14 @@
 //   k_frame_placements    : oMf = oMi(link) iMf of requested (link, frame) pairs from the resident q, one thread per
 //                           (instance, entry)
 //
-// k_pose_retarget itself is not touched: a handle without tasks runs the code it ran before, bit for bit.  The task kernel
-// needs neither the tiles nor A (A_c v = S_c v_f by construction, so b_c is the masked error itself), hence no template on the
-// handle's precision.  fp64 and untuned, as loik_pose.hpp says of its kernels.
+// The error, the err store, b and the tail are the retarget rule of loik_pose.hpp, which k_pose_retarget runs too: there is one
+// definition.  The task kernel needs neither the tiles nor A (pose_b_task), hence no template on the handle's precision.  fp64
+// and untuned, as loik_pose.hpp says of its kernels.
 #pragma once
 
 #include "loik_pose.hpp"
 
 namespace loikb {
-
-// task kinds (loik_amd_tasks.h)
-enum : int { TASK_POSE = 0, TASK_POSITION = 1, TASK_ORIENTATION = 2 };
-
-// one entry per active constraint, built by loikb_pose_set_tasks: iMf = (Rf row-major, pf)
-struct PoseTask {
-  int kind, pad;
-  double Rf[9], pf[3];
-};
-
-// (Rw, tw) = (R, t) * (Rf, pf); with the identity frame this returns (R, t) bit for bit (finite entries)
-__device__ __forceinline__ void frame_compose(const double* R, const double* t, const double* Rf, const double* pf, double* Rw,
-                                              double* tw)
-{
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) Rw[3 * r + c] = R[3 * r] * Rf[c] + R[3 * r + 1] * Rf[3 + c] + R[3 * r + 2] * Rf[6 + c];
-    tw[r] = t[r] + (R[3 * r] * pf[0] + R[3 * r + 1] * pf[1] + R[3 * r + 2] * pf[2]);
-  }
-}
 
 // One step of the pose loop for instance b on a handle with tasks.  The contract of k_pose_retarget with the error, b and the
 // reached test of loik_amd_tasks.h: instances already reached or stopped keep their status; the others get err = S_c e_c of the
@@ -55,47 +36,17 @@ __global__ void k_pose_retarget_tasks(const double* __restrict__ q, int nq, cons
     for (int i = 0; i < nq; ++i) finite = finite && isfinite(q_row[i]);
     double emax = 0.0;
     for (int c = 0; c < nc; ++c) {
-      double Ri[9], ti[3], R[9], t[3], Re[9], pe[3], e[6];
-      const PoseTask& tk = tasks[c];
-      link_placement(q_row, jd, idx_q, c_link[c], Ri, ti);
-      frame_compose(Ri, ti, tk.Rf, tk.pf, R, t);
-      const double* D = tgt + ((tgt_shared ? 0 : (size_t)b * nc) + c) * 12;
-      for (int r = 0; r < 3; ++r) {   // oMf^-1 oMdes = (R^T Rd, R^T (td - t))
-        for (int cc = 0; cc < 3; ++cc) Re[3 * r + cc] = R[r] * D[cc] + R[3 + r] * D[3 + cc] + R[6 + r] * D[6 + cc];
-        pe[r] = R[r] * (D[9] - t[0]) + R[3 + r] * (D[10] - t[1]) + R[6 + r] * (D[11] - t[2]);
-      }
-      if (tk.kind == TASK_POSITION) {
-        for (int r = 0; r < 3; ++r) { e[r] = pe[r]; e[3 + r] = 0.0; }
-      } else if (tk.kind == TASK_ORIENTATION) {
-        pose_log3(Re, e + 3);
-        for (int r = 0; r < 3; ++r) e[r] = 0.0;
-      } else {
-        pose_log6(Re, pe, e);
-      }
-      double* eo = err + ((size_t)b * nc + c) * 6;
-      for (int r = 0; r < 6; ++r) {
-        eo[r] = e[r];
-        finite = finite && isfinite(e[r]);
-        emax = fmax(emax, fabs(e[r]));
-      }
-      if (step) {
-        double* bo = b_out + ((size_t)c * B + b) * 6;
-        for (int r = 0; r < 6; ++r) bo[r] = k * e[r];
-      }
+      double e[6];
+      pose_error(q_row, jd, idx_q, c_link[c], tasks + c, tgt + ((tgt_shared ? 0 : (size_t)b * nc) + c) * 12, e);
+      pose_store_err(e, err + ((size_t)b * nc + c) * 6, finite, emax);
+      if (step) pose_b_task(e, k, b_out + ((size_t)c * B + b) * 6);
     }
     if (!finite) st |= POSE_STOPPED;
     else if (emax <= tol) st |= POSE_REACHED;
     run = !(st & (POSE_REACHED | POSE_STOPPED));
     status[b] = st;
   }
-  if (!step) return;
-  if (run) {
-    steps[b] += 1;
-    atomicAdd(running, 1u);
-  } else {
-    for (int c = 0; c < nc; ++c)
-      for (int r = 0; r < 6; ++r) b_out[((size_t)c * B + b) * 6 + r] = 0.0;
-  }
+  if (step) pose_count_or_idle(run, b, nc, B, b_out, steps, running);
 }
 
 // out[b][e] = (R row-major, t) of oMi(dev_link[e]) * frames[e]: k_link_placements' arithmetic, then the composition with iMf
