@@ -76,6 +76,12 @@ FIELD_ID["mu_updates"] = 97
 FIELD_ID["primal_residual_vec"] = 98
 FIELD_ID["dual_residual_vec"] = 99
 FIELD_ID.update({n: 32 + i for i, n in enumerate(_SCALAR_FIELDS)})
+INT_FIELDS = ("iter", "converged", "primal_infeasible", "status", "mu_updates")   # int32, the others float64
+# what loikb_get writes per instance, after [B]: "nb" bodies (njoints - 1), "nc" constraints in force; "scalars" is loikb_get_results' block.
+# r / Dinv / UDinv are inter-sweep temporaries of the device's elimination: per DoF, equal to upstream's per-joint values for 1-DoF joints only
+FIELD_DIMS = dict({n: ("nv",) for n in ("z", "nu", "w", "Stf_plus_w", "r", "Dinv")}, **{n: ("nb", 6) for n in ("vis", "fis", "g", "pis")},
+                  **{n: ("nc", 6) for n in ("yis", "Aty")}, **{n: ("6nb+nv",) for n in ("primal_residual_vec", "dual_residual_vec")},
+                  **{n: () for n in _SCALAR_FIELDS + list(INT_FIELDS)}, UDinv=("nv", 6), His=("nb", 21), liMi=("nb", 12), q=("nq",), scalars=(33,))
 
 # every symbol include/loik_amd.h and include/loik_amd_models.h declare
 EXPORTED_SYMBOLS = [
@@ -1036,23 +1042,19 @@ class BatchedLoik:
     def set_tol_tail_solve(self, x): _check(self.L.loikb_set_tol_tail_solve(self.h, float(x)))
     def set_warm_start(self, w): _check(self.L.loikb_set_warm_start(self.h, int(bool(w))))
 
+    def _shapes(self, names):
+        m, nc = self.model, self.L.loikb_num_eq_c(self.h)
+        d = {"nb": m.njoints - 1, "nv": m.nv, "nq": m.nq, "nc": nc, "6nb+nv": 6 * (m.njoints - 1) + m.nv}
+        return {n: (self.batch,) + tuple(d.get(x, x) for x in FIELD_DIMS[n]) for n in names}
+
     def get(self, name, out=None):
         """one field for the whole batch as a numpy array (or into a device pointer / torch tensor `out`)"""
         fid = FIELD_ID[name]
-        B, nb, nv, nc = self.batch, self.model.njoints - 1, self.model.nv, self.L.loikb_num_eq_c(self.h)
-        # per DoF: [B][nv]; per link: [B][nb].  r / Dinv / UDinv are inter-sweep temporaries of the device's
-        # elimination: per DoF, equal to upstream's per-joint values for 1-DoF joints only
-        shapes = {"z": (B, nv), "nu": (B, nv), "w": (B, nv), "Stf_plus_w": (B, nv), "r": (B, nv), "Dinv": (B, nv),
-                  "vis": (B, nb, 6), "fis": (B, nb, 6), "g": (B, nb, 6), "pis": (B, nb, 6), "UDinv": (B, nv, 6),
-                  "His": (B, nb, 21), "liMi": (B, nb, 12), "yis": (B, nc, 6), "Aty": (B, nc, 6),
-                  "q": (B, self.model.nq), "primal_residual_vec": (B, 6 * nb + nv),
-                  "dual_residual_vec": (B, 6 * nb + nv)}
-        is_int = name in ("iter", "converged", "primal_infeasible", "status", "mu_updates")
         if out is not None:
             p, dev = _ptr(out)
             _check(self.L.loikb_get(self.h, fid, p, OUT_DEVICE if dev else 0))
             return out
-        arr = np.empty(shapes.get(name, (B,)), dtype=np.int32 if is_int else np.float64)
+        arr = np.empty(self._shapes([name])[name], dtype=np.int32 if name in INT_FIELDS else np.float64)
         _check(self.L.loikb_get(self.h, fid, arr.ctypes.data_as(C.c_void_p), 0))
         return arr
 
@@ -1064,9 +1066,7 @@ class BatchedLoik:
         subset, in ONE call (loikb_get_results): {name: array}, the same values as get(name).  "scalars": [B][33] -- the 30 scalar getters'
         fields in FIELD_ID order from "primal_residual", then iter, the status bits, mu_updates (what get_iter() / get_convergence_status() / ...
         read), from the same gather"""
-        B, nb, nv, nc = self.batch, self.model.njoints - 1, self.model.nv, self.L.loikb_num_eq_c(self.h)
-        shapes = {"z": (B, nv), "nu": (B, nv), "w": (B, nv), "vis": (B, nb, 6), "fis": (B, nb, 6), "yis": (B, nc, 6), "scalars": (B, self.NSCALARS)}
-        mask, out, ptrs = 0, {}, []
+        mask, out, ptrs, shapes = 0, {}, [], self._shapes(self.RESULT_FIELDS)
         for k, name in enumerate(self.RESULT_FIELDS):
             if name in fields:
                 mask |= 1 << k

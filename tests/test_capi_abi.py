@@ -32,6 +32,20 @@ def test_library_exports_every_declared_symbol():
     assert L.loikb_version() == loik_amd.capi.ABI_VERSION == 602
 
 
+def test_every_field_has_a_shape_rule_and_every_int_field_is_a_field():
+    """BatchedLoik.get / get_results size their arrays from capi.FIELD_DIMS and capi.INT_FIELDS alone"""
+    assert set(capi.FIELD_DIMS) == set(capi.FIELD_ID) | {"scalars"}, set(capi.FIELD_DIMS) ^ set(capi.FIELD_ID)
+    assert set(capi.INT_FIELDS) <= set(capi.FIELD_ID) and len(set(capi.INT_FIELDS)) == len(capi.INT_FIELDS) == 5
+    assert set(loik_amd.BatchedLoik.RESULT_FIELDS) <= set(capi.FIELD_DIMS)
+    # the layouts include/loik_amd.h documents, every field
+    want = dict({n: ("nv",) for n in ("z", "nu", "w", "Stf_plus_w", "r", "Dinv")}, vis=("nb", 6), fis=("nb", 6), g=("nb", 6), pis=("nb", 6),
+                UDinv=("nv", 6), His=("nb", 21), liMi=("nb", 12), yis=("nc", 6), Aty=("nc", 6), q=("nq",),
+                primal_residual_vec=("6nb+nv",), dual_residual_vec=("6nb+nv",), scalars=(loik_amd.BatchedLoik.NSCALARS,))
+    for name in capi.FIELD_DIMS:
+        assert capi.FIELD_DIMS[name] == want.get(name, ()), name
+    assert len(want) == 19 and not set(want) & (set(capi._SCALAR_FIELDS) | set(capi.INT_FIELDS))
+
+
 def test_builtin_models():
     for name, nj in [("panda7", 8), ("panda9", 10), ("talos32", 33)]:
         m = loik_amd.builtin_model(name)
