@@ -21,6 +21,7 @@
 #include "../loik_amd_tasks.h"
 #include "../loik_amd_multistart.h"
 #include "../loik_amd_path.h"
+#include "../loik_amd_track.h"
 
 #include <array>
 #include <map>
@@ -538,6 +539,56 @@ public:
       check(loikb_path_get(h_, LOIKB_PATH_F_Q, r.q_path.data(), 0));
     }
     for (int b = 0; b < batch_; ++b) r.reached[b] = (r.status[b] & LOIKB_POSE_ST_REACHED) ? 1 : 0;
+    return r;
+  }
+  // ---- timed trajectories (include/loik_amd_track.h): closed-loop tracking of T + 1 samples per instance spaced dt apart, one inner
+  // solve per step, every instance in step with the clock
+  struct TrackResult {
+    std::vector<int> steps, status, ontrack, worst_at;  // [batch]; status: LOIKB_POSE_ST_* bits (REACHED is never set)
+    std::vector<int> inner;                             // [batch][T]: 1 = not converged, 2 = primal infeasible, 4 = a joint limit cut the box
+    DVec err;                                           // [batch][nc][6]: against X_T
+    DVec errmax, worst;                                 // [batch][T+1], [batch]
+    DVec q_traj, z_traj;                                // [batch][T+1][nq], [batch][T][nv], NaN rows after a stop; empty when not recorded
+    int n_steps = 0;
+    std::array<double, 4> timing{};                     // LOIKB_TRACK_F_TIMING
+  };
+  // samples: (T + 1) * nc (sample-major) for the whole batch, or batch * (T + 1) * nc instance-major; feedforward: LOIKB_TRACK_FF_*;
+  // record: LOIKB_TRACK_REC_* bits; q as SolvePose takes it
+  TrackResult TrackPose(const std::vector<SE3>& samples, int n_steps, double dt = 1.0, double gain = 1.0, double tol_track = 1e-4,
+                        int feedforward = LOIKB_TRACK_FF_DIFFERENCE, int record = LOIKB_TRACK_REC_Q | LOIKB_TRACK_REC_Z, const DVec* q = nullptr)
+  {
+    const std::size_t nc = (std::size_t)loikb_num_eq_c(h_), T = (std::size_t)(n_steps > 0 ? n_steps : 1);
+    int flags = 0;
+    if (samples.size() == (T + 1) * nc && batch_ > 1) flags |= LOIKB_POSE_TARGET_SHARED;
+    else if (samples.size() != (std::size_t)batch_ * (T + 1) * nc)
+      throw std::runtime_error("loik_amd: TrackPose needs n_steps + 1 placements per active constraint, shared or per instance");
+    if (q && q->size() != (std::size_t)batch_ * model_.nq) throw std::runtime_error("loik_amd: q must hold batch * model.nq values");
+    DVec t(samples.size() * 12);
+    for (std::size_t i = 0; i < samples.size(); ++i) std::copy(samples[i].begin(), samples[i].end(), t.begin() + 12 * i);
+    const loikb_track_params p{dt, gain, tol_track, n_steps, feedforward, record, 0};
+    check(loikb_track_pose(h_, q ? q->data() : nullptr, t.data(), flags, &p));
+    solved();
+    TrackResult r;
+    r.n_steps = n_steps;
+    r.steps.resize(batch_); r.status.resize(batch_); r.ontrack.resize(batch_); r.worst_at.resize(batch_); r.worst.resize(batch_);
+    r.inner.resize((std::size_t)batch_ * T); r.errmax.resize((std::size_t)batch_ * (T + 1)); r.err.resize((std::size_t)batch_ * nc * 6);
+    check(loikb_pose_get(h_, LOIKB_POSE_F_STEPS, r.steps.data(), 0));
+    check(loikb_pose_get(h_, LOIKB_POSE_F_STATUS, r.status.data(), 0));
+    check(loikb_pose_get(h_, LOIKB_POSE_F_ERR, r.err.data(), 0));
+    check(loikb_track_get(h_, LOIKB_TRACK_F_ERRMAX, r.errmax.data(), 0));
+    check(loikb_track_get(h_, LOIKB_TRACK_F_INNER, r.inner.data(), 0));
+    check(loikb_track_get(h_, LOIKB_TRACK_F_ONTRACK, r.ontrack.data(), 0));
+    check(loikb_track_get(h_, LOIKB_TRACK_F_WORST, r.worst.data(), 0));
+    check(loikb_track_get(h_, LOIKB_TRACK_F_WORST_AT, r.worst_at.data(), 0));
+    check(loikb_track_get(h_, LOIKB_TRACK_F_TIMING, r.timing.data(), 0));
+    if (record & LOIKB_TRACK_REC_Q) {
+      r.q_traj.resize((std::size_t)batch_ * (T + 1) * model_.nq);
+      check(loikb_track_get(h_, LOIKB_TRACK_F_Q, r.q_traj.data(), 0));
+    }
+    if (record & LOIKB_TRACK_REC_Z) {
+      r.z_traj.resize((std::size_t)batch_ * T * model_.nv);
+      check(loikb_track_get(h_, LOIKB_TRACK_F_Z, r.z_traj.data(), 0));
+    }
     return r;
   }
   // the resident configurations, [batch][nq]

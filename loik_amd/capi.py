@@ -132,6 +132,23 @@ PATH_F_CURSOR, PATH_F_STATUS, PATH_F_WSTEPS, PATH_F_Q, PATH_F_TIMING = range(5)
 PATH_ST_COMPLETE, PATH_ST_STALLED = 1, 2
 
 
+# include/loik_amd_track.h: timed pose trajectories with feed-forward in the pose loop; its own header and version again
+TRACK_ABI_VERSION = 1
+TRACK_SYMBOLS = ["loikb_track_version", "loikb_track_pose", "loikb_track_get"]
+TRACK_FF_NONE, TRACK_FF_DIFFERENCE = 0, 1
+TRACK_FFS = {"none": TRACK_FF_NONE, "difference": TRACK_FF_DIFFERENCE}
+TRACK_REC_Q, TRACK_REC_Z = 1, 2
+TRACK_RECS = {"q": TRACK_REC_Q, "z": TRACK_REC_Z}
+TRACK_F_Q, TRACK_F_Z, TRACK_F_ERRMAX, TRACK_F_INNER, TRACK_F_ONTRACK, TRACK_F_WORST, TRACK_F_WORST_AT, TRACK_F_TIMING = range(8)
+TRACK_IN_NOT_CONVERGED, TRACK_IN_INFEASIBLE, TRACK_IN_LIMIT = 1, 2, 4
+# what loikb_track_get writes per instance, after [B], in the manner of FIELD_DIMS / INT_FIELDS (which describe loikb_get's fields and
+# those alone): "T" steps, "T+1" samples
+TRACK_FIELD_ID = {"q_traj": TRACK_F_Q, "z_traj": TRACK_F_Z, "errmax": TRACK_F_ERRMAX, "inner": TRACK_F_INNER, "ontrack": TRACK_F_ONTRACK,
+                  "worst": TRACK_F_WORST, "worst_at": TRACK_F_WORST_AT}
+TRACK_FIELD_DIMS = {"q_traj": ("T+1", "nq"), "z_traj": ("T", "nv"), "errmax": ("T+1",), "inner": ("T",), "ontrack": (), "worst": (), "worst_at": ()}
+TRACK_INT_FIELDS = ("inner", "ontrack", "worst_at")   # int32, the others float64
+
+
 class PoseParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
 
@@ -142,6 +159,11 @@ class MultiStartParams(C.Structure):
 
 class PathParams(C.Structure):
     _fields_ = [("n_waypoints", C.c_int), ("max_steps_per_waypoint", C.c_int), ("record", C.c_int), ("flags", C.c_int)]
+
+
+class TrackParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_track", C.c_double), ("n_steps", C.c_int), ("feedforward", C.c_int),
+                ("record", C.c_int), ("flags", C.c_int)]
 
 
 _lib = None
@@ -217,6 +239,8 @@ def lib():
     L.loikb_multistart_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.loikb_solve_pose_path.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(PoseParams), C.POINTER(PathParams)]
     L.loikb_path_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_track_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TrackParams)]
+    L.loikb_track_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1029,6 +1053,107 @@ class BatchedLoik:
                              "wsteps": (PATH_F_WSTEPS, np.int32, (B, T)), "q_path": (PATH_F_Q, np.float64, (B, T, self.model.nq))}[name]
         arr = np.empty(shape, dtype=dtype)
         _check(self.L.loikb_path_get(self.h, fid, arr.ctypes.data_as(C.c_void_p), 0))
+        return arr
+
+    # ---- timed trajectories (include/loik_amd_track.h) -------------------------------------------------------
+    def TrackPose(self, samples, dt=1.0, gain=1.0, tol_track=1e-4, feedforward="difference", record=("q", "z"), q=None):
+        """closed-loop tracking of a pose trajectory sampled every dt (loikb_track_pose): T + 1 samples X_0 .. X_T per instance, one
+        inner solve per step, every instance in step with the clock.  Step k: e against X_k, b_c = A_c ((gain / dt) e_c + f_c) with
+        f_c the feed-forward twist from X_k to X_{k+1} over dt (feedforward="difference"; "none": f = 0), the step of SolvePose.
+        samples: [B][T+1][nc][4][4] / [B][T+1][nc][12], or [T+1][nc][4][4] / [T+1][nc][12] shared by the batch; a device tensor of
+        these shapes likewise, a flat one by its numel as SolvePosePath takes it.  record: any of "q", "z" (or the REC bits).
+        q as in SolvePose.
+        Returns SolvePose's dict (reached is never set: status carries the inner solves' bits and STOPPED; err is against X_T) plus
+        q_traj [B][T+1][nq] and z_traj [B][T][nv] (None when not recorded; NaN rows after a stop), errmax [B][T+1], inner [B][T]
+        TRACK_IN_* bits, ontrack [B] samples within tol_track, worst [B] / worst_at [B] = the largest errmax after sample 0."""
+        B, nc = self.batch, int(self.L.loikb_num_eq_c(self.h))
+        flags, keep = 0, []
+        if hasattr(samples, "data_ptr") and getattr(samples, "is_cuda", False):
+            n, shape = int(samples.numel()), tuple(getattr(samples, "shape", ()))
+            if len(shape) == 4 and shape[0] == B and shape[2] == nc:
+                Tn, shared = shape[1], False
+            elif len(shape) == 3 and shape[1] == nc:
+                Tn, shared = shape[0], True
+            elif n and n % (B * nc * 12) == 0:
+                Tn, shared = n // (B * nc * 12), False
+            elif n and n % (nc * 12) == 0:
+                Tn, shared = n // (nc * 12), True
+            else:
+                raise ValueError("samples: device tensor has %d elements, expected batch * (T + 1) * nc * 12 or (T + 1) * nc * 12" % n)
+            if n != (1 if shared else B) * Tn * nc * 12:
+                raise ValueError("samples: device tensor of shape %s is neither [B][T+1][nc][12] nor [T+1][nc][12]" % (shape,))
+            sp = C.c_void_p(samples.data_ptr())
+            flags |= IN_DEVICE
+        else:
+            t = self._placements12(samples.numpy() if hasattr(samples, "numpy") else samples, "samples")
+            if t.ndim == 4 and t.shape[0] == B and t.shape[2] == nc:
+                Tn, shared = t.shape[1], False
+            elif t.ndim == 3 and t.shape[1] == nc:
+                Tn, shared = t.shape[0], True
+            else:
+                raise ValueError("samples: shape %s, expected [batch = %d][T+1][nc = %d][12] or [T+1][nc][12]" % (t.shape, B, nc))
+            keep.append(t)
+            sp = t.ctypes.data_as(C.c_void_p)
+        if shared and B > 1:
+            flags |= POSE_TARGET_SHARED
+        qp = None
+        if q is not None:
+            if isinstance(q, int) or (hasattr(q, "data_ptr") and getattr(q, "is_cuda", False)):
+                if not flags & IN_DEVICE:
+                    raise ValueError("q and samples must both be host arrays or both device pointers")
+                qp = C.c_void_p(q if isinstance(q, int) else q.data_ptr())
+            else:
+                if flags & IN_DEVICE:
+                    raise ValueError("q and samples must both be host arrays or both device pointers")
+                qa = _f64(q)
+                if qa.size != B * self.model.nq:
+                    raise ValueError("q has %d elements, expected batch * nq = %d" % (qa.size, B * self.model.nq))
+                keep.append(qa)
+                qp = qa.ctypes.data_as(C.c_void_p)
+        if isinstance(feedforward, str):
+            if feedforward not in TRACK_FFS:
+                raise ValueError("feedforward %r: expected one of %s" % (feedforward, sorted(TRACK_FFS)))
+            feedforward = TRACK_FFS[feedforward]
+        if not isinstance(record, (int, np.integer)):
+            bits = 0
+            for r in ([record] if isinstance(record, str) else record):
+                if r not in TRACK_RECS:
+                    raise ValueError("record %r: expected any of %s" % (r, sorted(TRACK_RECS)))
+                bits |= TRACK_RECS[r]
+            record = bits
+        prm = TrackParams(float(dt), float(gain), float(tol_track), int(Tn) - 1, int(feedforward), int(record), 0)
+        _check(self.L.loikb_track_pose(self.h, qp, sp, flags, C.byref(prm)))
+        self._track_T = int(Tn) - 1
+        status = np.empty(B, dtype=np.int32)
+        steps = np.empty(B, dtype=np.int32)
+        err = np.empty((B, nc, 6))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_STATUS, status.ctypes.data_as(C.c_void_p), 0))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_STEPS, steps.ctypes.data_as(C.c_void_p), 0))
+        _check(self.L.loikb_pose_get(self.h, POSE_F_ERR, err.ctypes.data_as(C.c_void_p), 0))
+        out = dict(reached=(status & POSE_ST_REACHED) != 0, steps=steps, err=err, status=status)
+        recorded = {"q_traj": record & TRACK_REC_Q, "z_traj": record & TRACK_REC_Z}
+        for name in TRACK_FIELD_ID:
+            out[name] = self.track_get(name) if recorded.get(name, True) else None
+        if self._limits:
+            out["limit_flags"] = self.pose_limit_flags()
+        return out
+
+    def track_get(self, name, out=None):
+        """one result of the last TrackPose (loikb_track_get): q_traj / z_traj / errmax / inner / ontrack / worst / worst_at as a numpy
+        array (or into a device pointer / torch tensor `out`), or timing (a dict as pose_timing)"""
+        if name == "timing":
+            t = np.zeros(4)
+            _check(self.L.loikb_track_get(self.h, TRACK_F_TIMING, t.ctypes.data_as(C.c_void_p), 0))
+            return dict(steps=int(t[0]), total_ms=float(t[1]), solve_ms=float(t[2]), other_ms=float(t[3]))
+        fid = TRACK_FIELD_ID[name]
+        if out is not None:
+            p, dev = _ptr(out)
+            _check(self.L.loikb_track_get(self.h, fid, p, OUT_DEVICE if dev else 0))
+            return out
+        T = getattr(self, "_track_T", 1)
+        d = {"T": T, "T+1": T + 1, "nq": self.model.nq, "nv": self.model.nv}
+        arr = np.empty((self.batch,) + tuple(d[x] for x in TRACK_FIELD_DIMS[name]), dtype=np.int32 if name in TRACK_INT_FIELDS else np.float64)
+        _check(self.L.loikb_track_get(self.h, fid, arr.ctypes.data_as(C.c_void_p), 0))
         return arr
 
     # ------------------------------------------------------------------------------------------------------

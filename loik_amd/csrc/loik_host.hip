@@ -22,6 +22,7 @@
 #include "loik_pose_tasks.hpp"
 #include "loik_pose_multistart.hpp"
 #include "loik_pose_path.hpp"
+#include "loik_pose_track.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -38,6 +39,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_tasks.h"
 #include "../../include/loik_amd_multistart.h"
 #include "../../include/loik_amd_path.h"
+#include "../../include/loik_amd_track.h"
 
 #include <algorithm>
 #include <chrono>
@@ -405,6 +407,22 @@ struct loikb_solver_impl {
     bool recorded = false;             // it ran with record: d_Q is its result
     double timing[4] = {0, 0, 0, 0};   // LOIKB_PATH_F_TIMING
   } path;
+  // timed trajectories (loik_pose_track.hpp): buffers of loikb_track_pose, allocated by its first call.  The [B] arrays go with the
+  // handle's `allocs`; those sized by the step count are the tracker's own and grow with it (track_alloc_*)
+  struct TrackState {
+    int* d_ontrack = nullptr;          // [B] samples within tol_track
+    double* d_worst = nullptr;         // [B] the largest ERRMAX after sample 0
+    int* d_worst_at = nullptr;         // [B] the sample it was at
+    double* d_smp = nullptr;           // [B][T+1][nc][12] samples (shared: the first (T + 1) * nc rows)
+    double* d_errmax = nullptr;        // [B][T+1]
+    int* d_inner = nullptr;            // [B][T]
+    double* d_Q = nullptr;             // [B][T+1][nq], allocated by the first call with LOIKB_TRACK_REC_Q
+    double* d_Z = nullptr;             // [B][T][nv], allocated by the first call with LOIKB_TRACK_REC_Z
+    int cap_smp = 0, cap_T = 0, cap_TQ = 0, cap_TZ = 0;   // step counts d_smp, d_errmax / d_inner, d_Q and d_Z have room for
+    int T = 0;                         // of the last loikb_track_pose (0: none yet)
+    int record = 0;                    // its LOIKB_TRACK_REC_* bits: which of d_Q, d_Z are its result
+    double timing[4] = {0, 0, 0, 0};   // LOIKB_TRACK_F_TIMING
+  } track;
 };
 using Chunk = loikb_solver_impl::Chunk;
 
@@ -3097,6 +3115,8 @@ int loikb_destroy(loikb_solver* S)
   if (S->path.d_wp) (void)hipFree(S->path.d_wp);
   if (S->path.d_wsteps) (void)hipFree(S->path.d_wsteps);
   if (S->path.d_Q) (void)hipFree(S->path.d_Q);
+  for (void* p : {(void*)S->track.d_smp, (void*)S->track.d_errmax, (void*)S->track.d_inner, (void*)S->track.d_Q, (void*)S->track.d_Z})
+    if (p) (void)hipFree(p);
   (void)hipGetLastError();  // a failed free must not surface in the next solver's first launch check
   if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
   if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);

@@ -1,8 +1,9 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
-// (loik_amd_limits.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h) and waypoint paths
-// (loik_amd_path.h).  Included at the end of loik_host.hip, whose translation unit it belongs to: it is no header of its own.
+// (loik_amd_limits.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h), waypoint paths
+// (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
+// belongs to: it is no header of its own.
 //
-// What the three solves share is here once: pose_check_targets (the check before anything of the handle changes), pose_begin,
+// What the solves share is here once: pose_check_targets (the check before anything of the handle changes), pose_begin,
 // pose_loop (the step loop around the caller's re-target) with pose_step, and get_copy_out / get_timing_out for the getters.
 
 // ---- batched pose IK (include/loik_amd_pose.h, kernels in loik_pose.hpp) ---------------------------------------------------
@@ -197,13 +198,16 @@ static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxS
   return LOIKB_OK;
 }
 
+static int pose_no_after_step() { return LOIKB_OK; }
+
 // The step loop of a pose solve after pose_begin, and its end.  retarget(go) queues the caller's re-target of the resident q
 // (go = 0: the last one, which only judges), which leaves b_c in P.d_b and the count of running instances in P.d_count[0];
-// the loop reads that count back, stops at 0 and otherwise runs pose_step on `d_status`.  Then the base box is back in force,
-// the stream is drained and P.timing holds {steps, total since t_call, inner solves, the rest} in ms.
-template <class Retarget>
+// the loop reads that count back, stops at 0 and otherwise runs pose_step on `d_status`, then after_step() (what the caller
+// queues behind a step: loikb_track_pose its record).  Then the base box is back in force, the stream is drained and P.timing
+// holds {steps, total since t_call, inner solves, the rest} in ms.
+template <class Retarget, class AfterStep = int (&)()>
 static int pose_loop(loikb_solver* S, const loikb_pose_params* p, PoseBoxScope& box, int* d_status,
-                     std::chrono::steady_clock::time_point t_call, Retarget&& retarget)
+                     std::chrono::steady_clock::time_point t_call, Retarget&& retarget, AfterStep&& after_step = pose_no_after_step)
 {
   loikb_solver_impl::PoseState& P = S->pose;
   double solve_ms = 0.0;
@@ -217,7 +221,7 @@ static int pose_loop(loikb_solver* S, const loikb_pose_params* p, PoseBoxScope& 
     HIPCHK(hipMemcpyAsync(&running, P.d_count, sizeof(running), hipMemcpyDeviceToHost, S->stream));
     HIPCHK(hipStreamSynchronize(S->stream));
     if (running == 0) break;
-    if ((rc = pose_step(S, p, box, d_status, &solve_ms))) return rc;
+    if ((rc = pose_step(S, p, box, d_status, &solve_ms)) || (rc = after_step())) return rc;
     ++steps_run;
   }
   if ((rc = box.leave())) return rc;
@@ -856,6 +860,157 @@ int loikb_path_get(loikb_solver* S, int field, void* out, int out_flags)
     break;
   case LOIKB_PATH_F_TIMING: return get_timing_out(W.timing, sizeof(W.timing), out, out_flags & LOIKB_OUT_DEVICE);
   default: g_last_error = "path_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  return get_copy_out(S, src, bytes, out, out_flags);
+}
+
+// ---- include/loik_amd_track.h (kernels in loik_pose_track.hpp) ----------------------------------------------------------------
+int loikb_track_version(void) { return LOIKB_TRACK_VERSION; }
+
+// the [B] arrays on first use, and room for the T + 1 samples in the staging buffer.  Holds no result of an earlier call.
+static int track_alloc_inputs(loikb_solver_impl* S, int T)
+{
+  loikb_solver_impl::TrackState& K = S->track;
+  const size_t B = (size_t)S->B, nc = (size_t)std::max(S->nc, 1);
+  int rc;
+  if (!K.d_ontrack) {
+    if ((rc = alloc_dev(S, (void**)&K.d_worst, sizeof(double) * B)) || (rc = alloc_dev(S, (void**)&K.d_worst_at, sizeof(int) * B)) ||
+        (rc = alloc_dev(S, (void**)&K.d_ontrack, sizeof(int) * B))) {
+      K.d_ontrack = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+      return rc;
+    }
+  }
+  if (T > K.cap_smp) {
+    if ((rc = path_grow((void**)&K.d_smp, sizeof(double) * B * ((size_t)T + 1) * nc * 12))) return rc;
+    K.cap_smp = T;
+  }
+  return LOIKB_OK;
+}
+
+// ERRMAX, INNER and, as `record` says, Q and Z for T steps: they hold the results of the last call, so they are regrown only by a
+// call that has passed every check
+static int track_alloc_results(loikb_solver_impl* S, int T, int record)
+{
+  loikb_solver_impl::TrackState& K = S->track;
+  const size_t B = (size_t)S->B;
+  int rc;
+  if (T > K.cap_T) {
+    if ((rc = path_grow((void**)&K.d_errmax, sizeof(double) * B * ((size_t)T + 1))) || (rc = path_grow((void**)&K.d_inner, sizeof(int) * B * (size_t)T))) return rc;
+    K.cap_T = T;
+  }
+  if ((record & LOIKB_TRACK_REC_Q) && T > K.cap_TQ) {
+    if ((rc = path_grow((void**)&K.d_Q, sizeof(double) * B * ((size_t)T + 1) * S->nq))) return rc;
+    K.cap_TQ = T;
+  }
+  if ((record & LOIKB_TRACK_REC_Z) && T > K.cap_TZ) {
+    if ((rc = path_grow((void**)&K.d_Z, sizeof(double) * B * (size_t)T * S->nb))) return rc;
+    K.cap_TZ = T;
+  }
+  return LOIKB_OK;
+}
+
+int loikb_track_pose(loikb_solver* S, const double* q, const double* samples, int in_flags, const loikb_track_params* p)
+{
+  if (!S || !samples || !p) return LOIKB_ERR_ARG;
+  if (p->n_steps < 1 || p->feedforward < LOIKB_TRACK_FF_NONE || p->feedforward > LOIKB_TRACK_FF_DIFFERENCE || p->record < 0 ||
+      p->record > (LOIKB_TRACK_REC_Q | LOIKB_TRACK_REC_Z) || p->flags != 0) {
+    g_last_error = "track_pose: need n_steps >= 1, feedforward 0 or 1, record 0..3, flags 0";
+    return LOIKB_ERR_ARG;
+  }
+  // the loop's parameters as a pose solve has them: T steps at most, and tol_track where the tolerance is checked
+  const loikb_pose_params pose{p->dt, p->gain, p->tol_track, p->n_steps, 0};
+  if (int pre = pose_preconditions(S, &pose, !q)) return pre;
+  const auto t_call = std::chrono::steady_clock::now();
+  HIPCHK(hipSetDevice(S->device));
+  const int B = S->B, nc = S->nc_active, T = p->n_steps, Tn = T + 1, record = p->record, ff = p->feedforward;
+  const bool dev = in_flags & LOIKB_IN_DEVICE, smp_shared = in_flags & LOIKB_POSE_TARGET_SHARED;
+  if ((size_t)(smp_shared ? 1 : B) * Tn * nc > (size_t)0x7fffffff || (size_t)B * Tn * std::max(S->nq, S->nb) > (size_t)0x7fffffff) {
+    g_last_error = "track_pose: too many samples";
+    return LOIKB_ERR_ARG;
+  }
+  int rc;
+  if ((rc = pose_alloc(S)) || (rc = track_alloc_inputs(S, T))) return rc;
+  loikb_solver_impl::PoseState& P = S->pose;
+  loikb_solver_impl::TrackState& K = S->track;
+  // the samples, all of them, checked before anything of the handle changes
+  if ((rc = pose_check_targets(S, K.d_smp, samples, (size_t)(smp_shared ? 1 : B) * Tn * nc, dev, P.d_count,
+                               "track_pose: a sample rotation is not orthonormal with determinant 1 (tolerance 1e-9)")))
+    return rc;
+  if ((rc = track_alloc_results(S, T, record))) return rc;
+  ++S->inputs_epoch;
+  if ((rc = pose_begin(S, q, dev))) return rc;
+  K.T = T;
+  K.record = record;
+  double* Q = (record & LOIKB_TRACK_REC_Q) ? K.d_Q : nullptr;
+  double* Z = (record & LOIKB_TRACK_REC_Z) ? K.d_Z : nullptr;
+  const size_t nE = (size_t)B * Tn, nI = (size_t)B * T, nQ = Q ? nE * S->nq : 0, nZ = Z ? nI * S->nb : 0;
+  hipLaunchKernelGGL(k_track_setup, grid1(std::max(std::max(nE, nQ), nZ)), dim3(256), 0, S->stream, B, nE, nI, nQ, nZ, P.d_status, P.d_steps,
+                     K.d_ontrack, K.d_errmax, K.d_inner, Q, Z);
+  HIPCHK(hipGetLastError());
+  PoseBoxScope box{S};
+  if (P.have_limits) {
+    if ((rc = box.enter())) return rc;
+    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
+  }
+  const double k = p->gain / p->dt, inv_dt = 1.0 / p->dt;
+  const PoseTask* tasks = P.have_tasks ? (const PoseTask*)P.d_tasks : nullptr;
+  const double* A_sh = S->a_shared ? (const double*)P.d_A : nullptr;
+  int ks = -1;   // the step whose solve ran last: record(ks) stores Q[ks + 1] (before the loop: the starting q), Z[ks], INNER[ks]
+  auto record_step = [&]() -> int {
+    with_real(S, [&](auto t) {
+      hipLaunchKernelGGL(k_track_record<decltype(t)>, grid1((size_t)B * std::max(S->nq, S->nb)), dim3(256), 0, S->stream, (const double*)S->d_q,
+                         S->nq, S->nb, B, Tn, ks, (const int*)P.d_status, (const char*)S->home.tiles, S->L,
+                         box.active ? (const int*)P.d_lflags : nullptr, Q, Z, K.d_inner);
+    });
+    HIPCHK(hipGetLastError());
+    return LOIKB_OK;
+  };
+  if ((rc = record_step())) return rc;
+  rc = pose_loop(S, &pose, box, P.d_status, t_call,
+                 [&](int go) -> int {   // sample ks + 1: the loop re-targets once per step and once more to judge
+                   with_real(S, [&](auto t) {
+                     hipLaunchKernelGGL(k_track_retarget<decltype(t)>, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
+                                        S->d_idx_q, (const int*)P.d_clink, nc, tasks, (const double*)K.d_smp, (int)smp_shared, Tn, ks + 1, ff, A_sh,
+                                        (const char*)S->home.tiles, S->L, B, k, inv_dt, p->tol_track, go, P.d_b, P.d_err, P.d_status, P.d_steps,
+                                        K.d_errmax, K.d_ontrack, P.d_count);
+                   });
+                   HIPCHK(hipGetLastError());
+                   return LOIKB_OK;
+                 },
+                 [&]() -> int { ++ks; return record_step(); });
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_track_finish, grid1(B), dim3(256), 0, S->stream, (const double*)K.d_errmax, B, Tn, K.d_worst, K.d_worst_at);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(S->stream));
+  memcpy(K.timing, P.timing, sizeof(K.timing));
+  return LOIKB_OK;
+}
+
+int loikb_track_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  const loikb_solver_impl::TrackState& K = S->track;
+  if (K.T == 0) { g_last_error = "track_get before track_pose"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const size_t B = (size_t)S->B, T = (size_t)K.T;
+  switch (field) {
+  case LOIKB_TRACK_F_Q:
+    if (!(K.record & LOIKB_TRACK_REC_Q)) { g_last_error = "track_get: the last track_pose ran without LOIKB_TRACK_REC_Q"; return LOIKB_ERR_STATE; }
+    src = K.d_Q; bytes = sizeof(double) * B * (T + 1) * S->nq;
+    break;
+  case LOIKB_TRACK_F_Z:
+    if (!(K.record & LOIKB_TRACK_REC_Z)) { g_last_error = "track_get: the last track_pose ran without LOIKB_TRACK_REC_Z"; return LOIKB_ERR_STATE; }
+    src = K.d_Z; bytes = sizeof(double) * B * T * S->nb;
+    break;
+  case LOIKB_TRACK_F_ERRMAX: src = K.d_errmax; bytes = sizeof(double) * B * (T + 1); break;
+  case LOIKB_TRACK_F_INNER: src = K.d_inner; bytes = sizeof(int) * B * T; break;
+  case LOIKB_TRACK_F_ONTRACK: src = K.d_ontrack; bytes = sizeof(int) * B; break;
+  case LOIKB_TRACK_F_WORST: src = K.d_worst; bytes = sizeof(double) * B; break;
+  case LOIKB_TRACK_F_WORST_AT: src = K.d_worst_at; bytes = sizeof(int) * B; break;
+  case LOIKB_TRACK_F_TIMING: return get_timing_out(K.timing, sizeof(K.timing), out, out_flags & LOIKB_OUT_DEVICE);
+  default: g_last_error = "track_get: unknown field"; return LOIKB_ERR_ARG;
   }
   return get_copy_out(S, src, bytes, out, out_flags);
 }

@@ -6,7 +6,8 @@
 //   k_pose_retarget   : e_c = log6(oMi_c^-1 oMdes_c) per active constraint, b_c = A_c (gain / dt) e_c, the reached / stopped
 //                       bookkeeping and the count of instances still running, one thread per instance.  Its rule -- the error, the
 //                       err store, the two control laws, the tail -- is the `retarget rule` section below, the one definition
-//                       that k_pose_retarget_tasks (loik_pose_tasks.hpp) and k_path_retarget (loik_pose_path.hpp) are written over too
+//                       that k_pose_retarget_tasks (loik_pose_tasks.hpp), k_path_retarget (loik_pose_path.hpp) and
+//                       k_track_retarget (loik_pose_track.hpp) are written over too
 //   k_pose_integrate  : q <- q (+) dt z for the running instances only (advance_q_instance: the arithmetic of loikb_integrate)
 // and, on a handle with joint position limits (include/loik_amd_limits.h), around the same solve:
 //   k_pose_limit_box  : the step's velocity box [lo, hi] = the base box cut to the velocities that keep q (+) dt z in range, into
@@ -174,9 +175,10 @@ __global__ void k_pose_check_targets(const double* __restrict__ tgt, int n, doub
   if (!ok) atomicAdd(bad, 1u);
 }
 
-// ---- the retarget rule: what one re-target does for one instance, stated once.  k_pose_retarget, k_pose_retarget_tasks and
-// k_path_retarget are loops over these functions; a new control law goes here, beside pose_b_joint and pose_b_task.  The library
-// is built with -ffp-contract=on, which contracts within a statement only: a statement split or merged here changes bits.
+// ---- the retarget rule: what one re-target does for one instance, stated once.  k_pose_retarget, k_pose_retarget_tasks,
+// k_path_retarget and k_track_retarget are loops over these functions; a new control law goes here, beside pose_b_joint,
+// pose_b_task and pose_b_track.  The library is built with -ffp-contract=on, which contracts within a statement only: a
+// statement split or merged here changes bits.
 
 // task kinds (loik_amd_tasks.h)
 enum : int { TASK_POSE = 0, TASK_POSITION = 1, TASK_ORIENTATION = 2 };
@@ -197,10 +199,18 @@ __device__ __forceinline__ void frame_compose(const double* R, const double* t, 
   }
 }
 
+// what pose_error forms on its way to e, for a law that needs more than e (the feed-forward of loik_pose_track.hpp):
+// (Re, pe) = oMf^-1 oMdes, the desired frame seen from the actual one, and R = the world rotation of the task (or joint) frame
+struct PoseErrFrame {
+  double Re[9], pe[3], R[9];
+};
+
 // e of the constraint on `link` against the desired placement D [12], in the task frame oMf = oMi iMf and by the task's kind;
-// tk = nullptr: the joint frame, the full pose (e = log6(oMi^-1 oMdes))
-__device__ __forceinline__ void pose_error(const double* q_row, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q, int link,
-                                           const PoseTask* tk, const double* D, double* e)
+// tk = nullptr: the joint frame, the full pose (e = log6(oMi^-1 oMdes)).  FRAME: (Re, pe) and R go to `fr` as well; without it the
+// function is, instruction for instruction, what it was before a caller asked for them
+template <bool FRAME>
+__device__ __forceinline__ void pose_error_impl(const double* q_row, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q, int link,
+                                                const PoseTask* tk, const double* D, double* e, PoseErrFrame* fr)
 {
   double Ri[9], ti[3], Rw[9], tw[3], Re[9], pe[3];
   link_placement(q_row, jd, idx_q, link, Ri, ti);
@@ -213,6 +223,10 @@ __device__ __forceinline__ void pose_error(const double* q_row, const JointDesc*
     for (int cc = 0; cc < 3; ++cc) Re[3 * r + cc] = R[r] * D[cc] + R[3 + r] * D[3 + cc] + R[6 + r] * D[6 + cc];
     pe[r] = R[r] * (D[9] - t[0]) + R[3 + r] * (D[10] - t[1]) + R[6 + r] * (D[11] - t[2]);
   }
+  if constexpr (FRAME) {
+    for (int k = 0; k < 9; ++k) { fr->Re[k] = Re[k]; fr->R[k] = R[k]; }
+    for (int k = 0; k < 3; ++k) fr->pe[k] = pe[k];
+  }
   const int kind = tk ? tk->kind : TASK_POSE;
   if (kind == TASK_POSITION) {
     for (int r = 0; r < 3; ++r) { e[r] = pe[r]; e[3 + r] = 0.0; }
@@ -222,6 +236,12 @@ __device__ __forceinline__ void pose_error(const double* q_row, const JointDesc*
   } else {
     pose_log6(Re, pe, e);
   }
+}
+
+__device__ __forceinline__ void pose_error(const double* q_row, const JointDesc* __restrict__ jd, const int* __restrict__ idx_q, int link,
+                                           const PoseTask* tk, const double* D, double* e)
+{
+  pose_error_impl<false>(q_row, jd, idx_q, link, tk, D, e, nullptr);
 }
 
 // e into its err row eo, folded into the instance's `finite` and `emax`
@@ -256,6 +276,23 @@ __device__ __forceinline__ void pose_b_joint(const double* e, double k, const do
 __device__ __forceinline__ void pose_b_task(const double* e, double k, double* __restrict__ bo)
 {
   for (int r = 0; r < 6; ++r) bo[r] = k * e[r];
+}
+
+// the tracking law (loik_amd_track.h) bo = A_c (k e + f), with `task` bo = k e + f: f [6] = the feed-forward twist in the frame
+// of e, masked by the task's kind as e is.  It is the law above applied to u = k e + f with gain 1 (1.0 * u is u); f = nullptr is
+// the law above on (e, k) itself, the same statement on the same numbers: no feed-forward keeps the bits of the other loops
+template <typename T>
+__device__ __forceinline__ void pose_b_track(const double* e, double k, const double* f, bool task, const double* __restrict__ A_sh,
+                                             const char* tiles, const Layout& L, int b, int c, double* __restrict__ bo)
+{
+  double u[6];
+  if (f) {
+    for (int r = 0; r < 6; ++r) u[r] = k * e[r] + f[r];
+    e = u;
+    k = 1.0;
+  }
+  if (task) pose_b_task(e, k, bo);
+  else pose_b_joint<T>(e, k, A_sh, tiles, L, b, c, bo);
 }
 
 // the tail of a re-target with `step` set: an instance that runs counts the step and itself, one that does not gets b_c = 0

@@ -1,0 +1,26 @@
+"""The tracking layer of the C++ mirror (include/loik_amd/loik.hpp: TrackPose, TrackResult) compiles against
+include/loik_amd_track.h and links (CPU); tests/cpp/test_track.cpp runs on the GPU."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_cpp_track_mirror_compiles():
+    import loik_amd
+    loik_amd.lib()
+    src = os.path.join(ROOT, "tests", "cpp", "test_track.cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", "test_track")
+    libdir = os.path.join(ROOT, "loik_amd", "lib")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), src, "-o", exe,
+                           "-L", libdir, "-lloik_amd", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+    assert os.path.exists(exe)
+
+
+@pytest.mark.gpu
+def test_cpp_track_mirror_runs():
+    test_cpp_track_mirror_compiles()
+    out = subprocess.run([os.path.join(ROOT, "tests", "cpp", "test_track")], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "all track checks passed" in out.stdout, out.stdout + out.stderr
