@@ -1661,11 +1661,15 @@ __device__ __forceinline__ void advance_q_instance(double* __restrict__ q_row, c
       for (int k = 0; k < 4; ++k) qs[k] = qo[k];
     } else if (rot == ROT_PLANAR) {
       // SpecialEuclideanOperationTpl<2>::integrate: (x, y, cos, sin) * exp(vx, vy, w), first-order re-normalised (cos, sin)
+      // sin(w) / w and (1 - cos(w)) / w = sin(w / 2) (sin(w / 2) / (w / 2)): the quotient (1 - cos(w)) / w of the reference loses
+      // (w / 2) |v| to the rounding of cos(w) for small w (5e-10 |v| at w = 1e-9); below |w| = 1e-4 the two quotients are their
+      // series, whose next terms (w^4 / 120, w^5 / 720) are under 1e-18
       const double c0 = qs[2], s0 = qs[3], w = v[2];
-      double sw, cw, tx, ty;
+      double sw, cw, sh, ch, a, bq;
       sincos(w, &sw, &cw);
-      if (fabs(w) > 1e-14) { tx = (sw * v[0] - (1.0 - cw) * v[1]) / w; ty = ((1.0 - cw) * v[0] + sw * v[1]) / w; }
-      else { tx = v[0]; ty = v[1]; }
+      if (fabs(w) > 1e-4) { sincos(0.5 * w, &sh, &ch); a = sw / w; bq = sh * (sh / (0.5 * w)); }
+      else { a = 1.0 - w * w / 6.0; bq = 0.5 * w * (1.0 - w * w / 12.0); }
+      const double tx = a * v[0] - bq * v[1], ty = bq * v[0] + a * v[1];
       qs[0] += c0 * tx - s0 * ty;
       qs[1] += s0 * tx + c0 * ty;
       double c1 = c0 * cw - s0 * sw, s1 = s0 * cw + c0 * sw;

@@ -223,7 +223,9 @@ def integrate(model, q, v):
             vx, vy, w = v[iv:iv + 3]
             c0, s0 = q[iq + 2], q[iq + 3]
             sw, cw = np.sin(w), np.cos(w)
-            tx, ty = ((sw * vx - (1 - cw) * vy) / w, ((1 - cw) * vx + sw * vy) / w) if abs(w) > 1e-14 else (vx, vy)
+            # sin(w) / w and (1 - cos(w)) / w = sin(w / 2) sinc(w / 2): no quotient of rounded differences, exact at w = 0
+            a, b = np.sinc(w / np.pi), np.sin(0.5 * w) * np.sinc(0.5 * w / np.pi)
+            tx, ty = a * vx - b * vy, b * vx + a * vy
             out[iq], out[iq + 1] = q[iq] + c0 * tx - s0 * ty, q[iq + 1] + s0 * tx + c0 * ty
             c1, s1 = c0 * cw - s0 * sw, s0 * cw + c0 * sw
             n = 0.5 * (3 - (c1 * c1 + s1 * s1))

@@ -245,24 +245,54 @@ def _np_quat_mul(a, b):
                      a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]])
 
 
+def _sinc(x):
+    """sin(x) / x, 1 at x = 0"""
+    return float(np.sinc(x / np.pi))
+
+
+def _np_exp_quat(w):
+    """the quaternion (x, y, z, w) of exp([w]x): (sin(th / 2) / th) w, cos(th / 2) -- sin(th / 2) / th as half a sinc, so that it
+    is 1 / 2 at th = 0 and wherever th * th underflows"""
+    th = float(np.linalg.norm(w))
+    return np.r_[0.5 * _sinc(0.5 * th) * np.asarray(w, dtype=float), np.cos(0.5 * th)]
+
+
+def _np_se3_coefficients(th):
+    """(a, b) of exp6's translation p = v + a (w x v) + b (w x (w x v)): a = (1 - cos th) / th^2 written as sinc(th / 2)^2 / 2 (no
+    cancellation at any th), b = (th - sin th) / th^3 by its Maclaurin series sum_k (-1)^k th^(2k) / (2k + 3)! below th = 1 / 2
+    (eight terms: the next one is under 1e-19) and as it stands above, where the difference keeps all but five bits"""
+    a = 0.5 * _sinc(0.5 * th) ** 2
+    if th < 0.5:
+        t2, b, term = th * th, 0.0, 1.0 / 6.0
+        for k in range(8):
+            b += term
+            term *= -t2 / ((2 * k + 4) * (2 * k + 5))
+        return a, b
+    return a, (th - np.sin(th)) / th ** 3
+
+
 def _np_integrate(model, q, v):
-    """pinocchio::integrate for the supported joints, written with scipy's rotation exponential"""
+    """pinocchio::integrate for the supported joints: the exact exponentials of SE(3) (free-flyer) and SO(3) (spherical), finite
+    and accurate at every angle, zero included.  The free-flyer's quaternion stays in the hemisphere of the one it came from
+    (SpecialEuclideanOperationTpl<3>::integrate_impl), the spherical joint's is the plain product
+    (SpecialOrthogonalOperationTpl<3>::integrate_impl).  A quaternion that comes in off the unit sphere (one rounded to float32,
+    say) stands for the rotation of its direction, and the result is returned on the sphere"""
     from scipy.spatial.transform import Rotation
     out = q.copy()
     for i in range(1, model.njoints):
         t, iq, iv = int(model.jtype[i]), int(model.idx_q[i]), int(model.idx_v[i])
         if t == J_FREEFLYER:
-            R0 = Rotation.from_quat(q[iq + 3:iq + 7])
+            q0 = q[iq + 3:iq + 7]
             w, vl = v[iv + 3:iv + 6], v[iv:iv + 3]
-            th = np.linalg.norm(w)
-            K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-            V = np.eye(3) + ((1 - np.cos(th)) / th ** 2) * K + ((th - np.sin(th)) / th ** 3) * K @ K
-            out[iq:iq + 3] = q[iq:iq + 3] + R0.apply(V @ vl)
-            qn = (R0 * Rotation.from_rotvec(w)).as_quat()
-            out[iq + 3:iq + 7] = qn if qn @ q[iq + 3:iq + 7] >= 0 else -qn
+            a, b = _np_se3_coefficients(float(np.linalg.norm(w)))
+            wxv = np.cross(w, vl)
+            out[iq:iq + 3] = q[iq:iq + 3] + Rotation.from_quat(q0).apply(vl + a * wxv + b * np.cross(w, wxv))
+            qn = _np_quat_mul(q0, _np_exp_quat(w))
+            qn /= np.linalg.norm(qn)
+            out[iq + 3:iq + 7] = qn if qn @ q0 >= 0 else -qn
         elif t == J_SPHERICAL:
-            qn = (Rotation.from_quat(q[iq:iq + 4]) * Rotation.from_rotvec(v[iv:iv + 3])).as_quat()
-            out[iq:iq + 4] = qn if qn @ q[iq:iq + 4] >= 0 else -qn
+            qn = _np_quat_mul(q[iq:iq + 4], _np_exp_quat(v[iv:iv + 3]))
+            out[iq:iq + 4] = qn / np.linalg.norm(qn)
         elif t == J_TRANSLATION:
             out[iq:iq + 3] = q[iq:iq + 3] + v[iv:iv + 3]
         else:

@@ -158,18 +158,29 @@ def _check_selection(s, out, q0g, K, pick, weights, model, what):
 
 
 # (robot, G, K, tasks, max_steps: chosen on the CPU oracle so that every goal has reached seeds and seeds that are not, several of each)
-LOOP_CASES = [("talos32", 3, 70, True, 3), ("panda7", 6, 16, False, 12)]
+# multidof: _robot("multidof", 2) -- nq = 31, nv = 26, both links constrained; the seeds cost through the DoF-to-coordinate table.
+# Its sixth entry is the seed of the targets: at that seed and max_steps = 6 the oracle has 28, 25 and 15 of the 64 seeds of the three
+# goals reached
+LOOP_CASES = [("talos32", 3, 70, True, 3), ("panda7", 6, 16, False, 12), ("multidof", 3, 64, False, 6, 75)]
+
+
+def _multidof_targets(model, lo, hi, valid, G, seed, rng):
+    """FK of valid rows (unit quaternion and (cos, sin) pairs) whose sampled coordinates are redrawn inside their ranges"""
+    q_t = _goal_rows("multidof", model, lo, hi, valid, G, seed=seed)
+    j, c = M.sampled_dofs(model, lo, hi)
+    q_t[:, c] = rng.uniform(lo[j], hi[j], size=(G, j.size))
+    return q_t
 
 
 @pytest.mark.parametrize("case", LOOP_CASES, ids=lambda c: "%s-G%d-K%d%s" % (c[0], c[1], c[2], "-tasks" if c[3] else ""))
 def test_one_round_matches_solve_pose_on_the_numpy_seeds(case):
-    name, G, K, tasks, max_steps = case
-    nc = 2 if tasks else 1
-    model, links, lo, hi, _ = _robot(name, nc)
+    name, G, K, tasks, max_steps = case[:5]
+    nc = 2 if tasks or name == "multidof" else 1
+    model, links, lo, hi, valid = _robot(name, nc)
     B = G * K
     rng = np.random.default_rng(70 + G)
-    q0g = _goal_rows(name, model, lo, hi, None, G, seed=71)
-    q_t = rng.uniform(lo, hi, size=(G, model.nq))
+    q0g = _goal_rows(name, model, lo, hi, valid, G, seed=71)
+    q_t = _multidof_targets(model, lo, hi, valid, G, case[5], rng) if name == "multidof" else rng.uniform(lo, hi, size=(G, model.nq))
     frames = T.random_frames(rng, nc) if tasks else None
     tg = T.frame_fk12(model, q_t, links, frames) if tasks else P.fk12(model, q_t, links)
     q_init = np.repeat(q0g, K, axis=0)
@@ -192,6 +203,20 @@ def test_one_round_matches_solve_pose_on_the_numpy_seeds(case):
     out = a.SolvePoseMultiStart(tg, K, seed=SEED, q0=q0g, pick="first", **kw)
     o = _check_selection(a, out, q0g, K, M.PICK_FIRST, weights, model, (case, "first"))
     assert np.array_equal(out["winner"], o["winner"]) and not out["cost"][o["goal_status"] == M.GOAL_REACHED].any()
+    if name == "multidof":
+        # every goal has several seeds that reach and several that do not; out["q"] has nq columns; and with no step taken the
+        # winners' free-flyer blocks (never sampled, so moved by the solve alone) are the goals' q0
+        reached = ref["reached"].reshape(G, K).sum(axis=1)
+        assert np.all(reached >= 3) and np.all(K - reached >= 3), reached
+        assert model.nq > model.nv and out["q"].shape == (G, model.nq) and a.get("q").shape == (B, model.nq)
+        iq = int(model.idx_q[[int(t) for t in model.jtype].index(9)])
+        moved = np.abs(out["q"][:, iq:iq + 7] - q0g[:, iq:iq + 7]).max(axis=1)
+        assert np.all((moved > 0) == (steps[out["winner"]] > 0)), (moved, steps[out["winner"]])
+        for pick, rule in (("nearest", M.PICK_NEAREST), ("first", M.PICK_FIRST)):
+            out0 = a.SolvePoseMultiStart(tg, K, seed=SEED, q0=q0g, pick=pick, tol_pose=TOL, max_steps=0)
+            _check_selection(a, out0, q0g, K, rule, weights, model, (case, pick, "no step"))
+            assert out0["q"].shape == (G, model.nq) and np.array_equal(out0["q"][:, iq:iq + 7], q0g[:, iq:iq + 7])
+            assert np.array_equal(a.get("q"), M.sample(model, q0g, K, SEED, 0, lo, hi))
     a.close(); b.close()
 
 

@@ -70,7 +70,11 @@ def _wp_of(wp, idx):
 @pytest.mark.parametrize("name,nc,B", [("talos32", 2, 193), ("panda7", 1, 64), ("talos32", 1, 1)])
 def test_one_waypoint_is_solve_pose_bit_for_bit(name, nc, B, form):
     model = loik_amd.builtin_model(name)
-    links = _links(model, nc)
+    _check_one_waypoint_is_solve_pose(model, _links(model, nc), B, form)
+
+
+def _check_one_waypoint_is_solve_pose(model, links, B, form):
+    nc = len(links)
     rng = np.random.default_rng(3000 + B)
     frames = PT.random_frames(rng, nc) if form == "tasks" else None
     q0, wp, q_t = _path_workload(model, links, B, 1, seed=3001 + B + nc, frames=frames)

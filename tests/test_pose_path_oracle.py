@@ -8,8 +8,8 @@ import pytest
 
 import loik_amd
 
-from test_pose_ik import PRM, _links
-from test_pose_parity import _box, _seeds
+from test_pose_ik import PRM, _fk_models, _links
+from test_pose_parity import _box, _leaf_and_multidof, _seeds
 import pose_numpy as P
 import pose_path_numpy as PP
 
@@ -157,3 +157,33 @@ def test_one_waypoint_variants_are_the_limits_and_tasks_oracles(variant):
     for key in want:
         assert np.array_equal(got[key], want[key]), (variant, key)
     assert want["steps"].any()
+
+
+def test_single_instance_path_on_a_free_flyer_tree_is_chained_lockstep_pose_loops():
+    """nq != nv: a free-flyer root with ZYX, planar and (cos, sin) joints.  One instance never idles, so a path is the chain of
+    lockstep_pose_loop calls, each from where the last one ended.  A chained call starts a fresh solver: without warm starts the
+    inner solves are the same arithmetic and the two are np.array_equal; with them (PRM) the steps per waypoint are equal and q
+    differs by what two inner solves stopped at tol_abs = 1e-6 from different starts differ by, carried over at most 16 steps"""
+    from test_pose_path import _path_workload
+    model = _fk_models()[3]
+    assert model.nq > model.nv
+    links = _leaf_and_multidof(model)
+    T = 4
+    q0, wp, _ = _path_workload(model, links, 1, T, seed=1403, spread=(0.1, 0.15))
+    lb, ub = _box(model)
+    A = np.tile(np.eye(6), (2, 1, 1))
+    for warm in (False, True):
+        prm = dict(PRM, warm_start=warm)
+        o = PP.lockstep_path_loop(model, prm, q0, np.eye(6), np.zeros(6), links, A, lb, ub, wp, 1.0, 0.8, 1e-4, 100)
+        assert o["cursor"][0] == T and o["path_status"][0] == PP.PATH_COMPLETE and o["wsteps"].sum() == o["steps"][0] > T
+        assert o["q_path"].shape == (1, T, model.nq) and np.all(np.isfinite(o["q_path"]))
+        q = q0
+        for t in range(T):
+            leg = P.lockstep_pose_loop(model, prm, q, np.eye(6), np.zeros(6), links, A, lb, ub, wp[:, t], 1.0, 0.8, 1e-4, 100)
+            q = leg["q"]
+            assert leg["reached"][0] and leg["steps"][0] == o["wsteps"][0, t], (warm, t, leg["steps"], o["wsteps"])
+            if warm:
+                assert np.max(np.abs(q - o["q_path"][:, t])) < 1e-5, (t, np.max(np.abs(q - o["q_path"][:, t])))
+            else:
+                assert np.array_equal(q, o["q_path"][:, t]), (t, np.max(np.abs(q - o["q_path"][:, t])))
+        assert np.array_equal(q, o["q"]) or warm

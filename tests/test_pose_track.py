@@ -79,7 +79,11 @@ def _download(dev, shape, dtype):
 @pytest.mark.parametrize("name,nc,B", [("talos32", 2, 193), ("panda7", 1, 64), ("talos32", 1, 1)])
 def test_no_feedforward_on_constant_samples_is_solve_pose_bit_for_bit(name, nc, B, form):
     model = loik_amd.builtin_model(name)
-    links = _links(model, nc)
+    _check_no_feedforward_is_solve_pose(model, _links(model, nc), B, form)
+
+
+def _check_no_feedforward_is_solve_pose(model, links, B, form):
+    nc = len(links)
     T = 4
     rng = np.random.default_rng(4000 + B)
     frames = PT.random_frames(rng, nc) if form == "tasks" else None
@@ -223,7 +227,12 @@ def test_f32_handle_step_and_fp64_error():
 @pytest.mark.parametrize("name,nc,B", [("talos32", 2, 193), ("panda7", 1, 64)])
 def test_trajectories_are_consistent_and_feedforward_tracks_better(name, nc, B):
     model = loik_amd.builtin_model(name)
-    links = _links(model, nc)
+    _check_trajectories_and_feedforward(model, _links(model, nc), B)
+
+
+def _check_trajectories_and_feedforward(model, links, B):
+    """returns the two runs, {"none": out, "difference": out}"""
+    name, nc = model.name, len(links)
     T, dt, tol = 5, 0.5, 1e-4
     q0, smp, _ = _track_workload(model, links, B, T, seed=4301 + B, on_path=True)
     A = np.tile(np.eye(6), (nc, 1, 1))
@@ -249,27 +258,32 @@ def test_trajectories_are_consistent_and_feedforward_tracks_better(name, nc, B):
         name, res["none"]["worst"].min(), res["none"]["worst"].max(), res["difference"]["worst"].min(), res["difference"]["worst"].max()))
     assert np.all(res["difference"]["worst"] < res["none"]["worst"])
     assert np.all(res["difference"]["ontrack"] >= res["none"]["ontrack"])
+    return res
 
 
 # ---- 4. stops and errors --------------------------------------------------------------------------------------------------------------
 def test_nan_seed_stops_alone():
     model = loik_amd.builtin_model("panda7")
-    links = _links(model, 2)
-    B, T, bad = 64, 4, 37
+    _check_nan_seed_stops_alone(model, _links(model, 2), 64, 37, 2)
+
+
+def _check_nan_seed_stops_alone(model, links, B, bad, coord):
+    """the seed of instance `bad` with a NaN in coordinate `coord`"""
+    T = 4
     q0, smp, _ = _track_workload(model, links, B, T, seed=4401)
-    A = np.tile(np.eye(6), (2, 1, 1))
+    A = np.tile(np.eye(6), (len(links), 1, 1))
     res = []
     for with_nan in (False, True):
         qs = q0.copy()
         if with_nan:
-            qs[bad, 2] = np.nan
+            qs[bad, coord] = np.nan
         s = _handle(model, B, links, qs, A, PRM)
         res.append(s.TrackPose(smp, dt=0.5, gain=0.8))
         s.close()
     ref, out = res
     assert out["status"][bad] == capi.POSE_ST_STOPPED and out["steps"][bad] == 0 and out["ontrack"][bad] == 0
     want0 = q0[bad].copy()
-    want0[2] = np.nan
+    want0[coord] = np.nan
     assert np.array_equal(out["q_traj"][bad, 0], want0, equal_nan=True) and np.all(np.isnan(out["q_traj"][bad, 1:]))
     assert np.all(np.isnan(out["z_traj"][bad])) and np.all(np.isnan(out["errmax"][bad])) and not out["inner"][bad].any()
     assert np.isnan(out["worst"][bad]) and out["worst_at"][bad] == -1

@@ -8,8 +8,8 @@ import pytest
 
 import loik_amd
 
-from test_pose_ik import PRM, _links
-from test_pose_parity import _box, _seeds
+from test_pose_ik import PRM, _fk_models, _links
+from test_pose_parity import _box, _leaf_and_multidof, _seeds
 import pose_numpy as P
 import pose_tasks_numpy as PT
 import pose_track_numpy as TR
@@ -35,7 +35,18 @@ def _on_path_run(name, kind, gain, ff):
 @pytest.mark.parametrize("name,nc", [("talos32", 2), ("panda7", 1)])
 def test_no_feedforward_on_constant_samples_is_the_plain_lockstep_oracle(name, nc):
     model = loik_amd.builtin_model(name)
-    links = _links(model, nc)
+    _check_no_feedforward_is_the_plain_lockstep_oracle(model, _links(model, nc))
+
+
+def test_no_feedforward_on_constant_samples_is_the_plain_lockstep_oracle_on_a_free_flyer_tree():
+    """nq != nv: a free-flyer root with a spherical and a translation joint"""
+    model = _fk_models()[2]
+    assert model.nq > model.nv
+    _check_no_feedforward_is_the_plain_lockstep_oracle(model, _leaf_and_multidof(model))
+
+
+def _check_no_feedforward_is_the_plain_lockstep_oracle(model, links):
+    name, nc = model.name, len(links)
     B, T = 8, 4
     q0, tg = _seeds(model, B, links, seed=2000 + nc)
     lb, ub = _box(model)
