@@ -22,6 +22,7 @@
 #include "../loik_amd_multistart.h"
 #include "../loik_amd_path.h"
 #include "../loik_amd_track.h"
+#include "../loik_amd_accel.h"
 
 #include <array>
 #include <map>
@@ -404,6 +405,25 @@ public:
     check(loikb_pose_get_limit_flags(h_, f.data(), 0));
     return f;
   }
+  // ---- joint acceleration limits of the pose loops, braking-aware position limits (include/loik_amd_accel.h)
+  // a_max: [nv], entries > 0, +inf = no limit on that DoF; honoured by every later SolvePose / SolvePosePath / TrackPose.
+  // clearJointAccelLimits(): as if never set.
+  void setJointAccelLimits(const DVec& a_max) { check(loikb_set_joint_accel_limits(h_, a_max.data(), (int)a_max.size())); }
+  void clearJointAccelLimits() { check(loikb_set_joint_accel_limits(h_, nullptr, 0)); }
+  // v0: [batch][nv], the velocity the next pose loop starts from (then forgotten); empty = rest
+  void setStartVelocity(const DVec& v0)
+  {
+    if (!v0.empty() && v0.size() != (std::size_t)batch_ * model_.nv) throw std::runtime_error("loik_amd: v0 needs batch * nv entries");
+    check(loikb_accel_set_start_velocity(h_, v0.empty() ? nullptr : v0.data(), 0));
+  }
+  // [batch][nv] the velocity applied in the last step that moved each instance of the last pose loop with acceleration limits (0: never
+  // moved, reached or stopped; throws when it ran without)
+  DVec AppliedVelocity() const
+  {
+    DVec v((std::size_t)batch_ * model_.nv);
+    check(loikb_accel_get_velocity(h_, v.data(), 0));
+    return v;
+  }
   // ---- tool frames and position-only / orientation-only tasks of the pose loop (include/loik_amd_tasks.h)
   // kinds: LOIKB_TASK_POSE / _POSITION / _ORIENTATION, one per active constraint (active_task_constraint_ids order); frames: iMf of
   // the task frame on the constrained link, one per kind, or empty = the joint frame.  A formulation edit: every active constraint's
@@ -545,7 +565,7 @@ public:
   // solve per step, every instance in step with the clock
   struct TrackResult {
     std::vector<int> steps, status, ontrack, worst_at;  // [batch]; status: LOIKB_POSE_ST_* bits (REACHED is never set)
-    std::vector<int> inner;                             // [batch][T]: 1 = not converged, 2 = primal infeasible, 4 = a joint limit cut the box
+    std::vector<int> inner;                             // [batch][T]: 1 = not converged, 2 = primal infeasible, 4 = a joint limit cut the box, 8 = an acceleration limit did
     DVec err;                                           // [batch][nc][6]: against X_T
     DVec errmax, worst;                                 // [batch][T+1], [batch]
     DVec q_traj, z_traj;                                // [batch][T+1][nq], [batch][T][nv], NaN rows after a stop; empty when not recorded

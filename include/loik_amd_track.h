@@ -30,8 +30,9 @@
  *   6. the step of loikb_solve_pose, unchanged: the limit box if the handle has joint position limits (loik_amd_limits.h), the b
  *      edits, the tailored solve on the resident q, q <- q (+) dt z, the clamp.  With LOIKB_TRACK_REC_Z, Z[b][k] = the solve's z;
  *      with LOIKB_TRACK_REC_Q, Q[b][k + 1] = the integrated, clamped q (Q[b][0] = the starting q).  INNER[b][k] gets bit 1 when
- *      the inner solve did not converge, bit 2 when it certified primal infeasibility, bit 4 when a limit flag of the step is
- *      non-zero.
+ *      the inner solve did not converge, bit 2 when it certified primal infeasibility, bit 4 when a position-limit flag of the
+ *      step (bits 1, 2 of loik_amd_limits.h) is non-zero, bit 8 when an acceleration flag of the step (bits 4, 8 of
+ *      loik_amd_accel.h) is.
  *
  * After step T - 1 one judging re-target fills ERRMAX[b][T], ERR and ONTRACK against X_T; it writes no b and counts no step.
  * With LOIKB_TRACK_FF_NONE the loop is loikb_solve_pose's, bit for bit, as long as that one reaches nothing.
@@ -90,7 +91,8 @@ enum {
   LOIKB_TRACK_F_Q = 0,     /* double [B][T+1][nq]: q at every sample, NaN rows after a stop; LOIKB_ERR_STATE without REC_Q        */
   LOIKB_TRACK_F_Z,         /* double [B][T][nv]: z of every step, NaN rows for steps not run; LOIKB_ERR_STATE without REC_Z      */
   LOIKB_TRACK_F_ERRMAX,    /* double [B][T+1]: max_c |e_c|_inf at every sample, NaN from a stop on                              */
-  LOIKB_TRACK_F_INNER,     /* int [B][T]: 1 = inner solve not converged, 2 = primal infeasible, 4 = a joint limit cut the box   */
+  LOIKB_TRACK_F_INNER,     /* int [B][T]: 1 = inner solve not converged, 2 = primal infeasible, 4 = a joint limit cut the box,
+                              8 = an acceleration limit did (loik_amd_accel.h)                                                   */
   LOIKB_TRACK_F_ONTRACK,   /* int [B]: samples 0 .. T with ERRMAX <= tol_track                                                  */
   LOIKB_TRACK_F_WORST,     /* double [B]: the maximum of ERRMAX[b][1..T] over its finite entries (NaN when there is none)       */
   LOIKB_TRACK_F_WORST_AT,  /* int [B]: the first sample that attains it (-1 when there is none)                                 */

@@ -141,12 +141,22 @@ TRACK_REC_Q, TRACK_REC_Z = 1, 2
 TRACK_RECS = {"q": TRACK_REC_Q, "z": TRACK_REC_Z}
 TRACK_F_Q, TRACK_F_Z, TRACK_F_ERRMAX, TRACK_F_INNER, TRACK_F_ONTRACK, TRACK_F_WORST, TRACK_F_WORST_AT, TRACK_F_TIMING = range(8)
 TRACK_IN_NOT_CONVERGED, TRACK_IN_INFEASIBLE, TRACK_IN_LIMIT = 1, 2, 4
+TRACK_IN_ACCEL = 8   # (include/loik_amd_accel.h: an acceleration flag of the step is non-zero)
 # what loikb_track_get writes per instance, after [B], in the manner of FIELD_DIMS / INT_FIELDS (which describe loikb_get's fields and
 # those alone): "T" steps, "T+1" samples
 TRACK_FIELD_ID = {"q_traj": TRACK_F_Q, "z_traj": TRACK_F_Z, "errmax": TRACK_F_ERRMAX, "inner": TRACK_F_INNER, "ontrack": TRACK_F_ONTRACK,
                   "worst": TRACK_F_WORST, "worst_at": TRACK_F_WORST_AT}
 TRACK_FIELD_DIMS = {"q_traj": ("T+1", "nq"), "z_traj": ("T", "nv"), "errmax": ("T+1",), "inner": ("T",), "ontrack": (), "worst": (), "worst_at": ()}
 TRACK_INT_FIELDS = ("inner", "ontrack", "worst_at")   # int32, the others float64
+
+
+# include/loik_amd_accel.h: joint acceleration limits and braking-aware position limits in the pose loops; its own header and version again
+ACCEL_ABI_VERSION = 1
+ACCEL_SYMBOLS = ["loikb_accel_version", "loikb_set_joint_accel_limits", "loikb_accel_set_start_velocity", "loikb_accel_get_velocity"]
+LIMIT_ACCEL_LOWER, LIMIT_ACCEL_UPPER = 4, 8
+# what loikb_accel_get_velocity writes per instance, after [B], in the manner of TRACK_FIELD_DIMS / TRACK_INT_FIELDS
+ACCEL_FIELD_DIMS = {"applied_velocity": ("nv",)}
+ACCEL_INT_FIELDS = ()   # float64
 
 
 class PoseParams(C.Structure):
@@ -241,6 +251,9 @@ def lib():
     L.loikb_path_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.loikb_track_pose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TrackParams)]
     L.loikb_track_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_set_joint_accel_limits.argtypes = [C.c_void_p, _dp, C.c_int]
+    L.loikb_accel_set_start_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_accel_get_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -506,6 +519,7 @@ class BatchedLoik:
         _check(self.L.loikb_create(C.byref(self._desc), C.byref(self.opts), C.byref(h)))
         self.h = h
         self._limits = False   # set_joint_limits left a finite limit on the handle: SolvePose returns limit_flags
+        self._accel = False    # set_joint_accel_limits left a finite limit on the handle: the pose loops return limit_flags
         self._ms_goals = 0     # goals of the last SolvePoseMultiStart: the shapes of multistart_get
 
     def close(self):
@@ -565,6 +579,46 @@ class BatchedLoik:
         out = np.empty((self.batch, self.model.nv), dtype=np.int32)
         _check(self.L.loikb_pose_get_limit_flags(self.h, out.ctypes.data_as(C.c_void_p), 0))
         return out
+
+    # ---- joint acceleration limits (include/loik_amd_accel.h) -------------------------------------------------
+    def set_joint_accel_limits(self, a_max):
+        """joint acceleration limits [nv] (idx_v order, entries > 0, +inf = none) honoured by every later SolvePose / SolvePosePath /
+        TrackPose (loikb_set_joint_accel_limits): per step |z - z_previous| <= a_max dt, and position limits are approached at a
+        velocity the joint can brake from.  None clears them."""
+        if a_max is None:
+            _check(self.L.loikb_set_joint_accel_limits(self.h, None, 0))
+            self._accel = False
+            return
+        a = _f64(a_max).reshape(-1)
+        _check(self.L.loikb_set_joint_accel_limits(self.h, a.ctypes.data_as(_dp), int(a.size)))
+        self._accel = bool(np.isfinite(a).any())
+
+    def set_start_velocity(self, v0):
+        """the velocity [B][nv] the next pose loop on this handle starts from, then forgotten (loikb_accel_set_start_velocity): a
+        host array, a raw device pointer or anything with data_ptr(); None = rest"""
+        if v0 is None:
+            _check(self.L.loikb_accel_set_start_velocity(self.h, None, 0))
+            return
+        if not (isinstance(v0, int) or (hasattr(v0, "data_ptr") and getattr(v0, "is_cuda", False))):
+            v0 = _f64(v0.numpy() if hasattr(v0, "numpy") else v0)
+        n = None if isinstance(v0, int) else int(v0.numel() if hasattr(v0, "numel") else v0.size)
+        if n is not None and n != self.batch * self.model.nv:
+            raise ValueError("v0 has %d elements, expected batch * nv = %d" % (n, self.batch * self.model.nv))
+        p, dev = _ptr(v0)
+        _check(self.L.loikb_accel_set_start_velocity(self.h, p, IN_DEVICE if dev else 0))
+
+    def get_applied_velocity(self, out=None):
+        """[B][nv] the velocity applied in the last step that moved each instance of the last pose loop with acceleration limits
+        (loikb_accel_get_velocity; 0: never moved, reached or stopped), as a numpy array or into a device pointer / torch tensor `out`"""
+        if out is not None:
+            p, dev = _ptr(out)
+            _check(self.L.loikb_accel_get_velocity(self.h, p, OUT_DEVICE if dev else 0))
+            return out
+        d = {"nv": self.model.nv}
+        arr = np.empty((self.batch,) + tuple(d[x] for x in ACCEL_FIELD_DIMS["applied_velocity"]),
+                       dtype=np.int32 if "applied_velocity" in ACCEL_INT_FIELDS else np.float64)
+        _check(self.L.loikb_accel_get_velocity(self.h, arr.ctypes.data_as(C.c_void_p), 0))
+        return arr
 
     def set_pose_tasks(self, kinds, frames=None):
         """one task per active constraint (active_task_constraint_ids order) for every later SolvePose (loikb_pose_set_tasks).
@@ -784,7 +838,7 @@ class BatchedLoik:
         [nc][4][4] / [nc][12] (/ [4][4] / [12] for one constraint) shared by the batch; a device tensor is [B][nc][12] or
         [nc][12] by its numel.  q: None = the resident configurations, else [B][nq] replaces them first.
         Returns dict(reached [B] bool, steps [B], err [B][nc][6] = e_c of the final q, status [B] POSE_ST_* bits), and with joint
-        position limits on the handle (set_joint_limits) limit_flags [B][nv]."""
+        position limits (set_joint_limits) or acceleration limits (set_joint_accel_limits) on the handle limit_flags [B][nv]."""
         B, nc = self.batch, int(self.L.loikb_num_eq_c(self.h))
         flags, keep = 0, []
         if isinstance(targets, int) or (hasattr(targets, "data_ptr") and getattr(targets, "is_cuda", False)):
@@ -828,7 +882,7 @@ class BatchedLoik:
         _check(self.L.loikb_pose_get(self.h, POSE_F_STEPS, steps.ctypes.data_as(C.c_void_p), 0))
         _check(self.L.loikb_pose_get(self.h, POSE_F_ERR, err.ctypes.data_as(C.c_void_p), 0))
         out = dict(reached=(status & POSE_ST_REACHED) != 0, steps=steps, err=err, status=status)
-        if self._limits:
+        if self._limits or self._accel:
             out["limit_flags"] = self.pose_limit_flags()
         return out
 
@@ -1038,7 +1092,7 @@ class BatchedLoik:
         _check(self.L.loikb_pose_get(self.h, POSE_F_ERR, err.ctypes.data_as(C.c_void_p), 0))
         out = dict(reached=(status & POSE_ST_REACHED) != 0, cursor=self.path_get("cursor"), steps=steps, wsteps=self.path_get("wsteps"),
                    status=status, path_status=self.path_get("path_status"), err=err, q_path=self.path_get("q_path") if int(record) == 1 else None)
-        if self._limits:
+        if self._limits or self._accel:
             out["limit_flags"] = self.pose_limit_flags()
         return out
 
@@ -1134,7 +1188,7 @@ class BatchedLoik:
         recorded = {"q_traj": record & TRACK_REC_Q, "z_traj": record & TRACK_REC_Z}
         for name in TRACK_FIELD_ID:
             out[name] = self.track_get(name) if recorded.get(name, True) else None
-        if self._limits:
+        if self._limits or self._accel:
             out["limit_flags"] = self.pose_limit_flags()
         return out
 

@@ -23,6 +23,7 @@
 #include "loik_pose_multistart.hpp"
 #include "loik_pose_path.hpp"
 #include "loik_pose_track.hpp"
+#include "loik_pose_accel.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -40,6 +41,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_multistart.h"
 #include "../../include/loik_amd_path.h"
 #include "../../include/loik_amd_track.h"
+#include "../../include/loik_amd_accel.h"
 
 #include <algorithm>
 #include <chrono>
@@ -366,6 +368,16 @@ struct loikb_solver_impl {
     int* d_lflags = nullptr;           // [B][nv] limit flags
     unsigned char* d_inrange = nullptr;  // [nb][B] the coordinate was in range before the step
     double2* d_box = nullptr;          // [nb][B] the per-instance base box while a pose solve with limits runs
+    // joint acceleration limits (loik_amd_accel.h)
+    bool have_accel = false;           // loikb_set_joint_accel_limits left at least one finite limit on the handle
+    bool vel_valid = false;            // the last pose loop ran with acceleration limits: d_zp is its result
+    bool have_v0 = false;              // the start-velocity latch: d_v0 is zp of the first step of the next pose loop
+    std::vector<double> a_max;         // [nb] host copy of d_amax (+inf: none)
+    double* d_amax = nullptr;          // [nb]
+    double* d_zp = nullptr;            // [nb][B] the velocity applied in the previous step (0: not running)
+    double* d_v0 = nullptr;            // [B][nv] the latched start velocity
+    double* d_vout = nullptr;          // [B][nv] staging of loikb_accel_get_velocity
+    const int* vel_status = nullptr;   // the status word of the loop that wrote d_zp last (nullptr: no step ran)
     // tool frames and task kinds (loik_amd_tasks.h)
     bool have_tasks = false;           // loikb_pose_set_tasks wrote the A the handle holds: `tasks` describes it
     std::vector<PoseTask> tasks;       // [nc_active] host copy of d_tasks

@@ -1,5 +1,5 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
-// (loik_amd_limits.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h), waypoint paths
+// (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h), waypoint paths
 // (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
 // belongs to: it is no header of its own.
 //
@@ -36,6 +36,14 @@ static int pose_limits_alloc(loikb_solver_impl* S, bool need_box)
   return LOIKB_OK;
 }
 
+// ... and of one with acceleration limits (include/loik_amd_accel.h): the velocity state
+static int pose_accel_alloc(loikb_solver_impl* S)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (P.d_zp) return LOIKB_OK;
+  return alloc_dev(S, (void**)&P.d_zp, sizeof(double) * (size_t)S->B * S->nb);
+}
+
 static dim3 grid_dof(const loikb_solver_impl* S) { return dim3((unsigned)((S->B + 255) / 256), (unsigned)S->nb); }
 
 // JP_LBUB of the home tiles <-> PoseState::d_box
@@ -48,7 +56,7 @@ static int pose_box_copy(loikb_solver_impl* S, int restore)
   return LOIKB_OK;
 }
 
-// The handle while a pose solve with limits runs: per-instance-box mode (every engine, the compaction's move_bounds and the
+// The handle while a pose solve with limits (position, acceleration or both) runs: per-instance-box mode (every engine, the compaction's move_bounds and the
 // pass-level path read S->bnd_shared when a solve is launched: make_params in run_chunk, compact, pass_params), the base box
 // kept in the uniform buffer (shared) or in d_box (per instance).  Leaving the scope puts the base box back in force in the
 // mode it had, on every return path.
@@ -76,6 +84,18 @@ struct PoseBoxScope {
   }
   ~PoseBoxScope() { if (active) { (void)leave(); (void)hipStreamSynchronize(S->stream); } }
 };
+
+// what every pose loop does between pose_begin and its first step: with either kind of limit on the handle, into the scope, and
+// the limit flags start at 0
+static int pose_box_begin(loikb_solver_impl* S, PoseBoxScope& box)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!P.have_limits && !P.have_accel) return LOIKB_OK;
+  int rc;
+  if ((rc = box.enter())) return rc;
+  HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)S->B * S->nb, S->stream));
+  return LOIKB_OK;
+}
 
 static double ms_since(std::chrono::steady_clock::time_point t0)
 {
@@ -151,21 +171,38 @@ static int pose_begin(loikb_solver_impl* S, const double* q, bool dev)
   if (S->a_shared) HIPCHK(hipMemcpyAsync(P.d_A, S->A_host.data(), sizeof(double) * 36 * nc, hipMemcpyHostToDevice, S->stream));
   HIPCHK(hipMemsetAsync(P.d_status, 0, sizeof(int) * B, S->stream));
   HIPCHK(hipMemsetAsync(P.d_steps, 0, sizeof(int) * B, S->stream));
+  if (P.have_accel) {   // the velocity state of the first step: the latched start velocity, else rest
+    if ((rc = pose_accel_alloc(S))) return rc;
+    hipLaunchKernelGGL(k_accel_load_v0, grid_dof(S), dim3(256), 0, S->stream, P.have_v0 ? (const double*)P.d_v0 : nullptr, B, S->nb, P.d_zp);
+    HIPCHK(hipGetLastError());
+  }
   HIPCHK(hipStreamSynchronize(S->stream));   // (q, cl are the caller's / locals)
   P.nc = nc;
-  P.flags_valid = P.have_limits;
+  P.flags_valid = P.have_limits || P.have_accel;
+  P.vel_valid = P.have_accel;
+  P.vel_status = nullptr;
+  P.have_v0 = false;   // (used or not: the latch is for the next pose loop alone)
   return LOIKB_OK;
 }
 
 // One step of a pose loop after its re-target left b_c in P.d_b: the step's box (limits), the b edits, the tailored Solve, the
-// integrate and the clamp.  `d_status`: the word whose POSE_REACHED / POSE_STOPPED bits say which instances run (P.d_status for
+// integrate, the clamp and (acceleration limits) the keep of the applied z.  `d_status`: the word whose POSE_REACHED / POSE_STOPPED bits say which instances run (P.d_status for
 // loikb_solve_pose, the loop-private word for loikb_solve_pose_path).
 static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxScope& box, int* d_status, double* solve_ms)
 {
   loikb_solver_impl::PoseState& P = S->pose;
   const int B = S->B, nc = S->nc_active;
   int rc = LOIKB_OK;
-  if (box.active) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
+  if (box.active && P.have_accel) {   // the step's box by the rule of loik_amd_accel.h, from the resident q and the last velocity
+    with_real(S, [&](auto t) {
+      using T = decltype(t);
+      hipLaunchKernelGGL(k_pose_dyn_box<T>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq,
+                         P.have_limits ? (const PoseLimit*)P.d_lim : nullptr, (const double*)P.d_amax, (const double*)P.d_zp, B, p->dt,
+                         (const int*)d_status, box.was_shared ? (const T*)S->d_uni + S->nc * 57 : nullptr, (const double2*)P.d_box,
+                         S->home.tiles, S->L, P.d_lflags, P.d_inrange);
+    });
+    HIPCHK(hipGetLastError());
+  } else if (box.active) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
     with_real(S, [&](auto t) {
       using T = decltype(t);
       hipLaunchKernelGGL(k_pose_limit_box<T>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
@@ -189,10 +226,18 @@ static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxS
                        (const char*)S->home.tiles, p->dt, d_status);
   });
   HIPCHK(hipGetLastError());
-  if (box.active) {
+  if (box.active && P.have_limits) {
     hipLaunchKernelGGL(k_pose_limit_clamp, grid_dof(S), dim3(256), 0, S->stream, S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
                        (const unsigned char*)P.d_inrange);
     HIPCHK(hipGetLastError());
+  }
+  if (box.active && P.have_accel) {   // zp of the next step (the integrate read the same z; it changes neither the tiles nor who runs)
+    with_real(S, [&](auto t) {
+      hipLaunchKernelGGL(k_accel_keep_z<decltype(t)>, grid_dof(S), dim3(256), 0, S->stream, (const char*)S->home.tiles, S->L, B,
+                         (const int*)d_status, P.d_zp);
+    });
+    HIPCHK(hipGetLastError());
+    P.vel_status = d_status;
   }
   ++S->inputs_epoch;
   return LOIKB_OK;
@@ -278,10 +323,7 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
   ++S->inputs_epoch;
   if ((rc = pose_begin(S, q, dev))) return rc;
   PoseBoxScope box{S};
-  if (P.have_limits) {
-    if ((rc = box.enter())) return rc;
-    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
-  }
+  if ((rc = pose_box_begin(S, box))) return rc;
   const double k = p->gain / p->dt;
   return pose_loop(S, p, box, P.d_status, t_call, [&](int go) -> int {
     if (P.have_tasks)   // (loik_amd_tasks.h: the task-frame error by kind, b = k S e; needs neither the tiles nor A)
@@ -373,9 +415,72 @@ int loikb_set_joint_limits(loikb_solver* S, const double* q_lo, const double* q_
 int loikb_pose_get_limit_flags(loikb_solver* S, int* out, int out_flags)
 {
   if (!S || !out) return LOIKB_ERR_ARG;
-  if (S->pose.nc == 0 || !S->pose.flags_valid) { g_last_error = "pose_get_limit_flags: the last solve_pose ran without joint limits (or there was none)"; return LOIKB_ERR_STATE; }
+  if (S->pose.nc == 0 || !S->pose.flags_valid) { g_last_error = "pose_get_limit_flags: the last solve_pose ran without joint position or acceleration limits (or there was none)"; return LOIKB_ERR_STATE; }
   HIPCHK(hipSetDevice(S->device));
   return get_copy_out(S, S->pose.d_lflags, sizeof(int) * (size_t)S->B * S->nb, out, out_flags);
+}
+
+// ---- include/loik_amd_accel.h (kernels in loik_pose_accel.hpp) ---------------------------------------------------------------
+int loikb_accel_version(void) { return LOIKB_ACCEL_VERSION; }
+
+int loikb_set_joint_accel_limits(loikb_solver* S, const double* a_max, int n)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!a_max) { P.have_accel = false; return LOIKB_OK; }
+  if (n != S->nv) { g_last_error = "set_joint_accel_limits: need one limit per DoF, n == model.nv"; return LOIKB_ERR_ARG; }
+  bool any = false;
+  for (int j = 0; j < n; ++j) {
+    if (std::isnan(a_max[j]) || !(a_max[j] > 0.0)) {
+      char what[128];
+      snprintf(what, sizeof(what), "set_joint_accel_limits: DoF %d (joint %d): a limit is NaN or not > 0 (+inf = no limit)", j, S->dof_ext[j]);
+      g_last_error = what;
+      return LOIKB_ERR_ARG;
+    }
+    any = any || std::isfinite(a_max[j]);
+  }
+  if (!any) { P.have_accel = false; return LOIKB_OK; }   // (no finite limit anywhere: the handle runs what it runs without)
+  HIPCHK(hipSetDevice(S->device));
+  int rc;
+  if (!P.d_amax && (rc = alloc_dev(S, (void**)&P.d_amax, sizeof(double) * S->nb))) return rc;
+  P.a_max.assign(a_max, a_max + n);
+  HIPCHK(hipMemcpyAsync(P.d_amax, P.a_max.data(), sizeof(double) * S->nb, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  P.have_accel = true;
+  return LOIKB_OK;
+}
+
+int loikb_accel_set_start_velocity(loikb_solver* S, const double* v0, int in_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!v0) { P.have_v0 = false; return LOIKB_OK; }
+  HIPCHK(hipSetDevice(S->device));
+  const size_t bytes = sizeof(double) * (size_t)S->B * S->nb;
+  int rc;
+  if (!P.d_v0 && (rc = alloc_dev(S, (void**)&P.d_v0, bytes))) return rc;
+  HIPCHK(hipMemcpyAsync(P.d_v0, v0, bytes, (in_flags & LOIKB_IN_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (v0 is the caller's)
+  P.have_v0 = true;
+  return LOIKB_OK;
+}
+
+int loikb_accel_get_velocity(loikb_solver* S, double* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (P.nc == 0 || !P.vel_valid) { g_last_error = "accel_get_velocity: the last pose loop ran without joint acceleration limits (or there was none)"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const size_t n = (size_t)S->B * S->nb;
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  int rc;
+  if (!to_dev && !P.d_vout && (rc = alloc_dev(S, (void**)&P.d_vout, sizeof(double) * n))) return rc;
+  double* dst = to_dev ? out : P.d_vout;
+  hipLaunchKernelGGL(k_accel_get_v, grid1(n), dim3(256), 0, S->stream, (const double*)P.d_zp, P.vel_status, S->B, S->nb, dst);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, sizeof(double) * n, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
 }
 
 // ---- include/loik_amd_tasks.h -----------------------------------------------------------------------------------------------
@@ -637,6 +742,10 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
     g_last_error = "solve_pose_multistart: need seeds_per_goal >= 1 that divides the batch, rounds >= 1, pick 0 or 1, flags 0";
     return LOIKB_ERR_ARG;
   }
+  if (S->pose.have_accel) {
+    g_last_error = "solve_pose_multistart: the handle has joint acceleration limits (loikb_set_joint_accel_limits); the seeds of a multi-start are teleported into the resident q between rounds, a rate limit means nothing there -- clear the acceleration limits first";
+    return LOIKB_ERR_STATE;
+  }
   if (int pre = pose_preconditions(S, pose, !q0)) return pre;
   if (ms_resolve_ranges(S) == 0 && (K > 1 || R > 1)) {
     g_last_error = "solve_pose_multistart: no DoF to sample (set ranges with loikb_multistart_set_ranges or joint limits with a finite pair)";
@@ -813,10 +922,7 @@ int loikb_solve_pose_path(loikb_solver* S, const double* q, const double* waypoi
                      W.d_wfrom, W.d_lstatus, W.d_pstatus, W.d_wsteps, W.d_Q);
   HIPCHK(hipGetLastError());
   PoseBoxScope box{S};
-  if (P.have_limits) {
-    if ((rc = box.enter())) return rc;
-    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
-  }
+  if ((rc = pose_box_begin(S, box))) return rc;
   const double k = p->gain / p->dt;
   const PoseTask* tasks = P.have_tasks ? (const PoseTask*)P.d_tasks : nullptr;
   const double* A_sh = S->a_shared ? (const double*)P.d_A : nullptr;
@@ -948,10 +1054,7 @@ int loikb_track_pose(loikb_solver* S, const double* q, const double* samples, in
                      K.d_ontrack, K.d_errmax, K.d_inner, Q, Z);
   HIPCHK(hipGetLastError());
   PoseBoxScope box{S};
-  if (P.have_limits) {
-    if ((rc = box.enter())) return rc;
-    HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)B * S->nb, S->stream));
-  }
+  if ((rc = pose_box_begin(S, box))) return rc;
   const double k = p->gain / p->dt, inv_dt = 1.0 / p->dt;
   const PoseTask* tasks = P.have_tasks ? (const PoseTask*)P.d_tasks : nullptr;
   const double* A_sh = S->a_shared ? (const double*)P.d_A : nullptr;

@@ -22,7 +22,7 @@ namespace loikb {
 enum : int { TRACK_FF_NONE = 0, TRACK_FF_DIFFERENCE = 1 };
 enum : int { TRACK_REC_Q = 1, TRACK_REC_Z = 2 };
 // INNER bits
-enum : int { TRACK_IN_NOT_CONVERGED = 1, TRACK_IN_INFEASIBLE = 2, TRACK_IN_LIMIT = 4 };
+enum : int { TRACK_IN_NOT_CONVERGED = 1, TRACK_IN_INFEASIBLE = 2, TRACK_IN_LIMIT = 4, TRACK_IN_ACCEL = 8 };
 
 __device__ __forceinline__ double track_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
@@ -123,7 +123,8 @@ __global__ void k_track_retarget(const double* __restrict__ q, int nq, const Joi
 // After step ks (ks = -1: before the first, the starting q): thread (b, i) carries coordinate i of an instance that is not stopped, so
 // loads and stores of a wavefront run along the rows.  Q[b][ks + 1][i] = q[b][i] (i < nq, Q != nullptr); Z[b][ks][i] = z of DoF i of the
 // step's solve, from the joint records of the tiles as advance_q_instance reads it (i < nv, Z != nullptr); thread i = 0 writes
-// INNER[b][ks] from the tiles' status word and, with lflags ([B][nv], nullptr without joint limits), the step's limit flags.
+// INNER[b][ks] from the tiles' status word and, with lflags ([B][nv], nullptr without joint limits), the step's limit flags: bit 4
+// from their position bits (1, 2), bit 8 from their acceleration bits (4, 8: loik_amd_accel.h).
 template <typename T>
 __global__ void k_track_record(const double* __restrict__ q, int nq, int nv, int B, int Tn, int ks, const int* __restrict__ status,
                                const char* tiles, Layout L, const int* __restrict__ lflags, double* __restrict__ Q,
@@ -142,8 +143,11 @@ __global__ void k_track_record(const double* __restrict__ q, int nq, int nv, int
     const int in = (int)*elem_ptr<T>(const_cast<char*>(lp) + (size_t)L.off_s * pair_bytes<T>(), SP_ST, 0);
     int w = ((in & ST_CONVERGED) ? 0 : TRACK_IN_NOT_CONVERGED) | ((in & ST_PRIMAL_INF) ? TRACK_IN_INFEASIBLE : 0);
     if (lflags)
-      for (int j = 0; j < nv; ++j)
-        if (lflags[(size_t)b * nv + j]) w |= TRACK_IN_LIMIT;
+      for (int j = 0; j < nv; ++j) {
+        const int f = lflags[(size_t)b * nv + j];
+        if (f & 3) w |= TRACK_IN_LIMIT;
+        if (f & 12) w |= TRACK_IN_ACCEL;
+      }
     inner[(size_t)b * (Tn - 1) + ks] = w;
   }
 }
