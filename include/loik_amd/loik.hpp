@@ -23,6 +23,7 @@
 #include "../loik_amd_path.h"
 #include "../loik_amd_track.h"
 #include "../loik_amd_accel.h"
+#include "../loik_amd_axis.h"
 
 #include <array>
 #include <map>
@@ -425,7 +426,8 @@ public:
     return v;
   }
   // ---- tool frames and position-only / orientation-only tasks of the pose loop (include/loik_amd_tasks.h)
-  // kinds: LOIKB_TASK_POSE / _POSITION / _ORIENTATION, one per active constraint (active_task_constraint_ids order); frames: iMf of
+  // kinds: LOIKB_TASK_POSE / _POSITION / _ORIENTATION, or with the rotation about the frame's z axis free LOIKB_TASK_POSE_AXIS / _AXIS
+  // (include/loik_amd_axis.h), one per active constraint (active_task_constraint_ids order); frames: iMf of
   // the task frame on the constrained link, one per kind, or empty = the joint frame.  A formulation edit: every active constraint's
   // A becomes the shared A_c = S_c X_c^-1 and its b zero.  clearPoseTasks(): the specification goes, A stays.
   void setPoseTasks(const std::vector<int>& kinds, const std::vector<SE3>& frames = {})

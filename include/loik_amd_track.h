@@ -23,9 +23,13 @@
  *        pose (and the joint-frame loop): u = log6(X_k^-1 X_{k+1}) / dt, the body twist of the desired frame, carried to the
  *                     actual frame by the action of (Re, pe): f_w = Re u_w, f_v = Re u_v + pe x (Re u_w);
  *        position:    f_v = R^T (t_{k+1} - t_k) / dt, f_w = 0;
- *        orientation: f_w = Re log3(R_k^T R_{k+1}) / dt, f_v = 0.
- *      With e = 0 a frame that moves with f stays on the desired frame; for position tasks with gain = 1, dt f + e is exactly
- *      the error against X_{k+1};
+ *        orientation: f_w = Re log3(R_k^T R_{k+1}) / dt, f_v = 0;
+ *        the free-spin kinds (LOIKB_TASK_FREE_Z: the rotation about the task frame's z axis is free), by the difference rule of
+ *                     the position task, in the actual frame, with w_axis the axis error of those kinds:
+ *                     f_w = (w_axis(R^T R_{k+1}) - w_axis(R^T R_k)) / dt, and f_v = R^T (t_{k+1} - t_k) / dt for the kind with
+ *                     a position part, f_v = 0 for the kind without.
+ *      With e = 0 a frame that moves with f stays on the desired frame; for position tasks and for the free-spin kinds with
+ *      gain = 1, dt f + e is exactly the error against X_{k+1};
  *   5. b_c = A_c ((gain / dt) e_c + f_c) (A shared or per instance); with tasks b_c = (gain / dt) S_c e_c + S_c f_c;
  *   6. the step of loikb_solve_pose, unchanged: the limit box if the handle has joint position limits (loik_amd_limits.h), the b
  *      edits, the tailored solve on the resident q, q <- q (+) dt z, the clamp.  With LOIKB_TRACK_REC_Z, Z[b][k] = the solve's z;

@@ -12,7 +12,7 @@ HEADERS = ["loik_device.hpp", "loik_tail.hpp", "loik_lean.hpp", "loik_flat.hpp",
            os.path.join("..", "..", "include", "loik_amd_pose.h"), os.path.join("..", "..", "include", "loik_amd_limits.h"),
            os.path.join("..", "..", "include", "loik_amd_tasks.h"), os.path.join("..", "..", "include", "loik_amd_multistart.h"),
            os.path.join("..", "..", "include", "loik_amd_path.h"), os.path.join("..", "..", "include", "loik_amd_track.h"),
-           os.path.join("..", "..", "include", "loik_amd_accel.h")]
+           os.path.join("..", "..", "include", "loik_amd_accel.h"), os.path.join("..", "..", "include", "loik_amd_axis.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # Code generation of the flat iteration kernels' translation unit (loik_flat_kernels.hip; why: csrc/loik_flat_inst.hpp): neighbouring LDS
 # accesses stay single 64-bit instructions -- neither the IR load/store vectorizer (128-bit accesses, ds_read2_b64 where the alignment is

@@ -157,6 +157,13 @@ LIMIT_ACCEL_LOWER, LIMIT_ACCEL_UPPER = 4, 8
 # what loikb_accel_get_velocity writes per instance, after [B], in the manner of TRACK_FIELD_DIMS / TRACK_INT_FIELDS
 ACCEL_FIELD_DIMS = {"applied_velocity": ("nv",)}
 ACCEL_INT_FIELDS = ()   # float64
+# include/loik_amd_axis.h: axis-symmetric tool tasks (the rotation about the task frame's z axis is free): a modifier bit on the kinds of
+# loik_amd_tasks.h, in a header and version of its own.  TASK_KINDS above stays the tasks header's three; these are the two it adds
+AXIS_ABI_VERSION = 1
+AXIS_SYMBOLS = ["loikb_axis_version"]
+TASK_FREE_Z = 4
+TASK_POSE_AXIS, TASK_AXIS = TASK_POSE | TASK_FREE_Z, TASK_ORIENTATION | TASK_FREE_Z
+AXIS_TASK_KINDS = {"pose_axis": TASK_POSE_AXIS, "axis": TASK_AXIS}
 
 
 class PoseParams(C.Structure):
@@ -622,16 +629,18 @@ class BatchedLoik:
 
     def set_pose_tasks(self, kinds, frames=None):
         """one task per active constraint (active_task_constraint_ids order) for every later SolvePose (loikb_pose_set_tasks).
-        kinds: TASK_POSE / TASK_POSITION / TASK_ORIENTATION or "pose" / "position" / "orientation"; frames: iMf of the task frame
+        kinds: TASK_POSE / TASK_POSITION / TASK_ORIENTATION or "pose" / "position" / "orientation", or with the rotation about the
+        frame's z axis free (include/loik_amd_axis.h) TASK_POSE_AXIS / TASK_AXIS or "pose_axis" / "axis"; frames: iMf of the task frame
         on the constrained link, [nc][4][4] / [nc][12], None = the joint frame.  A formulation edit: every active constraint's A
         becomes the shared A_c = S_c X_c^-1 and its b zero; the handle's A must be shared."""
         kinds = [kinds] if isinstance(kinds, (str, int, np.integer)) else list(kinds)
         k = np.empty(len(kinds), dtype=np.int32)
         for i, x in enumerate(kinds):
             if isinstance(x, str):
-                if x not in TASK_KINDS:
-                    raise ValueError("task kind %r: expected one of %s" % (x, sorted(TASK_KINDS)))
-                x = TASK_KINDS[x]
+                names = dict(TASK_KINDS, **AXIS_TASK_KINDS)
+                if x not in names:
+                    raise ValueError("task kind %r: expected one of %s" % (x, sorted(names)))
+                x = names[x]
             k[i] = int(x)
         fp = None
         if frames is not None:
@@ -652,7 +661,7 @@ class BatchedLoik:
             return []
         k, f = np.zeros(n, dtype=np.int32), np.zeros((n, 12))
         self.L.loikb_pose_get_tasks(self.h, k.ctypes.data_as(_ip), f.ctypes.data_as(_dp), n)
-        names = {v: key for key, v in TASK_KINDS.items()}
+        names = {v: key for key, v in dict(TASK_KINDS, **AXIS_TASK_KINDS).items()}
         return [(names[int(k[c])], self._to44(f[c:c + 1])[0]) for c in range(n)]
 
     @staticmethod

@@ -42,6 +42,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_path.h"
 #include "../../include/loik_amd_track.h"
 #include "../../include/loik_amd_accel.h"
+#include "../../include/loik_amd_axis.h"
 
 #include <algorithm>
 #include <chrono>

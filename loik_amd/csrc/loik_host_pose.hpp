@@ -485,6 +485,8 @@ int loikb_accel_get_velocity(loikb_solver* S, double* out, int out_flags)
 
 // ---- include/loik_amd_tasks.h -----------------------------------------------------------------------------------------------
 int loikb_tasks_version(void) { return LOIKB_TASKS_VERSION; }
+// (include/loik_amd_axis.h: its two kinds are cases of loikb_pose_set_tasks below and of the retarget rule of loik_pose.hpp)
+int loikb_axis_version(void) { return LOIKB_AXIS_VERSION; }
 
 // iMf [12] = (R row-major, p): finite, R orthonormal with determinant 1 within 1e-9 per entry (k_pose_check_targets' rule)
 static bool frame_ok(const double* F)
@@ -512,7 +514,9 @@ int loikb_pose_set_tasks(loikb_solver* S, int nc, const int* kinds, const double
   for (int c = 0; c < nc; ++c) {
     char what[64];
     snprintf(what, sizeof(what), "pose_set_tasks: task %d", c);
-    if (kinds[c] < LOIKB_TASK_POSE || kinds[c] > LOIKB_TASK_ORIENTATION) { g_last_error = std::string(what) + ": unknown kind (LOIKB_TASK_POSE / POSITION / ORIENTATION)"; return LOIKB_ERR_ARG; }
+    const bool known = kinds[c] == LOIKB_TASK_POSE || kinds[c] == LOIKB_TASK_POSITION || kinds[c] == LOIKB_TASK_ORIENTATION ||
+                       kinds[c] == LOIKB_TASK_POSE_AXIS || kinds[c] == LOIKB_TASK_AXIS;
+    if (!known) { g_last_error = std::string(what) + ": unknown kind (LOIKB_TASK_POSE / POSITION / ORIENTATION / POSE_AXIS / AXIS)"; return LOIKB_ERR_ARG; }
     const double* F = frames ? frames + 12 * c : ident;
     if (!frame_ok(F)) { g_last_error = std::string(what) + ": the frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
     tasks[c].kind = kinds[c];
@@ -537,8 +541,13 @@ int loikb_pose_set_tasks(loikb_solver* S, int nc, const int* kinds, const double
         A[6 * (3 + r) + 3 + m] = rt;
         A[6 * r + 3 + m] = -(Rf[r] * px[m] + Rf[3 + r] * px[3 + m] + Rf[6 + r] * px[6 + m]);
       }
-    const int r0 = tasks[c].kind == LOIKB_TASK_ORIENTATION ? 0 : 3, r1 = tasks[c].kind == LOIKB_TASK_POSE ? 0 : r0 + 3;
-    for (int x = 6 * r0; x < 6 * r1; ++x) A[x] = 0.0;   // S_c: the masked-out rows
+    // S_c as six row bits: the base kind's rows, less the rotation about the frame's z with LOIKB_TASK_FREE_Z (loik_amd_axis.h)
+    const int base = tasks[c].kind & ~LOIKB_TASK_FREE_Z;
+    int rows = base == LOIKB_TASK_POSITION ? 0x07 : (base == LOIKB_TASK_ORIENTATION ? 0x38 : 0x3f);
+    if (tasks[c].kind & LOIKB_TASK_FREE_Z) rows &= ~0x20;
+    for (int r = 0; r < 6; ++r)
+      if (!((rows >> r) & 1))
+        for (int m = 0; m < 6; ++m) A[6 * r + m] = 0.0;   // the masked-out rows
     if ((rc = update_eq_single(S, S->active_ids[c], A, zero, LOIKB_A_SHARED | LOIKB_B_SHARED))) return rc;
   }
   S->pass_active = false;

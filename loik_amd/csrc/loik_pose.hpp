@@ -132,6 +132,29 @@ __device__ __forceinline__ void pose_log3(const double* R, double* w)
   w[0] = f * vx; w[1] = f * vy; w[2] = f * vz;
 }
 
+// the axis error of loik_amd_axis.h: the minimal rotation w (frame axes, w_z = 0) that carries the frame's z axis onto
+// d = (dx, dy, dz), the desired z axis seen from the frame (the third column of Re).  theta = atan2(s, dz) with s = |(dx, dy)| is
+// accurate at both ends and theta / s -> 1, so there is no series branch; s == 0 exactly is parallel (w = 0) or antiparallel
+// (w = (pi, 0, 0): any axis in the xy plane would do, x is the rule).  A d that is not finite gives NaN (0 * inf would hide an
+// infinite entry otherwise).  The same branches are restated in tests/pose_axis_numpy.py.
+__device__ __forceinline__ void pose_axis_error(double dx, double dy, double dz, double* w)
+{
+  const double s = sqrt(dx * dx + dy * dy);
+  w[2] = 0.0;
+  if (!(isfinite(s) && isfinite(dz))) {
+    w[0] = w[1] = __longlong_as_double(0x7ff8000000000000ll);
+    return;
+  }
+  if (s == 0.0) {
+    w[0] = dz < 0.0 ? 3.14159265358979323846 : 0.0;
+    w[1] = 0.0;
+    return;
+  }
+  const double f = atan2(s, dz) / s;
+  w[0] = -(f * dy);
+  w[1] = f * dx;
+}
+
 // log6 (pinocchio::log6) of (R, p): [v; w], w = log3(R), v = V^-1(w) p = p - w x p / 2 + beta w x (w x p),
 // beta = (1 - (theta / 2) cot(theta / 2)) / theta^2, its series below theta = 1e-3
 __device__ __forceinline__ void pose_log6(const double* R, const double* p, double* nu)
@@ -180,8 +203,9 @@ __global__ void k_pose_check_targets(const double* __restrict__ tgt, int n, doub
 // pose_b_task and pose_b_track.  The library is built with -ffp-contract=on, which contracts within a statement only: a
 // statement split or merged here changes bits.
 
-// task kinds (loik_amd_tasks.h)
+// task kinds (loik_amd_tasks.h) and the free-spin modifier bit with its two kinds (loik_amd_axis.h)
 enum : int { TASK_POSE = 0, TASK_POSITION = 1, TASK_ORIENTATION = 2 };
+enum : int { TASK_FREE_Z = 4, TASK_POSE_AXIS = TASK_POSE | TASK_FREE_Z, TASK_AXIS = TASK_ORIENTATION | TASK_FREE_Z };
 
 // one entry per active constraint, built by loikb_pose_set_tasks: iMf = (Rf row-major, pf)
 struct PoseTask {
@@ -228,7 +252,10 @@ __device__ __forceinline__ void pose_error_impl(const double* q_row, const Joint
     for (int k = 0; k < 3; ++k) fr->pe[k] = pe[k];
   }
   const int kind = tk ? tk->kind : TASK_POSE;
-  if (kind == TASK_POSITION) {
+  if (kind & TASK_FREE_Z) {   // POSE_AXIS: [pe; w_axis(Re)], AXIS: [0; w_axis(Re)]
+    pose_axis_error(Re[2], Re[5], Re[8], e + 3);
+    for (int r = 0; r < 3; ++r) e[r] = kind == TASK_POSE_AXIS ? pe[r] : 0.0;
+  } else if (kind == TASK_POSITION) {
     for (int r = 0; r < 3; ++r) { e[r] = pe[r]; e[3 + r] = 0.0; }
   } else if (kind == TASK_ORIENTATION) {
     pose_log3(Re, e + 3);

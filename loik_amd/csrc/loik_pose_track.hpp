@@ -51,6 +51,17 @@ __device__ __forceinline__ void track_feedforward(int kind, const double* X0, co
       f[r] = inv_dt * (fr.R[r] * (X1[9] - X0[9]) + fr.R[3 + r] * (X1[10] - X0[10]) + fr.R[6 + r] * (X1[11] - X0[11]));
     return;
   }
+  if (kind & TASK_FREE_Z) {   // (loik_amd_axis.h) the difference rule again: (w_axis(R^T R1) - w_axis(R^T R0)) / dt, R^T (t1 - t0) / dt
+    double w0[3], w1[3], d1[3];
+    for (int r = 0; r < 3; ++r) d1[r] = fr.R[r] * X1[2] + fr.R[3 + r] * X1[5] + fr.R[6 + r] * X1[8];
+    pose_axis_error(fr.Re[2], fr.Re[5], fr.Re[8], w0);
+    pose_axis_error(d1[0], d1[1], d1[2], w1);
+    for (int r = 0; r < 2; ++r) f[3 + r] = inv_dt * (w1[r] - w0[r]);
+    if (kind == TASK_POSE_AXIS)
+      for (int r = 0; r < 3; ++r)
+        f[r] = inv_dt * (fr.R[r] * (X1[9] - X0[9]) + fr.R[3 + r] * (X1[10] - X0[10]) + fr.R[6 + r] * (X1[11] - X0[11]));
+    return;
+  }
   double Rd[9], pd[3], u[6];   // X0^-1 X1 = (R0^T R1, R0^T (t1 - t0))
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) Rd[3 * r + c] = X0[r] * X1[c] + X0[3 + r] * X1[3 + c] + X0[6 + r] * X1[6 + c];
