@@ -78,6 +78,12 @@ def random_tree(seed, nb, branch_prob=0.35, all_types=True):
             path.pop()
         parents.append(path[-1])
         path.append(i)
+    return _drawn_model(rng, parents, all_types, "random_tree_%d_%d" % (seed, nb))
+
+
+def _drawn_model(rng, parents, all_types, name):
+    """the Model of a given tree: joint types, axes and placements drawn from `rng` (random_tree's draw, in its order)"""
+    nb = len(parents) - 1
     types = [0]
     axis = [np.zeros(3)]
     placement = [np.concatenate([np.eye(3).ravel(), np.zeros(3)])]
@@ -92,8 +98,69 @@ def random_tree(seed, nb, branch_prob=0.35, all_types=True):
         types.append(t)
         axis.append(a)
         placement.append(np.concatenate([random_rotation(rng).ravel(), rng.uniform(-0.4, 0.4, size=3)]))
-    return loik_amd.Model(parents, types, np.array(axis), np.array(placement), q_lo=-np.ones(nb), q_hi=np.ones(nb),
-                          name="random_tree_%d_%d" % (seed, nb))
+    return loik_amd.Model(parents, types, np.array(axis), np.array(placement), q_lo=-np.ones(nb), q_hi=np.ones(nb), name=name)
+
+
+def tree_from_parents(parents, seed, all_types=True, name=None):
+    """a given tree (parents[0] = 0 is the universe, parents[i] < i) with joint types, axes and placements drawn as random_tree
+    draws them: the shape is the caller's, by construction instead of by seed"""
+    parents = [int(p) for p in parents]
+    assert parents[0] == 0 and all(0 <= parents[i] < i for i in range(1, len(parents)))
+    return _drawn_model(np.random.default_rng(seed), parents, all_types, name or "tree_%d_%d" % (len(parents) - 1, seed))
+
+
+# ---- carrier trees of the flat kernels' census (tests/flat_census.py): shapes by construction ---------------------------------------------
+def comb_parents(nb, depth):
+    """joint 1 under the universe, nb - depth leaves on joint 1, then a chain of depth - 1 joints hanging off joint 1: depth-first
+    numbered, depth exactly `depth`, the largest subtree (joint 1's) is the whole robot"""
+    assert 2 <= depth <= nb
+    return [0, 0] + [1] * (nb - depth) + [1] + list(range(nb - depth + 2, nb))
+
+
+def caterpillar_parents(nb, depth):
+    """a spine of `depth` joints; the other nb - depth joints are leaves, one per spine joint from the top down, each numbered right
+    after its spine joint; the last spine joint stays a leaf"""
+    assert 0 <= nb - depth <= depth - 1
+    parents, spine, leaves = [0], 0, nb - depth
+    for d in range(depth):
+        parents.append(spine)
+        spine = len(parents) - 1
+        if leaves > 0 and d < depth - 1:
+            parents.append(spine)
+            leaves -= 1
+    return parents
+
+
+def star_parents(nb):
+    """every joint a child of the universe"""
+    return [0] * (nb + 1)
+
+
+def comb(nb, depth, seed=0):
+    return tree_from_parents(comb_parents(nb, depth), seed, name="comb_%d_%d" % (nb, depth))
+
+
+def caterpillar(nb, depth, seed=0):
+    return tree_from_parents(caterpillar_parents(nb, depth), seed, name="caterpillar_%d_%d" % (nb, depth))
+
+
+def star(nb, seed=0):
+    return tree_from_parents(star_parents(nb), seed, name="star_%d" % nb)
+
+
+SOLVER_INFO_LISTS = ["primal_residual_task_list", "primal_residual_slack_list", "primal_residual_list", "dual_residual_nu_list",
+                     "dual_residual_v_list", "dual_residual_list", "mu_list", "mu_eq_list", "mu_ineq_list"]
+
+
+def assert_solver_info_matches(info, it, tail, b, r, tol=1e-9):
+    """instance b of a logged device solve (info = solver_info(), it / tail = its iter / tail_solve_iter) against the oracle solver `r`
+    that ran the same problem: the iteration counts, the rows, the nine lists to `tol`, zeros behind the last row"""
+    assert it[b] == r.get_iter() and tail[b] == int(r.scalar("tail_solve_iter")), (b, it[b], r.get_iter())
+    n = len(r.solver_info(0))
+    assert info["rows"][b] == n == it[b] - tail[b]
+    for k, name in enumerate(SOLVER_INFO_LISTS):
+        assert_close(info[name][b, :n], r.solver_info(k), tol, "%s b%d" % (name, b))
+        assert np.all(info[name][b, n:] == 0.0)
 
 
 def helical_tree(seed, nb, n_helical, branch_prob=0.35):

@@ -37,7 +37,7 @@ def model_of(name):
         elif name == "tree20":
             m = random_tree(6, 20)
         elif name == "tree31":
-            m = random_tree(12, 31, branch_prob=0.3)   # (31 joints, at most four children, a tree the flat schedule takes: k_flat2's upper end)
+            m = random_tree(12, 31, branch_prob=0.3)   # (31 joints, at most four children, a tree the flat schedule takes; depth 14, 13 ancestors: too deep for k_flat2, and k_flat<double, 16> is refused by the plan -- tests/flat_census.py -- so the level-by-level engines run it)
         elif name == "tree35":
             m = random_tree(8, 35)
         elif name == "deep60":

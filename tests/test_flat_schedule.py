@@ -7,7 +7,7 @@ import pytest
 
 import loik_amd
 from loik_amd import capi
-from helpers import random_tree
+from helpers import caterpillar_parents, comb_parents, random_tree, star_parents
 
 
 def _tree(parents):
@@ -30,6 +30,13 @@ def _models():
     out = [(n, loik_amd.builtin_model(n).parents) for n in ("talos32", "talos44")]
     for seed, nb, bp in [(3, 21, 0.35), (8, 30, 0.35), (11, 40, 0.35), (3, 60, 0.6), (5, 60, 0.6)]:
         out.append(("tree%d_%d" % (seed, nb), random_tree(seed, nb, branch_prob=bp).parents))
+    # the carriers of the flat kernels' census (tests/flat_census.py): the limits of depth and lane count, by construction
+    for nb, depth in [(32, 11), (32, 12), (17, 17), (33, 11), (33, 12), (64, 17)]:
+        out.append(("comb%d_%d" % (nb, depth), np.array(comb_parents(nb, depth))))
+    for nb, depth in [(24, 17), (33, 17)]:
+        out.append(("caterpillar%d_%d" % (nb, depth), np.array(caterpillar_parents(nb, depth))))
+    for nb in (17, 33):
+        out.append(("star%d" % nb, np.array(star_parents(nb))))
     return out
 
 

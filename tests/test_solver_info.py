@@ -5,11 +5,9 @@ import numpy as np
 import pytest
 
 import loik_amd
-from helpers import FIXTURE, assert_close, feasible_batch, fixture_problem, problem_args, random_tree, random_tree_multidof
+from helpers import (FIXTURE, SOLVER_INFO_LISTS as LISTS, assert_close, assert_solver_info_matches, feasible_batch, fixture_problem,
+                     problem_args, random_tree, random_tree_multidof)
 from oracle import ref
-
-LISTS = ["primal_residual_task_list", "primal_residual_slack_list", "primal_residual_list", "dual_residual_nu_list",
-         "dual_residual_v_list", "dual_residual_list", "mu_list", "mu_eq_list", "mu_ineq_list"]
 
 
 def test_oracle_lists_follow_the_main_loop(talos):
@@ -99,12 +97,7 @@ def test_gpu_solver_info_from_the_flat_engine(talos):
     for b in range(B):
         r = ref.RefSolver(talos, **prm)
         r.Solve(*problem_args(wl, b))
-        assert it[b] == r.get_iter() and tail[b] == int(r.scalar("tail_solve_iter")), (b, it[b], r.get_iter())
-        n = len(r.solver_info(0))
-        assert info["rows"][b] == n == it[b] - tail[b]
-        for k, name in enumerate(LISTS):
-            assert_close(info[name][b, :n], r.solver_info(k), 1e-9, "%s b%d" % (name, b))
-            assert np.all(info[name][b, n:] == 0.0)
+        assert_solver_info_matches(info, it, tail, b, r, 1e-9)
         assert_close(z[b], r.z, 1e-9, "z")
     # the lists restart with every solve; a handle without logging gives the same answers (the same kernel without the lists)
     s.Solve()
@@ -156,12 +149,7 @@ def test_gpu_solver_info_from_the_flat_engines_with_any_reference_weight(robot, 
         if weight == "per_link":
             r.UpdateReferences(H_list, v_list)
         r.Solve()
-        assert it[b] == r.get_iter() and tail[b] == int(r.scalar("tail_solve_iter")), (b, it[b], r.get_iter())
-        n = len(r.solver_info(0))
-        assert info["rows"][b] == n == it[b] - tail[b]
-        for k, name in enumerate(LISTS):
-            assert_close(info[name][b, :n], r.solver_info(k), 1e-9, "%s b%d" % (name, b))
-            assert np.all(info[name][b, n:] == 0.0)
+        assert_solver_info_matches(info, it, tail, b, r, 1e-9)
         assert_close(z[b], r.z, 1e-9, "z")
     s.close()
 
