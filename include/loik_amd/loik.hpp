@@ -23,6 +23,7 @@
 #include "../loik_amd_path.h"
 #include "../loik_amd_track.h"
 #include "../loik_amd_accel.h"
+#include "../loik_amd_step.h"
 #include "../loik_amd_axis.h"
 
 #include <array>
@@ -348,6 +349,10 @@ public:
   struct PoseResult {
     std::vector<int> reached, steps, status;  // [batch]; status: LOIKB_POSE_ST_* bits
     DVec err;                                 // [batch][nc][6]: e_c of the final q, [linear; angular]
+    // with step control set (setStepControl), else empty: alpha of the last step that moved the instance (0: none), the sum of the
+    // accepted trial numbers, the searches that accepted no trial; LOIKB_POSE_ST_STALLED is a bit of `status`
+    DVec alpha;
+    std::vector<int> backtracks, failed;
   };
   // targets: one per active constraint (active_task_constraint_ids order) for the whole batch, or batch * nc instance-major;
   // q: nullptr = the resident configurations, else [batch][nq] replaces them first
@@ -371,6 +376,12 @@ public:
     check(loikb_pose_get(h_, LOIKB_POSE_F_STATUS, r.status.data(), 0));
     check(loikb_pose_get(h_, LOIKB_POSE_F_ERR, r.err.data(), 0));
     for (int b = 0; b < batch_; ++b) r.reached[b] = (r.status[b] & LOIKB_POSE_ST_REACHED) ? 1 : 0;
+    if (loikb_pose_get_step_control(h_, nullptr)) {
+      r.alpha.resize(batch_); r.backtracks.resize(batch_); r.failed.resize(batch_);
+      check(loikb_step_get(h_, LOIKB_STEP_F_ALPHA, r.alpha.data(), 0));
+      check(loikb_step_get(h_, LOIKB_STEP_F_BACKTRACKS, r.backtracks.data(), 0));
+      check(loikb_step_get(h_, LOIKB_STEP_F_FAILED, r.failed.data(), 0));
+    }
     return r;
   }
   // world placements oMi of `links` for the resident q: [batch][links.size()]
@@ -425,6 +436,16 @@ public:
     check(loikb_accel_get_velocity(h_, v.data(), 0));
     return v;
   }
+  // ---- backtracking step control and stall detection of SolvePose (include/loik_amd_step.h)
+  // per step the trials q (+) alpha dt z, alpha = 1, shrink, shrink^2, ... (max_backtracks + 1 of them); the first that brings the
+  // squared pose error down to (1 - sufficient alpha) of its value is taken, the plain step if none; patience > 0: an instance whose
+  // searches failed that many times in a row is LOIKB_POSE_ST_STALLED and left where it was.  clearStepControl(): as if never set.
+  void setStepControl(double shrink = 0.5, double sufficient = 1e-4, int max_backtracks = 6, int patience = 0)
+  {
+    const loikb_step_params p{shrink, sufficient, max_backtracks, patience, 0};
+    check(loikb_pose_set_step_control(h_, &p));
+  }
+  void clearStepControl() { check(loikb_pose_set_step_control(h_, nullptr)); }
   // ---- tool frames and position-only / orientation-only tasks of the pose loop (include/loik_amd_tasks.h)
   // kinds: LOIKB_TASK_POSE / _POSITION / _ORIENTATION, or with the rotation about the frame's z axis free LOIKB_TASK_POSE_AXIS / _AXIS
   // (include/loik_amd_axis.h), one per active constraint (active_task_constraint_ids order); frames: iMf of

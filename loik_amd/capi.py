@@ -164,10 +164,19 @@ AXIS_SYMBOLS = ["loikb_axis_version"]
 TASK_FREE_Z = 4
 TASK_POSE_AXIS, TASK_AXIS = TASK_POSE | TASK_FREE_Z, TASK_ORIENTATION | TASK_FREE_Z
 AXIS_TASK_KINDS = {"pose_axis": TASK_POSE_AXIS, "axis": TASK_AXIS}
+# include/loik_amd_step.h: backtracking step control and stall detection in SolvePose; its own header and version again
+STEP_ABI_VERSION = 1
+STEP_SYMBOLS = ["loikb_step_version", "loikb_pose_set_step_control", "loikb_pose_get_step_control", "loikb_step_get"]
+POSE_ST_STALLED = 16
+STEP_F_ALPHA, STEP_F_BACKTRACKS, STEP_F_FAILED = range(3)
 
 
 class PoseParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
+
+
+class StepParams(C.Structure):
+    _fields_ = [("shrink", C.c_double), ("sufficient", C.c_double), ("max_backtracks", C.c_int), ("patience", C.c_int), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -261,6 +270,9 @@ def lib():
     L.loikb_set_joint_accel_limits.argtypes = [C.c_void_p, _dp, C.c_int]
     L.loikb_accel_set_start_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_accel_get_velocity.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_pose_set_step_control.argtypes = [C.c_void_p, C.POINTER(StepParams)]
+    L.loikb_pose_get_step_control.argtypes = [C.c_void_p, C.POINTER(StepParams)]
+    L.loikb_step_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -627,6 +639,32 @@ class BatchedLoik:
         _check(self.L.loikb_accel_get_velocity(self.h, arr.ctypes.data_as(C.c_void_p), 0))
         return arr
 
+    # ---- step control (include/loik_amd_step.h) -----------------------------------------------------------------
+    def set_step_control(self, shrink=0.5, sufficient=1e-4, max_backtracks=6, patience=0):
+        """backtracking step control for every later SolvePose / SolvePoseMultiStart (loikb_pose_set_step_control): per step the
+        trials q (+) alpha dt z, alpha = 1, shrink, shrink^2, ... (max_backtracks + 1 of them), the first that brings the squared pose
+        error down to (1 - sufficient alpha) of its value is taken, the plain step if none; patience > 0: an instance whose
+        searches failed that many times in a row is POSE_ST_STALLED and left where it was"""
+        prm = StepParams(float(shrink), float(sufficient), int(max_backtracks), int(patience), 0)
+        _check(self.L.loikb_pose_set_step_control(self.h, C.byref(prm)))
+
+    def clear_step_control(self):
+        _check(self.L.loikb_pose_set_step_control(self.h, None))
+
+    def step_control(self):
+        """dict(shrink, sufficient, max_backtracks, patience) as set, None when step control is not set"""
+        prm = StepParams()
+        if not self.L.loikb_pose_get_step_control(self.h, C.byref(prm)):
+            return None
+        return dict(shrink=prm.shrink, sufficient=prm.sufficient, max_backtracks=prm.max_backtracks, patience=prm.patience)
+
+    def step_get(self, name):
+        """[B] of the last SolvePose with step control (loikb_step_get): alpha / backtracks / failed"""
+        fid, dtype = {"alpha": (STEP_F_ALPHA, np.float64), "backtracks": (STEP_F_BACKTRACKS, np.int32), "failed": (STEP_F_FAILED, np.int32)}[name]
+        arr = np.empty(self.batch, dtype=dtype)
+        _check(self.L.loikb_step_get(self.h, fid, arr.ctypes.data_as(C.c_void_p), 0))
+        return arr
+
     def set_pose_tasks(self, kinds, frames=None):
         """one task per active constraint (active_task_constraint_ids order) for every later SolvePose (loikb_pose_set_tasks).
         kinds: TASK_POSE / TASK_POSITION / TASK_ORIENTATION or "pose" / "position" / "orientation", or with the rotation about the
@@ -847,7 +885,8 @@ class BatchedLoik:
         [nc][4][4] / [nc][12] (/ [4][4] / [12] for one constraint) shared by the batch; a device tensor is [B][nc][12] or
         [nc][12] by its numel.  q: None = the resident configurations, else [B][nq] replaces them first.
         Returns dict(reached [B] bool, steps [B], err [B][nc][6] = e_c of the final q, status [B] POSE_ST_* bits), and with joint
-        position limits (set_joint_limits) or acceleration limits (set_joint_accel_limits) on the handle limit_flags [B][nv]."""
+        position limits (set_joint_limits) or acceleration limits (set_joint_accel_limits) on the handle limit_flags [B][nv], and with
+        step control (set_step_control) alpha [B], backtracks [B], failed [B] and stalled [B] bool (POSE_ST_STALLED)."""
         B, nc = self.batch, int(self.L.loikb_num_eq_c(self.h))
         flags, keep = 0, []
         if isinstance(targets, int) or (hasattr(targets, "data_ptr") and getattr(targets, "is_cuda", False)):
@@ -893,6 +932,9 @@ class BatchedLoik:
         out = dict(reached=(status & POSE_ST_REACHED) != 0, steps=steps, err=err, status=status)
         if self._limits or self._accel:
             out["limit_flags"] = self.pose_limit_flags()
+        if self.step_control() is not None:
+            out.update(alpha=self.step_get("alpha"), backtracks=self.step_get("backtracks"), failed=self.step_get("failed"),
+                       stalled=(status & POSE_ST_STALLED) != 0)
         return out
 
     def pose_timing(self):

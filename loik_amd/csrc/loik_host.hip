@@ -24,6 +24,7 @@
 #include "loik_pose_path.hpp"
 #include "loik_pose_track.hpp"
 #include "loik_pose_accel.hpp"
+#include "loik_pose_step.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -42,6 +43,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_path.h"
 #include "../../include/loik_amd_track.h"
 #include "../../include/loik_amd_accel.h"
+#include "../../include/loik_amd_step.h"
 #include "../../include/loik_amd_axis.h"
 
 #include <algorithm>
@@ -379,6 +381,15 @@ struct loikb_solver_impl {
     double* d_v0 = nullptr;            // [B][nv] the latched start velocity
     double* d_vout = nullptr;          // [B][nv] staging of loikb_accel_get_velocity
     const int* vel_status = nullptr;   // the status word of the loop that wrote d_zp last (nullptr: no step ran)
+    // step control (loik_amd_step.h)
+    bool have_step = false;            // loikb_pose_set_step_control set `step`
+    bool step_valid = false;           // the last pose loop ran with step control: d_alpha, d_backtracks, d_failed are its results
+    loikb_step_params step = {0.5, 1e-4, 6, 0, 0};
+    double* d_trial = nullptr;         // [B][nq] the trial row of each instance
+    double* d_alpha = nullptr;         // [B] LOIKB_STEP_F_ALPHA
+    int* d_backtracks = nullptr;       // [B] LOIKB_STEP_F_BACKTRACKS
+    int* d_failed = nullptr;           // [B] LOIKB_STEP_F_FAILED
+    int* d_frun = nullptr;             // [B] failed searches in a row
     // tool frames and task kinds (loik_amd_tasks.h)
     bool have_tasks = false;           // loikb_pose_set_tasks wrote the A the handle holds: `tasks` describes it
     std::vector<PoseTask> tasks;       // [nc_active] host copy of d_tasks

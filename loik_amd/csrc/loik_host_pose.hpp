@@ -1,5 +1,5 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
-// (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h), waypoint paths
+// (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), step control (loik_amd_step.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h), waypoint paths
 // (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
 // belongs to: it is no header of its own.
 //
@@ -42,6 +42,22 @@ static int pose_accel_alloc(loikb_solver_impl* S)
   loikb_solver_impl::PoseState& P = S->pose;
   if (P.d_zp) return LOIKB_OK;
   return alloc_dev(S, (void**)&P.d_zp, sizeof(double) * (size_t)S->B * S->nb);
+}
+
+// ... and of one with step control (include/loik_amd_step.h): the trial rows and the per-instance counters
+static int pose_step_alloc(loikb_solver_impl* S)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (P.d_frun) return LOIKB_OK;
+  const size_t B = (size_t)S->B;
+  int rc;
+  if ((rc = alloc_dev(S, (void**)&P.d_trial, sizeof(double) * B * S->nq)) || (rc = alloc_dev(S, (void**)&P.d_alpha, sizeof(double) * B)) ||
+      (rc = alloc_dev(S, (void**)&P.d_backtracks, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&P.d_failed, sizeof(int) * B)) ||
+      (rc = alloc_dev(S, (void**)&P.d_frun, sizeof(int) * B))) {
+    P.d_frun = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+    return rc;
+  }
+  return LOIKB_OK;
 }
 
 static dim3 grid_dof(const loikb_solver_impl* S) { return dim3((unsigned)((S->B + 255) / 256), (unsigned)S->nb); }
@@ -176,8 +192,16 @@ static int pose_begin(loikb_solver_impl* S, const double* q, bool dev)
     hipLaunchKernelGGL(k_accel_load_v0, grid_dof(S), dim3(256), 0, S->stream, P.have_v0 ? (const double*)P.d_v0 : nullptr, B, S->nb, P.d_zp);
     HIPCHK(hipGetLastError());
   }
+  if (P.have_step) {   // the counters of loik_amd_step.h and the run of failed searches start at 0
+    if ((rc = pose_step_alloc(S))) return rc;
+    HIPCHK(hipMemsetAsync(P.d_alpha, 0, sizeof(double) * B, S->stream));
+    HIPCHK(hipMemsetAsync(P.d_backtracks, 0, sizeof(int) * B, S->stream));
+    HIPCHK(hipMemsetAsync(P.d_failed, 0, sizeof(int) * B, S->stream));
+    HIPCHK(hipMemsetAsync(P.d_frun, 0, sizeof(int) * B, S->stream));
+  }
   HIPCHK(hipStreamSynchronize(S->stream));   // (q, cl are the caller's / locals)
   P.nc = nc;
+  P.step_valid = P.have_step;
   P.flags_valid = P.have_limits || P.have_accel;
   P.vel_valid = P.have_accel;
   P.vel_status = nullptr;
@@ -187,8 +211,16 @@ static int pose_begin(loikb_solver_impl* S, const double* q, bool dev)
 
 // One step of a pose loop after its re-target left b_c in P.d_b: the step's box (limits), the b edits, the tailored Solve, the
 // integrate, the clamp and (acceleration limits) the keep of the applied z.  `d_status`: the word whose POSE_REACHED / POSE_STOPPED bits say which instances run (P.d_status for
-// loikb_solve_pose, the loop-private word for loikb_solve_pose_path).
-static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxScope& box, int* d_status, double* solve_ms)
+// loikb_solve_pose, the loop-private word for loikb_solve_pose_path).  `sc`: the loop runs with step control (loik_amd_step.h) and
+// this is what its re-target ran with; the integrate and the clamp are then k_pose_step_control's.
+struct PoseStepTargets {
+  const double* tgt;   // [B][nc][12], or the first nc rows with `shared`
+  int shared;
+  const PoseTask* tasks;   // nullptr: the joint frames
+};
+
+static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxScope& box, int* d_status, double* solve_ms,
+                     const PoseStepTargets* sc = nullptr)
 {
   loikb_solver_impl::PoseState& P = S->pose;
   const int B = S->B, nc = S->nc_active;
@@ -221,6 +253,19 @@ static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxS
   const auto t_solve = std::chrono::steady_clock::now();
   if ((rc = loikb_solve_tailored(S, nullptr, -1, nullptr, nullptr, 0))) return rc;
   *solve_ms += ms_since(t_solve);
+  if (sc) {
+    const StepCtl ctl{P.step.shrink, P.step.sufficient, P.step.max_backtracks, P.step.patience};
+    const bool clamp = box.active && P.have_limits;
+    with_real(S, [&](auto t) {
+      hipLaunchKernelGGL(k_pose_step_control<decltype(t)>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
+                         (const char*)S->home.tiles, p->dt, (const int*)P.d_clink, nc, sc->tasks, sc->tgt, sc->shared, (const double*)P.d_err,
+                         clamp ? (const PoseLimit*)P.d_lim : nullptr, clamp ? (const unsigned char*)P.d_inrange : nullptr, ctl, P.d_trial,
+                         d_status, P.d_steps, P.d_alpha, P.d_backtracks, P.d_failed, P.d_frun);
+    });
+    HIPCHK(hipGetLastError());
+    ++S->inputs_epoch;
+    return LOIKB_OK;
+  }
   with_real(S, [&](auto t) {
     hipLaunchKernelGGL(k_pose_integrate<decltype(t)>, grid1(B), dim3(256), 0, S->stream, S->d_q, S->nq, S->d_jd, S->d_idx_q, S->L, B,
                        (const char*)S->home.tiles, p->dt, d_status);
@@ -249,10 +294,11 @@ static int pose_no_after_step() { return LOIKB_OK; }
 // (go = 0: the last one, which only judges), which leaves b_c in P.d_b and the count of running instances in P.d_count[0];
 // the loop reads that count back, stops at 0 and otherwise runs pose_step on `d_status`, then after_step() (what the caller
 // queues behind a step: loikb_track_pose its record).  Then the base box is back in force, the stream is drained and P.timing
-// holds {steps, total since t_call, inner solves, the rest} in ms.
+// holds {steps, total since t_call, inner solves, the rest} in ms.  `sc`: pose_step's.
 template <class Retarget, class AfterStep = int (&)()>
 static int pose_loop(loikb_solver* S, const loikb_pose_params* p, PoseBoxScope& box, int* d_status,
-                     std::chrono::steady_clock::time_point t_call, Retarget&& retarget, AfterStep&& after_step = pose_no_after_step)
+                     std::chrono::steady_clock::time_point t_call, Retarget&& retarget, AfterStep&& after_step = pose_no_after_step,
+                     const PoseStepTargets* sc = nullptr)
 {
   loikb_solver_impl::PoseState& P = S->pose;
   double solve_ms = 0.0;
@@ -266,7 +312,7 @@ static int pose_loop(loikb_solver* S, const loikb_pose_params* p, PoseBoxScope& 
     HIPCHK(hipMemcpyAsync(&running, P.d_count, sizeof(running), hipMemcpyDeviceToHost, S->stream));
     HIPCHK(hipStreamSynchronize(S->stream));
     if (running == 0) break;
-    if ((rc = pose_step(S, p, box, d_status, &solve_ms)) || (rc = after_step())) return rc;
+    if ((rc = pose_step(S, p, box, d_status, &solve_ms, sc)) || (rc = after_step())) return rc;
     ++steps_run;
   }
   if ((rc = box.leave())) return rc;
@@ -309,6 +355,10 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
 {
   if (!S || !targets || !p) return LOIKB_ERR_ARG;
   if (int pre = pose_preconditions(S, p, !q)) return pre;
+  if (S->pose.have_step && S->pose.have_accel) {
+    g_last_error = "solve_pose: the handle has both step control (loikb_pose_set_step_control) and joint acceleration limits (loikb_set_joint_accel_limits); a scaled step is not the velocity the braking box was built for -- clear one of them first";
+    return LOIKB_ERR_STATE;
+  }
   const auto t_call = std::chrono::steady_clock::now();
   HIPCHK(hipSetDevice(S->device));
   int rc;
@@ -325,6 +375,7 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
   PoseBoxScope box{S};
   if ((rc = pose_box_begin(S, box))) return rc;
   const double k = p->gain / p->dt;
+  const PoseStepTargets sc{(const double*)P.d_tgt, (int)tgt_shared, P.have_tasks ? (const PoseTask*)P.d_tasks : nullptr};
   return pose_loop(S, p, box, P.d_status, t_call, [&](int go) -> int {
     if (P.have_tasks)   // (loik_amd_tasks.h: the task-frame error by kind, b = k S e; needs neither the tiles nor A)
       hipLaunchKernelGGL(k_pose_retarget_tasks, grid1(B), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q,
@@ -338,7 +389,7 @@ int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, in
       });
     HIPCHK(hipGetLastError());
     return LOIKB_OK;
-  });
+  }, pose_no_after_step, P.have_step ? &sc : nullptr);
 }
 
 int loikb_pose_get(loikb_solver* S, int field, void* out, int out_flags)
@@ -481,6 +532,49 @@ int loikb_accel_get_velocity(loikb_solver* S, double* out, int out_flags)
   if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, sizeof(double) * n, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
   return LOIKB_OK;
+}
+
+// ---- include/loik_amd_step.h (kernel in loik_pose_step.hpp) -------------------------------------------------------------------
+int loikb_step_version(void) { return LOIKB_STEP_VERSION; }
+
+int loikb_pose_set_step_control(loikb_solver* S, const loikb_step_params* p)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!p) { P.have_step = false; return LOIKB_OK; }
+  // (written so that a NaN fails its comparison)
+  if (!(p->shrink > 0.0 && p->shrink < 1.0) || !(p->sufficient >= 0.0 && p->sufficient < 1.0) || p->max_backtracks < 0 || p->max_backtracks > 30 ||
+      p->patience < 0 || p->flags != 0) {
+    g_last_error = "pose_set_step_control: need shrink in (0, 1), sufficient in [0, 1), max_backtracks in 0..30, patience >= 0, flags 0";
+    return LOIKB_ERR_ARG;
+  }
+  P.step = *p;
+  P.have_step = true;
+  return LOIKB_OK;
+}
+
+int loikb_pose_get_step_control(const loikb_solver* S, loikb_step_params* out)
+{
+  if (!S || !S->pose.have_step) return 0;
+  if (out) *out = S->pose.step;
+  return 1;
+}
+
+int loikb_step_get(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  const loikb_solver_impl::PoseState& P = S->pose;
+  if (P.nc == 0 || !P.step_valid) { g_last_error = "step_get: the last solve_pose ran without step control (or there was none)"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const void* src = nullptr;
+  size_t bytes = 0;
+  switch (field) {
+  case LOIKB_STEP_F_ALPHA: src = P.d_alpha; bytes = sizeof(double) * (size_t)S->B; break;
+  case LOIKB_STEP_F_BACKTRACKS: src = P.d_backtracks; bytes = sizeof(int) * (size_t)S->B; break;
+  case LOIKB_STEP_F_FAILED: src = P.d_failed; bytes = sizeof(int) * (size_t)S->B; break;
+  default: g_last_error = "step_get: unknown field"; return LOIKB_ERR_ARG;
+  }
+  return get_copy_out(S, src, bytes, out, out_flags);
 }
 
 // ---- include/loik_amd_tasks.h -----------------------------------------------------------------------------------------------
@@ -908,6 +1002,10 @@ int loikb_solve_pose_path(loikb_solver* S, const double* q, const double* waypoi
     return LOIKB_ERR_ARG;
   }
   if (int pre = pose_preconditions(S, p, !q)) return pre;
+  if (S->pose.have_step) {
+    g_last_error = "solve_pose_path: the handle has step control set (loik_amd_step.h), which this loop does not run -- clear it with loikb_pose_set_step_control(s, NULL) first";
+    return LOIKB_ERR_STATE;
+  }
   const auto t_call = std::chrono::steady_clock::now();
   HIPCHK(hipSetDevice(S->device));
   const int B = S->B, nc = S->nc_active, T = path->n_waypoints, budget = path->max_steps_per_waypoint;
@@ -1035,6 +1133,10 @@ int loikb_track_pose(loikb_solver* S, const double* q, const double* samples, in
   // the loop's parameters as a pose solve has them: T steps at most, and tol_track where the tolerance is checked
   const loikb_pose_params pose{p->dt, p->gain, p->tol_track, p->n_steps, 0};
   if (int pre = pose_preconditions(S, &pose, !q)) return pre;
+  if (S->pose.have_step) {
+    g_last_error = "track_pose: the handle has step control set (loik_amd_step.h), which this loop does not run -- clear it with loikb_pose_set_step_control(s, NULL) first";
+    return LOIKB_ERR_STATE;
+  }
   const auto t_call = std::chrono::steady_clock::now();
   HIPCHK(hipSetDevice(S->device));
   const int B = S->B, nc = S->nc_active, T = p->n_steps, Tn = T + 1, record = p->record, ff = p->feedforward;

@@ -28,6 +28,9 @@ namespace loikb {
 
 // pose status bits (loik_amd_pose.h)
 enum : int { POSE_REACHED = 1, POSE_NOT_CONVERGED = 2, POSE_INFEASIBLE = 4, POSE_STOPPED = 8 };
+// ... and the bit of loik_amd_step.h (set by k_pose_step_control alone, loik_pose_step.hpp), with the mask of an instance that no
+// longer runs in a loikb_solve_pose step: reached, stopped or stalled
+enum : int { POSE_STALLED = 16, POSE_IDLE = POSE_REACHED | POSE_STOPPED | POSE_STALLED };
 
 // liMi of device joint i from its coordinates: the fp64 twin of joint_xform (which reads the same numbers from the tiles'
 // JP_CS pairs).  p = joint_q_pairs(q of the joint) for a joint that reads q; JF_NOQ joints (the later joints of a free-flyer /
@@ -350,7 +353,7 @@ __global__ void k_pose_retarget(const double* __restrict__ q, int nq, const Join
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   int st = status[b];
-  bool run = !(st & (POSE_REACHED | POSE_STOPPED));
+  bool run = !(st & POSE_IDLE);
   if (run) {
     const double* q_row = q + (size_t)b * nq;
     bool finite = true;
@@ -364,7 +367,7 @@ __global__ void k_pose_retarget(const double* __restrict__ q, int nq, const Join
     }
     if (!finite) st |= POSE_STOPPED;
     else if (emax <= tol) st |= POSE_REACHED;
-    run = !(st & (POSE_REACHED | POSE_STOPPED));
+    run = !(st & POSE_IDLE);
     status[b] = st;
   }
   if (step) pose_count_or_idle(run, b, nc, B, b_out, steps, running);
@@ -414,7 +417,7 @@ __global__ void k_pose_limit_box(const double* __restrict__ q, int nq, const Pos
   else { const double2 v = base_pi[(size_t)j * B + b]; lb = v.x; ub = v.y; }
   double lo = lb, hi = ub;
   unsigned char in = 0;
-  if (!(status[b] & (POSE_REACHED | POSE_STOPPED))) {
+  if (!(status[b] & POSE_IDLE)) {
     const PoseLimit m = lim[j];
     int f = 0;
     if (m.qi >= 0) {
@@ -430,6 +433,9 @@ __global__ void k_pose_limit_box(const double* __restrict__ q, int nq, const Pos
   stp<T>(lane_ptr<T>(tiles, L, b) + (size_t)j * JREC * pair_bytes<T>(), JP_LBUB, (T)lo, (T)hi);
 }
 
+// the clamp of one limited coordinate (a NaN stays)
+__device__ __forceinline__ double pose_clamp_coord(double v, const PoseLimit& m) { return v < m.lo ? m.lo : (v > m.hi ? m.hi : v); }
+
 // after the step's integrate: q_j <- clamp(q_j, q_lo, q_hi) where `inrange` says so (a NaN stays: the next re-target stops the instance)
 __global__ void k_pose_limit_clamp(double* __restrict__ q, int nq, const PoseLimit* __restrict__ lim, int B,
                                    const unsigned char* __restrict__ inrange)
@@ -438,8 +444,7 @@ __global__ void k_pose_limit_clamp(double* __restrict__ q, int nq, const PoseLim
   if (b >= B || !inrange[(size_t)j * B + b]) return;
   const PoseLimit m = lim[j];
   double* x = q + (size_t)b * nq + m.qi;
-  const double v = *x;
-  *x = v < m.lo ? m.lo : (v > m.hi ? m.hi : v);
+  *x = pose_clamp_coord(*x, m);
 }
 
 // JP_LBUB of DoF j of instance b -> scratch[j][b] (restore = 0) or back (restore = 1); fp64 holds a T exactly

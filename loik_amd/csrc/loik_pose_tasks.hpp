@@ -29,7 +29,7 @@ __global__ void k_pose_retarget_tasks(const double* __restrict__ q, int nq, cons
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   int st = status[b];
-  bool run = !(st & (POSE_REACHED | POSE_STOPPED));
+  bool run = !(st & POSE_IDLE);
   if (run) {
     const double* q_row = q + (size_t)b * nq;
     bool finite = true;
@@ -43,7 +43,7 @@ __global__ void k_pose_retarget_tasks(const double* __restrict__ q, int nq, cons
     }
     if (!finite) st |= POSE_STOPPED;
     else if (emax <= tol) st |= POSE_REACHED;
-    run = !(st & (POSE_REACHED | POSE_STOPPED));
+    run = !(st & POSE_IDLE);
     status[b] = st;
   }
   if (step) pose_count_or_idle(run, b, nc, B, b_out, steps, running);

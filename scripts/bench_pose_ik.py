@@ -7,7 +7,8 @@ Reported: poses reached per second, mean / p99 steps of the reached, ms per step
 (re-target, b, integrate, read-backs).
 
   python scripts/bench_pose_ik.py [--workload talos32|panda7|all] [--batch 65536] [--targets 1024] [--steps 30] [--tol 1e-4]
-                                  [--no-host]"""
+                                  [--no-host] [--step-control]
+--step-control: the device loop with the default step control of include/loik_amd_step.h (the host loop has none: use --no-host)."""
 import argparse
 import json
 import os
@@ -97,6 +98,8 @@ def run_device(model, link, q0, tgt, prm, args):
     s = loik_amd.BatchedLoik(model, B, **prm)
     s.SolveInit(q0, np.eye(6), np.zeros(6), np.array([link], dtype=np.int32), np.eye(6)[None], np.zeros((B, 1, 6)),
                 -args.bound * np.ones(model.nv), args.bound * np.ones(model.nv))
+    if args.step_control:
+        s.set_step_control()
     s.synchronize()
     t0 = time.perf_counter()
     out = s.SolvePose(tgt, dt=1.0, gain=1.0, tol_pose=args.tol, max_steps=args.steps, q=q0)
@@ -148,6 +151,7 @@ def main():
     ap.add_argument("--spread", type=float, default=0.2)
     ap.add_argument("--bound", type=float, default=2.0)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--step-control", action="store_true")
     args = ap.parse_args()
     names = list(WORKLOADS) if args.workload == "all" else [args.workload]
     for name in names:
@@ -157,8 +161,8 @@ def main():
         prm = dict(W.FIXTURE_PARAMS, max_iter=300, tol_abs=1e-5, tol_rel=0.0, warm_start=True)
         run_device(model, link, q0[:min(args.batch, 4096)], tgt[:min(args.batch, 4096)], prm, args)   # (warm-up: code objects, allocations)
         r = run_device(model, link, q0, tgt, prm, args)
-        print(json.dumps(summary("device (loikb_solve_pose)", name, args.batch, args.targets, *r, args)), flush=True)
-        if not args.no_host:
+        print(json.dumps(summary("device (loikb_solve_pose%s)" % (", step control" if args.step_control else ""), name, args.batch, args.targets, *r, args)), flush=True)
+        if not args.no_host and not args.step_control:
             r = run_host(model, link, q0, tgt, prm, args)
             print(json.dumps(summary("host (FK, log6, integrate in numpy; tailored Solve with q and b)", name, args.batch, args.targets,
                                      *r, args)), flush=True)
