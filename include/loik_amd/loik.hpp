@@ -25,6 +25,7 @@
 #include "../loik_amd_accel.h"
 #include "../loik_amd_step.h"
 #include "../loik_amd_axis.h"
+#include "../loik_amd_jacobian.h"
 
 #include <array>
 #include <map>
@@ -484,6 +485,58 @@ public:
     std::vector<SE3> M((std::size_t)batch_ * l.size());
     for (std::size_t i = 0; i < M.size(); ++i) std::copy(out.begin() + 12 * i, out.begin() + 12 * (i + 1), M[i].begin());
     return M;
+  }
+  // ---- frame Jacobians and dexterity of the resident q (include/loik_amd_jacobian.h)
+  // J [batch][links.size()][6][nv] with v_f = J nu, v_f = [linear; angular] of the frame oMi(links[e]) * frames[e] (frames empty =
+  // the joint frames), in LOIKB_JAC_LOCAL / _LOCAL_WORLD_ALIGNED / _WORLD
+  DVec FrameJacobians(const std::vector<Index>& links, const std::vector<SE3>& frames = {}, int reference_frame = LOIKB_JAC_LOCAL) const
+  {
+    if (!frames.empty() && frames.size() != links.size()) throw std::runtime_error("loik_amd: links and frames differ in size");
+    if (links.empty()) return {};
+    std::vector<int> l(links.begin(), links.end());
+    DVec f(frames.size() * 12), out((std::size_t)batch_ * l.size() * 6 * model_.nv);
+    for (std::size_t i = 0; i < frames.size(); ++i) std::copy(frames[i].begin(), frames[i].end(), f.begin() + 12 * i);
+    check(loikb_frame_jacobians(h_, l.data(), frames.empty() ? nullptr : f.data(), (int)l.size(), reference_frame, out.data(), 0));
+    return out;
+  }
+  // [batch][n][LOIKB_DEX_N]: sigma_0 .. sigma_5 (descending, 0 past the selected rows), manipulability, inverse condition number of
+  // diag(1/length x 3, 1 x 3) S_rows J_local.  rows: 6-bit masks, empty = all six rows.  TaskDexterity(length): the same for the handle's
+  // tasks -- the active constraint links with the frames and rows of setPoseTasks (identity, all six rows without tasks)
+  DVec FrameDexterity(const std::vector<Index>& links, const std::vector<SE3>& frames = {}, const std::vector<int>& rows = {},
+                      double length = 1.0) const
+  {
+    if ((!frames.empty() && frames.size() != links.size()) || (!rows.empty() && rows.size() != links.size()))
+      throw std::runtime_error("loik_amd: links, frames and rows differ in size");
+    if (links.empty()) return {};
+    std::vector<int> l(links.begin(), links.end());
+    DVec f(frames.size() * 12), out((std::size_t)batch_ * l.size() * LOIKB_DEX_N);
+    for (std::size_t i = 0; i < frames.size(); ++i) std::copy(frames[i].begin(), frames[i].end(), f.begin() + 12 * i);
+    const loikb_dexterity_params p{length, 0};
+    check(loikb_frame_dexterity(h_, l.data(), frames.empty() ? nullptr : f.data(), rows.empty() ? nullptr : rows.data(), (int)l.size(), &p,
+                                out.data(), 0));
+    return out;
+  }
+  DVec TaskDexterity(double length = 1.0) const
+  {
+    const int nc = loikb_num_eq_c(h_);
+    if (nc <= 0) return {};
+    DVec out((std::size_t)batch_ * (std::size_t)nc * LOIKB_DEX_N);
+    const loikb_dexterity_params p{length, 0};
+    check(loikb_frame_dexterity(h_, nullptr, nullptr, nullptr, nc, &p, out.data(), 0));
+    return out;
+  }
+  // the dexterous pick of SolvePoseMultiStart: among the reached seeds of a goal, the one whose worst task has the largest smallest
+  // singular value (cost = -min_c sigma_min of TaskDexterity(length)); clear: as if never set.  Returns the length, 0 when not set
+  void setMultiStartPickDexterous(double length = 1.0)
+  {
+    const loikb_dexterity_params p{length, 0};
+    check(loikb_dexterity_set_multistart_pick(h_, &p));
+  }
+  void clearMultiStartPickDexterous() { check(loikb_dexterity_set_multistart_pick(h_, nullptr)); }
+  double MultiStartPickDexterous() const
+  {
+    loikb_dexterity_params p{0.0, 0};
+    return loikb_dexterity_get_multistart_pick(h_, &p) ? p.length : 0.0;
   }
   // ---- multi-start pose IK (include/loik_amd_multistart.h): batch = G goals * K seeds, instance g * K + k is seed k of goal g
   // the ranges [nv] the seeds are drawn from (a DoF is sampled iff both ends are finite; both empty = the joint limits) and the

@@ -169,6 +169,14 @@ STEP_ABI_VERSION = 1
 STEP_SYMBOLS = ["loikb_step_version", "loikb_pose_set_step_control", "loikb_pose_get_step_control", "loikb_step_get"]
 POSE_ST_STALLED = 16
 STEP_F_ALPHA, STEP_F_BACKTRACKS, STEP_F_FAILED = range(3)
+# include/loik_amd_jacobian.h: frame Jacobians and dexterity measures of the resident q, the dexterous multi-start pick; its own header and
+# version again (MS_PICKS stays the multi-start header's two)
+JACOBIAN_ABI_VERSION = 1
+JACOBIAN_SYMBOLS = ["loikb_jacobian_version", "loikb_frame_jacobians", "loikb_frame_dexterity", "loikb_dexterity_set_multistart_pick",
+                    "loikb_dexterity_get_multistart_pick"]
+JAC_LOCAL, JAC_LOCAL_WORLD_ALIGNED, JAC_WORLD = 0, 1, 2
+JAC_REFERENCES = {"local": JAC_LOCAL, "local_world_aligned": JAC_LOCAL_WORLD_ALIGNED, "world": JAC_WORLD}
+DEX_SIGMA0, DEX_MANIPULABILITY, DEX_INV_CONDITION, DEX_N = 0, 6, 7, 8
 
 
 class PoseParams(C.Structure):
@@ -177,6 +185,10 @@ class PoseParams(C.Structure):
 
 class StepParams(C.Structure):
     _fields_ = [("shrink", C.c_double), ("sufficient", C.c_double), ("max_backtracks", C.c_int), ("patience", C.c_int), ("flags", C.c_int)]
+
+
+class DexterityParams(C.Structure):
+    _fields_ = [("length", C.c_double), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -273,6 +285,10 @@ def lib():
     L.loikb_pose_set_step_control.argtypes = [C.c_void_p, C.POINTER(StepParams)]
     L.loikb_pose_get_step_control.argtypes = [C.c_void_p, C.POINTER(StepParams)]
     L.loikb_step_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_frame_jacobians.argtypes = [C.c_void_p, _ip, _dp, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_frame_dexterity.argtypes = [C.c_void_p, _ip, _dp, _ip, C.c_int, C.POINTER(DexterityParams), C.c_void_p, C.c_int]
+    L.loikb_dexterity_set_multistart_pick.argtypes = [C.c_void_p, C.POINTER(DexterityParams)]
+    L.loikb_dexterity_get_multistart_pick.argtypes = [C.c_void_p, C.POINTER(DexterityParams)]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -970,6 +986,79 @@ class BatchedLoik:
         _check(self.L.loikb_frame_placements(self.h, links.ctypes.data_as(_ip), fp, n, out.ctypes.data_as(C.c_void_p), 0))
         return self._to44(out)
 
+    # ---- frame Jacobians and dexterity (include/loik_amd_jacobian.h) ----------------------------------------
+    def _links_frames(self, links, frames):
+        """(links int32 [n], n, frames float64 [n][12] or None) of the two getters"""
+        links = np.ascontiguousarray(np.atleast_1d(links), dtype=np.int32)
+        n = int(links.size)
+        f = None
+        if frames is not None:
+            f = self._placements12(frames, "frames").reshape(-1, 12)
+            if f.shape[0] != n:
+                raise ValueError("frames: %d placements for %d links" % (f.shape[0], n))
+        return links, n, f
+
+    def frame_jacobians(self, links, frames=None, reference="local", out=None):
+        """J [B][n][6][nv] with v_f = J nu for the resident q (loikb_frame_jacobians): v_f = [linear; angular] of the frame
+        oMi(links[e]) * frames[e], nu in idx_v order.  frames [n][4][4] / [n][12], None = the joint frames; reference: "local" (in
+        the frame), "local_world_aligned" (the frame's origin, the world's axes) or "world", or a JAC_* value.  A numpy array, or
+        into a device pointer / torch tensor `out` of B * n * 6 * nv float64."""
+        links, n, f = self._links_frames(links, frames)
+        if isinstance(reference, str):
+            if reference not in JAC_REFERENCES:
+                raise ValueError("reference %r: expected one of %s" % (reference, sorted(JAC_REFERENCES)))
+            reference = JAC_REFERENCES[reference]
+        fp = None if f is None else f.ctypes.data_as(_dp)
+        if out is not None:
+            p, dev = _ptr(out)
+            _check(self.L.loikb_frame_jacobians(self.h, links.ctypes.data_as(_ip), fp, n, int(reference), p, OUT_DEVICE if dev else 0))
+            return out
+        arr = np.empty((self.batch, n, 6, self.model.nv))
+        _check(self.L.loikb_frame_jacobians(self.h, links.ctypes.data_as(_ip), fp, n, int(reference), arr.ctypes.data_as(C.c_void_p), 0))
+        return arr
+
+    def frame_dexterity(self, links=None, frames=None, rows=None, length=1.0):
+        """singular values, Yoshikawa manipulability and inverse condition number of the task Jacobian of the resident q
+        (loikb_frame_dexterity): of D S_r J_local, D = diag(1/length x 3, 1 x 3), S_r the rows the 6-bit mask rows[e] selects (None =
+        all six) of the frame oMi(links[e]) * frames[e].  links=None: the handle's tasks -- the active constraint links with the
+        frames and rows of set_pose_tasks (identity and all six rows without tasks).
+        Returns dict(sigma [B][n][6] descending, zero past the selected rows; manipulability [B][n]; inv_condition [B][n])."""
+        prm = DexterityParams(float(length), 0)
+        if links is None:
+            if frames is not None or rows is not None:
+                raise ValueError("links=None takes the frames and rows of the handle's tasks: give neither")
+            n = int(self.L.loikb_num_eq_c(self.h))
+            lp = fp = rp = None
+        else:
+            links, n, f = self._links_frames(links, frames)
+            lp = links.ctypes.data_as(_ip)
+            fp = None if f is None else f.ctypes.data_as(_dp)
+            rp = None
+            if rows is not None:
+                r = np.ascontiguousarray(np.atleast_1d(rows), dtype=np.int32)
+                if r.size != n:
+                    raise ValueError("rows: %d masks for %d links" % (r.size, n))
+                rp = r.ctypes.data_as(_ip)
+        out = np.empty((self.batch, max(n, 0), DEX_N))
+        _check(self.L.loikb_frame_dexterity(self.h, lp, fp, rp, n, C.byref(prm), out.ctypes.data_as(C.c_void_p), 0))
+        return dict(sigma=out[..., :6].copy(), manipulability=out[..., DEX_MANIPULABILITY].copy(), inv_condition=out[..., DEX_INV_CONDITION].copy())
+
+    def set_multistart_pick_dexterous(self, length=1.0):
+        """every later SolvePoseMultiStart picks, among the reached seeds of a goal, the one whose worst task has the largest
+        smallest singular value (loikb_dexterity_set_multistart_pick): cost = -min_c sigma_min of frame_dexterity(links=None, length)"""
+        prm = DexterityParams(float(length), 0)
+        _check(self.L.loikb_dexterity_set_multistart_pick(self.h, C.byref(prm)))
+
+    def clear_multistart_pick_dexterous(self):
+        _check(self.L.loikb_dexterity_set_multistart_pick(self.h, None))
+
+    def multistart_pick_dexterous(self):
+        """dict(length) as set, None when the dexterous pick is not set"""
+        prm = DexterityParams()
+        if not self.L.loikb_dexterity_get_multistart_pick(self.h, C.byref(prm)):
+            return None
+        return dict(length=prm.length)
+
     # ---- multi-start pose IK (include/loik_amd_multistart.h) ------------------------------------------------
     def set_seed_ranges(self, s_lo=None, s_hi=None, weights=None):
         """the ranges [nv] (idx_v order) the seeds are drawn from (loikb_multistart_set_ranges): a DoF is sampled iff both ends are
@@ -1005,15 +1094,29 @@ class BatchedLoik:
         _check(self.L.loikb_multistart_sample(self.h, qp, qf, int(seed), K, int(round)))
 
     def SolvePoseMultiStart(self, targets, seeds_per_goal, rounds=1, seed=0, pick="nearest", q0=None, dt=1.0, gain=1.0, tol_pose=1e-6,
-                            max_steps=100):
+                            max_steps=100, length=1.0):
         """G = batch / seeds_per_goal goals, K = seeds_per_goal seeds each (loikb_solve_pose_multistart): instance g * K + k is seed k
         of goal g.  Seeds are drawn on the device inside the seed ranges (set_seed_ranges; default the joint limits), SolvePose
         runs on the whole batch, instances without REACHED are re-seeded for up to rounds - 1 restarts while a goal is
         unanswered, and one winner per goal is selected on the device.
         targets: [G][nc][4][4] / [G][nc][12], or [nc][..] shared by the goals (a device tensor by its numel).  q0: [G][nq], [nq]
         shared, None = the resident q of each goal's instance g * K; seed 0 of round 0 is q0 itself.
+        pick: "nearest" (to q0), "first", or "dexterous" (include/loik_amd_jacobian.h: the reached seed whose worst task has the
+        largest smallest singular value, linear rows scaled by 1 / length; set for this call alone -- a pick latched with
+        set_multistart_pick_dexterous is back in force afterwards, and is what ranks the reached seeds whenever it is set).
         Returns dict(winner [G], goal_status [G] MS_GOAL_* bits, q [G][nq], err [G][nc][6], cost [G], nreached [G], round [B],
         rounds_run, timing)."""
+        if pick == "dexterous":
+            before = self.multistart_pick_dexterous()
+            self.set_multistart_pick_dexterous(length)
+            try:
+                return self.SolvePoseMultiStart(targets, seeds_per_goal, rounds=rounds, seed=seed, pick=MS_PICK_FIRST, q0=q0, dt=dt, gain=gain,
+                                                tol_pose=tol_pose, max_steps=max_steps)
+            finally:
+                if before is None:
+                    self.clear_multistart_pick_dexterous()
+                else:
+                    self.set_multistart_pick_dexterous(before["length"])
         B, nc, K = self.batch, int(self.L.loikb_num_eq_c(self.h)), int(seeds_per_goal)
         G = B // K if K >= 1 and B % K == 0 else 1   # (a K the library rejects: it says so)
         flags, keep = 0, []

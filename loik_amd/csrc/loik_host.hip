@@ -25,6 +25,7 @@
 #include "loik_pose_track.hpp"
 #include "loik_pose_accel.hpp"
 #include "loik_pose_step.hpp"
+#include "loik_pose_jacobian.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -45,6 +46,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_accel.h"
 #include "../../include/loik_amd_step.h"
 #include "../../include/loik_amd_axis.h"
+#include "../../include/loik_amd_jacobian.h"
 
 #include <algorithm>
 #include <chrono>
@@ -394,6 +396,9 @@ struct loikb_solver_impl {
     bool have_tasks = false;           // loikb_pose_set_tasks wrote the A the handle holds: `tasks` describes it
     std::vector<PoseTask> tasks;       // [nc_active] host copy of d_tasks
     PoseTask* d_tasks = nullptr;       // [nc] (slot capacity), allocated by the first loikb_pose_set_tasks
+    // the dexterous multi-start pick (loik_amd_jacobian.h)
+    bool have_dex = false;             // loikb_dexterity_set_multistart_pick set `dex`
+    loikb_dexterity_params dex = {1.0, 0};
   } pose;
   // multi-start pose IK (loik_pose_multistart.hpp): buffers of loikb_multistart_sample / loikb_solve_pose_multistart, allocated by
   // the first call of either (sizes: batch and slot capacity; a goal count G <= B fits whatever K is)
@@ -412,6 +417,13 @@ struct loikb_solver_impl {
     int *d_winner = nullptr, *d_gstatus = nullptr, *d_nreached = nullptr;   // [G]
     double *d_cost = nullptr, *d_wq = nullptr, *d_werr = nullptr;           // [G], [G][nq], [G][nc][6]
     unsigned int* d_count = nullptr;   // [2] goals with a reached seed, target rotations rejected
+    // the dexterous pick (loik_amd_jacobian.h), allocated by the first multi-start that runs with it
+    double* d_dex = nullptr;           // [B][nc][LOIKB_DEX_N] k_frame_dexterity's records of the active constraints
+    double* d_dexcost = nullptr;       // [B] - min_c sigma_{m_c - 1}: the cost of class 0
+    double* d_dexfr = nullptr;         // [nc][12] the tasks' frames
+    int* d_dexrows = nullptr;          // [nc] the tasks' row masks
+    std::vector<double> dex_fr;        // host staging of d_dexfr (outlives the copy)
+    std::vector<int> dex_rows;         // likewise, d_dexrows
     int G = 0, nc = 0;                 // of the last loikb_solve_pose_multistart (G = 0: none yet)
     double timing[6] = {0, 0, 0, 0, 0, 0};   // LOIKB_MS_F_TIMING
   } ms;

@@ -1,5 +1,6 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
-// (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), step control (loik_amd_step.h), tool frames and tasks (loik_amd_tasks.h), multi-start (loik_amd_multistart.h), waypoint paths
+// (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), step control (loik_amd_step.h), tool frames and tasks (loik_amd_tasks.h), frame
+// Jacobians and dexterity (loik_amd_jacobian.h), multi-start (loik_amd_multistart.h), waypoint paths
 // (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
 // belongs to: it is no header of its own.
 //
@@ -596,6 +597,15 @@ static bool frame_ok(const double* F)
   return std::fabs(det - 1.0) <= 1e-9;
 }
 
+// S_c of a task kind as six row bits: the base kind's rows, less the rotation about the frame's z with LOIKB_TASK_FREE_Z (loik_amd_axis.h)
+static int task_rows(int kind)
+{
+  const int base = kind & ~LOIKB_TASK_FREE_Z;
+  int rows = base == LOIKB_TASK_POSITION ? 0x07 : (base == LOIKB_TASK_ORIENTATION ? 0x38 : 0x3f);
+  if (kind & LOIKB_TASK_FREE_Z) rows &= ~0x20;
+  return rows;
+}
+
 int loikb_pose_set_tasks(loikb_solver* S, int nc, const int* kinds, const double* frames)
 {
   if (!S) return LOIKB_ERR_ARG;
@@ -635,10 +645,7 @@ int loikb_pose_set_tasks(loikb_solver* S, int nc, const int* kinds, const double
         A[6 * (3 + r) + 3 + m] = rt;
         A[6 * r + 3 + m] = -(Rf[r] * px[m] + Rf[3 + r] * px[3 + m] + Rf[6 + r] * px[6 + m]);
       }
-    // S_c as six row bits: the base kind's rows, less the rotation about the frame's z with LOIKB_TASK_FREE_Z (loik_amd_axis.h)
-    const int base = tasks[c].kind & ~LOIKB_TASK_FREE_Z;
-    int rows = base == LOIKB_TASK_POSITION ? 0x07 : (base == LOIKB_TASK_ORIENTATION ? 0x38 : 0x3f);
-    if (tasks[c].kind & LOIKB_TASK_FREE_Z) rows &= ~0x20;
+    const int rows = task_rows(tasks[c].kind);
     for (int r = 0; r < 6; ++r)
       if (!((rows >> r) & 1))
         for (int m = 0; m < 6; ++m) A[6 * r + m] = 0.0;   // the masked-out rows
@@ -701,6 +708,178 @@ int loikb_frame_placements(loikb_solver* S, const int* links, const double* fram
   HIPCHK(hipGetLastError());
   if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));   // (dl and the caller's frames have been read)
+  return LOIKB_OK;
+}
+
+// ---- include/loik_amd_jacobian.h (kernels in loik_pose_jacobian.hpp) -----------------------------------------------------------
+int loikb_jacobian_version(void) { return LOIKB_JACOBIAN_VERSION; }
+
+static const double IDENT12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+
+static bool dex_params_ok(const loikb_dexterity_params* p) { return p && std::isfinite(p->length) && p->length > 0.0 && p->flags == 0; }
+
+// what both getters ask of (links, frames) given by the caller
+static int jac_check_entries(const loikb_solver_impl* S, const char* fn, const int* links, const double* frames, int n)
+{
+  for (int e = 0; e < n; ++e) {
+    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = std::string(fn) + ": link id out of range"; return LOIKB_ERR_ARG; }
+    if (frames && !frame_ok(frames + 12 * e)) {
+      g_last_error = std::string(fn) + ": a frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)";
+      return LOIKB_ERR_ARG;
+    }
+  }
+  return LOIKB_OK;
+}
+
+// "the handle's tasks" (links == NULL of loikb_frame_dexterity): the frames and row masks of the active constraints
+static void dex_task_entries(const loikb_solver_impl* S, std::vector<double>& fr, std::vector<int>& rows)
+{
+  const int nc = S->nc_active;
+  fr.resize((size_t)nc * 12);
+  rows.resize(nc);
+  for (int c = 0; c < nc; ++c) {
+    const bool tk = S->pose.have_tasks && c < (int)S->pose.tasks.size();
+    if (tk) { memcpy(&fr[12 * c], S->pose.tasks[c].Rf, 9 * sizeof(double)); memcpy(&fr[12 * c + 9], S->pose.tasks[c].pf, 3 * sizeof(double)); }
+    else memcpy(&fr[12 * c], IDENT12, sizeof(IDENT12));
+    rows[c] = tk ? task_rows(S->pose.tasks[c].kind) : 0x3f;
+  }
+}
+
+// scratch 1 of the getters: the frames [n][12], then the device joints [n] and (rows != NULL) the row masks [n]; queued
+static int jac_stage_entries(loikb_solver_impl* S, const int* dl, const double* fr, const int* rows, int n, double** d_fr, int** d_dl, int** d_rows)
+{
+  const size_t fbytes = sizeof(double) * (size_t)n * 12, ibytes = sizeof(int) * (size_t)n;
+  int rc;
+  if ((rc = ensure_getscr(S, 1, fbytes + 2 * ibytes))) return rc;
+  *d_fr = (double*)S->d_getscr[1];
+  *d_dl = (int*)((char*)S->d_getscr[1] + fbytes);
+  *d_rows = *d_dl + n;
+  HIPCHK(hipMemcpyAsync(*d_fr, fr, fbytes, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(*d_dl, dl, ibytes, hipMemcpyHostToDevice, S->stream));
+  if (rows) HIPCHK(hipMemcpyAsync(*d_rows, rows, ibytes, hipMemcpyHostToDevice, S->stream));
+  return LOIKB_OK;
+}
+
+int loikb_frame_jacobians(loikb_solver* S, const int* links, const double* frames, int n, int reference_frame, double* out, int out_flags)
+{
+  if (!S || !out || n < 0 || (n > 0 && !links)) return LOIKB_ERR_ARG;
+  if (reference_frame < LOIKB_JAC_LOCAL || reference_frame > LOIKB_JAC_WORLD) { g_last_error = "frame_jacobians: reference_frame must be LOIKB_JAC_LOCAL, _LOCAL_WORLD_ALIGNED or _WORLD"; return LOIKB_ERR_ARG; }
+  int rc;
+  if ((rc = jac_check_entries(S, "frame_jacobians", links, frames, n))) return rc;
+  if (!S->have_q) { g_last_error = "frame_jacobians: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  // the wavefronts of a workgroup: as many of JAC_WAVES as 64 KB of LDS hold root paths for
+  int waves = JAC_WAVES;
+  while (waves > 1 && waves * jac_wave_doubles(S->nb) * sizeof(double) > 65536) waves >>= 1;
+  const size_t lds = waves * jac_wave_doubles(S->nb) * sizeof(double);
+  if (lds > 65536) { g_last_error = "frame_jacobians: the model has more DoFs than one wavefront's root path fits in 64 KB of LDS for (630)"; return LOIKB_ERR_ARG; }
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  std::vector<int> dl(n);
+  std::vector<double> fr((size_t)n * 12);
+  for (int e = 0; e < n; ++e) {
+    dl[e] = S->link_of[links[e]];
+    memcpy(&fr[(size_t)12 * e], frames ? frames + 12 * e : IDENT12, sizeof(IDENT12));
+  }
+  const size_t pairs = (size_t)S->B * n, bytes = sizeof(double) * pairs * 6 * S->nb;
+  double* d_fr; int *d_dl, *d_rows;
+  if ((rc = jac_stage_entries(S, dl.data(), fr.data(), nullptr, n, &d_fr, &d_dl, &d_rows))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  hipLaunchKernelGGL(k_frame_jacobians, dim3((unsigned)((pairs + waves - 1) / waves)), dim3(64 * waves), lds, S->stream, (const double*)S->d_q, S->nq,
+                     S->d_jd, S->d_idx_q, (const int*)d_dl, (const double*)d_fr, n, S->B, S->nb, reference_frame, dst);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (dl and fr are locals)
+  return LOIKB_OK;
+}
+
+int loikb_frame_dexterity(loikb_solver* S, const int* links, const double* frames, const int* rows, int n, const loikb_dexterity_params* p,
+                          double* out, int out_flags)
+{
+  if (!S || !out || n < 0) return LOIKB_ERR_ARG;
+  if (!dex_params_ok(p)) { g_last_error = "frame_dexterity: need params with a finite length > 0 and flags 0"; return LOIKB_ERR_ARG; }
+  int rc;
+  if (!links) {
+    if (!S->have_problem) { g_last_error = "frame_dexterity: links == NULL (the handle's tasks) before SolveInit()"; return LOIKB_ERR_STATE; }
+    if (n != S->nc_active) { g_last_error = "frame_dexterity: links == NULL (the handle's tasks) needs n == loikb_num_eq_c()"; return LOIKB_ERR_ARG; }
+  } else {
+    if ((rc = jac_check_entries(S, "frame_dexterity", links, frames, n))) return rc;
+    for (int e = 0; rows && e < n; ++e)
+      if (rows[e] < 1 || rows[e] > 0x3f) { g_last_error = "frame_dexterity: a row mask must select at least one of the six rows (1..0x3f)"; return LOIKB_ERR_ARG; }
+  }
+  if (!S->have_q) { g_last_error = "frame_dexterity: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  std::vector<int> dl(n), rw(n, 0x3f);
+  std::vector<double> fr((size_t)n * 12);
+  if (!links) {
+    for (int c = 0; c < n; ++c) dl[c] = S->link_of[S->active_ids[c]];
+    dex_task_entries(S, fr, rw);
+  } else {
+    for (int e = 0; e < n; ++e) {
+      dl[e] = S->link_of[links[e]];
+      memcpy(&fr[(size_t)12 * e], frames ? frames + 12 * e : IDENT12, sizeof(IDENT12));
+      if (rows) rw[e] = rows[e];
+    }
+  }
+  const size_t pairs = (size_t)S->B * n, bytes = sizeof(double) * pairs * DEX_N;
+  double* d_fr; int *d_dl, *d_rows;
+  if ((rc = jac_stage_entries(S, dl.data(), fr.data(), rw.data(), n, &d_fr, &d_dl, &d_rows))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  hipLaunchKernelGGL(k_frame_dexterity, grid1(pairs), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q, (const int*)d_dl,
+                     (const double*)d_fr, (const int*)d_rows, n, S->B, p->length, dst);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (dl, fr and rw are locals)
+  return LOIKB_OK;
+}
+
+int loikb_dexterity_set_multistart_pick(loikb_solver* S, const loikb_dexterity_params* p)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState& P = S->pose;
+  if (!p) { P.have_dex = false; return LOIKB_OK; }
+  if (!dex_params_ok(p)) { g_last_error = "dexterity_set_multistart_pick: need a finite length > 0 and flags 0"; return LOIKB_ERR_ARG; }
+  P.dex = *p;
+  P.have_dex = true;
+  return LOIKB_OK;
+}
+
+int loikb_dexterity_get_multistart_pick(const loikb_solver* S, loikb_dexterity_params* out)
+{
+  if (!S || !S->pose.have_dex) return 0;
+  if (out) *out = S->pose.dex;
+  return 1;
+}
+
+// The cost of class 0 of a dexterous multi-start selection into M.d_dexcost: k_frame_dexterity in the links == NULL mode over all B
+// resident rows (the device joints of the active constraints are P.d_clink, which the pose loop just left), then the reduction
+// to - min_c sigma_{m_c - 1}.  Queued; the staging is the handle's.
+static int ms_dex_cost(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  const loikb_solver_impl::PoseState& P = S->pose;
+  const size_t B = (size_t)S->B, ncap = (size_t)std::max(S->nc, 1);
+  const int nc = S->nc_active;
+  int rc;
+  if (!M.d_dexcost) {
+    if ((rc = alloc_dev(S, (void**)&M.d_dex, sizeof(double) * B * ncap * DEX_N)) || (rc = alloc_dev(S, (void**)&M.d_dexfr, sizeof(double) * ncap * 12)) ||
+        (rc = alloc_dev(S, (void**)&M.d_dexrows, sizeof(int) * ncap)) || (rc = alloc_dev(S, (void**)&M.d_dexcost, sizeof(double) * B))) {
+      M.d_dexcost = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+      return rc;
+    }
+  }
+  dex_task_entries(S, M.dex_fr, M.dex_rows);
+  HIPCHK(hipMemcpyAsync(M.d_dexfr, M.dex_fr.data(), sizeof(double) * 12 * nc, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(M.d_dexrows, M.dex_rows.data(), sizeof(int) * nc, hipMemcpyHostToDevice, S->stream));
+  hipLaunchKernelGGL(k_frame_dexterity, grid1(B * nc), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q, (const int*)P.d_clink,
+                     (const double*)M.d_dexfr, (const int*)M.d_dexrows, nc, S->B, P.dex.length, M.d_dex);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_dex_cost, grid1(B), dim3(256), 0, S->stream, (const double*)M.d_dex, (const int*)M.d_dexrows, nc, S->B, M.d_dexcost);
+  HIPCHK(hipGetLastError());
   return LOIKB_OK;
 }
 
@@ -878,11 +1057,17 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
   M.G = 0;
   const loikb_solver_impl::PoseState& P = S->pose;
   auto select = [&](int count_only) -> int {
+    const double* cost_in = nullptr;   // the dexterous pick (loik_amd_jacobian.h): the final selection's cost of a reached seed
+    if (!count_only && P.have_dex) {
+      int rcd;
+      if ((rcd = ms_dex_cost(S))) return rcd;
+      cost_in = M.d_dexcost;
+    }
     HIPCHK(hipMemsetAsync(M.d_count, 0, sizeof(unsigned int), S->stream));
     hipLaunchKernelGGL(k_ms_select, dim3((unsigned)G), dim3(MS_SELECT_THREADS), 0, S->stream, (const int*)P.d_status, (const double*)P.d_err,
                        (const double*)S->d_q, (const double*)M.d_q0, (const int*)M.d_dofq, M.w.empty() ? (const double*)nullptr : (const double*)M.d_w,
                        S->nv, S->nq, nc, K, (int)(ms->pick == LOIKB_MS_PICK_FIRST), count_only, M.d_count, M.d_winner, M.d_gstatus, M.d_cost,
-                       M.d_nreached, M.d_wq, M.d_werr);
+                       M.d_nreached, M.d_wq, M.d_werr, cost_in);
     HIPCHK(hipGetLastError());
     return LOIKB_OK;
   };

@@ -84,12 +84,13 @@ __device__ __forceinline__ bool ms_before(const MsKey& a, const MsKey& b)
 
 constexpr int MS_SELECT_THREADS = 256;
 
-// dofq [nv]: the coordinate of a plain-sum DoF in a row of q, -1 for every other DoF (lim_q of the host); w [nv] or NULL = 1
+// dofq [nv]: the coordinate of a plain-sum DoF in a row of q, -1 for every other DoF (lim_q of the host); w [nv] or NULL = 1;
+// cost_in [B] or NULL: the cost of a reached instance is read from it instead (the dexterous pick of loik_amd_jacobian.h)
 __global__ void __launch_bounds__(MS_SELECT_THREADS)
 k_ms_select(const int* __restrict__ status, const double* __restrict__ err, const double* __restrict__ q, const double* __restrict__ q0,
             const int* __restrict__ dofq, const double* __restrict__ w, int nv, int nq, int nc, int K, int pick_first, int count_only,
             unsigned int* __restrict__ goals_reached, int* __restrict__ winner, int* __restrict__ goal_status, double* __restrict__ cost_out,
-            int* __restrict__ nreached, double* __restrict__ q_out, double* __restrict__ err_out)
+            int* __restrict__ nreached, double* __restrict__ q_out, double* __restrict__ err_out, const double* __restrict__ cost_in)
 {
   __shared__ MsKey sh_key[MS_SELECT_THREADS / 64];
   __shared__ int sh_n[MS_SELECT_THREADS / 64];
@@ -112,6 +113,8 @@ k_ms_select(const int* __restrict__ status, const double* __restrict__ err, cons
         }
         cur.cost = m;
       }
+    } else if (!count_only && cost_in) {
+      cur.cost = cost_in[b];
     } else if (!count_only && !pick_first) {
       const double *row = q + (size_t)b * nq, *ref = q0 + (size_t)g * nq;
       double sum = 0.0;
