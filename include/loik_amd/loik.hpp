@@ -26,6 +26,7 @@
 #include "../loik_amd_step.h"
 #include "../loik_amd_axis.h"
 #include "../loik_amd_jacobian.h"
+#include "../loik_amd_collision.h"
 
 #include <array>
 #include <map>
@@ -538,6 +539,60 @@ public:
     loikb_dexterity_params p{0.0, 0};
     return loikb_dexterity_get_multistart_pick(h_, &p) ? p.length : 0.0;
   }
+  // ---- collision clearance (include/loik_amd_collision.h): a sphere model of the robot against a world of spheres and oriented boxes and
+  // against itself.  spheres [ns][4] = (x, y, z, r) in the frame of links[s] (0 = the universe); empty clears the spheres and the self pairs
+  void setCollisionSpheres(const std::vector<Index>& links, const DVec& spheres)
+  {
+    if (spheres.size() != 4 * links.size()) throw std::runtime_error("loik_amd: need four numbers per sphere");
+    std::vector<int> l(links.begin(), links.end());
+    check(loikb_collision_set_spheres(h_, l.data(), spheres.data(), (int)l.size()));
+  }
+  // world spheres [nws][4] = (x, y, z, r) and oriented boxes [nwb][15] = (R row-major, p, half extents); both empty clears the world
+  void setCollisionWorld(const DVec& wspheres = {}, const DVec& wboxes = {})
+  {
+    if (wspheres.size() % 4 != 0 || wboxes.size() % 15 != 0) throw std::runtime_error("loik_amd: need 4 numbers per world sphere, 15 per box");
+    check(loikb_collision_set_world(h_, wspheres.data(), (int)(wspheres.size() / 4), wboxes.data(), (int)(wboxes.size() / 15)));
+  }
+  // the sphere pairs (a < b) whose links differ, are not parent and child and are not in `ignore` (link pairs, either order)
+  void setSelfCollision(bool enable = true, const std::vector<std::array<Index, 2>>& ignore = {})
+  {
+    std::vector<int> ig;
+    for (const auto& pr : ignore) { ig.push_back((int)pr[0]); ig.push_back((int)pr[1]); }
+    check(loikb_collision_set_self_pairs(h_, enable ? 1 : 0, ig.data(), (int)ignore.size()));
+  }
+  int NumSelfPairs() const { return loikb_collision_num_self_pairs(h_); }
+  struct ClearanceResult {
+    DVec min, min_world, min_self;   // [n]; +inf over an empty set of pairs, NaN for a q that is not finite
+    std::vector<int> witness;        // [n][3] = (LOIKB_CLR_* kind, robot sphere, obstacle or other sphere) of the pair that achieves min
+  };
+  // of the resident q of the batch (q = nullptr), or of any number of configurations q [n][nq]
+  ClearanceResult Clearance(const DVec* q = nullptr) const
+  {
+    const std::size_t n = q ? q->size() / (std::size_t)model_.nq : (std::size_t)batch_;
+    if (q && q->size() != n * (std::size_t)model_.nq) throw std::runtime_error("loik_amd: q is not a whole number of configurations");
+    DVec m(3 * n);
+    ClearanceResult r;
+    r.witness.resize(3 * n);
+    check(loikb_clearance(h_, q ? q->data() : nullptr, (int)n, 0, m.data(), r.witness.data(), 0));
+    r.min.resize(n); r.min_world.resize(n); r.min_self.resize(n);
+    for (std::size_t i = 0; i < n; ++i) { r.min[i] = m[3 * i]; r.min_world[i] = m[3 * i + 1]; r.min_self[i] = m[3 * i + 2]; }
+    return r;
+  }
+  // the collision-aware SolvePoseMultiStart: a goal is answered only by a reached seed whose clearance is >= margin; clear: as if never
+  // set.  MultiStartClearance(&margin) returns whether it is set
+  void setMultiStartClearance(double margin = 0.0)
+  {
+    const loikb_clearance_params p{margin, 0};
+    check(loikb_clearance_set_multistart(h_, &p));
+  }
+  void clearMultiStartClearance() { check(loikb_clearance_set_multistart(h_, nullptr)); }
+  bool MultiStartClearance(double* margin = nullptr) const
+  {
+    loikb_clearance_params p{0.0, 0};
+    if (!loikb_clearance_get_multistart(h_, &p)) return false;
+    if (margin) *margin = p.margin;
+    return true;
+  }
   // ---- multi-start pose IK (include/loik_amd_multistart.h): batch = G goals * K seeds, instance g * K + k is seed k of goal g
   // the ranges [nv] the seeds are drawn from (a DoF is sampled iff both ends are finite; both empty = the joint limits) and the
   // weights [nv] of the nearest-seed metric (empty = 1)
@@ -560,6 +615,9 @@ public:
     DVec q, err, cost;                               // [G][nq], [G][nc][6], [G]
     int rounds_run = 0;
     std::array<double, 6> timing{};                  // LOIKB_MS_F_TIMING
+    // with setMultiStartClearance (include/loik_amd_collision.h), else empty: the winner's clearance and witness, the goal's clear seeds
+    DVec clearance;                                  // [G]
+    std::vector<int> witness, nclear;                // [G][3], [G]
   };
   // targets: one per goal and active constraint (G * nc, goal-major), or nc shared by the goals; q0 as SampleSeeds takes it
   MultiStartResult SolvePoseMultiStart(const std::vector<SE3>& targets, int seeds_per_goal, int rounds = 1, unsigned long long seed = 0,
@@ -591,6 +649,12 @@ public:
     check(loikb_multistart_get(h_, LOIKB_MS_F_COST, r.cost.data(), 0));
     check(loikb_multistart_get(h_, LOIKB_MS_F_TIMING, r.timing.data(), 0));
     r.rounds_run = (int)r.timing[0];
+    if (MultiStartClearance()) {
+      r.clearance.resize(G); r.witness.resize(3 * G); r.nclear.resize(G);
+      check(loikb_clearance_get_multistart_result(h_, LOIKB_CLR_MS_F_CLEARANCE, r.clearance.data(), 0));
+      check(loikb_clearance_get_multistart_result(h_, LOIKB_CLR_MS_F_WITNESS, r.witness.data(), 0));
+      check(loikb_clearance_get_multistart_result(h_, LOIKB_CLR_MS_F_NCLEAR, r.nclear.data(), 0));
+    }
     return r;
   }
   // ---- waypoint paths (include/loik_amd_path.h): SolvePose along T waypoints per instance, each instance at its own pace

@@ -177,6 +177,16 @@ JACOBIAN_SYMBOLS = ["loikb_jacobian_version", "loikb_frame_jacobians", "loikb_fr
 JAC_LOCAL, JAC_LOCAL_WORLD_ALIGNED, JAC_WORLD = 0, 1, 2
 JAC_REFERENCES = {"local": JAC_LOCAL, "local_world_aligned": JAC_LOCAL_WORLD_ALIGNED, "world": JAC_WORLD}
 DEX_SIGMA0, DEX_MANIPULABILITY, DEX_INV_CONDITION, DEX_N = 0, 6, 7, 8
+# include/loik_amd_collision.h: clearance of a sphere model against a world of spheres and boxes and against itself, and the
+# collision-aware multi-start; its own header and version again (the MS_GOAL_* of the multi-start header stay its three)
+COLLISION_ABI_VERSION = 1
+COLLISION_SYMBOLS = ["loikb_collision_version", "loikb_collision_set_spheres", "loikb_collision_set_world", "loikb_collision_set_self_pairs",
+                     "loikb_collision_num_self_pairs", "loikb_clearance", "loikb_clearance_set_multistart", "loikb_clearance_get_multistart",
+                     "loikb_clearance_get_multistart_result"]
+CLR_NONE, CLR_WORLD_SPHERE, CLR_WORLD_BOX, CLR_SELF = 0, 1, 2, 3
+CLR_MAX_SPHERES = 2048
+MS_GOAL_IN_COLLISION = 8
+CLR_MS_F_CLEARANCE, CLR_MS_F_WITNESS, CLR_MS_F_NCLEAR, CLR_MS_F_INSTANCE = range(4)
 
 
 class PoseParams(C.Structure):
@@ -189,6 +199,10 @@ class StepParams(C.Structure):
 
 class DexterityParams(C.Structure):
     _fields_ = [("length", C.c_double), ("flags", C.c_int)]
+
+
+class ClearanceParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -289,6 +303,14 @@ def lib():
     L.loikb_frame_dexterity.argtypes = [C.c_void_p, _ip, _dp, _ip, C.c_int, C.POINTER(DexterityParams), C.c_void_p, C.c_int]
     L.loikb_dexterity_set_multistart_pick.argtypes = [C.c_void_p, C.POINTER(DexterityParams)]
     L.loikb_dexterity_get_multistart_pick.argtypes = [C.c_void_p, C.POINTER(DexterityParams)]
+    L.loikb_collision_set_spheres.argtypes = [C.c_void_p, _ip, _dp, C.c_int]
+    L.loikb_collision_set_world.argtypes = [C.c_void_p, _dp, C.c_int, _dp, C.c_int]
+    L.loikb_collision_set_self_pairs.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int]
+    L.loikb_collision_num_self_pairs.argtypes = [C.c_void_p]
+    L.loikb_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_clearance_set_multistart.argtypes = [C.c_void_p, C.POINTER(ClearanceParams)]
+    L.loikb_clearance_get_multistart.argtypes = [C.c_void_p, C.POINTER(ClearanceParams)]
+    L.loikb_clearance_get_multistart_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1059,6 +1081,99 @@ class BatchedLoik:
             return None
         return dict(length=prm.length)
 
+    # ---- collision clearance (include/loik_amd_collision.h) --------------------------------------------------
+    def set_collision_spheres(self, links, spheres):
+        """the robot's sphere model (loikb_collision_set_spheres): links [ns] joint ids (0 = the universe), spheres [ns][4] = (x, y, z, r) in
+        the link's frame.  Empty arrays clear the spheres and the self pairs."""
+        links = np.ascontiguousarray(np.atleast_1d(links), dtype=np.int32).reshape(-1)
+        sph = _f64(spheres).reshape(-1, 4)
+        if sph.shape[0] != links.size:
+            raise ValueError("spheres: %d rows for %d links" % (sph.shape[0], links.size))
+        _check(self.L.loikb_collision_set_spheres(self.h, links.ctypes.data_as(_ip), sph.ctypes.data_as(_dp), int(links.size)))
+
+    def set_collision_world(self, spheres=None, boxes=None):
+        """the world every instance shares (loikb_collision_set_world): spheres [nws][4] = (x, y, z, r); boxes [nwb][15] = (R row-major, p,
+        half extents), or a list of (T [4][4], half_extents [3]).  None, None clears the world."""
+        ws = np.zeros((0, 4)) if spheres is None else _f64(spheres).reshape(-1, 4)
+        if boxes is None:
+            wb = np.zeros((0, 15))
+        elif isinstance(boxes, np.ndarray):
+            wb = _f64(boxes).reshape(-1, 15)
+        else:
+            rows = []
+            for bx in boxes:
+                if len(bx) == 2:
+                    T, h = np.asarray(bx[0], dtype=np.float64), np.asarray(bx[1], dtype=np.float64).reshape(3)
+                    rows.append(np.concatenate([T[:3, :3].reshape(9), T[:3, 3], h]))
+                else:
+                    rows.append(np.asarray(bx, dtype=np.float64).reshape(15))
+            wb = _f64(rows).reshape(-1, 15)
+        _check(self.L.loikb_collision_set_world(self.h, ws.ctypes.data_as(_dp), int(ws.shape[0]), wb.ctypes.data_as(_dp), int(wb.shape[0])))
+
+    def set_self_collision(self, enable=True, ignore=()):
+        """self pairs on or off (loikb_collision_set_self_pairs): with enable the sphere pairs (a < b) whose links differ, are not parent
+        and child and are not in ignore [(link_i, link_j), ...] (either order)"""
+        ig = np.ascontiguousarray(np.asarray(list(ignore), dtype=np.int32).reshape(-1, 2))
+        _check(self.L.loikb_collision_set_self_pairs(self.h, 1 if enable else 0, ig.ctypes.data_as(_ip), int(ig.shape[0])))
+
+    def num_self_pairs(self):
+        return int(self.L.loikb_collision_num_self_pairs(self.h))
+
+    def clearance(self, q=None, out=None):
+        """the minimum clearance of configurations and the pair that achieves it (loikb_clearance).  q None: the resident q of the batch;
+        else [n][nq] on the host, or a device pointer / torch tensor (then give n rows by its numel; a raw pointer as (ptr, n)).
+        Returns dict(min [n], min_world [n], min_self [n], witness [n][3] = (CLR_* kind, robot sphere, obstacle or other sphere)), or
+        with out = (min_dev, witness_dev) device buffers of 3 n float64 / 3 n int32 (witness_dev may be None) writes there and returns out."""
+        nq = self.model.nq
+        flags = 0
+        keep = None
+        if q is None:
+            qp, n = None, self.batch
+        elif isinstance(q, tuple):
+            qp, n, flags = C.c_void_p(int(q[0])), int(q[1]), IN_DEVICE
+        elif hasattr(q, "data_ptr") and getattr(q, "is_cuda", False):
+            qp, n, flags = C.c_void_p(q.data_ptr()), int(q.numel()) // nq, IN_DEVICE
+        else:
+            keep = _f64(q.numpy() if hasattr(q, "numpy") else q).reshape(-1, nq)
+            qp, n = keep.ctypes.data_as(C.c_void_p), int(keep.shape[0])
+        if out is not None:
+            mp, _ = _ptr(out[0])
+            wp, _ = _ptr(out[1])
+            _check(self.L.loikb_clearance(self.h, qp, n, flags, mp, wp, OUT_DEVICE))
+            return out
+        mins = np.empty((n, 3))
+        wit = np.empty((n, 3), dtype=np.int32)
+        _check(self.L.loikb_clearance(self.h, qp, n, flags, mins.ctypes.data_as(C.c_void_p), wit.ctypes.data_as(C.c_void_p), 0))
+        return dict(min=mins[:, 0].copy(), min_world=mins[:, 1].copy(), min_self=mins[:, 2].copy(), witness=wit)
+
+    def set_multistart_clearance(self, margin=0.0):
+        """every later SolvePoseMultiStart answers a goal only with a reached seed whose clearance is >= margin
+        (loikb_clearance_set_multistart)"""
+        prm = ClearanceParams(float(margin), 0)
+        _check(self.L.loikb_clearance_set_multistart(self.h, C.byref(prm)))
+
+    def clear_multistart_clearance(self):
+        _check(self.L.loikb_clearance_set_multistart(self.h, None))
+
+    def multistart_clearance(self):
+        """dict(margin) as set, None when the collision-aware selection is not set"""
+        prm = ClearanceParams()
+        if not self.L.loikb_clearance_get_multistart(self.h, C.byref(prm)):
+            return None
+        return dict(margin=prm.margin)
+
+    def multistart_clearance_get(self, name):
+        """one result of the last SolvePoseMultiStart that ran with the collision-aware selection
+        (loikb_clearance_get_multistart_result): clearance [G] / witness [G][3] / nclear [G] / instance [B]"""
+        fid, dtype, per = {"clearance": (CLR_MS_F_CLEARANCE, np.float64, 1), "witness": (CLR_MS_F_WITNESS, np.int32, 3),
+                           "nclear": (CLR_MS_F_NCLEAR, np.int32, 1), "instance": (CLR_MS_F_INSTANCE, np.float64, 1)}[name]
+        big = np.empty(self.batch * per, dtype=dtype)
+        _check(self.L.loikb_clearance_get_multistart_result(self.h, fid, big.ctypes.data_as(C.c_void_p), 0))
+        if name == "instance":
+            return big
+        G = self._ms_goals
+        return big[:G * per].reshape((G, 3) if per == 3 else (G,)).copy()
+
     # ---- multi-start pose IK (include/loik_amd_multistart.h) ------------------------------------------------
     def set_seed_ranges(self, s_lo=None, s_hi=None, weights=None):
         """the ranges [nv] (idx_v order) the seeds are drawn from (loikb_multistart_set_ranges): a DoF is sampled iff both ends are
@@ -1094,7 +1209,7 @@ class BatchedLoik:
         _check(self.L.loikb_multistart_sample(self.h, qp, qf, int(seed), K, int(round)))
 
     def SolvePoseMultiStart(self, targets, seeds_per_goal, rounds=1, seed=0, pick="nearest", q0=None, dt=1.0, gain=1.0, tol_pose=1e-6,
-                            max_steps=100, length=1.0):
+                            max_steps=100, length=1.0, clearance_margin=None):
         """G = batch / seeds_per_goal goals, K = seeds_per_goal seeds each (loikb_solve_pose_multistart): instance g * K + k is seed k
         of goal g.  Seeds are drawn on the device inside the seed ranges (set_seed_ranges; default the joint limits), SolvePose
         runs on the whole batch, instances without REACHED are re-seeded for up to rounds - 1 restarts while a goal is
@@ -1104,8 +1219,23 @@ class BatchedLoik:
         pick: "nearest" (to q0), "first", or "dexterous" (include/loik_amd_jacobian.h: the reached seed whose worst task has the
         largest smallest singular value, linear rows scaled by 1 / length; set for this call alone -- a pick latched with
         set_multistart_pick_dexterous is back in force afterwards, and is what ranks the reached seeds whenever it is set).
+        clearance_margin: a number sets the collision-aware selection of include/loik_amd_collision.h for this call alone (a latch set
+        with set_multistart_clearance is back in force afterwards): a goal is answered only by a reached seed whose clearance is >= the
+        margin, a goal with only colliding answers gets MS_GOAL_IN_COLLISION, and the result gains clearance [G], witness [G][3] and
+        nclear [G] (as it does whenever the latch is set).
         Returns dict(winner [G], goal_status [G] MS_GOAL_* bits, q [G][nq], err [G][nc][6], cost [G], nreached [G], round [B],
         rounds_run, timing)."""
+        if clearance_margin is not None:
+            held = self.multistart_clearance()
+            self.set_multistart_clearance(clearance_margin)
+            try:
+                return self.SolvePoseMultiStart(targets, seeds_per_goal, rounds=rounds, seed=seed, pick=pick, q0=q0, dt=dt, gain=gain,
+                                                tol_pose=tol_pose, max_steps=max_steps, length=length)
+            finally:
+                if held is None:
+                    self.clear_multistart_clearance()
+                else:
+                    self.set_multistart_clearance(held["margin"])
         if pick == "dexterous":
             before = self.multistart_pick_dexterous()
             self.set_multistart_pick_dexterous(length)
@@ -1151,6 +1281,9 @@ class BatchedLoik:
         self._ms_goals = G
         out = {name: self.multistart_get(name) for name in ("winner", "goal_status", "q", "err", "cost", "nreached", "round", "timing")}
         out["rounds_run"] = out["timing"]["rounds"]
+        if self.multistart_clearance() is not None:
+            for name in ("clearance", "witness", "nclear"):
+                out[name] = self.multistart_clearance_get(name)
         return out
 
     def multistart_get(self, name):

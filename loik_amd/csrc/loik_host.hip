@@ -26,6 +26,7 @@
 #include "loik_pose_accel.hpp"
 #include "loik_pose_step.hpp"
 #include "loik_pose_jacobian.hpp"
+#include "loik_pose_collision.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -47,6 +48,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_step.h"
 #include "../../include/loik_amd_axis.h"
 #include "../../include/loik_amd_jacobian.h"
+#include "../../include/loik_amd_collision.h"
 
 #include <algorithm>
 #include <chrono>
@@ -399,6 +401,23 @@ struct loikb_solver_impl {
     // the dexterous multi-start pick (loik_amd_jacobian.h)
     bool have_dex = false;             // loikb_dexterity_set_multistart_pick set `dex`
     loikb_dexterity_params dex = {1.0, 0};
+    // the collision model (loik_amd_collision.h): spheres, world and self pairs, each uploaded when it is set, and the latch of the
+    // collision-aware multi-start.  The device buffers are the model's own (replaced when a latch is set again, freed by loikb_destroy)
+    struct Collision {
+      std::vector<int> links;            // [ns] the caller's link of each sphere
+      std::vector<int> car, scar;        // the distinct device joints that carry spheres; [ns] each sphere's index into car
+      int ns = 0, nws = 0, nwb = 0;
+      bool self_on = false;              // loikb_collision_set_self_pairs(enable = 1)
+      std::vector<int> ignore;           // [ni][2] the caller's link pairs never tested
+      std::vector<unsigned short> pairs; // [npairs][2] host copy of d_pairs
+      double *d_sph = nullptr, *d_wsph = nullptr, *d_wbox = nullptr;   // [ns][4], [nws][4], [nwb][15]
+      int *d_scar = nullptr, *d_car = nullptr;                         // [ns], [ncar]
+      unsigned short* d_pairs = nullptr;                               // [npairs][2]
+      double* d_place = nullptr;         // [n][ncar][12] k_link_placements' output for k_clearance<true>, grown on demand
+      size_t place_cap = 0;              // bytes of d_place
+      bool have_ms = false;              // loikb_clearance_set_multistart set `ms`
+      loikb_clearance_params ms = {0.0, 0};
+    } col;
   } pose;
   // multi-start pose IK (loik_pose_multistart.hpp): buffers of loikb_multistart_sample / loikb_solve_pose_multistart, allocated by
   // the first call of either (sizes: batch and slot capacity; a goal count G <= B fits whatever K is)
@@ -424,6 +443,13 @@ struct loikb_solver_impl {
     int* d_dexrows = nullptr;          // [nc] the tasks' row masks
     std::vector<double> dex_fr;        // host staging of d_dexfr (outlives the copy)
     std::vector<int> dex_rows;         // likewise, d_dexrows
+    // the collision-aware selection (loik_amd_collision.h), allocated by the first multi-start that runs with it
+    double* d_clr = nullptr;           // [B][3] k_clearance's minima of the resident q after the last pose loop
+    int* d_clrwit = nullptr;           // [B][3] its witnesses
+    int* d_lstatus = nullptr;          // [B] the loop-private status word of the re-sampler: REACHED cleared on class 0c
+    double *d_iclr = nullptr, *d_wclr = nullptr;   // [B] LOIKB_CLR_MS_F_INSTANCE, [G] LOIKB_CLR_MS_F_CLEARANCE
+    int *d_wwit = nullptr, *d_nclear = nullptr;    // [G][3] LOIKB_CLR_MS_F_WITNESS, [G] LOIKB_CLR_MS_F_NCLEAR
+    bool clr_valid = false;            // the last loikb_solve_pose_multistart ran with the latch: the four above are its results
     int G = 0, nc = 0;                 // of the last loikb_solve_pose_multistart (G = 0: none yet)
     double timing[6] = {0, 0, 0, 0, 0, 0};   // LOIKB_MS_F_TIMING
   } ms;
@@ -3152,6 +3178,9 @@ int loikb_destroy(loikb_solver* S)
   if (S->path.d_wsteps) (void)hipFree(S->path.d_wsteps);
   if (S->path.d_Q) (void)hipFree(S->path.d_Q);
   for (void* p : {(void*)S->track.d_smp, (void*)S->track.d_errmax, (void*)S->track.d_inner, (void*)S->track.d_Q, (void*)S->track.d_Z})
+    if (p) (void)hipFree(p);
+  for (void* p : {(void*)S->pose.col.d_sph, (void*)S->pose.col.d_wsph, (void*)S->pose.col.d_wbox, (void*)S->pose.col.d_scar, (void*)S->pose.col.d_car,
+                  (void*)S->pose.col.d_pairs, (void*)S->pose.col.d_place})
     if (p) (void)hipFree(p);
   (void)hipGetLastError();  // a failed free must not surface in the next solver's first launch check
   if (S->own_stream) (void)hipStreamDestroy(S->own_stream);

@@ -1,6 +1,6 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
 // (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), step control (loik_amd_step.h), tool frames and tasks (loik_amd_tasks.h), frame
-// Jacobians and dexterity (loik_amd_jacobian.h), multi-start (loik_amd_multistart.h), waypoint paths
+// Jacobians and dexterity (loik_amd_jacobian.h), collision clearance (loik_amd_collision.h), multi-start (loik_amd_multistart.h), waypoint paths
 // (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
 // belongs to: it is no header of its own.
 //
@@ -883,6 +883,289 @@ static int ms_dex_cost(loikb_solver_impl* S)
   return LOIKB_OK;
 }
 
+// ---- include/loik_amd_collision.h (kernels in loik_pose_collision.hpp) ---------------------------------------------------------
+int loikb_collision_version(void) { return LOIKB_COLLISION_VERSION; }
+
+using Collision = loikb_solver_impl::PoseState::Collision;
+
+// a device copy of `bytes` of host memory in a buffer of its own (nullptr for bytes == 0); complete on return
+static int col_upload(loikb_solver_impl* S, const void* src, size_t bytes, void** out)
+{
+  *out = nullptr;
+  if (bytes == 0) return LOIKB_OK;
+  void* p = nullptr;
+  HIPCHK(hipMalloc(&p, bytes));
+  if (hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, S->stream) != hipSuccess || hipStreamSynchronize(S->stream) != hipSuccess) {
+    (void)hipFree(p);
+    (void)hipGetLastError();
+    g_last_error = "collision: the upload of the model failed";
+    return LOIKB_ERR_HIP;
+  }
+  *out = p;
+  return LOIKB_OK;
+}
+
+// the parent of every link in the caller's tree, from the device tree: the link whose last chain joint is the parent of the first
+static std::vector<int> col_ext_parents(const loikb_solver_impl* S)
+{
+  std::vector<int> ext_of(S->nj, 0), par(S->ext_nj, -1);
+  for (int i = 1; i < S->ext_nj; ++i) ext_of[S->link_of[i]] = i;
+  for (int i = 1; i < S->ext_nj; ++i) par[i] = ext_of[S->parents[S->first_of[i]]];
+  return par;
+}
+
+// the self-pair list of `links` [ns] under `ignore` [ni][2]: (a < b) lexicographic, the links differ, neither is the other's parent,
+// the link pair is not ignored
+static std::vector<unsigned short> col_build_pairs(const loikb_solver_impl* S, const std::vector<int>& links, const std::vector<int>& ignore)
+{
+  const std::vector<int> par = col_ext_parents(S);
+  const int ns = (int)links.size(), nl = S->ext_nj;
+  std::vector<char> skip((size_t)nl * nl, 0);
+  for (size_t k = 0; k + 1 < ignore.size(); k += 2) {
+    skip[(size_t)ignore[k] * nl + ignore[k + 1]] = 1;
+    skip[(size_t)ignore[k + 1] * nl + ignore[k]] = 1;
+  }
+  std::vector<unsigned short> pairs;
+  for (int a = 0; a < ns; ++a)
+    for (int b = a + 1; b < ns; ++b) {
+      const int la = links[a], lb = links[b];
+      if (la == lb || par[la] == lb || par[lb] == la || skip[(size_t)la * nl + lb]) continue;
+      pairs.push_back((unsigned short)a);
+      pairs.push_back((unsigned short)b);
+    }
+  return pairs;
+}
+
+// the ordinal of a pair is 32 bits with one value kept for "none"
+static bool col_ordinals_fit(size_t ns, size_t nws, size_t nwb, size_t npairs) { return ns * (nws + nwb) + npairs < (size_t)0x7fffffff; }
+
+int loikb_collision_set_spheres(loikb_solver* S, const int* links, const double* spheres, int ns)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (ns < 0 || (ns > 0 && (!links || !spheres))) { g_last_error = "collision_set_spheres: need ns >= 0 and both arrays when ns > 0"; return LOIKB_ERR_ARG; }
+  if (ns > LOIKB_CLR_MAX_SPHERES) { g_last_error = "collision_set_spheres: more than LOIKB_CLR_MAX_SPHERES spheres"; return LOIKB_ERR_ARG; }
+  for (int i = 0; i < ns; ++i) {
+    const std::string what = "collision_set_spheres: sphere " + std::to_string(i);
+    if (links[i] < 0 || links[i] >= S->ext_nj) { g_last_error = what + ": link id out of range"; return LOIKB_ERR_ARG; }
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(spheres[4 * i + k])) { g_last_error = what + ": a number is not finite"; return LOIKB_ERR_ARG; }
+    if (spheres[4 * i + 3] < 0.0) { g_last_error = what + ": negative radius"; return LOIKB_ERR_ARG; }
+  }
+  Collision& C = S->pose.col;
+  HIPCHK(hipSetDevice(S->device));
+  std::vector<int> lk(links, links + ns), car, scar(ns), slot(S->nj, -1);
+  for (int i = 0; i < ns; ++i) {
+    const int dj = S->link_of[lk[i]];
+    if (slot[dj] < 0) { slot[dj] = (int)car.size(); car.push_back(dj); }
+    scar[i] = slot[dj];
+  }
+  std::vector<unsigned short> pairs;
+  if (ns > 0 && C.self_on) pairs = col_build_pairs(S, lk, C.ignore);
+  if (!col_ordinals_fit(ns, C.nws, C.nwb, pairs.size() / 2)) { g_last_error = "collision_set_spheres: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  void *d_sph, *d_scar = nullptr, *d_car = nullptr, *d_pairs = nullptr;
+  int rc;
+  if ((rc = col_upload(S, spheres, sizeof(double) * 4 * ns, &d_sph)) || (rc = col_upload(S, scar.data(), sizeof(int) * ns, &d_scar)) ||
+      (rc = col_upload(S, car.data(), sizeof(int) * car.size(), &d_car)) || (rc = col_upload(S, pairs.data(), sizeof(unsigned short) * pairs.size(), &d_pairs))) {
+    for (void* p : {d_sph, d_scar, d_car, d_pairs}) if (p) (void)hipFree(p);
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (nothing queued reads the buffers that go)
+  for (void* p : {(void*)C.d_sph, (void*)C.d_scar, (void*)C.d_car, (void*)C.d_pairs}) if (p) (void)hipFree(p);
+  C.d_sph = (double*)d_sph; C.d_scar = (int*)d_scar; C.d_car = (int*)d_car; C.d_pairs = (unsigned short*)d_pairs;
+  C.links.swap(lk); C.car.swap(car); C.scar.swap(scar); C.pairs.swap(pairs);
+  C.ns = ns;
+  if (ns == 0) { C.self_on = false; C.ignore.clear(); }
+  return LOIKB_OK;
+}
+
+int loikb_collision_set_world(loikb_solver* S, const double* wspheres, int nws, const double* wboxes, int nwb)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (nws < 0 || nwb < 0 || (nws > 0 && !wspheres) || (nwb > 0 && !wboxes)) { g_last_error = "collision_set_world: need counts >= 0 and an array for a positive count"; return LOIKB_ERR_ARG; }
+  for (int i = 0; i < nws; ++i) {
+    const std::string what = "collision_set_world: sphere " + std::to_string(i);
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(wspheres[4 * i + k])) { g_last_error = what + ": a number is not finite"; return LOIKB_ERR_ARG; }
+    if (wspheres[4 * i + 3] < 0.0) { g_last_error = what + ": negative radius"; return LOIKB_ERR_ARG; }
+  }
+  for (int i = 0; i < nwb; ++i) {
+    const std::string what = "collision_set_world: box " + std::to_string(i);
+    const double* W = wboxes + 15 * i;
+    for (int k = 0; k < 15; ++k)
+      if (!std::isfinite(W[k])) { g_last_error = what + ": a number is not finite"; return LOIKB_ERR_ARG; }
+    if (!frame_ok(W)) { g_last_error = what + ": the rotation is not orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+    for (int k = 12; k < 15; ++k)
+      if (!(W[k] > 0.0)) { g_last_error = what + ": a half extent is not > 0"; return LOIKB_ERR_ARG; }
+  }
+  Collision& C = S->pose.col;
+  if (!col_ordinals_fit(C.ns, nws, nwb, C.pairs.size() / 2)) { g_last_error = "collision_set_world: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  HIPCHK(hipSetDevice(S->device));
+  void *d_wsph, *d_wbox = nullptr;
+  int rc;
+  if ((rc = col_upload(S, wspheres, sizeof(double) * 4 * nws, &d_wsph)) || (rc = col_upload(S, wboxes, sizeof(double) * 15 * nwb, &d_wbox))) {
+    if (d_wsph) (void)hipFree(d_wsph);
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));
+  if (C.d_wsph) (void)hipFree(C.d_wsph);
+  if (C.d_wbox) (void)hipFree(C.d_wbox);
+  C.d_wsph = (double*)d_wsph; C.d_wbox = (double*)d_wbox;
+  C.nws = nws; C.nwb = nwb;
+  return LOIKB_OK;
+}
+
+int loikb_collision_set_self_pairs(loikb_solver* S, int enable, const int* ignore_links, int ni)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (ni < 0 || (ni > 0 && !ignore_links)) { g_last_error = "collision_set_self_pairs: need ni >= 0 and ignore_links when ni > 0"; return LOIKB_ERR_ARG; }
+  for (int i = 0; i < 2 * ni; ++i)
+    if (ignore_links[i] < 0 || ignore_links[i] >= S->ext_nj) {
+      g_last_error = "collision_set_self_pairs: ignore pair " + std::to_string(i / 2) + ": link id out of range";
+      return LOIKB_ERR_ARG;
+    }
+  Collision& C = S->pose.col;
+  if (enable && C.ns == 0) { g_last_error = "collision_set_self_pairs: enable = 1 with no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  std::vector<int> ignore;
+  std::vector<unsigned short> pairs;
+  if (enable) {
+    ignore.assign(ignore_links, ignore_links + 2 * (size_t)ni);
+    pairs = col_build_pairs(S, C.links, ignore);
+  }
+  if (!col_ordinals_fit(C.ns, C.nws, C.nwb, pairs.size() / 2)) { g_last_error = "collision_set_self_pairs: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  void* d_pairs;
+  int rc;
+  if ((rc = col_upload(S, pairs.data(), sizeof(unsigned short) * pairs.size(), &d_pairs))) return rc;
+  HIPCHK(hipStreamSynchronize(S->stream));
+  if (C.d_pairs) (void)hipFree(C.d_pairs);
+  C.d_pairs = (unsigned short*)d_pairs;
+  C.pairs.swap(pairs);
+  C.ignore.swap(ignore);
+  C.self_on = enable != 0;
+  return LOIKB_OK;
+}
+
+int loikb_collision_num_self_pairs(const loikb_solver* S) { return S ? (int)(S->pose.col.pairs.size() / 2) : 0; }
+
+// One clearance launch over n rows of the device array dq [n][nq] into d_min [n][3] and d_wit [n][3] (or nullptr).  Queued.
+// As many of CLR_WAVES configurations per workgroup as 64 KB of LDS hold; a model of which one does not fit takes the carriers'
+// placements from k_link_placements through C.d_place
+static int col_launch(loikb_solver_impl* S, const double* dq, int n, double* d_min, int* d_wit)
+{
+  Collision& C = S->pose.col;
+  const int ncar = (int)C.car.size();
+  const bool hbm = clr_wave_doubles(S->nb, ncar, C.ns, false) * sizeof(double) > 65536;
+  const size_t per = clr_wave_doubles(S->nb, ncar, C.ns, hbm) * sizeof(double);
+  int waves = CLR_WAVES;
+  while (waves > 1 && waves * per > 65536) waves >>= 1;
+  int lp = 0;
+  while (lp < 6 && (1 << lp) < C.ns) ++lp;
+  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, ncar, C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const dim3 grid((unsigned)(((size_t)n + waves - 1) / waves)), block(64 * waves);
+  if (hbm) {
+    const size_t need = sizeof(double) * (size_t)n * ncar * 12;
+    if (need > C.place_cap) {
+      HIPCHK(hipStreamSynchronize(S->stream));
+      if (C.d_place) HIPCHK(hipFree(C.d_place));
+      C.d_place = nullptr;
+      C.place_cap = 0;
+      HIPCHK(hipMalloc((void**)&C.d_place, need));
+      C.place_cap = need;
+    }
+    hipLaunchKernelGGL(k_link_placements, grid1((size_t)n * ncar), dim3(256), 0, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, (const int*)C.d_car,
+                       ncar, n, C.d_place);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_clearance<true>, grid, block, waves * per, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, S->nb, n, m,
+                       (const double*)C.d_place, d_min, d_wit);
+  } else {
+    hipLaunchKernelGGL(k_clearance<false>, grid, block, waves * per, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, S->nb, n, m,
+                       (const double*)nullptr, d_min, d_wit);
+  }
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+int loikb_clearance(loikb_solver* S, const double* q, int n, int in_flags, double* out_min, int* out_witness, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (n < 0 || (n > 0 && !out_min)) { g_last_error = "clearance: need n >= 0 and out_min when n > 0"; return LOIKB_ERR_ARG; }
+  if (!q && n != S->B) { g_last_error = "clearance: q == NULL (the resident q) needs n == the batch"; return LOIKB_ERR_ARG; }
+  if (S->pose.col.ns == 0) { g_last_error = "clearance: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (!q && !S->have_q) { g_last_error = "clearance: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const size_t mbytes = sizeof(double) * 3 * (size_t)n, wbytes = sizeof(int) * 3 * (size_t)n;
+  int rc;
+  const void* dq = S->d_q;
+  if (q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) return rc;
+  if (!to_dev && (rc = ensure_getscr(S, 0, mbytes + wbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* d_min = to_dev ? out_min : (double*)S->d_getscr[0];
+  int* d_wit = to_dev ? out_witness : (out_witness ? (int*)((char*)S->d_getscr[0] + mbytes) : nullptr);
+  if ((rc = col_launch(S, (const double*)dq, n, d_min, d_wit))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  if (!to_dev) {
+    HIPCHK(hipMemcpyAsync(out_min, d_min, mbytes, hipMemcpyDeviceToHost, S->stream));
+    if (out_witness) HIPCHK(hipMemcpyAsync(out_witness, d_wit, wbytes, hipMemcpyDeviceToHost, S->stream));
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q has been read)
+  return LOIKB_OK;
+}
+
+int loikb_clearance_set_multistart(loikb_solver* S, const loikb_clearance_params* p)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  Collision& C = S->pose.col;
+  if (!p) { C.have_ms = false; return LOIKB_OK; }
+  if (!std::isfinite(p->margin) || p->flags != 0) { g_last_error = "clearance_set_multistart: need a finite margin and flags 0"; return LOIKB_ERR_ARG; }
+  if (C.ns == 0) { g_last_error = "clearance_set_multistart: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  C.ms = *p;
+  C.have_ms = true;
+  return LOIKB_OK;
+}
+
+int loikb_clearance_get_multistart(const loikb_solver* S, loikb_clearance_params* out)
+{
+  if (!S || !S->pose.col.have_ms) return 0;
+  if (out) *out = S->pose.col.ms;
+  return 1;
+}
+
+// the buffers of the collision-aware selection, on first use
+static int ms_clr_alloc(loikb_solver_impl* S)
+{
+  loikb_solver_impl::MultiStartState& M = S->ms;
+  if (M.d_nclear) return LOIKB_OK;
+  const size_t B = (size_t)S->B;
+  int rc;
+  if ((rc = alloc_dev(S, (void**)&M.d_clr, sizeof(double) * B * 3)) || (rc = alloc_dev(S, (void**)&M.d_clrwit, sizeof(int) * B * 3)) ||
+      (rc = alloc_dev(S, (void**)&M.d_lstatus, sizeof(int) * B)) || (rc = alloc_dev(S, (void**)&M.d_iclr, sizeof(double) * B)) ||
+      (rc = alloc_dev(S, (void**)&M.d_wclr, sizeof(double) * B)) || (rc = alloc_dev(S, (void**)&M.d_wwit, sizeof(int) * B * 3)) ||
+      (rc = alloc_dev(S, (void**)&M.d_nclear, sizeof(int) * B))) {
+    M.d_nclear = nullptr;   // (as pose_alloc: what was allocated goes with the handle; the next call allocates afresh)
+    return rc;
+  }
+  return LOIKB_OK;
+}
+
+int loikb_clearance_get_multistart_result(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  const loikb_solver_impl::MultiStartState& M = S->ms;
+  if (M.G == 0 || !M.clr_valid) { g_last_error = "clearance_get_multistart_result: the last solve_pose_multistart did not run with loikb_clearance_set_multistart"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const void* src = nullptr;
+  size_t bytes = 0;
+  const size_t G = (size_t)M.G;
+  switch (field) {
+  case LOIKB_CLR_MS_F_CLEARANCE: src = M.d_wclr; bytes = sizeof(double) * G; break;
+  case LOIKB_CLR_MS_F_WITNESS: src = M.d_wwit; bytes = sizeof(int) * G * 3; break;
+  case LOIKB_CLR_MS_F_NCLEAR: src = M.d_nclear; bytes = sizeof(int) * G; break;
+  case LOIKB_CLR_MS_F_INSTANCE: src = M.d_iclr; bytes = sizeof(double) * (size_t)S->B; break;
+  default: g_last_error = "clearance_get_multistart_result: unknown field"; return LOIKB_ERR_ARG;
+  }
+  return get_copy_out(S, src, bytes, out, out_flags);
+}
+
 // ---- include/loik_amd_multistart.h (kernels in loik_pose_multistart.hpp) ------------------------------------------------------
 int loikb_multistart_version(void) { return LOIKB_MULTISTART_VERSION; }
 
@@ -1029,6 +1312,10 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
     return LOIKB_ERR_STATE;
   }
   if (int pre = pose_preconditions(S, pose, !q0)) return pre;
+  if (S->pose.col.have_ms && S->pose.col.ns == 0) {
+    g_last_error = "solve_pose_multistart: the handle has the collision-aware selection (loikb_clearance_set_multistart) and no spheres (loikb_collision_set_spheres)";
+    return LOIKB_ERR_STATE;
+  }
   if (ms_resolve_ranges(S) == 0 && (K > 1 || R > 1)) {
     g_last_error = "solve_pose_multistart: no DoF to sample (set ranges with loikb_multistart_set_ranges or joint limits with a finite pair)";
     return LOIKB_ERR_STATE;
@@ -1038,6 +1325,9 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
   int rc;
   if ((rc = ms_alloc(S))) return rc;
   loikb_solver_impl::MultiStartState& M = S->ms;
+  const bool have_clr = S->pose.col.have_ms;   // the collision-aware selection (loik_amd_collision.h)
+  const double margin = S->pose.col.ms.margin;
+  if (have_clr && (rc = ms_clr_alloc(S))) return rc;
   const int B = S->B, G = B / K, nc = S->nc_active;
   const bool dev = in_flags & LOIKB_IN_DEVICE, tgt_shared = in_flags & LOIKB_POSE_TARGET_SHARED;
   // the targets, checked as loikb_solve_pose checks them, before anything of the handle changes
@@ -1067,7 +1357,8 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
     hipLaunchKernelGGL(k_ms_select, dim3((unsigned)G), dim3(MS_SELECT_THREADS), 0, S->stream, (const int*)P.d_status, (const double*)P.d_err,
                        (const double*)S->d_q, (const double*)M.d_q0, (const int*)M.d_dofq, M.w.empty() ? (const double*)nullptr : (const double*)M.d_w,
                        S->nv, S->nq, nc, K, (int)(ms->pick == LOIKB_MS_PICK_FIRST), count_only, M.d_count, M.d_winner, M.d_gstatus, M.d_cost,
-                       M.d_nreached, M.d_wq, M.d_werr, cost_in);
+                       M.d_nreached, M.d_wq, M.d_werr, cost_in, have_clr ? (const double*)M.d_clr : nullptr, (const int*)M.d_clrwit, margin,
+                       M.d_iclr, M.d_wclr, M.d_wwit, M.d_nclear);
     HIPCHK(hipGetLastError());
     return LOIKB_OK;
   };
@@ -1077,6 +1368,8 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
     if ((rc = loikb_solve_pose(S, nullptr, M.d_tgt, LOIKB_IN_DEVICE, pose))) return rc;
     solve_ms += ms_since(t_solve);
     ++rounds_run;
+    // clr[b] of the resident q the round left: one launch, read on the device by the selection and the re-sampler's status word
+    if (have_clr && (rc = col_launch(S, (const double*)S->d_q, B, M.d_clr, M.d_clrwit))) return rc;
     if (r == R - 1) break;
     // goals that own a reached seed: one counter back to the host
     const auto t_count = std::chrono::steady_clock::now();
@@ -1087,7 +1380,13 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
     select_ms += ms_since(t_count);
     if (answered == (unsigned int)G) break;
     const auto t_again = std::chrono::steady_clock::now();
-    if ((rc = ms_sample(S, ms->seed, K, r + 1, P.d_status))) return rc;
+    const int* again = P.d_status;
+    if (have_clr) {   // class 0c is drawn anew: a loop-private status word, the pose status the caller reads is not edited
+      hipLaunchKernelGGL(k_ms_loop_status, grid1(B), dim3(256), 0, S->stream, (const int*)P.d_status, (const double*)M.d_clr, margin, B, M.d_lstatus);
+      HIPCHK(hipGetLastError());
+      again = M.d_lstatus;
+    }
+    if ((rc = ms_sample(S, ms->seed, K, r + 1, again))) return rc;
     HIPCHK(hipStreamSynchronize(S->stream));
     sample_ms += ms_since(t_again);
   }
@@ -1097,6 +1396,7 @@ int loikb_solve_pose_multistart(loikb_solver* S, const double* q0, const double*
   select_ms += ms_since(t_select);
   M.G = G;
   M.nc = nc;
+  M.clr_valid = have_clr;
   const double total = ms_since(t_call);
   M.timing[0] = rounds_run; M.timing[1] = total; M.timing[2] = solve_ms; M.timing[3] = sample_ms; M.timing[4] = select_ms;
   M.timing[5] = total - solve_ms - sample_ms - select_ms;
