@@ -27,6 +27,7 @@
 #include "../loik_amd_axis.h"
 #include "../loik_amd_jacobian.h"
 #include "../loik_amd_collision.h"
+#include "../loik_amd_motion.h"
 
 #include <array>
 #include <map>
@@ -593,6 +594,43 @@ public:
     if (margin) *margin = p.margin;
     return true;
   }
+  // ---- motions (include/loik_amd_motion.h).  Difference: v [n][nv] with q0 (+) v = q1 under Integrate's arithmetic
+  DVec Difference(const DVec& q0, const DVec& q1) const
+  {
+    const std::size_t n = q0.size() / (std::size_t)model_.nq;
+    if (q0.size() != q1.size() || q0.size() != n * (std::size_t)model_.nq) throw std::runtime_error("loik_amd: q0 and q1 are not the same whole number of configurations");
+    DVec v(n * (std::size_t)model_.nv);
+    check(loikb_difference(h_, q0.data(), q1.data(), (int)n, 0, v.data(), 0));
+    return v;
+  }
+  struct MotionResult {
+    std::vector<int> status, evals;     // [n]; status: LOIKB_MOTION_*
+    DVec s_free, min_sampled, s_at_min; // [n]
+    std::vector<int> witness;           // [n][3] of min_sampled, as ClearanceResult::witness
+  };
+  // the certified check of the segments q(s) = qa (+) s dv, s in [0, 1]: qa [n][nq], dv [n][nv]
+  MotionResult MotionClearance(const DVec& qa, const DVec& dv, double margin = 0.0, double tol = 1e-3, int max_evals = 256) const
+  {
+    const std::size_t n = qa.size() / (std::size_t)model_.nq;
+    if (qa.size() != n * (std::size_t)model_.nq || dv.size() != n * (std::size_t)model_.nv) throw std::runtime_error("loik_amd: qa and dv are not the same whole number of rows");
+    const loikb_motion_params p{margin, tol, max_evals, 0};
+    DVec val(3 * n);
+    std::vector<int> info(5 * n);
+    check(loikb_motion_clearance(h_, qa.data(), dv.data(), (int)n, 0, &p, val.data(), info.data(), 0));
+    return motion_result(val, info);
+  }
+  // ... of every segment between consecutive samples of q_path [B][T][nq]: the result has B (T - 1) rows, path major
+  MotionResult PathClearance(const DVec& q_path, int T, double margin = 0.0, double tol = 1e-3, int max_evals = 256) const
+  {
+    const std::size_t per = (std::size_t)(T > 0 ? T : 1) * (std::size_t)model_.nq, B = q_path.size() / per;
+    if (q_path.size() != B * per) throw std::runtime_error("loik_amd: q_path is not a whole number of paths of T samples");
+    const loikb_motion_params p{margin, tol, max_evals, 0};
+    const std::size_t n = B * (std::size_t)(T > 1 ? T - 1 : 0);
+    DVec val(3 * n);
+    std::vector<int> info(5 * n);
+    check(loikb_motion_clearance_path(h_, q_path.data(), (int)B, T, 0, &p, val.data(), info.data(), 0));
+    return motion_result(val, info);
+  }
   // ---- multi-start pose IK (include/loik_amd_multistart.h): batch = G goals * K seeds, instance g * K + k is seed k of goal g
   // the ranges [nv] the seeds are drawn from (a DoF is sampled iff both ends are finite; both empty = the joint limits) and the
   // weights [nv] of the nearest-seed metric (empty = 1)
@@ -1007,6 +1045,19 @@ private:
     if (q0->size() == G * (std::size_t)model_.nq) return 0;
     if (q0->size() == (std::size_t)model_.nq) return LOIKB_Q_SHARED;
     throw std::runtime_error("loik_amd: q0 must hold model.nq values (shared by the goals) or goals * model.nq");
+  }
+  // out_val [n][3], out_info [n][5] of loik_amd_motion.h by field
+  static MotionResult motion_result(const DVec& val, const std::vector<int>& info)
+  {
+    const std::size_t n = val.size() / 3;
+    MotionResult r;
+    r.status.resize(n); r.evals.resize(n); r.s_free.resize(n); r.min_sampled.resize(n); r.s_at_min.resize(n); r.witness.resize(3 * n);
+    for (std::size_t i = 0; i < n; ++i) {
+      r.s_free[i] = val[3 * i]; r.min_sampled[i] = val[3 * i + 1]; r.s_at_min[i] = val[3 * i + 2];
+      r.status[i] = info[5 * i]; r.evals[i] = info[5 * i + 1];
+      for (int k = 0; k < 3; ++k) r.witness[3 * i + k] = info[5 * i + 2 + k];
+    }
+    return r;
   }
   loikb_solver* h_ = nullptr;
   int batch_, nc_;

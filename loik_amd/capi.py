@@ -187,6 +187,10 @@ CLR_NONE, CLR_WORLD_SPHERE, CLR_WORLD_BOX, CLR_SELF = 0, 1, 2, 3
 CLR_MAX_SPHERES = 2048
 MS_GOAL_IN_COLLISION = 8
 CLR_MS_F_CLEARANCE, CLR_MS_F_WITNESS, CLR_MS_F_NCLEAR, CLR_MS_F_INSTANCE = range(4)
+# include/loik_amd_motion.h: certified collision checks of joint-space motions and the inverse of integrate; its own header and version
+MOTION_ABI_VERSION = 1
+MOTION_SYMBOLS = ["loikb_motion_version", "loikb_difference", "loikb_motion_clearance", "loikb_motion_clearance_path"]
+MOTION_FREE, MOTION_BLOCKED, MOTION_UNDECIDED, MOTION_INVALID = 0, 1, 2, 3
 
 
 class PoseParams(C.Structure):
@@ -203,6 +207,10 @@ class DexterityParams(C.Structure):
 
 class ClearanceParams(C.Structure):
     _fields_ = [("margin", C.c_double), ("flags", C.c_int)]
+
+
+class MotionParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("max_evals", C.c_int), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -311,6 +319,9 @@ def lib():
     L.loikb_clearance_set_multistart.argtypes = [C.c_void_p, C.POINTER(ClearanceParams)]
     L.loikb_clearance_get_multistart.argtypes = [C.c_void_p, C.POINTER(ClearanceParams)]
     L.loikb_clearance_get_multistart_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_difference.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_motion_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(MotionParams), C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_motion_clearance_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MotionParams), C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1145,6 +1156,85 @@ class BatchedLoik:
         wit = np.empty((n, 3), dtype=np.int32)
         _check(self.L.loikb_clearance(self.h, qp, n, flags, mins.ctypes.data_as(C.c_void_p), wit.ctypes.data_as(C.c_void_p), 0))
         return dict(min=mins[:, 0].copy(), min_world=mins[:, 1].copy(), min_self=mins[:, 2].copy(), witness=wit)
+
+    # ---- motions (include/loik_amd_motion.h) ----------------------------------------------------------------------
+    def _rows(self, a, width):
+        """a host array or device tensor of rows of `width` doubles -> (void*, rows, is_device, keep-alive)"""
+        if isinstance(a, tuple):
+            return C.c_void_p(int(a[0])), int(a[1]), True, None
+        if hasattr(a, "data_ptr") and getattr(a, "is_cuda", False):
+            return C.c_void_p(a.data_ptr()), int(a.numel()) // width, True, a
+        keep = _f64(a.numpy() if hasattr(a, "numpy") else a).reshape(-1, width)
+        return keep.ctypes.data_as(C.c_void_p), int(keep.shape[0]), False, keep
+
+    def difference(self, q0, q1, out=None):
+        """v [n][nv] with q0 (+) v = q1 under integrate's arithmetic (loikb_difference).  q0, q1 [n][nq] both on the host or both on the
+        device; with out = a device buffer of n nv float64 writes there and returns out."""
+        p0, n, dev, k0 = self._rows(q0, self.model.nq)
+        p1, n1, dev1, k1 = self._rows(q1, self.model.nq)
+        if n != n1 or dev != dev1:
+            raise ValueError("difference: q0 and q1 differ in rows or in where they live")
+        if out is not None:
+            _check(self.L.loikb_difference(self.h, p0, p1, n, IN_DEVICE if dev else 0, _ptr(out)[0], OUT_DEVICE))
+            return out
+        v = np.empty((n, self.model.nv))
+        _check(self.L.loikb_difference(self.h, p0, p1, n, IN_DEVICE if dev else 0, v.ctypes.data_as(C.c_void_p), 0))
+        return v
+
+    @staticmethod
+    def _motion_result(val, info):
+        return dict(status=info[:, 0].copy(), evals=info[:, 1].copy(), s_free=val[:, 0].copy(), min_sampled=val[:, 1].copy(),
+                    s_at_min=val[:, 2].copy(), witness=info[:, 2:5].copy())
+
+    def motion_clearance(self, qa, qb=None, dv=None, margin=0.0, tol=1e-3, max_evals=256, out=None):
+        """the certified check of the segments q(s) = qa (+) s dv, s in [0, 1] (loikb_motion_clearance), against the sphere model, the
+        world and the self pairs of the handle.  Give dv [n][nv], or qb [n][nq] (then dv = difference(qa, qb)); qa and dv / qb both on the
+        host or both on the device.  Returns dict(status [n] MOTION_*, evals [n], s_free [n], min_sampled [n], s_at_min [n], witness
+        [n][3]), or with out = (val_dev, info_dev) device buffers of 3 n float64 / 5 n int32 writes there and returns out."""
+        if (qb is None) == (dv is None):
+            raise ValueError("motion_clearance: give exactly one of qb and dv")
+        tmp = None
+        if dv is None:
+            if hasattr(qb, "data_ptr") and getattr(qb, "is_cuda", False):
+                tmp = dv = self.difference(qa, qb, out=DeviceArray(np.empty(int(qb.numel()) // self.model.nq * self.model.nv)))
+            else:
+                dv = self.difference(qa, qb)
+        pa, n, dev, ka = self._rows(qa, self.model.nq)
+        pd, nd, devd, kd = self._rows(dv, self.model.nv)
+        if n != nd or dev != devd:
+            raise ValueError("motion_clearance: qa and dv differ in rows or in where they live")
+        prm = MotionParams(float(margin), float(tol), int(max_evals), 0)
+        try:
+            if out is not None:
+                _check(self.L.loikb_motion_clearance(self.h, pa, pd, n, IN_DEVICE if dev else 0, C.byref(prm), _ptr(out[0])[0], _ptr(out[1])[0], OUT_DEVICE))
+                return out
+            val, info = np.empty((n, 3)), np.empty((n, 5), dtype=np.int32)
+            _check(self.L.loikb_motion_clearance(self.h, pa, pd, n, IN_DEVICE if dev else 0, C.byref(prm), val.ctypes.data_as(C.c_void_p),
+                                                 info.ctypes.data_as(C.c_void_p), 0))
+        finally:
+            if tmp is not None:
+                tmp.free()
+        return self._motion_result(val, info)
+
+    def path_clearance(self, q_path, margin=0.0, tol=1e-3, max_evals=256, out=None):
+        """the certified check of every segment between consecutive samples of q_path [B][T][nq] (loikb_motion_clearance_path; a host array,
+        or a device tensor with that shape).  Returns the dict of motion_clearance with [B][T-1] leading axes, or writes to out = (val_dev,
+        info_dev) of 3 B (T-1) float64 / 5 B (T-1) int32."""
+        shape = tuple(q_path.shape)
+        if len(shape) != 3 or shape[2] != self.model.nq:
+            raise ValueError("path_clearance: q_path must be [B][T][nq]")
+        B, T = int(shape[0]), int(shape[1])
+        pq, _, dev, keep = self._rows(q_path, self.model.nq)
+        prm = MotionParams(float(margin), float(tol), int(max_evals), 0)
+        if out is not None:
+            _check(self.L.loikb_motion_clearance_path(self.h, pq, B, T, IN_DEVICE if dev else 0, C.byref(prm), _ptr(out[0])[0], _ptr(out[1])[0], OUT_DEVICE))
+            return out
+        n = B * max(T - 1, 0)
+        val, info = np.empty((n, 3)), np.empty((n, 5), dtype=np.int32)
+        _check(self.L.loikb_motion_clearance_path(self.h, pq, B, T, IN_DEVICE if dev else 0, C.byref(prm), val.ctypes.data_as(C.c_void_p),
+                                                  info.ctypes.data_as(C.c_void_p), 0))
+        r = self._motion_result(val, info)
+        return {k: v.reshape((B, T - 1) + v.shape[1:]) for k, v in r.items()}
 
     def set_multistart_clearance(self, margin=0.0):
         """every later SolvePoseMultiStart answers a goal only with a reached seed whose clearance is >= margin

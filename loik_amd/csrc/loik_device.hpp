@@ -1637,6 +1637,56 @@ __device__ __forceinline__ void se3_integrate(double* q7, const double* v)
 // outer loop: q <- q (+) dt * z on the resident configurations (1-DoF and translation joints: a plain sum; free-flyer
 // and spherical joints: the Lie-group update above), `src` != nullptr first (re)fills the resident copy from a
 // caller's q (one shared row or one row per instance)
+// one joint of it: qs <- qs (+) v, qs the coordinates of device joint d (not JF_NOQ), v the 6 / 3 / 1 velocities of its chain
+__device__ __forceinline__ void advance_q_joint(double* __restrict__ qs, const JointDesc& d, const double* v)
+{
+  const int rot = d.rot;
+  if (rot == ROT_FREE) {
+    se3_integrate(qs, v);
+  } else if (rot == ROT_SPH) {
+    double qe[4], qo[4];
+    so3_exp_quat(v, qe);
+    quat_mul_xyzw(qs, qe, qo);
+    quat_first_order_normalize(qo);
+    for (int k = 0; k < 4; ++k) qs[k] = qo[k];
+  } else if (rot == ROT_PLANAR) {
+    // SpecialEuclideanOperationTpl<2>::integrate: (x, y, cos, sin) * exp(vx, vy, w), first-order re-normalised (cos, sin)
+    // sin(w) / w and (1 - cos(w)) / w = sin(w / 2) (sin(w / 2) / (w / 2)): the quotient (1 - cos(w)) / w of the reference loses
+    // (w / 2) |v| to the rounding of cos(w) for small w (5e-10 |v| at w = 1e-9); below |w| = 1e-4 the two quotients are their
+    // series, whose next terms (w^4 / 120, w^5 / 720) are under 1e-18
+    const double c0 = qs[2], s0 = qs[3], w = v[2];
+    double sw, cw, sh, ch, a, bq;
+    sincos(w, &sw, &cw);
+    if (fabs(w) > 1e-4) { sincos(0.5 * w, &sh, &ch); a = sw / w; bq = sh * (sh / (0.5 * w)); }
+    else { a = 1.0 - w * w / 6.0; bq = 0.5 * w * (1.0 - w * w / 12.0); }
+    const double tx = a * v[0] - bq * v[1], ty = bq * v[0] + a * v[1];
+    qs[0] += c0 * tx - s0 * ty;
+    qs[1] += s0 * tx + c0 * ty;
+    double c1 = c0 * cw - s0 * sw, s1 = s0 * cw + c0 * sw;
+    const double nrm = 0.5 * (3.0 - (c1 * c1 + s1 * s1));
+    qs[2] = c1 * nrm; qs[3] = s1 * nrm;
+  } else if (d.flags & JF_CS_DIRECT) {
+    // SpecialOrthogonalOperationTpl<2>::integrate: (cos, sin) rotated by w, first-order re-normalised
+    const double c0 = qs[0], s0 = qs[1];
+    double sw, cw;
+    sincos(v[0], &sw, &cw);
+    double c1 = c0 * cw - s0 * sw, s1 = s0 * cw + c0 * sw;
+    const double nrm = 0.5 * (3.0 - (c1 * c1 + s1 * s1));
+    qs[0] = c1 * nrm; qs[1] = s1 * nrm;
+  } else {
+    const int n = rot == ROT_TRANS ? 3 : 1;
+    for (int k = 0; k < n; ++k) qs[k] += v[k];
+  }
+}
+// the velocities / the coordinates a device joint that reads q owns (its chain's DoFs; what joint_q_pairs reads)
+__device__ __forceinline__ int joint_nv(const JointDesc& d)
+{
+  return d.rot == ROT_FREE ? 6 : (d.rot == ROT_SPH || d.rot == ROT_TRANS || d.rot == ROT_PLANAR) ? 3 : 1;
+}
+__device__ __forceinline__ int joint_nq(const JointDesc& d)
+{
+  return d.rot == ROT_FREE ? 7 : (d.rot == ROT_SPH || d.rot == ROT_PLANAR) ? 4 : d.rot == ROT_TRANS ? 3 : (d.flags & JF_CS_DIRECT) ? 2 : 1;
+}
 // one instance of it: q_row <- q_row (+) dt * z, z read from the instance's joint records `lp`
 template <typename T>
 __device__ __forceinline__ void advance_q_instance(double* __restrict__ q_row, const JointDesc* __restrict__ jd,
@@ -1646,46 +1696,10 @@ __device__ __forceinline__ void advance_q_instance(double* __restrict__ q_row, c
   for (int i = 1; i <= nb; ++i) {
     if (jd[i].flags & JF_NOQ) continue;
     const char* rec = lp + (size_t)(i - 1) * RB;
-    double* qs = q_row + idx_q[i];
-    const int rot = jd[i].rot;
-    const int n = rot == ROT_FREE ? 6 : (rot == ROT_SPH || rot == ROT_TRANS || rot == ROT_PLANAR) ? 3 : 1;
+    const int n = joint_nv(jd[i]);
     double v[6];
     for (int k = 0; k < n; ++k) v[k] = dt * (double)ldp<T>(rec + k * RB, JP_WZ).y;  // z of the chain's joints
-    if (rot == ROT_FREE) {
-      se3_integrate(qs, v);
-    } else if (rot == ROT_SPH) {
-      double qe[4], qo[4];
-      so3_exp_quat(v, qe);
-      quat_mul_xyzw(qs, qe, qo);
-      quat_first_order_normalize(qo);
-      for (int k = 0; k < 4; ++k) qs[k] = qo[k];
-    } else if (rot == ROT_PLANAR) {
-      // SpecialEuclideanOperationTpl<2>::integrate: (x, y, cos, sin) * exp(vx, vy, w), first-order re-normalised (cos, sin)
-      // sin(w) / w and (1 - cos(w)) / w = sin(w / 2) (sin(w / 2) / (w / 2)): the quotient (1 - cos(w)) / w of the reference loses
-      // (w / 2) |v| to the rounding of cos(w) for small w (5e-10 |v| at w = 1e-9); below |w| = 1e-4 the two quotients are their
-      // series, whose next terms (w^4 / 120, w^5 / 720) are under 1e-18
-      const double c0 = qs[2], s0 = qs[3], w = v[2];
-      double sw, cw, sh, ch, a, bq;
-      sincos(w, &sw, &cw);
-      if (fabs(w) > 1e-4) { sincos(0.5 * w, &sh, &ch); a = sw / w; bq = sh * (sh / (0.5 * w)); }
-      else { a = 1.0 - w * w / 6.0; bq = 0.5 * w * (1.0 - w * w / 12.0); }
-      const double tx = a * v[0] - bq * v[1], ty = bq * v[0] + a * v[1];
-      qs[0] += c0 * tx - s0 * ty;
-      qs[1] += s0 * tx + c0 * ty;
-      double c1 = c0 * cw - s0 * sw, s1 = s0 * cw + c0 * sw;
-      const double nrm = 0.5 * (3.0 - (c1 * c1 + s1 * s1));
-      qs[2] = c1 * nrm; qs[3] = s1 * nrm;
-    } else if (jd[i].flags & JF_CS_DIRECT) {
-      // SpecialOrthogonalOperationTpl<2>::integrate: (cos, sin) rotated by w, first-order re-normalised
-      const double c0 = qs[0], s0 = qs[1];
-      double sw, cw;
-      sincos(v[0], &sw, &cw);
-      double c1 = c0 * cw - s0 * sw, s1 = s0 * cw + c0 * sw;
-      const double nrm = 0.5 * (3.0 - (c1 * c1 + s1 * s1));
-      qs[0] = c1 * nrm; qs[1] = s1 * nrm;
-    } else {
-      for (int k = 0; k < n; ++k) qs[k] += v[k];
-    }
+    advance_q_joint(q_row + idx_q[i], jd[i], v);
   }
 }
 template <typename T>

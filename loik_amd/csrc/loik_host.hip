@@ -27,6 +27,7 @@
 #include "loik_pose_step.hpp"
 #include "loik_pose_jacobian.hpp"
 #include "loik_pose_collision.hpp"
+#include "loik_pose_motion.hpp"
 #include "loik_flat_inst.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
@@ -49,6 +50,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_axis.h"
 #include "../../include/loik_amd_jacobian.h"
 #include "../../include/loik_amd_collision.h"
+#include "../../include/loik_amd_motion.h"
 
 #include <algorithm>
 #include <chrono>
@@ -415,6 +417,8 @@ struct loikb_solver_impl {
       unsigned short* d_pairs = nullptr;                               // [npairs][2]
       double* d_place = nullptr;         // [n][ncar][12] k_link_placements' output for k_clearance<true>, grown on demand
       size_t place_cap = 0;              // bytes of d_place
+      double* d_mslab = nullptr;         // one slab of Lambda, liM and carrier records per resident wavefront of k_motion_clearance<true>
+      size_t mslab_cap = 0;              // (loik_amd_motion.h), grown on demand; bytes of d_mslab
       bool have_ms = false;              // loikb_clearance_set_multistart set `ms`
       loikb_clearance_params ms = {0.0, 0};
     } col;
@@ -3180,7 +3184,7 @@ int loikb_destroy(loikb_solver* S)
   for (void* p : {(void*)S->track.d_smp, (void*)S->track.d_errmax, (void*)S->track.d_inner, (void*)S->track.d_Q, (void*)S->track.d_Z})
     if (p) (void)hipFree(p);
   for (void* p : {(void*)S->pose.col.d_sph, (void*)S->pose.col.d_wsph, (void*)S->pose.col.d_wbox, (void*)S->pose.col.d_scar, (void*)S->pose.col.d_car,
-                  (void*)S->pose.col.d_pairs, (void*)S->pose.col.d_place})
+                  (void*)S->pose.col.d_pairs, (void*)S->pose.col.d_place, (void*)S->pose.col.d_mslab})
     if (p) (void)hipFree(p);
   (void)hipGetLastError();  // a failed free must not surface in the next solver's first launch check
   if (S->own_stream) (void)hipStreamDestroy(S->own_stream);

@@ -1,6 +1,6 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
 // (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), step control (loik_amd_step.h), tool frames and tasks (loik_amd_tasks.h), frame
-// Jacobians and dexterity (loik_amd_jacobian.h), collision clearance (loik_amd_collision.h), multi-start (loik_amd_multistart.h), waypoint paths
+// Jacobians and dexterity (loik_amd_jacobian.h), collision clearance (loik_amd_collision.h), motion checks (loik_amd_motion.h), multi-start (loik_amd_multistart.h), waypoint paths
 // (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
 // belongs to: it is no header of its own.
 //
@@ -1128,6 +1128,158 @@ int loikb_clearance_get_multistart(const loikb_solver* S, loikb_clearance_params
   if (!S || !S->pose.col.have_ms) return 0;
   if (out) *out = S->pose.col.ms;
   return 1;
+}
+
+// ---- include/loik_amd_motion.h (kernels in loik_pose_motion.hpp) ---------------------------------------------------------------
+int loikb_motion_version(void) { return LOIKB_MOTION_VERSION; }
+
+// the two input arrays of a call on the device: device pointers pass through, host arrays go side by side into the staging buffer
+// (to_device has room for one).  b may be NULL.  Queued
+static int motion_inputs(loikb_solver_impl* S, const double* a, size_t abytes, const double* b, size_t bbytes, bool dev, const double** da,
+                         const double** db)
+{
+  if (dev) { *da = a; *db = b; return LOIKB_OK; }
+  const size_t off = (abytes + 255) & ~(size_t)255;
+  int rc;
+  if ((rc = ensure_stage(S, off + bbytes))) return rc;
+  HIPCHK(hipMemcpyAsync(S->d_stage, a, abytes, hipMemcpyHostToDevice, S->stream));
+  if (b) HIPCHK(hipMemcpyAsync((char*)S->d_stage + off, b, bbytes, hipMemcpyHostToDevice, S->stream));
+  *da = (const double*)S->d_stage;
+  *db = b ? (const double*)((char*)S->d_stage + off) : nullptr;
+  return LOIKB_OK;
+}
+
+int loikb_difference(loikb_solver* S, const double* q0, const double* q1, int n, int in_flags, double* out_v, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (n < 0 || (n > 0 && (!q0 || !q1 || !out_v))) { g_last_error = "difference: need n >= 0 and q0, q1, out_v when n > 0"; return LOIKB_ERR_ARG; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const size_t qbytes = sizeof(double) * (size_t)n * S->nq, vbytes = sizeof(double) * (size_t)n * S->nv;
+  const double *d0, *d1;
+  int rc;
+  if ((rc = motion_inputs(S, q0, qbytes, q1, qbytes, in_flags & LOIKB_IN_DEVICE, &d0, &d1))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  if (!to_dev && (rc = ensure_getscr(S, 0, vbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* d_v = to_dev ? out_v : (double*)S->d_getscr[0];
+  hipLaunchKernelGGL(k_difference, grid1((size_t)n, 64), dim3(64), 0, S->stream, d0, d1, S->nq, S->d_jd, S->d_idx_q, S->nb, n, 0, d_v);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out_v, d_v, vbytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
+  return LOIKB_OK;
+}
+
+static int motion_check_params(const loikb_motion_params* p, const char* who)
+{
+  const char* bad = !p ? "p == NULL"
+                    : !std::isfinite(p->margin) ? "the margin is not finite"
+                    : !(std::isfinite(p->tol) && p->tol >= 1e-9) ? "tol is not finite and >= 1e-9"
+                    : (p->max_evals < 1 || p->max_evals > 65536) ? "max_evals is outside 1 .. 65536"
+                    : p->flags != 0 ? "flags != 0" : nullptr;
+  if (!bad) return LOIKB_OK;
+  g_last_error = std::string(who) + ": " + bad;
+  return LOIKB_ERR_ARG;
+}
+
+// wavefronts that k_motion_clearance<true> keeps a slab for: the grid of a model whose records do not fit the LDS
+constexpr int MOTION_SLAB_WAVES = 512;
+
+// One advancement launch over n segments: qa rows by motion_row(i, T) of dqa, dv [n][nv].  Queued
+static int motion_launch(loikb_solver_impl* S, const double* dqa, const double* ddv, int n, int T, const loikb_motion_params& p, double* d_val,
+                         int* d_info)
+{
+  Collision& C = S->pose.col;
+  const int ncar = (int)C.car.size();
+  const size_t aux = motion_aux_doubles(S->nb, ncar, C.ns);
+  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) > 65536;
+  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
+  int lp = 0;
+  while (lp < 6 && (1 << lp) < C.ns) ++lp;
+  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, ncar, C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const MotionPrm prm{p.margin, p.tol, p.max_evals};
+  if (slab) {
+    const int waves = std::min(n, MOTION_SLAB_WAVES);
+    const size_t need = sizeof(double) * aux * (size_t)waves;
+    if (need > C.mslab_cap) {
+      HIPCHK(hipStreamSynchronize(S->stream));
+      if (C.d_mslab) HIPCHK(hipFree(C.d_mslab));
+      C.d_mslab = nullptr;
+      C.mslab_cap = 0;
+      HIPCHK(hipMalloc((void**)&C.d_mslab, need));
+      C.mslab_cap = need;
+    }
+    hipLaunchKernelGGL(k_motion_clearance<true>, dim3(waves), dim3(64), lds, S->stream, dqa, ddv, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T, m, prm,
+                       C.d_mslab, d_val, d_info);
+  } else {
+    hipLaunchKernelGGL(k_motion_clearance<false>, dim3(n), dim3(64), lds, S->stream, dqa, ddv, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T, m, prm,
+                       (double*)nullptr, d_val, d_info);
+  }
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+// the shared body of the two checks: dqa as motion_launch takes it, ddv [n][nv] or nullptr = the differences of the path (T > 0)
+static int motion_run(loikb_solver_impl* S, const double* dqa, const double* ddv, int n, int T, const loikb_motion_params& p, double* out_val,
+                      int* out_info, bool to_dev)
+{
+  const size_t vbytes = sizeof(double) * 3 * (size_t)n, ibytes = sizeof(int) * 5 * (size_t)n;
+  int rc;
+  if (!ddv) {
+    if ((rc = ensure_getscr(S, 1, sizeof(double) * (size_t)n * S->nv))) return rc;
+    hipLaunchKernelGGL(k_difference, grid1((size_t)n, 64), dim3(64), 0, S->stream, dqa, (const double*)nullptr, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T,
+                       (double*)S->d_getscr[1]);
+    HIPCHK(hipGetLastError());
+    ddv = (const double*)S->d_getscr[1];
+  }
+  if (!to_dev && (rc = ensure_getscr(S, 0, vbytes + ibytes))) return rc;
+  double* d_val = to_dev ? out_val : (double*)S->d_getscr[0];
+  int* d_info = to_dev ? out_info : (int*)((char*)S->d_getscr[0] + vbytes);
+  if ((rc = motion_launch(S, dqa, ddv, n, T, p, d_val, d_info))) return rc;
+  if (!to_dev) {
+    HIPCHK(hipMemcpyAsync(out_val, d_val, vbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(out_info, d_info, ibytes, hipMemcpyDeviceToHost, S->stream));
+  }
+  return LOIKB_OK;
+}
+
+int loikb_motion_clearance(loikb_solver* S, const double* qa, const double* dv, int n, int in_flags, const loikb_motion_params* p, double* out_val,
+                           int* out_info, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (n < 0 || (n > 0 && (!qa || !dv || !out_val || !out_info))) { g_last_error = "motion_clearance: need n >= 0 and qa, dv, out_val, out_info when n > 0"; return LOIKB_ERR_ARG; }
+  int rc;
+  if ((rc = motion_check_params(p, "motion_clearance"))) return rc;
+  if (S->pose.col.ns == 0) { g_last_error = "motion_clearance: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const double *dqa, *ddv;
+  if (!(rc = motion_inputs(S, qa, sizeof(double) * (size_t)n * S->nq, dv, sizeof(double) * (size_t)n * S->nv, in_flags & LOIKB_IN_DEVICE, &dqa, &ddv)))
+    rc = motion_run(S, dqa, ddv, n, 0, *p, out_val, out_info, out_flags & LOIKB_OUT_DEVICE);
+  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
+  return LOIKB_OK;
+}
+
+int loikb_motion_clearance_path(loikb_solver* S, const double* q_path, int B, int T, int in_flags, const loikb_motion_params* p, double* out_val,
+                                int* out_info, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (T < 2) { g_last_error = "motion_clearance_path: need T >= 2"; return LOIKB_ERR_ARG; }
+  if (B < 0 || (size_t)B * (size_t)(T - 1) > (size_t)0x7fffffff || (B > 0 && (!q_path || !out_val || !out_info))) {
+    g_last_error = "motion_clearance_path: need B >= 0, fewer than 2^31 segments and q_path, out_val, out_info when B > 0";
+    return LOIKB_ERR_ARG;
+  }
+  int rc;
+  if ((rc = motion_check_params(p, "motion_clearance_path"))) return rc;
+  if (S->pose.col.ns == 0) { g_last_error = "motion_clearance_path: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (B == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const double *dq, *none;
+  if (!(rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, nullptr, 0, in_flags & LOIKB_IN_DEVICE, &dq, &none)))
+    rc = motion_run(S, dq, nullptr, B * (T - 1), T, *p, out_val, out_info, out_flags & LOIKB_OUT_DEVICE);
+  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
 }
 
 // the buffers of the collision-aware selection, on first use
