@@ -29,6 +29,7 @@
 #include "loik_pose_collision.hpp"
 #include "loik_pose_motion.hpp"
 #include "loik_flat_inst.hpp"
+#include "loik_devmem.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
 // k_flat2 / k_flat1 are instantiated in loik_flat_kernels.hip (its own code-generation switches: loik_flat_inst.hpp); here they are only launched
 LOIKB_FLAT2_INSTANCES(LOIKB_FLAT2_DECL)
@@ -53,6 +54,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_motion.h"
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -79,7 +81,34 @@ static thread_local std::string g_last_error;
     }                                                                                                      \
   } while (0)
 
+// as HIPCHK, for OwnedBuf::regrow / replace (false: the allocation failed, the runtime's last error says why)
+#define BUFCHK(expr)                                                                                       \
+  do {                                                                                                     \
+    if (!(expr)) {                                                                                         \
+      char _buf[512];                                                                                      \
+      snprintf(_buf, sizeof(_buf), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(hipGetLastError()), __FILE__, __LINE__); \
+      g_last_error = _buf;                                                                                 \
+      return LOIKB_ERR_HIP;                                                                                \
+    }                                                                                                      \
+  } while (0)
+
 namespace {
+
+// The two allocator policies of loik_devmem.hpp, and what is live through them in this process: allocations and bytes, device
+// then pinned (loikb_debug_device_memory).  Chunk threads allocate their work sets concurrently, hence atomics.
+std::atomic<unsigned long long> g_devmem[4];
+inline bool count_alloc(bool ok, int k, size_t bytes) { if (ok) { ++g_devmem[k]; g_devmem[k + 1] += bytes; } return ok; }
+inline void count_free(int k, size_t bytes) { --g_devmem[k]; g_devmem[k + 1] -= bytes; }
+struct DeviceMem {
+  static bool allocate(void** out, size_t bytes) { return count_alloc(hipMalloc(out, bytes) == hipSuccess, 0, bytes); }
+  static void free(void* p, size_t bytes) { (void)hipFree(p); count_free(0, bytes); }
+};
+struct PinnedMem {
+  static bool allocate(void** out, size_t bytes) { return count_alloc(hipHostMalloc(out, bytes) == hipSuccess, 2, bytes); }
+  static void free(void* p, size_t bytes) { (void)hipHostFree(p); count_free(2, bytes); }
+};
+template <class T = void> using DevBuf = OwnedBuf<DeviceMem, T>;
+template <class T = void> using PinBuf = OwnedBuf<PinnedMem, T>;
 
 constexpr int ROWMAP_CAP = 8192;
 
@@ -246,7 +275,7 @@ struct loikb_solver_impl {
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;  // LOIKB_OPT_OWN_STREAM
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
-  std::vector<void*> allocs;
+  std::vector<DevBuf<>> allocs;        // the arena (alloc_dev): what lives as long as the handle and never changes size
   std::mutex alloc_mu;
   JointDesc* d_jd = nullptr;
   int* d_idx_q = nullptr;
@@ -259,30 +288,28 @@ struct loikb_solver_impl {
   bool offer_queue = false;            // the full / tailored Solve: FwdPassInit's closing reset goes straight into the main loop -- reset_home(.., with_queue)
   // ... and, inside such a section, small host inputs do not travel by a copy operation at all: they are put into a pinned, device-visible
   // buffer (h_pin, bump-allocated from pin_off; the section's final synchronisation makes it free again) and the upload kernels read them there
-  char* h_pin = nullptr;
+  PinBuf<char> h_pin;
   size_t pin_cap = 0, pin_off = 0;
   std::vector<double> uni_host;         // fp64 handles: the host's copy of d_uni -- inside a deferred section upload_uni only writes here, flush_uni sends it once
   bool uni_dirty = false;
   std::vector<int> cslots_on_device;    // the joints' constraint slots as upload_jd last sent them: a SolveInit with the same task links sends nothing
   double* d_q = nullptr;               // [B][nq] configurations resident on the device (outer loop)
   void* d_uni = nullptr;               // A[nc][36], AtA[nc][21], lb[nb], ub[nb] (T)
-  void* d_stage = nullptr;             // staging for host<->device copies
-  void* d_getscr[2] = {nullptr, nullptr};  // scratch of the getters that rebuild members (His / pis / UDinv): kept, not malloc'ed per call
+  DevBuf<> d_stage;                    // staging for host<->device copies
+  DevBuf<> d_getscr[2];                // scratch of the getters that rebuild members (His / pis / UDinv): kept, not malloc'ed per call
   // loikb_get_results: the row map of the requested members on the device (rebuilt when the request or the constraint set changes) and a
   // pinned, device-visible host buffer the gather kernel writes into
-  struct ResMap { int* d = nullptr; int key[6] = {-1, -1, -1, -1, -1, -1}; int n = 0; int off[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };   // key: mask, nc_active, nb, nl, off_c, crec
+  struct ResMap { DevBuf<int> d; int key[6] = {-1, -1, -1, -1, -1, -1}; int n = 0; int off[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };   // key: mask, nc_active, nb, nl, off_c, crec
   ResMap resmaps[4];                   // (a caller uses one or two masks; replaced round robin)
   int resmap_next = 0;
-  double* h_res = nullptr;
-  size_t h_res_bytes = 0;
-  size_t getscr_bytes[2] = {0, 0};
-  size_t stage_bytes = 0;
+  PinBuf<double> h_res;
   // tile layouts: A per instance needs the long constraint record
   Layout L{};
   struct Set {
-    char* tiles = nullptr;
+    char* tiles = nullptr;               // the tiles: tiles_mem's, or (a chunk's set[0]) a view into the home tiles
     int ntiles = 0;
-    int *map = nullptr, *wave_live = nullptr, *wave_off = nullptr;
+    DevBuf<char> tiles_mem;
+    DevBuf<int> map, wave_live, wave_off;
   };
   Set home;  // tile t, lane l <-> instance 64 t + l
   // The batch is solved as `chunks.size()` independent contiguous ranges of tiles, each driven by its own host
@@ -295,29 +322,25 @@ struct loikb_solver_impl {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_k2 = nullptr;
-    unsigned int* d_counters = nullptr;
-    unsigned int* h_counters = nullptr;  // pinned
-    int* d_slots = nullptr;              // list of the live instances handed to the tail kernel
-    int* d_slots2 = nullptr;             // instances that left the lean kernel unfinished (same capacity)
-    int* d_order = nullptr;              // the chunk's instances, longest first by the iteration counts of the previous solve
-    unsigned int* d_order_bins = nullptr;  // [2 ORDER_BINS] counts / offsets of the counting sort
+    DevBuf<unsigned int> d_counters;
+    PinBuf<unsigned int> h_counters;
+    DevBuf<int> d_slots;                 // list of the live instances handed to the tail kernel
+    DevBuf<int> d_slots2;                // instances that left the lean kernel unfinished (same capacity)
+    DevBuf<int> d_order;                 // the chunk's instances, longest first by the iteration counts of the previous solve
+    DevBuf<unsigned int> d_order_bins;   // [2 ORDER_BINS] counts / offsets of the counting sort
     int order_n = 0;                     // instances d_order lists (0: none yet)
     unsigned long long order_epoch = 0;  // S->inputs_epoch of the solve whose iteration counts d_order sorts
     int order_holdoff = 0;               // solves to go in arrival order after an order that predicted badly
     int arrival_n = 0;                   // the flat engine's last launch in arrival order: instances, ...
     double arrival_ms = 0.0;             // ... its duration (0: none yet)
-    int* d_ring = nullptr;               // work queue of the lean kernel: ring of instance slots (ring_cap, a power of two)
+    DevBuf<int> d_ring;                  // work queue of the lean kernel: ring of instance slots (ring_cap, a power of two)
     int ring_cap = 0;
-    void* d_hslots = nullptr;            // decade slots of the lean tail kernel (H, Dinv, UDinv per joint and decade)
-    size_t hslots_bytes = 0;
-    void* d_fslots = nullptr;            // decade slots of the flat engine (W rows, Dinv per joint and decade)
-    size_t fslots_bytes = 0;
-    void* d_park = nullptr;              // k_flat2<.., SLICED>: where instances whose time slice is used up are parked
-    unsigned int* d_fmask = nullptr;     // k_flat2<.., MUR = 2>: per instance, which decades of the slot table are populated
-    size_t fmask_n = 0;
-    void** d_aux = nullptr;              // k_flat2's cold pointers behind one argument: {TailTopo*, child list, fmask}
+    DevBuf<> d_hslots;                   // decade slots of the lean tail kernel (H, Dinv, UDinv per joint and decade)
+    DevBuf<> d_fslots;                   // decade slots of the flat engine (W rows, Dinv per joint and decade)
+    DevBuf<> d_park;                     // k_flat2<.., SLICED>: where instances whose time slice is used up are parked
+    DevBuf<unsigned int> d_fmask;        // k_flat2<.., MUR = 2>: per instance, which decades of the slot table are populated
+    DevBuf<void*> d_aux;                 // k_flat2's cold pointers behind one argument: {TailTopo*, child list, fmask}
     const void* aux_h[4] = {nullptr, nullptr, nullptr, nullptr};   // (what d_aux holds)
-    size_t park_bytes = 0;
     std::vector<int> h_wave;             // host scratch for the compaction scan
     loikb_stats stats{};
     bool unfinished_counted = false;     // stats.n_unfinished of the last solve came with the on-chip launch's own counters (small batches)
@@ -345,16 +368,16 @@ struct loikb_solver_impl {
   double tab_H[36] = {0}, tab_v[6] = {0};
   int log_truncated = 0;     // instances of the last logged solve whose SolverInfo lists end early (see run_logged)
   PassLayout PL{};
-  double* d_pass = nullptr;
-  int* d_pass_cslot = nullptr;
+  DevBuf<double> d_pass;
+  DevBuf<int> d_pass_cslot;
   // decades of mu the lean engine's instances actually visited in the solves of this handle so far (absolute exponents): the
   // next solve builds slots for [seen_lo - 1, seen_hi + 1] only (within the configured range); an escape widens it again
   int seen_lo = 1 << 20, seen_hi = -(1 << 20);
   unsigned long long end_hist[32] = {0}, end_hist_n = 0;   // decades (kexp + 16) the instances of the last flat solve ended in
   unsigned long long solve_serial = 0, end_hist_epoch = 0; // (run_main_loop_t counts the solves; the solve end_hist was taken in)
   // SolverInfo lists of a handle created with logging = 1 (k_pass_solve)
-  double* d_log = nullptr;
-  int* d_log_rows = nullptr;
+  DevBuf<double> d_log;
+  DevBuf<int> d_log_rows;
   int log_rows_cap = 0;
   bool have_log = false;
   // batched pose IK (loik_pose.hpp): buffers of loikb_solve_pose, allocated by its first call (sizes: batch and slot capacity)
@@ -404,7 +427,7 @@ struct loikb_solver_impl {
     bool have_dex = false;             // loikb_dexterity_set_multistart_pick set `dex`
     loikb_dexterity_params dex = {1.0, 0};
     // the collision model (loik_amd_collision.h): spheres, world and self pairs, each uploaded when it is set, and the latch of the
-    // collision-aware multi-start.  The device buffers are the model's own (replaced when a latch is set again, freed by loikb_destroy)
+    // collision-aware multi-start.  The device buffers are the model's own (replaced when a latch is set again, freed with the handle)
     struct Collision {
       std::vector<int> links;            // [ns] the caller's link of each sphere
       std::vector<int> car, scar;        // the distinct device joints that carry spheres; [ns] each sphere's index into car
@@ -412,13 +435,12 @@ struct loikb_solver_impl {
       bool self_on = false;              // loikb_collision_set_self_pairs(enable = 1)
       std::vector<int> ignore;           // [ni][2] the caller's link pairs never tested
       std::vector<unsigned short> pairs; // [npairs][2] host copy of d_pairs
-      double *d_sph = nullptr, *d_wsph = nullptr, *d_wbox = nullptr;   // [ns][4], [nws][4], [nwb][15]
-      int *d_scar = nullptr, *d_car = nullptr;                         // [ns], [ncar]
-      unsigned short* d_pairs = nullptr;                               // [npairs][2]
-      double* d_place = nullptr;         // [n][ncar][12] k_link_placements' output for k_clearance<true>, grown on demand
-      size_t place_cap = 0;              // bytes of d_place
-      double* d_mslab = nullptr;         // one slab of Lambda, liM and carrier records per resident wavefront of k_motion_clearance<true>
-      size_t mslab_cap = 0;              // (loik_amd_motion.h), grown on demand; bytes of d_mslab
+      DevBuf<double> d_sph, d_wsph, d_wbox;   // [ns][4], [nws][4], [nwb][15]
+      DevBuf<int> d_scar, d_car;              // [ns], [ncar]
+      DevBuf<unsigned short> d_pairs;         // [npairs][2]
+      DevBuf<double> d_place;            // [n][ncar][12] k_link_placements' output for k_clearance<true>, grown on demand
+      DevBuf<double> d_mslab;            // one slab of Lambda, liM and carrier records per resident wavefront of k_motion_clearance<true>
+                                         // (loik_amd_motion.h), grown on demand
       bool have_ms = false;              // loikb_clearance_set_multistart set `ms`
       loikb_clearance_params ms = {0.0, 0};
     } col;
@@ -465,10 +487,9 @@ struct loikb_solver_impl {
     int* d_wfrom = nullptr;            // [B] the cursor before the last re-target (k_path_record stores the rows [wfrom, cursor))
     int* d_lstatus = nullptr;          // [B] the loop-private status word handed to k_pose_integrate / k_pose_limit_box
     int* d_pstatus = nullptr;          // [B] LOIKB_PATH_ST_* bits
-    double* d_wp = nullptr;            // [B][T][nc][12] waypoints (shared: the first T * nc rows)
-    int* d_wsteps = nullptr;           // [B][T]
-    double* d_Q = nullptr;             // [B][T][nq], allocated by the first call with record
-    int cap_wp = 0, cap_T = 0, cap_TQ = 0;   // waypoint counts d_wp, d_wsteps and d_Q have room for
+    DevBuf<double> d_wp;               // [B][T][nc][12] waypoints (shared: the first T * nc rows)
+    DevBuf<int> d_wsteps;              // [B][T]
+    DevBuf<double> d_Q;                // [B][T][nq], allocated by the first call with record
     int T = 0;                         // of the last loikb_solve_pose_path (0: none yet)
     bool recorded = false;             // it ran with record: d_Q is its result
     double timing[4] = {0, 0, 0, 0};   // LOIKB_PATH_F_TIMING
@@ -479,12 +500,11 @@ struct loikb_solver_impl {
     int* d_ontrack = nullptr;          // [B] samples within tol_track
     double* d_worst = nullptr;         // [B] the largest ERRMAX after sample 0
     int* d_worst_at = nullptr;         // [B] the sample it was at
-    double* d_smp = nullptr;           // [B][T+1][nc][12] samples (shared: the first (T + 1) * nc rows)
-    double* d_errmax = nullptr;        // [B][T+1]
-    int* d_inner = nullptr;            // [B][T]
-    double* d_Q = nullptr;             // [B][T+1][nq], allocated by the first call with LOIKB_TRACK_REC_Q
-    double* d_Z = nullptr;             // [B][T][nv], allocated by the first call with LOIKB_TRACK_REC_Z
-    int cap_smp = 0, cap_T = 0, cap_TQ = 0, cap_TZ = 0;   // step counts d_smp, d_errmax / d_inner, d_Q and d_Z have room for
+    DevBuf<double> d_smp;              // [B][T+1][nc][12] samples (shared: the first (T + 1) * nc rows)
+    DevBuf<double> d_errmax;           // [B][T+1]
+    DevBuf<int> d_inner;               // [B][T]
+    DevBuf<double> d_Q;                // [B][T+1][nq], allocated by the first call with LOIKB_TRACK_REC_Q
+    DevBuf<double> d_Z;                // [B][T][nv], allocated by the first call with LOIKB_TRACK_REC_Z
     int T = 0;                         // of the last loikb_track_pose (0: none yet)
     int record = 0;                    // its LOIKB_TRACK_REC_* bits: which of d_Q, d_Z are its result
     double timing[4] = {0, 0, 0, 0};   // LOIKB_TRACK_F_TIMING
@@ -492,50 +512,50 @@ struct loikb_solver_impl {
 };
 using Chunk = loikb_solver_impl::Chunk;
 
-// `st`: the stream that will use the buffer first (the zero fill is ordered on it); chunk threads allocate their
-// work sets concurrently, hence the lock around the bookkeeping
+// A zero-filled device buffer of `bytes` (16 for none) in `b`.  `st`: the stream that will use the buffer first (the zero fill is
+// ordered on it).  For a member that goes before the handle does (chunk lists, tile sets) ...
+template <class T>
+int alloc_zeroed(loikb_solver_impl* S, DevBuf<T>& b, size_t bytes, hipStream_t st = nullptr, bool use_st = false)
+{
+  BUFCHK(b.regrow(bytes ? bytes : 16));
+  HIPCHK(hipMemsetAsync(b, 0, b.bytes(), use_st ? st : S->stream));
+  return LOIKB_OK;
+}
+
+// ... and the arena: the same buffer behind a raw pointer, freed with the handle.  Chunk threads allocate their work sets
+// concurrently, hence the lock around the bookkeeping
 int alloc_dev(loikb_solver_impl* S, void** out, size_t bytes, hipStream_t st = nullptr, bool use_st = false)
 {
-  void* p = nullptr;
-  HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
-  HIPCHK(hipMemsetAsync(p, 0, bytes ? bytes : 16, use_st ? st : S->stream));
-  {
-    std::lock_guard<std::mutex> lock(S->alloc_mu);
-    S->allocs.push_back(p);
+  DevBuf<> b;
+  if (int rc = alloc_zeroed(S, b, bytes, st, use_st)) return rc;
+  *out = b;
+  std::lock_guard<std::mutex> lock(S->alloc_mu);
+  S->allocs.push_back(std::move(b));
+  return LOIKB_OK;
+}
+
+// OwnedBuf::regrow / replace as a step of an entry point: LOIKB_ERR_HIP and the runtime's error text when there is no room
+template <class Buf> int regrow(Buf& b, size_t bytes) { BUFCHK(b.regrow(bytes)); return LOIKB_OK; }
+template <class Buf> int replace(Buf& b, size_t bytes) { BUFCHK(b.replace(bytes)); return LOIKB_OK; }
+
+// (the collision setters, loik_host_pose.hpp) a device copy of `bytes` of host memory in the (empty) buffer `out` (left empty for bytes == 0); complete on return
+template <class T>
+int col_upload(loikb_solver_impl* S, const void* src, size_t bytes, DevBuf<T>& out)
+{
+  if (bytes == 0) return LOIKB_OK;
+  BUFCHK(out.regrow(bytes));
+  if (hipMemcpyAsync(out, src, bytes, hipMemcpyHostToDevice, S->stream) != hipSuccess || hipStreamSynchronize(S->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    g_last_error = "collision: the upload of the model failed";
+    return LOIKB_ERR_HIP;
   }
-  *out = p;
-  return LOIKB_OK;
-}
-
-int ensure_stage(loikb_solver_impl* S, size_t bytes)
-{
-  if (bytes <= S->stage_bytes) return LOIKB_OK;
-  if (S->d_stage) HIPCHK(hipFree(S->d_stage));
-  S->d_stage = nullptr;
-  S->stage_bytes = 0;
-  HIPCHK(hipMalloc(&S->d_stage, bytes));
-  S->stage_bytes = bytes;
-  return LOIKB_OK;
-}
-
-int ensure_getscr(loikb_solver_impl* S, int k, size_t bytes)
-{
-  if (bytes <= S->getscr_bytes[k]) return LOIKB_OK;
-  if (S->d_getscr[k]) HIPCHK(hipFree(S->d_getscr[k]));
-  S->d_getscr[k] = nullptr;
-  S->getscr_bytes[k] = 0;
-  HIPCHK(hipMalloc(&S->d_getscr[k], bytes));
-  S->getscr_bytes[k] = bytes;
   return LOIKB_OK;
 }
 
 // the getters' scratch goes back when a solve-side buffer needs the room (decade slots, park records): ADVICE r04
 static size_t release_getscr(loikb_solver_impl* S)
 {
-  size_t freed = 0;
-  for (int k = 0; k < 2; ++k) {
-    if (S->d_getscr[k]) { (void)hipFree(S->d_getscr[k]); S->d_getscr[k] = nullptr; freed += S->getscr_bytes[k]; S->getscr_bytes[k] = 0; }
-  }
+  const size_t freed = S->d_getscr[0].release() + S->d_getscr[1].release();
   (void)hipGetLastError();
   return freed;
 }
@@ -557,17 +577,12 @@ int alloc_set(loikb_solver_impl* S, loikb_solver_impl::Set& W, int ntiles, hipSt
 {
   if (W.tiles) return LOIKB_OK;
   int rc;
-  void* tmp = nullptr;
-  if ((rc = alloc_dev(S, &tmp, tile_bytes(S) * ntiles, st, use_st))) return rc;
-  W.tiles = (char*)tmp;
+  if ((rc = alloc_zeroed(S, W.tiles_mem, tile_bytes(S) * ntiles, st, use_st))) return rc;
+  W.tiles = W.tiles_mem;
   W.ntiles = ntiles;
-  if ((rc = alloc_dev(S, &tmp, sizeof(int) * (size_t)ntiles * WAVE, st, use_st))) return rc;
-  W.map = (int*)tmp;
-  if ((rc = alloc_dev(S, &tmp, sizeof(int) * ((size_t)ntiles + 1), st, use_st))) return rc;
-  W.wave_live = (int*)tmp;
-  if ((rc = alloc_dev(S, &tmp, sizeof(int) * ((size_t)ntiles + 1), st, use_st))) return rc;
-  W.wave_off = (int*)tmp;
-  return LOIKB_OK;
+  if ((rc = alloc_zeroed(S, W.map, sizeof(int) * (size_t)ntiles * WAVE, st, use_st))) return rc;
+  if ((rc = alloc_zeroed(S, W.wave_live, sizeof(int) * ((size_t)ntiles + 1), st, use_st))) return rc;
+  return alloc_zeroed(S, W.wave_off, sizeof(int) * ((size_t)ntiles + 1), st, use_st);
 }
 
 
@@ -1145,9 +1160,9 @@ int to_device(loikb_solver_impl* S, const void* src, size_t bytes, bool src_devi
   if (src_device) { *out = src; return LOIKB_OK; }
   if (S->defer_sync && bytes <= ((size_t)64 << 10)) {
     // (one problem per call: q, lb, ub, A, b are a few hundred bytes each -- five copy operations cost SolveInit 40 us of its 120)
-    if (S->h_pin == nullptr) {
-      if (hipHostMalloc((void**)&S->h_pin, (size_t)512 << 10) == hipSuccess) S->pin_cap = (size_t)512 << 10;
-      else { S->h_pin = nullptr; (void)hipGetLastError(); }
+    if (!S->h_pin) {
+      if (S->h_pin.regrow((size_t)512 << 10)) S->pin_cap = S->h_pin.bytes();
+      else (void)hipGetLastError();
     }
     const size_t need = (bytes + 255) & ~(size_t)255;
     if (S->h_pin && S->pin_off + need <= S->pin_cap) {
@@ -1157,8 +1172,7 @@ int to_device(loikb_solver_impl* S, const void* src, size_t bytes, bool src_devi
       return LOIKB_OK;
     }
   }
-  int rc = ensure_stage(S, bytes);
-  if (rc) return rc;
+  BUFCHK(S->d_stage.regrow(bytes));
   HIPCHK(hipMemcpyAsync(S->d_stage, src, bytes, hipMemcpyHostToDevice, S->stream));
   *out = S->d_stage;
   return LOIKB_OK;
@@ -1331,22 +1345,11 @@ void plan_engines(loikb_solver_impl* S);
 void destroy_chunks(loikb_solver_impl* S)
 {
   for (Chunk& C : S->chunks) {
-    if (C.h_counters) (void)hipHostFree(C.h_counters);
-    if (C.d_hslots) (void)hipFree(C.d_hslots);
-    if (C.d_fslots) (void)hipFree(C.d_fslots);
-    if (C.d_park) (void)hipFree(C.d_park);
-    if (C.d_fmask) (void)hipFree(C.d_fmask);
-    if (C.d_aux) (void)hipFree(C.d_aux);
-    if (C.ev_k0) (void)hipEventDestroy(C.ev_k0);
-    if (C.ev_k2) (void)hipEventDestroy(C.ev_k2);
-    if (C.ev_k1) (void)hipEventDestroy(C.ev_k1);
-    if (C.own_stream && C.stream) (void)hipStreamDestroy(C.stream);
-    void* ptrs[6] = {C.d_counters, C.d_slots, C.d_slots2, C.d_ring, C.d_order, C.d_order_bins};
-    for (void* p : ptrs)
-      if (p) {
-        (void)hipFree(p);
-        for (auto& a : S->allocs) if (a == p) a = nullptr;
-      }
+    const hipEvent_t ev[3] = {C.ev_k0, C.ev_k2, C.ev_k1};
+    const hipStream_t st = C.own_stream ? C.stream : nullptr;
+    C = Chunk{};   // (its buffers go first)
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    if (st) (void)hipStreamDestroy(st);
   }
   S->chunks.clear();
 }
@@ -1358,32 +1361,24 @@ int build_chunks(loikb_solver_impl* S, int nchunks)
   const int per = (ntiles + nchunks - 1) / nchunks;
   S->chunks.clear();
   for (int t0 = 0; t0 < ntiles; t0 += per) {
-    Chunk C;
+    Chunk& C = S->chunks.emplace_back();
     C.first_tile = t0;
     C.B = std::min(S->B - t0 * WAVE, per * WAVE);
-    S->chunks.push_back(C);
   }
-  void* tmp = nullptr;
   int rc;
   for (Chunk& C : S->chunks) {
     HIPCHK(hipEventCreate(&C.ev_k2));
     HIPCHK(hipEventCreate(&C.ev_k0));
     HIPCHK(hipEventCreate(&C.ev_k1));
-    HIPCHK(hipHostMalloc((void**)&C.h_counters, NCOUNTERS * sizeof(unsigned int)));
-    if ((rc = alloc_dev(S, &tmp, NCOUNTERS * sizeof(unsigned int)))) return rc;
-    C.d_counters = (unsigned int*)tmp;
-    if ((rc = alloc_dev(S, &tmp, sizeof(int) * (size_t)(C.B + WAVE)))) return rc;
-    C.d_slots = (int*)tmp;
-    if ((rc = alloc_dev(S, &tmp, sizeof(int) * (size_t)(C.B + WAVE)))) return rc;
-    C.d_slots2 = (int*)tmp;
-    if ((rc = alloc_dev(S, &tmp, sizeof(int) * (size_t)(C.B + WAVE)))) return rc;
-    C.d_order = (int*)tmp;
-    if ((rc = alloc_dev(S, &tmp, sizeof(unsigned int) * 2 * ORDER_BINS))) return rc;
-    C.d_order_bins = (unsigned int*)tmp;
+    BUFCHK(C.h_counters.regrow(NCOUNTERS * sizeof(unsigned int)));
+    if ((rc = alloc_zeroed(S, C.d_counters, NCOUNTERS * sizeof(unsigned int)))) return rc;
+    if ((rc = alloc_zeroed(S, C.d_slots, sizeof(int) * (size_t)(C.B + WAVE)))) return rc;
+    if ((rc = alloc_zeroed(S, C.d_slots2, sizeof(int) * (size_t)(C.B + WAVE)))) return rc;
+    if ((rc = alloc_zeroed(S, C.d_order, sizeof(int) * (size_t)(C.B + WAVE)))) return rc;
+    if ((rc = alloc_zeroed(S, C.d_order_bins, sizeof(unsigned int) * 2 * ORDER_BINS))) return rc;
     C.ring_cap = 64;
     while (C.ring_cap < 2 * (C.B + WAVE)) C.ring_cap <<= 1;
-    if ((rc = alloc_dev(S, &tmp, sizeof(int) * (size_t)C.ring_cap))) return rc;
-    C.d_ring = (int*)tmp;
+    if ((rc = alloc_zeroed(S, C.d_ring, sizeof(int) * (size_t)C.ring_cap))) return rc;
     if (S->chunks.size() > 1) {
       HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
       C.own_stream = true;
@@ -1531,20 +1526,15 @@ int ensure_hslots(loikb_solver_impl* S)
 {
   if (S->plan.flat && S->have_problem && !flat_applicable(S)) {
     // (the problem in force cannot use the flat engine: its decade slots -- ~1 GB per 65 536 Talos instances -- go back)
-    for (Chunk& C : S->chunks)
-      if (C.d_fslots) { HIPCHK(hipFree(C.d_fslots)); C.d_fslots = nullptr; C.fslots_bytes = 0; }
+    for (Chunk& C : S->chunks) C.d_fslots.release();
   }
   if (S->plan.flat && (flat_applicable(S) || !S->have_problem)) {
     // decade slots of the flat engine: (ancestors + 1) scalars per lane, decade and instance
     for (Chunk& C : S->chunks) {
       const int frows = S->flat.fblk;  // (scalars per decade slot)
       const size_t need = (size_t)C.B * (flat_any_mu(S) ? 1 : S->plan.ndec) * frows * S->esz;   // (OSQP: mu0's slot only)
-      if (need <= C.fslots_bytes) continue;
-      if (C.d_fslots) HIPCHK(hipFree(C.d_fslots));
-      C.d_fslots = nullptr; C.fslots_bytes = 0;
-      if (hipMalloc(&C.d_fslots, need) != hipSuccess && !(release_getscr(S) > 0 && hipMalloc(&C.d_fslots, need) == hipSuccess)) {
+      if (!C.d_fslots.regrow(need) && !(release_getscr(S) > 0 && C.d_fslots.regrow(need))) {
         (void)hipGetLastError();
-        C.d_fslots = nullptr;
         char buf[400];
         snprintf(buf, sizeof(buf), "the flat engine needs %.2f GB of decade slots for %d instances (%d decades x %d rows x %d lanes x %d B) "
                  "and the device has no room for them: create the solver with a smaller batch, or set LOIKB_FLAT=0 LOIKB_LEAN=0 to use "
@@ -1552,27 +1542,16 @@ int ensure_hslots(loikb_solver_impl* S)
         g_last_error = buf;
         return LOIKB_ERR_HIP;
       }
-      C.fslots_bytes = need;
     }
     if (flat_kind(S) == FlatKind::Flat2 && S->tune.flat_build) {   // (the lazily populated table's per-instance masks)
-      for (Chunk& C : S->chunks) {
-        if ((size_t)C.B <= C.fmask_n) continue;
-        if (C.d_fmask) HIPCHK(hipFree(C.d_fmask));
-        C.d_fmask = nullptr; C.fmask_n = 0;
-        HIPCHK(hipMalloc((void**)&C.d_fmask, sizeof(unsigned int) * (size_t)C.B));
-        C.fmask_n = (size_t)C.B;
-      }
+      for (Chunk& C : S->chunks) BUFCHK(C.d_fmask.regrow(sizeof(unsigned int) * (size_t)C.B));
     }
     // park records of the time-sliced launch (k_flat2 only: 17..32 joints): ~19 KB per instance, allocated for the batch sizes the
     // slices are used on (flat_slice_window); a handle that cannot have them simply runs unsliced
     if (flat_kind(S) == FlatKind::Flat2 && flat_slice_for(S, S->B, false) > 0) {
       for (Chunk& C : S->chunks) {
         const size_t need = (size_t)C.B * flat2_park_stride(S->nc, true) * sizeof(double);
-        if (need <= C.park_bytes) continue;
-        if (C.d_park) HIPCHK(hipFree(C.d_park));
-        C.d_park = nullptr; C.park_bytes = 0;
-        if (hipMalloc(&C.d_park, need) != hipSuccess && !(release_getscr(S) > 0 && hipMalloc(&C.d_park, need) == hipSuccess)) { (void)hipGetLastError(); C.d_park = nullptr; continue; }
-        C.park_bytes = need;
+        if (!C.d_park.regrow(need) && !(release_getscr(S) > 0 && C.d_park.regrow(need))) (void)hipGetLastError();
       }
     }
     if (flat_applicable(S) || !S->plan.lean) return LOIKB_OK;
@@ -1582,20 +1561,15 @@ int ensure_hslots(loikb_solver_impl* S)
   const int G = lanes_per_instance(S);
   for (Chunk& C : S->chunks) {
     const size_t need = (size_t)C.B * S->plan.ndec * HSLOT_PAIRS * G * 2 * S->esz;
-    if (need <= C.hslots_bytes) continue;
-    if (C.d_hslots) HIPCHK(hipFree(C.d_hslots));
-    C.d_hslots = nullptr; C.hslots_bytes = 0;
-    if (hipMalloc(&C.d_hslots, need) != hipSuccess) {
+    if (!C.d_hslots.regrow(need)) {
       (void)hipGetLastError();
       char buf[400];
       snprintf(buf, sizeof(buf), "the lean engine needs %.2f GB of decade slots for %d instances (%d decades x %d B x %d lanes each) "
                "and the device has no room for them: create the solver with a smaller batch, or set LOIKB_LEAN=0 to use the "
                "k_solve + k_tail engines, which need none", need / 1e9, C.B, S->plan.ndec, (int)(HSLOT_PAIRS * 2 * S->esz), G);
       g_last_error = buf;
-      C.d_hslots = nullptr;
       return LOIKB_ERR_HIP;
     }
-    C.hslots_bytes = need;
   }
   return LOIKB_OK;
 }
@@ -1620,19 +1594,10 @@ int ensure_layout(loikb_solver_impl* S, bool a_shared)
   const bool relayout = !S->home.tiles || L.crec != S->L.crec;
   const bool rechunk = (int)S->chunks.size() != S->plan.nchunks;
   if (!relayout && !rechunk) return ensure_hslots(S);
-  auto free_set = [&](loikb_solver_impl::Set& W, bool owns_tiles) {
-    void* ptrs[4] = {owns_tiles ? W.tiles : nullptr, W.map, W.wave_live, W.wave_off};
-    for (void* p : ptrs)
-      if (p) {
-        (void)hipFree(p);
-        for (auto& a : S->allocs) if (a == p) a = nullptr;
-      }
-    W = loikb_solver_impl::Set{};
-  };
   int rc;
   if (S->home.tiles) HIPCHK(hipStreamSynchronize(S->stream));
   for (Chunk& C : S->chunks)
-    for (int k = 0; k < 3; ++k) free_set(C.set[k], k != 0);
+    for (int k = 0; k < 3; ++k) C.set[k] = loikb_solver_impl::Set{};
   if (rechunk) {
     destroy_chunks(S);
     if ((rc = build_chunks(S, S->plan.nchunks))) return rc;
@@ -1640,7 +1605,7 @@ int ensure_layout(loikb_solver_impl* S, bool a_shared)
   if (relayout) {
     if (S->home.tiles) {
       // sharing mode of A changed: every tile has a different size now
-      free_set(S->home, true);
+      S->home = loikb_solver_impl::Set{};
       S->have_problem = false;
     }
     S->L = L;
@@ -1651,11 +1616,8 @@ int ensure_layout(loikb_solver_impl* S, bool a_shared)
     loikb_solver_impl::Set& V = C.set[0];
     V.tiles = S->home.tiles + (size_t)C.first_tile * tile_bytes(S);
     V.ntiles = (C.B + WAVE - 1) / WAVE;
-    void* tmp = nullptr;
-    if ((rc = alloc_dev(S, &tmp, sizeof(int) * ((size_t)V.ntiles + 1)))) return rc;
-    V.wave_live = (int*)tmp;
-    if ((rc = alloc_dev(S, &tmp, sizeof(int) * ((size_t)V.ntiles + 1)))) return rc;
-    V.wave_off = (int*)tmp;
+    if ((rc = alloc_zeroed(S, V.wave_live, sizeof(int) * ((size_t)V.ntiles + 1)))) return rc;
+    if ((rc = alloc_zeroed(S, V.wave_off, sizeof(int) * ((size_t)V.ntiles + 1)))) return rc;
   }
   if ((rc = ensure_hslots(S))) return rc;
   // fresh tiles: the reference ctor state is all-zero data (loik-loid-data-optimized.hxx:40-86) + ResetSolver
@@ -2182,7 +2144,7 @@ static int flat_launch_slice(const loikb_solver_impl* S, const Chunk* C, FlatKin
   // (k_flat1: time slicing as in k_flat2, same window: whole body, four tasks, B = 65 536: 34.7 ms without; OSQP's rule: unsliced)
   if (kind == FlatKind::Flat1) return mur == 1 ? 0 : flat_slice_for(S, n, ordered);
   int q = flat_slice_for(S, n, ordered);
-  if (q > 0 && (C->d_park == nullptr || (size_t)n_cur * flat2_park_stride(S->nc, true) * sizeof(double) > C->park_bytes)) q = 0;
+  if (q > 0 && (!C->d_park || (size_t)n_cur * flat2_park_stride(S->nc, true) * sizeof(double) > C->d_park.bytes())) q = 0;
   // (OSQP's rule runs unsliced unless LOIKB_FLAT_SLICE asks: a parked instance rebuilds its factors when it is taken up again --
   //  headline batch, first solve: 12.7 ms with the default slices, 11.4 without: profiles/r05_d_mu_rules.jsonl)
   if (mur == 1 && S->tune.flat_slice < 0) q = 0;
@@ -2234,7 +2196,7 @@ static int launch_flat_kernel(TailCtx<T>& X, FlatLaunch& F)
   const int cus = (int)(F.cu_sh + 0.5);
   if (one_per_wave(F.kind)) {   // (what only the in-wave builder / the lazily populated table read, behind one kernel argument)
     // (uploaded when one of the pointers changes -- synchronously, from the chunk's own copy: ADVICE r05)
-    if (C->d_aux == nullptr) HIPCHK(hipMalloc((void**)&C->d_aux, 4 * sizeof(void*)));
+    BUFCHK(C->d_aux.regrow(4 * sizeof(void*)));
     const void* auxh[4] = {S->d_topo, S->d_child_list, C->d_fmask, nullptr};
     if (memcmp(auxh, C->aux_h, sizeof(auxh)) != 0) {
       memcpy(C->aux_h, auxh, sizeof(auxh));
@@ -2254,9 +2216,9 @@ static int launch_flat_kernel(TailCtx<T>& X, FlatLaunch& F)
     F.grid = dim3((unsigned)std::min(n, per_cu * cus));
     const int win_bits = (int)(((F.nw >= 16 ? 0xFFFFu : ((1u << F.nw) - 1u)) << F.dw0) & 0xFFFFu);
     hipLaunchKernelGGL(flat_kernel(FLAT2_TABLE, v, FLAT_NA_SMALL), F.grid, dim3(WAVE), lds2, C->stream, Pd, Bd, (const JointDesc*)S->d_jd, (const FlatLane*)S->flat.d_lanes,
-                       F.nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, (const double*)C->d_fslots, F.frows, F.kexp_lo, F.ndec, (double)S->Href[0],
+                       F.nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, C->d_fslots.as<const double>(), F.frows, F.kexp_lo, F.ndec, (double)S->Href[0],
                        (int)((unsigned int)has_hv | ((unsigned int)(S->maxdepth & 0xFF) << 8) | ((unsigned int)win_bits << 16)), C->ring_cap - 1,
-                       quantum, (double*)C->d_park, flat2_park_stride(S->nc, true), (const void* const*)C->d_aux);
+                       quantum, C->d_park.as<double>(), flat2_park_stride(S->nc, true), (const void* const*)C->d_aux);
   } else if (F.kind == FlatKind::Flat1) {
     // k_flat1, one instance per wavefront anyway (33..64 joints): the build with nested loops, prefix-sum subtree sums, DPP fold
     // one decade slot in LDS instead of two when that buys wavefronts per CU (whole body, four task constraints: 6 -> 8)
@@ -2268,7 +2230,7 @@ static int launch_flat_kernel(TailCtx<T>& X, FlatLaunch& F)
     if (S->tune.lean_wg_per_cu > 0) per_cu1 = std::min(per_cu1, S->tune.lean_wg_per_cu);
     F.grid = dim3((unsigned)std::min(n, per_cu1 * cus));
     hipLaunchKernelGGL(flat_kernel(FLAT1_TABLE, v, F.small_na ? FLAT_NA_SMALL : FLAT_MAXA), F.grid, dim3(WAVE), lds1, C->stream, Pd, Bd, (const JointDesc*)S->d_jd,
-                       (const FlatLane*)S->flat.d_lanes, F.nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, (const double*)C->d_fslots, F.frows,
+                       (const FlatLane*)S->flat.d_lanes, F.nanc, S->flat.nscan, S->flat.njmp, C->d_ring, n, C->d_fslots.as<const double>(), F.frows,
                        F.kexp_lo, F.ndec, (double)S->Href[0], has_hv | (one_buf ? 2 : 0) | ((S->maxdepth & 0xFF) << 8), C->ring_cap - 1, quantum,
                        (const void* const*)C->d_aux);
   } else {
@@ -2280,7 +2242,7 @@ static int launch_flat_kernel(TailCtx<T>& X, FlatLaunch& F)
     auto* kernel = S->opt.logging ? (F.small_na ? k_flat<T, FLAT_NA_SMALL, true> : k_flat<T, FLAT_MAXA, true>)
                                   : (F.small_na ? k_flat<T, FLAT_NA_SMALL> : k_flat<T, FLAT_MAXA>);
     hipLaunchKernelGGL(kernel, F.grid, dim3(WAVE), flds, C->stream, X.P, X.Bf, (const JointDesc*)S->d_jd, (const FlatLane*)S->flat.d_lanes, F.nanc,
-                       S->flat.nscan, S->flat.njmp, (const int*)C->d_ring, n, lgG, (const T*)C->d_fslots, F.frows, F.kexp_lo, F.ndec, (T)S->Href[0], has_hv);
+                       S->flat.nscan, S->flat.njmp, (const int*)C->d_ring, n, lgG, C->d_fslots.as<const T>(), F.frows, F.kexp_lo, F.ndec, (T)S->Href[0], has_hv);
   }
   HIPCHK(hipGetLastError());
   return LOIKB_OK;
@@ -2355,7 +2317,7 @@ static int launch_flat(TailCtx<T>& X)
   if (F.mur == 1) { F.ndec = 1; F.kexp_lo = 0; }   // (the table holds mu0's slot: where every cold solve starts)
   if (F.mur == 2) { F.ndec = S->plan.ndec; F.kexp_lo = S->plan.kexp_lo; }   // (the lazily populated table keeps its whole range: addresses, not work)
   const size_t need = (size_t)n_cur * F.ndec * F.frows * sizeof(T);
-  if (need > C->fslots_bytes) { g_last_error = "internal: decade-slot buffer of the flat engine smaller than the chunk"; return LOIKB_ERR_STATE; }
+  if (need > C->d_fslots.bytes()) { g_last_error = "internal: decade-slot buffer of the flat engine smaller than the chunk"; return LOIKB_ERR_STATE; }
   P.max_launch_iters = S->opt.max_iter + 1;
   const int mode_keep = P.mode;
   if (whole_set && S->zero_state && S->tune.flat_zero_state) P.mode |= MODE_ZERO_STATE;
@@ -2380,7 +2342,7 @@ static int launch_flat(TailCtx<T>& X)
     auto* fslots = F.small_na ? k_fslots<T, FLAT_NA_SMALL> : k_fslots<T, FLAT_MAXA>;
     hipLaunchKernelGGL(fslots, hgrid, dim3(WAVE), slds, C->stream, P, X.Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
                        (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth, F.nanc, F.frows, S->flat.njmp, X.list, n,
-                       X.G, (T*)C->d_fslots, F.kexp_lo, F.ndec, F.dw0, F.nw, F.mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
+                       X.G, C->d_fslots.as<T>(), F.kexp_lo, F.ndec, F.dw0, F.nw, F.mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
     HIPCHK(hipGetLastError());
   }
   // (no event between k_fslots and the engine in the short sequence: loikb_stats::hslots_ms reads 0 there -- an event costs a lone
@@ -2422,7 +2384,7 @@ static int launch_lean(TailCtx<T>& X)
   // decade slots are indexed by the instance's slot in the set (relaunches with shorter lists find them again);
   // the buffer was sized for the chunk at SolveInit (ensure_hslots)
   const size_t need = (size_t)n_cur * ndec * HSLOT_PAIRS * G * 2 * sizeof(T);
-  if (need > C->hslots_bytes) { g_last_error = "internal: decade-slot buffer smaller than the chunk"; return LOIKB_ERR_STATE; }
+  if (need > C->d_hslots.bytes()) { g_last_error = "internal: decade-slot buffer smaller than the chunk"; return LOIKB_ERR_STATE; }
   const int waves_cu = S->plan.lean_waves_cu;
   const int ltw = S->plan.lean_wg_waves;  // wavefronts per workgroup
   const size_t lds = ltw * lean_lds_bytes<T>(S->nc, G, S->a_shared);
@@ -2445,12 +2407,12 @@ static int launch_lean(TailCtx<T>& X)
   const size_t hlds = (size_t)(WAVE + 1) * 22 * sizeof(T);
   auto* hslots = per_link ? k_hslots<T, false, true> : S->href_diag ? k_hslots<T, true> : k_hslots<T, false>;
   hipLaunchKernelGGL(hslots, hgrid, dim3(WAVE), hlds, C->stream, P, Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
-                     (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G, (T*)C->d_hslots, kexp_lo, ndec);
+                     (const int*)S->d_child_list, S->maxdepth, S->maxchild, list, n, G, C->d_hslots.as<T>(), kexp_lo, ndec);
   HIPCHK(hipEventRecord(C->ev_k2, C->stream));
   hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, list, n, C->d_counters);
   auto* lean = per_link ? k_lean<T, false, true> : S->href_diag ? k_lean<T, true> : k_lean<T, false>;
   hipLaunchKernelGGL(lean, grid, dim3(WAVE * ltw), lds, C->stream, P, Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
-                     (const int*)S->d_child_list, S->maxdepth, S->maxchild, C->d_ring, n, G, (const T*)C->d_hslots, kexp_lo, ndec, S->multi_from);
+                     (const int*)S->d_child_list, S->maxdepth, S->maxchild, C->d_ring, n, G, C->d_hslots.as<const T>(), kexp_lo, ndec, S->multi_from);
   HIPCHK(hipGetLastError());
   // the instances that are still iterating: k_tail's list (ping-pong between the two list buffers)
   int* next = (list == C->d_slots) ? C->d_slots2 : C->d_slots;
@@ -3167,31 +3129,14 @@ int loikb_destroy(loikb_solver* S)
 {
   if (!S) return LOIKB_OK;
   (void)hipSetDevice(S->device);
-  destroy_chunks(S);  // (first: it takes its buffers out of `allocs`)
-  for (void* a : S->allocs) if (a) (void)hipFree(a);
-  if (S->d_stage) (void)hipFree(S->d_stage);
-  for (int k = 0; k < 2; ++k) if (S->d_getscr[k]) (void)hipFree(S->d_getscr[k]);
-  for (auto& rmap : S->resmaps) if (rmap.d) (void)hipFree(rmap.d);
-  if (S->h_pin) (void)hipHostFree(S->h_pin);
-  if (S->h_res) (void)hipHostFree(S->h_res);
-  if (S->d_pass) (void)hipFree(S->d_pass);
-  if (S->d_pass_cslot) (void)hipFree(S->d_pass_cslot);
-  if (S->d_log) (void)hipFree(S->d_log);
-  if (S->d_log_rows) (void)hipFree(S->d_log_rows);
-  if (S->path.d_wp) (void)hipFree(S->path.d_wp);
-  if (S->path.d_wsteps) (void)hipFree(S->path.d_wsteps);
-  if (S->path.d_Q) (void)hipFree(S->path.d_Q);
-  for (void* p : {(void*)S->track.d_smp, (void*)S->track.d_errmax, (void*)S->track.d_inner, (void*)S->track.d_Q, (void*)S->track.d_Z})
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)S->pose.col.d_sph, (void*)S->pose.col.d_wsph, (void*)S->pose.col.d_wbox, (void*)S->pose.col.d_scar, (void*)S->pose.col.d_car,
-                  (void*)S->pose.col.d_pairs, (void*)S->pose.col.d_place, (void*)S->pose.col.d_mslab})
-    if (p) (void)hipFree(p);
-  (void)hipGetLastError();  // a failed free must not surface in the next solver's first launch check
-  if (S->own_stream) (void)hipStreamDestroy(S->own_stream);
-  if (S->ev_fork) (void)hipEventDestroy(S->ev_fork);
-  if (S->ev_t0) (void)hipEventDestroy(S->ev_t0);
-  if (S->ev_t1) (void)hipEventDestroy(S->ev_t1);
+  // (buffers first, then the streams and events; every buffer is a member and goes with its struct)
+  destroy_chunks(S);
+  const hipStream_t own_stream = S->own_stream;
+  const hipEvent_t ev[3] = {S->ev_fork, S->ev_t0, S->ev_t1};
   delete S;
+  if (own_stream) (void)hipStreamDestroy(own_stream);
+  for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  (void)hipGetLastError();  // a failed free must not surface in the next solver's first launch check
   return LOIKB_OK;
 }
 
@@ -3464,12 +3409,8 @@ static int ensure_pass_state(loikb_solver_impl* S, const PassParams& P)
 {
   if (S->pass_active) return LOIKB_OK;
   const PassLayout PL = make_pass_layout(S->nj, S->nv, S->nc, S->B);
-  if (!S->d_pass || PL.stride != S->PL.stride) {
-    if (S->d_pass) HIPCHK(hipFree(S->d_pass));
-    S->d_pass = nullptr;
-    HIPCHK(hipMalloc((void**)&S->d_pass, sizeof(double) * (size_t)PL.stride * S->B));
-    if (!S->d_pass_cslot) HIPCHK(hipMalloc((void**)&S->d_pass_cslot, sizeof(int) * S->nj));
-  }
+  BUFCHK(S->d_pass.regrow(sizeof(double) * (size_t)PL.stride * S->B));
+  BUFCHK(S->d_pass_cslot.regrow(sizeof(int) * S->nj));
   S->PL = PL;
   std::vector<int> cs(S->nj, -1);
   for (int i = 1; i < S->nj; ++i) cs[i] = S->jd[i].cslot;
@@ -3571,22 +3512,18 @@ int run_pass_solve(loikb_solver_impl* S, bool logged)
 static int ensure_log(loikb_solver_impl* S)
 {
   const int cap = std::max(S->opt.max_iter - 1, 1);
-  if (!S->d_log || cap != S->log_rows_cap) {
-    if (S->d_log) HIPCHK(hipFree(S->d_log));
-    S->d_log = nullptr;
-    const size_t bytes = sizeof(double) * (size_t)S->B * cap * LOG_NLIST;
-    if (hipMalloc((void**)&S->d_log, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      char buf[256];
-      snprintf(buf, sizeof(buf), "logging: the SolverInfo lists need %.2f GB (batch %d x (max_iter - 1) %d x %d lists x 8 B)",
-               bytes / 1e9, S->B, cap, (int)LOG_NLIST);
-      g_last_error = buf;
-      return LOIKB_ERR_HIP;
-    }
-    if (!S->d_log_rows) HIPCHK(hipMalloc((void**)&S->d_log_rows, sizeof(int) * S->B));
-    S->log_rows_cap = cap;
+  const size_t bytes = sizeof(double) * (size_t)S->B * cap * LOG_NLIST;
+  if (!S->d_log.regrow(bytes)) {
+    (void)hipGetLastError();
+    char buf[256];
+    snprintf(buf, sizeof(buf), "logging: the SolverInfo lists need %.2f GB (batch %d x (max_iter - 1) %d x %d lists x 8 B)",
+             bytes / 1e9, S->B, cap, (int)LOG_NLIST);
+    g_last_error = buf;
+    return LOIKB_ERR_HIP;
   }
-  HIPCHK(hipMemsetAsync(S->d_log, 0, sizeof(double) * (size_t)S->B * cap * LOG_NLIST, S->stream));
+  BUFCHK(S->d_log_rows.regrow(sizeof(int) * S->B));
+  S->log_rows_cap = cap;
+  HIPCHK(hipMemsetAsync(S->d_log, 0, bytes, S->stream));
   return LOIKB_OK;
 }
 
@@ -3608,8 +3545,8 @@ static int finish_logged(loikb_solver_impl* S, const PassParams& P)
     // n_unfinished, and instance_iterations as the other engines count it: the iterations of every instance, tail solve included
     Chunk* C0 = &S->chunks[0];
     int rc;
-    if ((rc = ensure_stage(S, sizeof(unsigned long long)))) return rc;
-    unsigned long long* d_sum = (unsigned long long*)S->d_stage;
+    if ((rc = regrow(S->d_stage, sizeof(unsigned long long)))) return rc;
+    unsigned long long* d_sum = S->d_stage.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(C0->d_counters, 0, sizeof(unsigned int), S->stream));
     HIPCHK(hipMemsetAsync(d_sum, 0, sizeof(unsigned long long), S->stream));
     with_real(S, [&](auto t) {
@@ -3713,8 +3650,8 @@ static int pass_get(loikb_solver_impl* S, int field, void* out, bool to_dev)
   if (scal >= 0) { off = L.scal + scal; n = 1; }
   const size_t bytes = sizeof(double) * (size_t)S->B * n;
   int rc;
-  if ((rc = ensure_stage(S, bytes))) return rc;
-  double* dst = (to_dev && !is_int) ? (double*)out : (double*)S->d_stage;
+  if ((rc = regrow(S->d_stage, bytes))) return rc;
+  double* dst = (to_dev && !is_int) ? (double*)out : S->d_stage.as<double>();
   if (field == LOIKB_F_HIS)
     hipLaunchKernelGGL(k_pass_get_his, grid1(S->B), dim3(256), 0, S->stream, S->PL, (const double*)S->d_pass, (const int*)S->d_link_sel, nl, dst);
   else if (width)
@@ -3823,8 +3760,8 @@ const char* loikb_plan_string(loikb_solver* S)
   }
   {   // device memory the handle holds besides the instances' tiles (the kept getter scratch was nowhere to be seen)
     size_t fs = 0, pk = 0, hs = 0;
-    for (const Chunk& C : S->chunks) { fs += C.fslots_bytes; pk += C.park_bytes; hs += C.hslots_bytes; }
-    const size_t gs = S->getscr_bytes[0] + S->getscr_bytes[1];
+    for (const Chunk& C : S->chunks) { fs += C.d_fslots.bytes(); pk += C.d_park.bytes(); hs += C.d_hslots.bytes(); }
+    const size_t gs = S->d_getscr[0].bytes() + S->d_getscr[1].bytes();
     if (fs + pk + hs + gs > 0) {
       char b4[240];
       snprintf(b4, sizeof(b4), "; device buffers: decade slots %.0f MB, park records %.0f MB, getters' scratch %.0f MB (kept between calls; "
@@ -3918,9 +3855,9 @@ int loikb_get_results(loikb_solver* S, unsigned int mask, double* z, double* nu,
     }
     R->off[NF] = off;
     R->n = off;
-    if (R->d) { HIPCHK(hipStreamSynchronize(S->stream)); HIPCHK(hipFree(R->d)); R->d = nullptr; }
+    if (R->d) { HIPCHK(hipStreamSynchronize(S->stream)); R->d.release(); }
     R->key[0] = -1;
-    HIPCHK(hipMalloc((void**)&R->d, sizeof(int) * (size_t)std::max(off, 1)));
+    BUFCHK(R->d.regrow(sizeof(int) * (size_t)std::max(off, 1)));
     HIPCHK(hipMemcpy(R->d, rm.data(), sizeof(int) * (size_t)off, hipMemcpyHostToDevice));   // (synchronous: rm is a local)
     memcpy(R->key, key, sizeof(key));
   }
@@ -3956,18 +3893,17 @@ int loikb_get_results(loikb_solver* S, unsigned int mask, double* z, double* nu,
     }
     return LOIKB_OK;
   }
-  if (bytes > S->h_res_bytes) {
-    if (S->h_res) { HIPCHK(hipStreamSynchronize(S->stream)); HIPCHK(hipHostFree(S->h_res)); S->h_res = nullptr; S->h_res_bytes = 0; }
-    HIPCHK(hipHostMalloc((void**)&S->h_res, bytes));
-    S->h_res_bytes = bytes;
+  if (bytes > S->h_res.bytes()) {
+    if (S->h_res) HIPCHK(hipStreamSynchronize(S->stream));
+    BUFCHK(S->h_res.regrow(bytes));
   }
   // one element per thread (a thread per instance walks its ~400 rows one dependent load after the other: 0.25 ms whatever the batch);
   // a handful of instances straight into the pinned buffer, more through the staging buffer and ONE copy
   const bool direct = bytes <= ((size_t)256 << 10);
   double* dst = S->h_res;
   if (!direct) {
-    if ((rc = ensure_stage(S, bytes))) return rc;
-    dst = (double*)S->d_stage;
+    if ((rc = regrow(S->d_stage, bytes))) return rc;
+    dst = S->d_stage.as<double>();
   }
   {
     const long long total = (long long)S->B * n;
@@ -4070,18 +4006,18 @@ int loikb_get(loikb_solver* S, int field, void* out, int out_flags)
   double* dst = (double*)out;
   int rc;
   if (!to_dev) {
-    if ((rc = ensure_stage(S, bytes))) return rc;
-    dst = (double*)S->d_stage;
+    if ((rc = regrow(S->d_stage, bytes))) return rc;
+    dst = S->d_stage.as<double>();
   }
   if (select) {
     final_dst = dst;
-    if ((rc = ensure_getscr(S, 0, sizeof(double) * (size_t)S->B * nb * (field == LOIKB_F_HIS ? 21 : 6)))) return rc;
+    if ((rc = regrow(S->d_getscr[0], sizeof(double) * (size_t)S->B * nb * (field == LOIKB_F_HIS ? 21 : 6)))) return rc;
     d_tmp = S->d_getscr[0];
     dst = (double*)d_tmp;
   }
   if ((field == LOIKB_F_UDINV || field == LOIKB_F_PIS) && S->ud_stale) {
     // instances left by the flat engine carry neither UDinv nor pis (tag -2 in their scalar record): rebuilt in place
-    if ((rc = ensure_getscr(S, 1, S->esz * (size_t)S->B * nb * 21))) return rc;
+    if ((rc = regrow(S->d_getscr[1], S->esz * (size_t)S->B * nb * 21))) return rc;
     void* d_scr = S->d_getscr[1];
     with_real(S, [&](auto t) {
       using T = decltype(t);
@@ -4120,10 +4056,9 @@ int loikb_get(loikb_solver* S, int field, void* out, int out_flags)
     if (!to_dev && n > 0 && dbytes <= ((size_t)256 << 10)) {
       // a small batch, a host destination: one element per thread straight into the pinned buffer (loikb_get_results' path) and ONE synchronisation --
       // no copy operation; the int fields' masks (k_download_rows') applied here
-      if (dbytes > S->h_res_bytes) {
-        if (S->h_res) { HIPCHK(hipStreamSynchronize(S->stream)); HIPCHK(hipHostFree(S->h_res)); S->h_res = nullptr; S->h_res_bytes = 0; }
-        HIPCHK(hipHostMalloc((void**)&S->h_res, (size_t)256 << 10));
-        S->h_res_bytes = (size_t)256 << 10;
+      if (dbytes > S->h_res.bytes()) {
+        if (S->h_res) HIPCHK(hipStreamSynchronize(S->stream));
+        BUFCHK(S->h_res.regrow((size_t)256 << 10));
       }
       const long long total = (long long)S->B * n;
       const dim3 g((unsigned)((total + 255) / 256));
@@ -4157,6 +4092,15 @@ int loikb_get(loikb_solver* S, int field, void* out, int out_flags)
   }
   if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));
+  return LOIKB_OK;
+}
+
+// undeclared debug export: what this process holds through the library's two allocators right now --
+// {device allocations, their bytes, pinned allocations, their bytes}.  The tests ask whether close() gives back what a handle took.
+int loikb_debug_device_memory(unsigned long long out[4])
+{
+  if (!out) return LOIKB_ERR_ARG;
+  for (int k = 0; k < 4; ++k) out[k] = g_devmem[k].load();
   return LOIKB_OK;
 }
 

@@ -340,12 +340,12 @@ int loikb_forward_kinematics(loikb_solver* S, const int* links, int n, double* o
   for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
   const size_t bytes = sizeof(double) * (size_t)S->B * n * 12;
   int rc;
-  if ((rc = ensure_getscr(S, 1, sizeof(int) * (size_t)n))) return rc;
-  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) return rc;
-  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  if ((rc = regrow(S->d_getscr[1], sizeof(int) * (size_t)n))) return rc;
+  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) return rc;
+  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
   HIPCHK(hipMemcpyAsync(S->d_getscr[1], dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
   hipLaunchKernelGGL(k_link_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
-                     S->d_idx_q, (const int*)S->d_getscr[1], n, S->B, dst);
+                     S->d_idx_q, S->d_getscr[1].as<const int>(), n, S->B, dst);
   HIPCHK(hipGetLastError());
   if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
   HIPCHK(hipStreamSynchronize(S->stream));   // (dl is a local)
@@ -696,11 +696,11 @@ int loikb_frame_placements(loikb_solver* S, const int* links, const double* fram
   for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
   const size_t bytes = sizeof(double) * (size_t)S->B * n * 12, fbytes = sizeof(double) * (size_t)n * 12;
   int rc;
-  if ((rc = ensure_getscr(S, 1, fbytes + sizeof(int) * (size_t)n))) return rc;
-  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) return rc;
-  double* dst = to_dev ? out : (double*)S->d_getscr[0];
-  double* d_fr = (double*)S->d_getscr[1];
-  int* d_dl = (int*)((char*)S->d_getscr[1] + fbytes);
+  if ((rc = regrow(S->d_getscr[1], fbytes + sizeof(int) * (size_t)n))) return rc;
+  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) return rc;
+  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
+  double* d_fr = S->d_getscr[1].as<double>();
+  int* d_dl = (int*)(S->d_getscr[1].as<char>() + fbytes);
   HIPCHK(hipMemcpyAsync(d_fr, frames, fbytes, hipMemcpyHostToDevice, S->stream));
   HIPCHK(hipMemcpyAsync(d_dl, dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
   hipLaunchKernelGGL(k_frame_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
@@ -750,9 +750,9 @@ static int jac_stage_entries(loikb_solver_impl* S, const int* dl, const double* 
 {
   const size_t fbytes = sizeof(double) * (size_t)n * 12, ibytes = sizeof(int) * (size_t)n;
   int rc;
-  if ((rc = ensure_getscr(S, 1, fbytes + 2 * ibytes))) return rc;
-  *d_fr = (double*)S->d_getscr[1];
-  *d_dl = (int*)((char*)S->d_getscr[1] + fbytes);
+  if ((rc = regrow(S->d_getscr[1], fbytes + 2 * ibytes))) return rc;
+  *d_fr = S->d_getscr[1].as<double>();
+  *d_dl = (int*)(S->d_getscr[1].as<char>() + fbytes);
   *d_rows = *d_dl + n;
   HIPCHK(hipMemcpyAsync(*d_fr, fr, fbytes, hipMemcpyHostToDevice, S->stream));
   HIPCHK(hipMemcpyAsync(*d_dl, dl, ibytes, hipMemcpyHostToDevice, S->stream));
@@ -784,8 +784,8 @@ int loikb_frame_jacobians(loikb_solver* S, const int* links, const double* frame
   const size_t pairs = (size_t)S->B * n, bytes = sizeof(double) * pairs * 6 * S->nb;
   double* d_fr; int *d_dl, *d_rows;
   if ((rc = jac_stage_entries(S, dl.data(), fr.data(), nullptr, n, &d_fr, &d_dl, &d_rows))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
   hipLaunchKernelGGL(k_frame_jacobians, dim3((unsigned)((pairs + waves - 1) / waves)), dim3(64 * waves), lds, S->stream, (const double*)S->d_q, S->nq,
                      S->d_jd, S->d_idx_q, (const int*)d_dl, (const double*)d_fr, n, S->B, S->nb, reference_frame, dst);
   HIPCHK(hipGetLastError());
@@ -827,8 +827,8 @@ int loikb_frame_dexterity(loikb_solver* S, const int* links, const double* frame
   const size_t pairs = (size_t)S->B * n, bytes = sizeof(double) * pairs * DEX_N;
   double* d_fr; int *d_dl, *d_rows;
   if ((rc = jac_stage_entries(S, dl.data(), fr.data(), rw.data(), n, &d_fr, &d_dl, &d_rows))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev && (rc = ensure_getscr(S, 0, bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* dst = to_dev ? out : (double*)S->d_getscr[0];
+  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
   hipLaunchKernelGGL(k_frame_dexterity, grid1(pairs), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q, (const int*)d_dl,
                      (const double*)d_fr, (const int*)d_rows, n, S->B, p->length, dst);
   HIPCHK(hipGetLastError());
@@ -888,23 +888,6 @@ int loikb_collision_version(void) { return LOIKB_COLLISION_VERSION; }
 
 using Collision = loikb_solver_impl::PoseState::Collision;
 
-// a device copy of `bytes` of host memory in a buffer of its own (nullptr for bytes == 0); complete on return
-static int col_upload(loikb_solver_impl* S, const void* src, size_t bytes, void** out)
-{
-  *out = nullptr;
-  if (bytes == 0) return LOIKB_OK;
-  void* p = nullptr;
-  HIPCHK(hipMalloc(&p, bytes));
-  if (hipMemcpyAsync(p, src, bytes, hipMemcpyHostToDevice, S->stream) != hipSuccess || hipStreamSynchronize(S->stream) != hipSuccess) {
-    (void)hipFree(p);
-    (void)hipGetLastError();
-    g_last_error = "collision: the upload of the model failed";
-    return LOIKB_ERR_HIP;
-  }
-  *out = p;
-  return LOIKB_OK;
-}
-
 // the parent of every link in the caller's tree, from the device tree: the link whose last chain joint is the parent of the first
 static std::vector<int> col_ext_parents(const loikb_solver_impl* S)
 {
@@ -962,16 +945,15 @@ int loikb_collision_set_spheres(loikb_solver* S, const int* links, const double*
   std::vector<unsigned short> pairs;
   if (ns > 0 && C.self_on) pairs = col_build_pairs(S, lk, C.ignore);
   if (!col_ordinals_fit(ns, C.nws, C.nwb, pairs.size() / 2)) { g_last_error = "collision_set_spheres: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
-  void *d_sph, *d_scar = nullptr, *d_car = nullptr, *d_pairs = nullptr;
+  DevBuf<double> d_sph;
+  DevBuf<int> d_scar, d_car;
+  DevBuf<unsigned short> d_pairs;
   int rc;
-  if ((rc = col_upload(S, spheres, sizeof(double) * 4 * ns, &d_sph)) || (rc = col_upload(S, scar.data(), sizeof(int) * ns, &d_scar)) ||
-      (rc = col_upload(S, car.data(), sizeof(int) * car.size(), &d_car)) || (rc = col_upload(S, pairs.data(), sizeof(unsigned short) * pairs.size(), &d_pairs))) {
-    for (void* p : {d_sph, d_scar, d_car, d_pairs}) if (p) (void)hipFree(p);
+  if ((rc = col_upload(S, spheres, sizeof(double) * 4 * ns, d_sph)) || (rc = col_upload(S, scar.data(), sizeof(int) * ns, d_scar)) ||
+      (rc = col_upload(S, car.data(), sizeof(int) * car.size(), d_car)) || (rc = col_upload(S, pairs.data(), sizeof(unsigned short) * pairs.size(), d_pairs)))
     return rc;
-  }
-  HIPCHK(hipStreamSynchronize(S->stream));   // (nothing queued reads the buffers that go)
-  for (void* p : {(void*)C.d_sph, (void*)C.d_scar, (void*)C.d_car, (void*)C.d_pairs}) if (p) (void)hipFree(p);
-  C.d_sph = (double*)d_sph; C.d_scar = (int*)d_scar; C.d_car = (int*)d_car; C.d_pairs = (unsigned short*)d_pairs;
+  HIPCHK(hipStreamSynchronize(S->stream));   // (nothing queued reads the buffers that go: the locals take them)
+  C.d_sph.swap(d_sph); C.d_scar.swap(d_scar); C.d_car.swap(d_car); C.d_pairs.swap(d_pairs);
   C.links.swap(lk); C.car.swap(car); C.scar.swap(scar); C.pairs.swap(pairs);
   C.ns = ns;
   if (ns == 0) { C.self_on = false; C.ignore.clear(); }
@@ -1000,16 +982,11 @@ int loikb_collision_set_world(loikb_solver* S, const double* wspheres, int nws, 
   Collision& C = S->pose.col;
   if (!col_ordinals_fit(C.ns, nws, nwb, C.pairs.size() / 2)) { g_last_error = "collision_set_world: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
   HIPCHK(hipSetDevice(S->device));
-  void *d_wsph, *d_wbox = nullptr;
+  DevBuf<double> d_wsph, d_wbox;
   int rc;
-  if ((rc = col_upload(S, wspheres, sizeof(double) * 4 * nws, &d_wsph)) || (rc = col_upload(S, wboxes, sizeof(double) * 15 * nwb, &d_wbox))) {
-    if (d_wsph) (void)hipFree(d_wsph);
-    return rc;
-  }
+  if ((rc = col_upload(S, wspheres, sizeof(double) * 4 * nws, d_wsph)) || (rc = col_upload(S, wboxes, sizeof(double) * 15 * nwb, d_wbox))) return rc;
   HIPCHK(hipStreamSynchronize(S->stream));
-  if (C.d_wsph) (void)hipFree(C.d_wsph);
-  if (C.d_wbox) (void)hipFree(C.d_wbox);
-  C.d_wsph = (double*)d_wsph; C.d_wbox = (double*)d_wbox;
+  C.d_wsph.swap(d_wsph); C.d_wbox.swap(d_wbox);
   C.nws = nws; C.nwb = nwb;
   return LOIKB_OK;
 }
@@ -1033,12 +1010,11 @@ int loikb_collision_set_self_pairs(loikb_solver* S, int enable, const int* ignor
     pairs = col_build_pairs(S, C.links, ignore);
   }
   if (!col_ordinals_fit(C.ns, C.nws, C.nwb, pairs.size() / 2)) { g_last_error = "collision_set_self_pairs: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
-  void* d_pairs;
+  DevBuf<unsigned short> d_pairs;
   int rc;
-  if ((rc = col_upload(S, pairs.data(), sizeof(unsigned short) * pairs.size(), &d_pairs))) return rc;
+  if ((rc = col_upload(S, pairs.data(), sizeof(unsigned short) * pairs.size(), d_pairs))) return rc;
   HIPCHK(hipStreamSynchronize(S->stream));
-  if (C.d_pairs) (void)hipFree(C.d_pairs);
-  C.d_pairs = (unsigned short*)d_pairs;
+  C.d_pairs.swap(d_pairs);
   C.pairs.swap(pairs);
   C.ignore.swap(ignore);
   C.self_on = enable != 0;
@@ -1064,13 +1040,9 @@ static int col_launch(loikb_solver_impl* S, const double* dq, int n, double* d_m
   const dim3 grid((unsigned)(((size_t)n + waves - 1) / waves)), block(64 * waves);
   if (hbm) {
     const size_t need = sizeof(double) * (size_t)n * ncar * 12;
-    if (need > C.place_cap) {
+    if (need > C.d_place.bytes()) {
       HIPCHK(hipStreamSynchronize(S->stream));
-      if (C.d_place) HIPCHK(hipFree(C.d_place));
-      C.d_place = nullptr;
-      C.place_cap = 0;
-      HIPCHK(hipMalloc((void**)&C.d_place, need));
-      C.place_cap = need;
+      BUFCHK(C.d_place.regrow(need));
     }
     hipLaunchKernelGGL(k_link_placements, grid1((size_t)n * ncar), dim3(256), 0, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, (const int*)C.d_car,
                        ncar, n, C.d_place);
@@ -1099,9 +1071,9 @@ int loikb_clearance(loikb_solver* S, const double* q, int n, int in_flags, doubl
   int rc;
   const void* dq = S->d_q;
   if (q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) return rc;
-  if (!to_dev && (rc = ensure_getscr(S, 0, mbytes + wbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* d_min = to_dev ? out_min : (double*)S->d_getscr[0];
-  int* d_wit = to_dev ? out_witness : (out_witness ? (int*)((char*)S->d_getscr[0] + mbytes) : nullptr);
+  if (!to_dev && (rc = regrow(S->d_getscr[0], mbytes + wbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* d_min = to_dev ? out_min : S->d_getscr[0].as<double>();
+  int* d_wit = to_dev ? out_witness : (out_witness ? (int*)(S->d_getscr[0].as<char>() + mbytes) : nullptr);
   if ((rc = col_launch(S, (const double*)dq, n, d_min, d_wit))) { (void)hipStreamSynchronize(S->stream); return rc; }
   if (!to_dev) {
     HIPCHK(hipMemcpyAsync(out_min, d_min, mbytes, hipMemcpyDeviceToHost, S->stream));
@@ -1141,11 +1113,11 @@ static int motion_inputs(loikb_solver_impl* S, const double* a, size_t abytes, c
   if (dev) { *da = a; *db = b; return LOIKB_OK; }
   const size_t off = (abytes + 255) & ~(size_t)255;
   int rc;
-  if ((rc = ensure_stage(S, off + bbytes))) return rc;
+  if ((rc = regrow(S->d_stage, off + bbytes))) return rc;
   HIPCHK(hipMemcpyAsync(S->d_stage, a, abytes, hipMemcpyHostToDevice, S->stream));
-  if (b) HIPCHK(hipMemcpyAsync((char*)S->d_stage + off, b, bbytes, hipMemcpyHostToDevice, S->stream));
-  *da = (const double*)S->d_stage;
-  *db = b ? (const double*)((char*)S->d_stage + off) : nullptr;
+  if (b) HIPCHK(hipMemcpyAsync(S->d_stage.as<char>() + off, b, bbytes, hipMemcpyHostToDevice, S->stream));
+  *da = S->d_stage.as<const double>();
+  *db = b ? (const double*)(S->d_stage.as<char>() + off) : nullptr;
   return LOIKB_OK;
 }
 
@@ -1160,8 +1132,8 @@ int loikb_difference(loikb_solver* S, const double* q0, const double* q1, int n,
   const double *d0, *d1;
   int rc;
   if ((rc = motion_inputs(S, q0, qbytes, q1, qbytes, in_flags & LOIKB_IN_DEVICE, &d0, &d1))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev && (rc = ensure_getscr(S, 0, vbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* d_v = to_dev ? out_v : (double*)S->d_getscr[0];
+  if (!to_dev && (rc = regrow(S->d_getscr[0], vbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  double* d_v = to_dev ? out_v : S->d_getscr[0].as<double>();
   hipLaunchKernelGGL(k_difference, grid1((size_t)n, 64), dim3(64), 0, S->stream, d0, d1, S->nq, S->d_jd, S->d_idx_q, S->nb, n, 0, d_v);
   HIPCHK(hipGetLastError());
   if (!to_dev) HIPCHK(hipMemcpyAsync(out_v, d_v, vbytes, hipMemcpyDeviceToHost, S->stream));
@@ -1200,13 +1172,9 @@ static int motion_launch(loikb_solver_impl* S, const double* dqa, const double* 
   if (slab) {
     const int waves = std::min(n, MOTION_SLAB_WAVES);
     const size_t need = sizeof(double) * aux * (size_t)waves;
-    if (need > C.mslab_cap) {
+    if (need > C.d_mslab.bytes()) {
       HIPCHK(hipStreamSynchronize(S->stream));
-      if (C.d_mslab) HIPCHK(hipFree(C.d_mslab));
-      C.d_mslab = nullptr;
-      C.mslab_cap = 0;
-      HIPCHK(hipMalloc((void**)&C.d_mslab, need));
-      C.mslab_cap = need;
+      BUFCHK(C.d_mslab.regrow(need));
     }
     hipLaunchKernelGGL(k_motion_clearance<true>, dim3(waves), dim3(64), lds, S->stream, dqa, ddv, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T, m, prm,
                        C.d_mslab, d_val, d_info);
@@ -1225,15 +1193,15 @@ static int motion_run(loikb_solver_impl* S, const double* dqa, const double* ddv
   const size_t vbytes = sizeof(double) * 3 * (size_t)n, ibytes = sizeof(int) * 5 * (size_t)n;
   int rc;
   if (!ddv) {
-    if ((rc = ensure_getscr(S, 1, sizeof(double) * (size_t)n * S->nv))) return rc;
+    if ((rc = regrow(S->d_getscr[1], sizeof(double) * (size_t)n * S->nv))) return rc;
     hipLaunchKernelGGL(k_difference, grid1((size_t)n, 64), dim3(64), 0, S->stream, dqa, (const double*)nullptr, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T,
-                       (double*)S->d_getscr[1]);
+                       S->d_getscr[1].as<double>());
     HIPCHK(hipGetLastError());
-    ddv = (const double*)S->d_getscr[1];
+    ddv = S->d_getscr[1].as<const double>();
   }
-  if (!to_dev && (rc = ensure_getscr(S, 0, vbytes + ibytes))) return rc;
-  double* d_val = to_dev ? out_val : (double*)S->d_getscr[0];
-  int* d_info = to_dev ? out_info : (int*)((char*)S->d_getscr[0] + vbytes);
+  if (!to_dev && (rc = regrow(S->d_getscr[0], vbytes + ibytes))) return rc;
+  double* d_val = to_dev ? out_val : S->d_getscr[0].as<double>();
+  int* d_info = to_dev ? out_info : (int*)(S->d_getscr[0].as<char>() + vbytes);
   if ((rc = motion_launch(S, dqa, ddv, n, T, p, d_val, d_info))) return rc;
   if (!to_dev) {
     HIPCHK(hipMemcpyAsync(out_val, d_val, vbytes, hipMemcpyDeviceToHost, S->stream));
@@ -1581,15 +1549,9 @@ int loikb_multistart_get(loikb_solver* S, int field, void* out, int out_flags)
 // ---- include/loik_amd_path.h (kernels in loik_pose_path.hpp) ------------------------------------------------------------------
 int loikb_path_version(void) { return LOIKB_PATH_VERSION; }
 
-// a buffer of the path state that is sized by the waypoint count: grown (never shrunk) to `bytes`, its contents are not kept
-static int path_grow(void** buf, size_t bytes)
-{
-  void* p = nullptr;
-  HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
-  if (*buf) HIPCHK(hipFree(*buf));
-  *buf = p;
-  return LOIKB_OK;
-}
+// The buffers of the path and track states that are sized by the waypoint / step count are grown (never shrunk) with replace():
+// a call that fails to grow one keeps the results of the last; their contents are not kept across a growth.  (No size is zero:
+// both entry points insist on a count >= 1.)
 
 // the [B] arrays on first use, and room for T waypoints in the staging buffer.  Holds no result of an earlier call.
 static int path_alloc_inputs(loikb_solver_impl* S, int T)
@@ -1605,11 +1567,7 @@ static int path_alloc_inputs(loikb_solver_impl* S, int T)
       return rc;
     }
   }
-  if (T > W.cap_wp) {
-    if ((rc = path_grow((void**)&W.d_wp, sizeof(double) * B * (size_t)T * nc * 12))) return rc;
-    W.cap_wp = T;
-  }
-  return LOIKB_OK;
+  return replace(W.d_wp, sizeof(double) * B * (size_t)T * nc * 12);
 }
 
 // WSTEPS and, with record, Q for T waypoints: they hold the results of the last call, so they are regrown only by a call that
@@ -1619,15 +1577,8 @@ static int path_alloc_results(loikb_solver_impl* S, int T, bool record)
   loikb_solver_impl::PathState& W = S->path;
   const size_t B = (size_t)S->B;
   int rc;
-  if (T > W.cap_T) {
-    if ((rc = path_grow((void**)&W.d_wsteps, sizeof(int) * B * (size_t)T))) return rc;
-    W.cap_T = T;
-  }
-  if (record && T > W.cap_TQ) {
-    if ((rc = path_grow((void**)&W.d_Q, sizeof(double) * B * (size_t)T * S->nq))) return rc;
-    W.cap_TQ = T;
-  }
-  return LOIKB_OK;
+  if ((rc = replace(W.d_wsteps, sizeof(int) * B * (size_t)T))) return rc;
+  return record ? replace(W.d_Q, sizeof(double) * B * (size_t)T * S->nq) : LOIKB_OK;
 }
 
 int loikb_solve_pose_path(loikb_solver* S, const double* q, const double* waypoints, int in_flags, const loikb_pose_params* p,
@@ -1730,11 +1681,7 @@ static int track_alloc_inputs(loikb_solver_impl* S, int T)
       return rc;
     }
   }
-  if (T > K.cap_smp) {
-    if ((rc = path_grow((void**)&K.d_smp, sizeof(double) * B * ((size_t)T + 1) * nc * 12))) return rc;
-    K.cap_smp = T;
-  }
-  return LOIKB_OK;
+  return replace(K.d_smp, sizeof(double) * B * ((size_t)T + 1) * nc * 12);
 }
 
 // ERRMAX, INNER and, as `record` says, Q and Z for T steps: they hold the results of the last call, so they are regrown only by a
@@ -1744,18 +1691,9 @@ static int track_alloc_results(loikb_solver_impl* S, int T, int record)
   loikb_solver_impl::TrackState& K = S->track;
   const size_t B = (size_t)S->B;
   int rc;
-  if (T > K.cap_T) {
-    if ((rc = path_grow((void**)&K.d_errmax, sizeof(double) * B * ((size_t)T + 1))) || (rc = path_grow((void**)&K.d_inner, sizeof(int) * B * (size_t)T))) return rc;
-    K.cap_T = T;
-  }
-  if ((record & LOIKB_TRACK_REC_Q) && T > K.cap_TQ) {
-    if ((rc = path_grow((void**)&K.d_Q, sizeof(double) * B * ((size_t)T + 1) * S->nq))) return rc;
-    K.cap_TQ = T;
-  }
-  if ((record & LOIKB_TRACK_REC_Z) && T > K.cap_TZ) {
-    if ((rc = path_grow((void**)&K.d_Z, sizeof(double) * B * (size_t)T * S->nb))) return rc;
-    K.cap_TZ = T;
-  }
+  if ((rc = replace(K.d_errmax, sizeof(double) * B * ((size_t)T + 1))) || (rc = replace(K.d_inner, sizeof(int) * B * (size_t)T))) return rc;
+  if ((record & LOIKB_TRACK_REC_Q) && (rc = replace(K.d_Q, sizeof(double) * B * ((size_t)T + 1) * S->nq))) return rc;
+  if ((record & LOIKB_TRACK_REC_Z) && (rc = replace(K.d_Z, sizeof(double) * B * (size_t)T * S->nb))) return rc;
   return LOIKB_OK;
 }
 
