@@ -1,8 +1,9 @@
 """GPU: the clearance query of include/loik_amd_collision.h against the numpy reference of tests/clearance_numpy.py (proven on the CPU by
-test_clearance_numpy.py): six robots (a chain, a tree, nq != nv, helical / prismatic joints, a 170-joint tree that launches fewer
-configurations per workgroup, a 330-joint tree whose liM records do not fit one wavefront's LDS and takes the placements from HBM), the
-sizes at which the kernel changes its path, the witness, ties, the sphere / box branches, the q routes, a NaN row, neutrality towards
-the solves and the validation."""
+test_clearance_numpy.py): eight robots (a chain, a tree, nq != nv, helical / prismatic joints, a 170-joint tree that launches fewer
+configurations per workgroup, a 330-joint tree whose liM records do not fit one wavefront's LDS and takes the placements from HBM, a
+tree with composite joints whose links are several device joints each, a second multi-DoF tree), the sizes at which the kernel
+changes its path, the caller's parents and ignore pairs on composite links, the witness, ties, the sphere / box branches, the q
+routes, a NaN row, neutrality towards the solves and the validation."""
 import ctypes as C
 
 import numpy as np
@@ -12,7 +13,7 @@ import loik_amd
 from loik_amd import capi
 
 from helpers import random_rotation, random_tree
-from test_pose_ik import PRM, _handle, _links
+from test_pose_ik import PRM, _fk_models, _handle, _links
 import clearance_numpy as CN
 import pose_numpy as P
 import qp_cases as QC
@@ -25,13 +26,16 @@ BOUND = 1e-13
 # name -> (configurations, spheres per link).  tree170: 170 * 96 * 2 + 170 * 32 bytes = 38 KB a wavefront, one configuration per
 # workgroup instead of four; tree330: 74 KB > 64 KB, the HBM-placement instantiation.  The reference walks every root path in Python,
 # so the two big trees take fewer configurations
-ROBOTS = {"panda7": (65, 3), "talos32": (65, 2), "multidof20": (65, 2), "helical24": (65, 2), "tree170": (9, 1), "tree330": (3, 1)}
+ROBOTS = {"panda7": (65, 3), "talos32": (65, 2), "multidof20": (65, 2), "helical24": (65, 2), "tree170": (9, 1), "tree330": (3, 1),
+          "composite20": (65, 2), "multidof13": (65, 2)}
 BIG_TREES = {"tree170": (52, 170), "tree330": (53, 330)}
 
 _CASES = {}
 
 
 def _model(name):
+    if name == "multidof13":   # free-flyer root, translation, two ZYX, planar, three (cos, sin) revolutes
+        return _fk_models()[3]
     return random_tree(*BIG_TREES[name]) if name in BIG_TREES else QC.model_of(name)
 
 
@@ -91,7 +95,7 @@ def _compare(got, want, spheres, what):
     return worst
 
 
-# ---- 1. against numpy on six robots --------------------------------------------------------------------------------------------------
+# ---- 1. against numpy on eight robots ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(ROBOTS))
 def test_clearance_matches_numpy(name):
     c = _case(name)
@@ -177,6 +181,63 @@ def test_one_self_pair_and_more_than_64():
     s.set_self_collision(True)
     s.set_collision_spheres([], np.zeros((0, 4)))
     assert s.num_self_pairs() == 0
+    s.close()
+
+
+# ---- 2b. a caller's link that is several device joints ---------------------------------------------------------------------------------
+def _family(model, c):
+    """(the parent, c, the first child) of link c in the caller's tree"""
+    return int(model.parents[c]), c, min(i for i in range(1, model.njoints) if int(model.parents[i]) == c)
+
+
+def test_composite_links_keep_the_callers_parents():
+    """composite20: link 1 is two device joints, link 5 three, link 9 four.  The self-pair list goes by the caller's tree: the parent of
+    a composite link is the link that carries the parent of its first device joint, its child hangs on its last one.  Spheres on a
+    composite link, its parent and its child: only parent against child is a pair.  Then every link: no witness names a pair that
+    the caller's parents exclude"""
+    model = _model("composite20")
+    assert {c: len(v) for c, v in model.composite.items()} == {1: 2, 5: 3, 9: 4}
+    q = model.random_configurations(np.random.default_rng(560), 65)
+    s = _open(model, q)
+    for c in sorted(model.composite):
+        fam = _family(model, c)
+        lk, spheres = CN.make_spheres(model, 2, 561 + c, links=fam)
+        spheres[:, 3] += 0.1     # (large enough that neighbours overlap: a parent / child pair wrongly listed would be the minimum)
+        pairs = CN.self_pairs(model.parents, lk)
+        assert pairs == [(a, b) for a in (0, 1) for b in (4, 5)]
+        s.set_collision_spheres(lk, spheres)
+        s.set_self_collision(True)
+        assert s.num_self_pairs() == len(pairs) == 4
+        got = s.clearance()
+        _compare(got, CN.clearance(model, q, lk, spheres, pairs=pairs), spheres, "composite20 link %d, its parent and its child" % c)
+        assert np.all(got["witness"][:, 0] == CN.SELF) and {(int(a), int(b)) for _, a, b in got["witness"]} <= set(pairs)
+    k = _case("composite20")
+    s.set_collision_spheres(k["links"], k["spheres"])
+    s.set_self_collision(True)
+    linked = {(int(k["links"][a]), int(k["links"][b])) for a, b in k["pairs"]}
+    for c in sorted(model.composite):
+        par, _, kid = _family(model, c)
+        assert not linked & {(par, c), (c, par), (c, kid), (kid, c)} and ((par, kid) in linked or par == 0)
+    got = s.clearance()
+    _compare(got, CN.clearance(model, q, k["links"], k["spheres"], pairs=k["pairs"]), k["spheres"], "composite20 self pairs alone")
+    assert np.all(got["witness"][:, 0] == CN.SELF) and {(int(a), int(b)) for _, a, b in got["witness"]} <= set(k["pairs"])
+    s.close()
+
+
+def test_an_ignore_pair_that_names_a_composite_link():
+    k = _case("composite20")
+    model, q, links, spheres = k["model"], k["q"], k["links"], k["spheres"]
+    s = _open(model, q)
+    s.set_collision_spheres(links, spheres)
+    # composite against single, composite against composite, either order; (9, 10) is parent and child whatever the list says
+    s.set_self_collision(True, ignore=[(5, 12), (1, 9), (17, 9), (9, 10)])
+    pairs = CN.self_pairs(model.parents, links, ignore=[(12, 5), (9, 1), (9, 17), (10, 9)])
+    assert s.num_self_pairs() == len(pairs) == len(k["pairs"]) - 3 * 4
+    got = s.clearance()
+    _compare(got, CN.clearance(model, q, links, spheres, pairs=pairs), spheres, "composite20 ignore, self pairs alone")
+    assert {(int(a), int(b)) for _, a, b in got["witness"]} <= set(pairs)
+    s.set_collision_world(k["ws"], k["wb"])
+    _compare(s.clearance(), CN.clearance(model, q, links, spheres, k["ws"], k["wb"], pairs), spheres, "composite20 ignore")
     s.close()
 
 

@@ -166,7 +166,7 @@ def test_a_thin_box_between_clear_samples_blocks():
 
 
 # ---- 5. the segments of the GPU tests -----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["panda7", "talos32", "multidof20", "helical24"])
+@pytest.mark.parametrize("name", ["panda7", "talos32", "multidof20", "helical24", "composite20", "multidof13"])
 def test_gpu_cases_stay_clear_of_their_thresholds(name):
     """tests/test_motion_clearance.py leaves a segment out of the comparison when a decision of the reference lies within 1e-9 of its
     threshold, at most 2 % of a robot's: with its seeds the reference alone stays within that, and all three outcomes occur"""
@@ -176,3 +176,27 @@ def test_gpu_cases_stay_clear_of_their_thresholds(name):
     assert want["near"].sum() <= 0.02 * c["n"], (name, int(want["near"].sum()))
     for st in (MN.FREE, MN.BLOCKED, MN.UNDECIDED):
         assert (want["status"] == st).any(), (name, st)
+
+
+def test_gpu_path_cases_stay_clear_of_their_thresholds():
+    """... and so do the paths of tests/test_motion_path.py, whose segments are compared under the same cap; over each robot's paths
+    all three outcomes occur"""
+    from test_motion_path import PATH_ROBOTS, PATH_SIZES, path_case
+    for name in PATH_ROBOTS:
+        seen = set()
+        for B, T in PATH_SIZES:
+            want = path_case(name, B, T)["want"]
+            assert want["status"].shape == (B * (T - 1),)
+            assert want["near"].sum() <= 0.02 * want["near"].size, (name, B, T, int(want["near"].sum()))
+            seen |= {int(st) for st in want["status"]}
+        assert seen == {MN.FREE, MN.BLOCKED, MN.UNDECIDED}, (name, seen)
+
+
+def test_gpu_composite_cases_stay_clear_of_their_thresholds():
+    """... and the segments of test_motion_clearance.test_a_sphere_on_the_universal_joint_alone"""
+    from test_motion_clearance import universal_case
+    c = universal_case()
+    want = c["want"]
+    assert want["near"].sum() <= 0.02 * c["n"], int(want["near"].sum())
+    for st in (MN.FREE, MN.BLOCKED, MN.UNDECIDED):
+        assert (want["status"] == st).any(), st
