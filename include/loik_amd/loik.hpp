@@ -28,6 +28,7 @@
 #include "../loik_amd_jacobian.h"
 #include "../loik_amd_collision.h"
 #include "../loik_amd_motion.h"
+#include "../loik_amd_avoid.h"
 
 #include <array>
 #include <map>
@@ -547,6 +548,7 @@ public:
     if (spheres.size() != 4 * links.size()) throw std::runtime_error("loik_amd: need four numbers per sphere");
     std::vector<int> l(links.begin(), links.end());
     check(loikb_collision_set_spheres(h_, l.data(), spheres.data(), (int)l.size()));
+    nspheres_ = l.size();
   }
   // world spheres [nws][4] = (x, y, z, r) and oriented boxes [nwb][15] = (R row-major, p, half extents); both empty clears the world
   void setCollisionWorld(const DVec& wspheres = {}, const DVec& wboxes = {})
@@ -630,6 +632,64 @@ public:
     std::vector<int> info(5 * n);
     check(loikb_motion_clearance_path(h_, q_path.data(), (int)B, T, 0, &p, val.data(), info.data(), 0));
     return motion_result(val, info);
+  }
+  // ---- collision avoidance (include/loik_amd_avoid.h): every later pose loop narrows the velocity box of each step so that the spheres
+  // keep away from the world and from each other; clear: as if never set.  CollisionAvoidance(&p) returns whether it is set
+  void SetCollisionAvoidance(double d_safe, double d_influence, double kappa = 0.5)
+  {
+    const loikb_avoid_params p{d_safe, d_influence, kappa, 0};
+    check(loikb_avoid_set(h_, &p));
+  }
+  void ClearCollisionAvoidance() { check(loikb_avoid_set(h_, nullptr)); }
+  bool CollisionAvoidance(loikb_avoid_params* p = nullptr) const { return loikb_avoid_get(h_, p) != 0; }
+  struct AvoidResult {
+    DVec min_seen;                        // [batch] the least clearance at the start of any step the instance ran
+    std::vector<int> active_steps, flags; // [batch], [batch][nv] (bit 0: lower side narrowed, bit 1: upper side)
+  };
+  // of the last pose loop, which ran with collision avoidance set
+  AvoidResult AvoidanceResult() const
+  {
+    AvoidResult r;
+    r.min_seen.resize(batch_); r.active_steps.resize(batch_); r.flags.resize((std::size_t)batch_ * model_.nv);
+    check(loikb_avoid_get_result(h_, LOIKB_AVOID_F_MIN_SEEN, r.min_seen.data(), 0));
+    check(loikb_avoid_get_result(h_, LOIKB_AVOID_F_ACTIVE_STEPS, r.active_steps.data(), 0));
+    check(loikb_avoid_get_result(h_, LOIKB_AVOID_F_FLAGS, r.flags.data(), 0));
+    return r;
+  }
+  struct ClearanceGradientResult {
+    ClearanceResult clearance;   // as Clearance()
+    DVec grad;                   // [n][nv]: d(min)/dt = grad . z under Integrate
+  };
+  ClearanceGradientResult ClearanceGradient(const DVec* q = nullptr) const
+  {
+    const std::size_t n = q ? q->size() / (std::size_t)model_.nq : (std::size_t)batch_;
+    if (q && q->size() != n * (std::size_t)model_.nq) throw std::runtime_error("loik_amd: q is not a whole number of configurations");
+    DVec m(3 * n);
+    ClearanceGradientResult r;
+    r.clearance.witness.resize(3 * n);
+    r.grad.resize(n * (std::size_t)model_.nv);
+    check(loikb_clearance_gradient(h_, q ? q->data() : nullptr, (int)n, 0, m.data(), r.clearance.witness.data(), r.grad.data(), 0));
+    r.clearance.min.resize(n); r.clearance.min_world.resize(n); r.clearance.min_self.resize(n);
+    for (std::size_t i = 0; i < n; ++i) { r.clearance.min[i] = m[3 * i]; r.clearance.min_world[i] = m[3 * i + 1]; r.clearance.min_self[i] = m[3 * i + 2]; }
+    return r;
+  }
+  struct AvoidanceBoxResult {
+    DVec lo, hi;                 // [n][nv]
+    DVec pairs;                  // [n][ns][2]: each sphere's nearest-world and nearest-self clearance
+    std::vector<int> partner;    // [n][ns][2]: the world object (spheres first, then nws + box) / the other sphere, or -1
+  };
+  // the box a pose step with collision avoidance would hand its inner solve, for a shared [lb, ub] [nv]; q = nullptr: the resident q
+  AvoidanceBoxResult AvoidanceBox(const DVec* q, double dt, const DVec& lb, const DVec& ub, double d_safe, double d_influence, double kappa = 0.5) const
+  {
+    const std::size_t n = q ? q->size() / (std::size_t)model_.nq : (std::size_t)batch_;
+    if (q && q->size() != n * (std::size_t)model_.nq) throw std::runtime_error("loik_amd: q is not a whole number of configurations");
+    if (lb.size() != (std::size_t)model_.nv || ub.size() != (std::size_t)model_.nv) throw std::runtime_error("loik_amd: lb and ub are [nv]");
+    const loikb_avoid_params p{d_safe, d_influence, kappa, 0};
+    AvoidanceBoxResult r;
+    r.lo.resize(n * (std::size_t)model_.nv); r.hi.resize(n * (std::size_t)model_.nv);
+    r.pairs.resize(2 * n * nspheres_); r.partner.resize(2 * n * nspheres_);
+    check(loikb_avoid_box(h_, q ? q->data() : nullptr, (int)n, 0, dt, lb.data(), ub.data(), &p, r.lo.data(), r.hi.data(), r.pairs.data(), r.partner.data(), 0));
+    return r;
   }
   // ---- multi-start pose IK (include/loik_amd_multistart.h): batch = G goals * K seeds, instance g * K + k is seed k of goal g
   // the ranges [nv] the seeds are drawn from (a DoF is sampled iff both ends are finite; both empty = the joint limits) and the
@@ -1061,6 +1121,7 @@ private:
   }
   loikb_solver* h_ = nullptr;
   int batch_, nc_;
+  std::size_t nspheres_ = 0;   // of the last setCollisionSpheres: AvoidanceBox sizes its per-sphere results by it
   int max_iter_ = 0;
   double rho_ = 0.0, tol_tail_solve_ = 0.0, tol_primal_inf_ = 0.0, tol_dual_inf_ = 0.0;
   double tol_primal_ = 0.0, tol_dual_ = 0.0;

@@ -191,6 +191,12 @@ CLR_MS_F_CLEARANCE, CLR_MS_F_WITNESS, CLR_MS_F_NCLEAR, CLR_MS_F_INSTANCE = range
 MOTION_ABI_VERSION = 1
 MOTION_SYMBOLS = ["loikb_motion_version", "loikb_difference", "loikb_motion_clearance", "loikb_motion_clearance_path"]
 MOTION_FREE, MOTION_BLOCKED, MOTION_UNDECIDED, MOTION_INVALID = 0, 1, 2, 3
+# include/loik_amd_avoid.h: collision avoidance in the pose loops and clearance gradients; its own header and version
+AVOID_ABI_VERSION = 1
+AVOID_SYMBOLS = ["loikb_avoid_version", "loikb_clearance_gradient", "loikb_avoid_set", "loikb_avoid_get", "loikb_avoid_box",
+                 "loikb_avoid_get_result"]
+AVOID_MAX_SPHERES = 256
+AVOID_F_MIN_SEEN, AVOID_F_ACTIVE_STEPS, AVOID_F_FLAGS = range(3)
 
 
 class PoseParams(C.Structure):
@@ -211,6 +217,10 @@ class ClearanceParams(C.Structure):
 
 class MotionParams(C.Structure):
     _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("max_evals", C.c_int), ("flags", C.c_int)]
+
+
+class AvoidParams(C.Structure):
+    _fields_ = [("d_safe", C.c_double), ("d_influence", C.c_double), ("kappa", C.c_double), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -322,6 +332,12 @@ def lib():
     L.loikb_difference.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
     L.loikb_motion_clearance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(MotionParams), C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_motion_clearance_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MotionParams), C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_clearance_gradient.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_avoid_set.argtypes = [C.c_void_p, C.POINTER(AvoidParams)]
+    L.loikb_avoid_get.argtypes = [C.c_void_p, C.POINTER(AvoidParams)]
+    L.loikb_avoid_box.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, C.POINTER(AvoidParams), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_avoid_get_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -981,6 +997,7 @@ class BatchedLoik:
         out = dict(reached=(status & POSE_ST_REACHED) != 0, steps=steps, err=err, status=status)
         if self._limits or self._accel:
             out["limit_flags"] = self.pose_limit_flags()
+        self._avoid_results(out)
         if self.step_control() is not None:
             out.update(alpha=self.step_get("alpha"), backtracks=self.step_get("backtracks"), failed=self.step_get("failed"),
                        stalled=(status & POSE_ST_STALLED) != 0)
@@ -1101,6 +1118,7 @@ class BatchedLoik:
         if sph.shape[0] != links.size:
             raise ValueError("spheres: %d rows for %d links" % (sph.shape[0], links.size))
         _check(self.L.loikb_collision_set_spheres(self.h, links.ctypes.data_as(_ip), sph.ctypes.data_as(_dp), int(links.size)))
+        self._n_spheres = int(links.size)   # (avoidance_box sizes its per-sphere outputs by it)
 
     def set_collision_world(self, spheres=None, boxes=None):
         """the world every instance shares (loikb_collision_set_world): spheres [nws][4] = (x, y, z, r); boxes [nwb][15] = (R row-major, p,
@@ -1156,6 +1174,81 @@ class BatchedLoik:
         wit = np.empty((n, 3), dtype=np.int32)
         _check(self.L.loikb_clearance(self.h, qp, n, flags, mins.ctypes.data_as(C.c_void_p), wit.ctypes.data_as(C.c_void_p), 0))
         return dict(min=mins[:, 0].copy(), min_world=mins[:, 1].copy(), min_self=mins[:, 2].copy(), witness=wit)
+
+    # ---- collision avoidance (include/loik_amd_avoid.h) -------------------------------------------------------------
+    def set_collision_avoidance(self, d_safe, d_influence, kappa=0.5):
+        """every later pose loop (SolvePose, SolvePosePath, TrackPose, SolvePoseMultiStart) narrows the velocity box of each step so
+        that the spheres keep away from the world and from each other (loikb_avoid_set): a constraint is active below d_influence, one
+        step may spend the share kappa of d - d_safe, and at or below d_safe no DoF may approach"""
+        prm = AvoidParams(float(d_safe), float(d_influence), float(kappa), 0)
+        _check(self.L.loikb_avoid_set(self.h, C.byref(prm)))
+
+    def clear_collision_avoidance(self):
+        _check(self.L.loikb_avoid_set(self.h, None))
+
+    def collision_avoidance(self):
+        """dict(d_safe, d_influence, kappa) as set, None when collision avoidance is not set"""
+        prm = AvoidParams()
+        if not self.L.loikb_avoid_get(self.h, C.byref(prm)):
+            return None
+        return dict(d_safe=prm.d_safe, d_influence=prm.d_influence, kappa=prm.kappa)
+
+    def avoid_get(self, name):
+        """one result of the last pose loop that ran with collision avoidance (loikb_avoid_get_result): min_seen [B] / active_steps [B] /
+        flags [B][nv]"""
+        fid, dtype, per = {"min_seen": (AVOID_F_MIN_SEEN, np.float64, 1), "active_steps": (AVOID_F_ACTIVE_STEPS, np.int32, 1),
+                           "flags": (AVOID_F_FLAGS, np.int32, self.model.nv)}[name]
+        out = np.empty((self.batch, per) if per > 1 else self.batch, dtype=dtype)
+        _check(self.L.loikb_avoid_get_result(self.h, fid, out.ctypes.data_as(C.c_void_p), 0))
+        return out
+
+    def _avoid_results(self, out):
+        if self.collision_avoidance() is not None:
+            out.update(avoid_min_seen=self.avoid_get("min_seen"), avoid_active_steps=self.avoid_get("active_steps"),
+                       avoid_flags=self.avoid_get("flags"))
+
+    def _q_rows(self, q):
+        """q of a query: None (the resident q), a host array, a device tensor or (ptr, n) -> (void*, n, in_flags, keep-alive)"""
+        if q is None:
+            return None, self.batch, 0, None
+        p, n, dev, keep = self._rows(q, self.model.nq)
+        return p, n, IN_DEVICE if dev else 0, keep
+
+    def clearance_gradient(self, q=None, out=None):
+        """clearance() plus the derivative of the witness pair's clearance with respect to the joint velocities
+        (loikb_clearance_gradient): dict(min [n], min_world [n], min_self [n], witness [n][3], grad [n][nv]) with d(min)/dt = grad . z
+        under integrate.  With out = (min_dev, witness_dev, grad_dev) device buffers of 3 n float64 / 3 n int32 / n nv float64 writes there
+        and returns out."""
+        qp, n, flags, keep = self._q_rows(q)
+        if out is not None:
+            _check(self.L.loikb_clearance_gradient(self.h, qp, n, flags, _ptr(out[0])[0], _ptr(out[1])[0], _ptr(out[2])[0], OUT_DEVICE))
+            return out
+        mins, wit, grad = np.empty((n, 3)), np.empty((n, 3), dtype=np.int32), np.empty((n, self.model.nv))
+        _check(self.L.loikb_clearance_gradient(self.h, qp, n, flags, mins.ctypes.data_as(C.c_void_p), wit.ctypes.data_as(C.c_void_p),
+                                               grad.ctypes.data_as(C.c_void_p), 0))
+        return dict(min=mins[:, 0].copy(), min_world=mins[:, 1].copy(), min_self=mins[:, 2].copy(), witness=wit, grad=grad)
+
+    def avoidance_box(self, q, dt, lb, ub, d_safe, d_influence, kappa=0.5, out=None):
+        """the velocity box a pose step with collision avoidance would hand its inner solve, as a pure query (loikb_avoid_box): the
+        shared box [lb, ub] [nv] narrowed for each row of q (None: the resident q).  Returns dict(lo [n][nv], hi [n][nv], pairs [n][ns][2] =
+        each sphere's nearest-world and nearest-self clearance, partner [n][ns][2] = the world object (spheres first, then nws + box) /
+        the other sphere, or -1), or with out = (lo_dev, hi_dev, pairs_dev, partner_dev) writes there and returns out."""
+        qp, n, flags, keep = self._q_rows(q)
+        nv = self.model.nv
+        lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), (nv,)))
+        ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), (nv,)))
+        prm = AvoidParams(float(d_safe), float(d_influence), float(kappa), 0)
+        if out is not None:
+            _check(self.L.loikb_avoid_box(self.h, qp, n, flags, float(dt), lb.ctypes.data_as(_dp), ub.ctypes.data_as(_dp), C.byref(prm),
+                                          _ptr(out[0])[0], _ptr(out[1])[0], _ptr(out[2])[0], _ptr(out[3])[0], OUT_DEVICE))
+            return out
+        ns = getattr(self, "_n_spheres", 0)
+        lo, hi = np.empty((n, nv)), np.empty((n, nv))
+        pairs, partner = np.empty((n, ns, 2)), np.empty((n, ns, 2), dtype=np.int32)
+        _check(self.L.loikb_avoid_box(self.h, qp, n, flags, float(dt), lb.ctypes.data_as(_dp), ub.ctypes.data_as(_dp), C.byref(prm),
+                                      lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), pairs.ctypes.data_as(C.c_void_p),
+                                      partner.ctypes.data_as(C.c_void_p), 0))
+        return dict(lo=lo, hi=hi, pairs=pairs, partner=partner)
 
     # ---- motions (include/loik_amd_motion.h) ----------------------------------------------------------------------
     def _rows(self, a, width):
@@ -1374,6 +1467,7 @@ class BatchedLoik:
         if self.multistart_clearance() is not None:
             for name in ("clearance", "witness", "nclear"):
                 out[name] = self.multistart_clearance_get(name)
+        self._avoid_results(out)
         return out
 
     def multistart_get(self, name):
@@ -1471,6 +1565,7 @@ class BatchedLoik:
                    status=status, path_status=self.path_get("path_status"), err=err, q_path=self.path_get("q_path") if int(record) == 1 else None)
         if self._limits or self._accel:
             out["limit_flags"] = self.pose_limit_flags()
+        self._avoid_results(out)
         return out
 
     def path_get(self, name):
@@ -1567,6 +1662,7 @@ class BatchedLoik:
             out[name] = self.track_get(name) if recorded.get(name, True) else None
         if self._limits or self._accel:
             out["limit_flags"] = self.pose_limit_flags()
+        self._avoid_results(out)
         return out
 
     def track_get(self, name, out=None):

@@ -28,6 +28,7 @@
 #include "loik_pose_jacobian.hpp"
 #include "loik_pose_collision.hpp"
 #include "loik_pose_motion.hpp"
+#include "loik_pose_avoid.hpp"
 #include "loik_flat_inst.hpp"
 #include "loik_devmem.hpp"
 #ifdef LOIKB_FLAT_SEPARATE_TU
@@ -52,6 +53,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_jacobian.h"
 #include "../../include/loik_amd_collision.h"
 #include "../../include/loik_amd_motion.h"
+#include "../../include/loik_amd_avoid.h"
 
 #include <algorithm>
 #include <atomic>
@@ -444,6 +446,17 @@ struct loikb_solver_impl {
       bool have_ms = false;              // loikb_clearance_set_multistart set `ms`
       loikb_clearance_params ms = {0.0, 0};
     } col;
+    // collision avoidance (loik_amd_avoid.h): the latch, the results of the last pose loop that ran with it, and what the kernel
+    // of a model that does not fit the LDS reads (the placements of every device joint, k_avoid_placements' output)
+    struct Avoid {
+      bool have = false;               // loikb_avoid_set set `prm`
+      loikb_avoid_params prm = {0.0, 0.0, 1.0, 0};
+      bool valid = false;              // the last pose loop ran with the latch: the three below are its results
+      DevBuf<double> d_minseen;        // [B] LOIKB_AVOID_F_MIN_SEEN
+      DevBuf<int> d_asteps, d_aflags;  // [B] LOIKB_AVOID_F_ACTIVE_STEPS, [B][nv] LOIKB_AVOID_F_FLAGS
+      DevBuf<double> d_place;          // [n][nb][12] k_avoid_placements' output, grown on demand
+      DevBuf<double> d_base;           // lb [nb], ub [nb] of loikb_avoid_box
+    } avoid;
   } pose;
   // multi-start pose IK (loik_pose_multistart.hpp): buffers of loikb_multistart_sample / loikb_solve_pose_multistart, allocated by
   // the first call of either (sizes: batch and slot capacity; a goal count G <= B fits whatever K is)
@@ -3780,6 +3793,12 @@ const char* loikb_plan_string(loikb_solver* S)
   else if (S->opt.logging) out = "logging = 1: every solve runs on the plain pass-by-pass implementation (k_pass_solve) and fills SolverInfo; without it: " + out;
   if (S->per_link && flat_applicable(S)) out += "; per-link references in force (UpdateReferences): the flat engine reads the links' table";
   else if (pl.lean && S->per_link) out += "; per-link references in force (UpdateReferences): k_hslots + k_lean in their per-link instantiations until the next SolveInit";
+  if (S->pose.avoid.have) {
+    char b6[200];
+    snprintf(b6, sizeof(b6), "; collision avoidance (loikb_avoid_set): k_avoid_box narrows the velocity box of every pose step (d_safe %g, d_influence %g, kappa %g)",
+             S->pose.avoid.prm.d_safe, S->pose.avoid.prm.d_influence, S->pose.avoid.prm.kappa);
+    out += b6;
+  }
   return out.c_str();
 }
 

@@ -1,6 +1,6 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
 // (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), step control (loik_amd_step.h), tool frames and tasks (loik_amd_tasks.h), frame
-// Jacobians and dexterity (loik_amd_jacobian.h), collision clearance (loik_amd_collision.h), motion checks (loik_amd_motion.h), multi-start (loik_amd_multistart.h), waypoint paths
+// Jacobians and dexterity (loik_amd_jacobian.h), collision clearance (loik_amd_collision.h), collision avoidance (loik_amd_avoid.h), motion checks (loik_amd_motion.h), multi-start (loik_amd_multistart.h), waypoint paths
 // (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
 // belongs to: it is no header of its own.
 //
@@ -73,7 +73,7 @@ static int pose_box_copy(loikb_solver_impl* S, int restore)
   return LOIKB_OK;
 }
 
-// The handle while a pose solve with limits (position, acceleration or both) runs: per-instance-box mode (every engine, the compaction's move_bounds and the
+// The handle while a pose solve with limits (position, acceleration or both) or with collision avoidance runs: per-instance-box mode (every engine, the compaction's move_bounds and the
 // pass-level path read S->bnd_shared when a solve is launched: make_params in run_chunk, compact, pass_params), the base box
 // kept in the uniform buffer (shared) or in d_box (per instance).  Leaving the scope puts the base box back in force in the
 // mode it had, on every return path.
@@ -102,15 +102,21 @@ struct PoseBoxScope {
   ~PoseBoxScope() { if (active) { (void)leave(); (void)hipStreamSynchronize(S->stream); } }
 };
 
-// what every pose loop does between pose_begin and its first step: with either kind of limit on the handle, into the scope, and
-// the limit flags start at 0
+// (collision avoidance, loik_amd_avoid.h: defined beside the collision block below)
+static int avoid_begin(loikb_solver_impl* S);
+static int avoid_step(loikb_solver_impl* S, double dt, const PoseBoxScope& box, const int* d_status, bool from_tiles);
+
+// what every pose loop does between pose_begin and its first step: with either kind of limit or the avoidance latch on the handle,
+// into the scope, the limit flags start at 0 and the avoidance results are reset
 static int pose_box_begin(loikb_solver_impl* S, PoseBoxScope& box)
 {
   loikb_solver_impl::PoseState& P = S->pose;
-  if (!P.have_limits && !P.have_accel) return LOIKB_OK;
+  if (!P.have_limits && !P.have_accel && !P.avoid.have) { P.avoid.valid = false; return LOIKB_OK; }
   int rc;
   if ((rc = box.enter())) return rc;
   HIPCHK(hipMemsetAsync(P.d_lflags, 0, sizeof(int) * (size_t)S->B * S->nb, S->stream));
+  if (P.avoid.have) return avoid_begin(S);   // (the results of the last latched loop stand until this one has reset them)
+  P.avoid.valid = false;
   return LOIKB_OK;
 }
 
@@ -235,7 +241,7 @@ static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxS
                          S->home.tiles, S->L, P.d_lflags, P.d_inrange);
     });
     HIPCHK(hipGetLastError());
-  } else if (box.active) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
+  } else if (box.active && P.have_limits) {   // the step's velocity box from the resident q (the base box for the instances that no longer run)
     with_real(S, [&](auto t) {
       using T = decltype(t);
       hipLaunchKernelGGL(k_pose_limit_box<T>, grid_dof(S), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, (const PoseLimit*)P.d_lim, B,
@@ -244,6 +250,8 @@ static int pose_step(loikb_solver* S, const loikb_pose_params* p, const PoseBoxS
     });
     HIPCHK(hipGetLastError());
   }
+  // collision avoidance (loik_amd_avoid.h): the interval the kernels above left, or the base box, narrowed from the resident q
+  if (box.active && P.avoid.have && (rc = avoid_step(S, p->dt, box, d_status, P.have_limits || P.have_accel))) return rc;
   // UpdateEqConstraint(c, NULL, b_c, LOIKB_IN_DEVICE) for every active constraint, queued behind each other (the solve below
   // synchronises), then the tailored Solve on the resident q without a constraint rewrite
   S->defer_sync = true;
@@ -935,6 +943,11 @@ int loikb_collision_set_spheres(loikb_solver* S, const int* links, const double*
     if (spheres[4 * i + 3] < 0.0) { g_last_error = what + ": negative radius"; return LOIKB_ERR_ARG; }
   }
   Collision& C = S->pose.col;
+  if (S->pose.avoid.have && (ns == 0 || ns > LOIKB_AVOID_MAX_SPHERES)) {
+    g_last_error = "collision_set_spheres: collision avoidance is set on the handle (loikb_avoid_set), which needs 1 .. LOIKB_AVOID_MAX_SPHERES = " +
+                   std::to_string(LOIKB_AVOID_MAX_SPHERES) + " spheres -- clear it first";
+    return LOIKB_ERR_STATE;
+  }
   HIPCHK(hipSetDevice(S->device));
   std::vector<int> lk(links, links + ns), car, scar(ns), slot(S->nj, -1);
   for (int i = 0; i < ns; ++i) {
@@ -1100,6 +1113,221 @@ int loikb_clearance_get_multistart(const loikb_solver* S, loikb_clearance_params
   if (!S || !S->pose.col.have_ms) return 0;
   if (out) *out = S->pose.col.ms;
   return 1;
+}
+
+// ---- include/loik_amd_avoid.h (kernels in loik_pose_avoid.hpp) -----------------------------------------------------------------
+int loikb_avoid_version(void) { return LOIKB_AVOID_VERSION; }
+
+static_assert(AVD_MAX_SPHERES == LOIKB_AVOID_MAX_SPHERES, "the kernel's table and the header's limit");
+static_assert(AVD_MAX_SPHERES < (int)AVD_NO_SPHERE, "a list entry holds a sphere index in 16 bits, 0xffff for none");
+
+// the state every avoidance call asks for: 1 .. LOIKB_AVOID_MAX_SPHERES spheres, and a model whose table fits one wavefront's LDS
+static int avoid_check_model(const loikb_solver_impl* S, const char* fn)
+{
+  const Collision& C = S->pose.col;
+  const std::string f(fn);
+  if (C.ns == 0) { g_last_error = f + ": no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (C.ns > LOIKB_AVOID_MAX_SPHERES) {
+    g_last_error = f + ": " + std::to_string(C.ns) + " spheres set, more than LOIKB_AVOID_MAX_SPHERES = " + std::to_string(LOIKB_AVOID_MAX_SPHERES);
+    return LOIKB_ERR_STATE;
+  }
+  if (avd_wave_doubles(S->nb, C.ns, true) * sizeof(double) > 65536) {
+    g_last_error = f + ": the ancestor table of a model with this many DoFs does not fit one wavefront's 64 KB of LDS";
+    return LOIKB_ERR_STATE;
+  }
+  return LOIKB_OK;
+}
+
+static bool avoid_params_ok(const loikb_avoid_params* p)
+{
+  return p && std::isfinite(p->d_safe) && std::isfinite(p->d_influence) && p->d_influence > p->d_safe && p->kappa > 0.0 && p->kappa <= 1.0 && p->flags == 0;
+}
+
+// One k_avoid_box launch in `mode` over n rows of the device array dq [n][nq].  Queued.  The launch rule of col_launch
+static int avoid_launch(loikb_solver_impl* S, int mode, const double* dq, int n, const AvoidPrm& prm, const AvoidIO& io)
+{
+  Collision& C = S->pose.col;
+  loikb_solver_impl::PoseState::Avoid& A = S->pose.avoid;
+  const bool hbm = avd_wave_doubles(S->nb, C.ns, false) * sizeof(double) > 65536;
+  const size_t per = avd_wave_doubles(S->nb, C.ns, hbm) * sizeof(double);
+  int waves = CLR_WAVES;
+  while (waves > 1 && waves * per > 65536) waves >>= 1;
+  int lp = 0;
+  while (lp < 6 && (1 << lp) < C.ns) ++lp;
+  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, (int)C.car.size(), C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const dim3 grid((unsigned)(((size_t)n + waves - 1) / waves)), block(64 * waves);
+  const size_t lds = waves * per;
+  const double* place = nullptr;
+  if (hbm) {
+    const size_t need = sizeof(double) * (size_t)n * S->nb * 12;
+    if (need > A.d_place.bytes()) {
+      HIPCHK(hipStreamSynchronize(S->stream));
+      BUFCHK(A.d_place.regrow(need));
+    }
+    // (the rounding of the LDS stages: the centres have the bits of k_avoid_box<false> and of k_clearance<false>)
+    hipLaunchKernelGGL(k_avoid_placements, grid1((size_t)n * S->nb), dim3(256), 0, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, S->nb, n, (double*)A.d_place);
+    HIPCHK(hipGetLastError());
+    place = A.d_place;
+  }
+#define LOIKB_AVD_LAUNCH(H, M, T) \
+  hipLaunchKernelGGL((k_avoid_box<H, M, T>), grid, block, lds, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, S->nb, n, m, place, prm, io)
+  if (mode == AVD_GRAD) { if (hbm) LOIKB_AVD_LAUNCH(true, AVD_GRAD, double); else LOIKB_AVD_LAUNCH(false, AVD_GRAD, double); }
+  else if (mode == AVD_QUERY) { if (hbm) LOIKB_AVD_LAUNCH(true, AVD_QUERY, double); else LOIKB_AVD_LAUNCH(false, AVD_QUERY, double); }
+  else if (S->f32) { if (hbm) LOIKB_AVD_LAUNCH(true, AVD_STEP, float); else LOIKB_AVD_LAUNCH(false, AVD_STEP, float); }
+  else { if (hbm) LOIKB_AVD_LAUNCH(true, AVD_STEP, double); else LOIKB_AVD_LAUNCH(false, AVD_STEP, double); }
+#undef LOIKB_AVD_LAUNCH
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+// a pose loop that runs with the latch starts: its result buffers (pose_box_begin)
+static int avoid_begin(loikb_solver_impl* S)
+{
+  loikb_solver_impl::PoseState::Avoid& A = S->pose.avoid;
+  int rc;
+  if ((rc = avoid_check_model(S, "a pose loop with collision avoidance (loikb_avoid_set)"))) return rc;
+  const size_t B = (size_t)S->B;
+  if ((rc = regrow(A.d_minseen, sizeof(double) * B)) || (rc = regrow(A.d_asteps, sizeof(int) * B)) || (rc = regrow(A.d_aflags, sizeof(int) * B * S->nb)))
+    return rc;
+  hipLaunchKernelGGL(k_avoid_reset, grid1(B * S->nb), dim3(256), 0, S->stream, S->B, S->nb, (double*)A.d_minseen, (int*)A.d_asteps, (int*)A.d_aflags);
+  HIPCHK(hipGetLastError());
+  A.valid = true;
+  return LOIKB_OK;
+}
+
+// the step's box narrowed from the resident q (pose_step)
+static int avoid_step(loikb_solver_impl* S, double dt, const PoseBoxScope& box, const int* d_status, bool from_tiles)
+{
+  loikb_solver_impl::PoseState& P = S->pose;
+  loikb_solver_impl::PoseState::Avoid& A = P.avoid;
+  AvoidIO io{};
+  io.status = d_status;
+  io.base_sh = box.was_shared ? (const void*)((const char*)S->d_uni + (size_t)S->nc * 57 * S->esz) : nullptr;
+  io.base_pi = (const double2*)P.d_box;
+  io.from_tiles = from_tiles ? 1 : 0;
+  io.tiles = S->home.tiles;
+  io.L = S->L;
+  io.min_seen = A.d_minseen; io.asteps = A.d_asteps; io.aflags = A.d_aflags;
+  const AvoidPrm prm{A.prm.d_safe, A.prm.d_influence, A.prm.kappa, dt};
+  return avoid_launch(S, AVD_STEP, (const double*)S->d_q, S->B, prm, io);
+}
+
+// what loikb_clearance asks of (q, n), for the two queries of this header
+static int avoid_check_rows(const loikb_solver_impl* S, const char* fn, const double* q, int n, bool outputs)
+{
+  const std::string f(fn);
+  if (n < 0 || (n > 0 && !outputs)) { g_last_error = f + ": need n >= 0 and every output array when n > 0"; return LOIKB_ERR_ARG; }
+  if (!q && n != S->B) { g_last_error = f + ": q == NULL (the resident q) needs n == the batch"; return LOIKB_ERR_ARG; }
+  return LOIKB_OK;
+}
+
+int loikb_clearance_gradient(loikb_solver* S, const double* q, int n, int in_flags, double* out_min, int* out_witness, double* out_grad, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  int rc;
+  if ((rc = avoid_check_rows(S, "clearance_gradient", q, n, out_min && out_witness && out_grad))) return rc;
+  if ((rc = avoid_check_model(S, "clearance_gradient"))) return rc;
+  if (!q && !S->have_q) { g_last_error = "clearance_gradient: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const size_t mbytes = sizeof(double) * 3 * (size_t)n, gbytes = sizeof(double) * (size_t)n * S->nb, wbytes = sizeof(int) * 3 * (size_t)n;
+  const void* dq = S->d_q;
+  if (q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) return rc;
+  if (!to_dev && (rc = regrow(S->d_getscr[0], mbytes + gbytes + wbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  AvoidIO io{};
+  io.out_min = to_dev ? out_min : S->d_getscr[0].as<double>();
+  io.out_grad = to_dev ? out_grad : (double*)(S->d_getscr[0].as<char>() + mbytes);
+  io.out_wit = to_dev ? out_witness : (int*)(S->d_getscr[0].as<char>() + mbytes + gbytes);
+  const AvoidPrm prm{0.0, 0.0, 1.0, 1.0};
+  if ((rc = avoid_launch(S, AVD_GRAD, (const double*)dq, n, prm, io))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  if (!to_dev) {
+    HIPCHK(hipMemcpyAsync(out_min, io.out_min, mbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(out_grad, io.out_grad, gbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(out_witness, io.out_wit, wbytes, hipMemcpyDeviceToHost, S->stream));
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q has been read)
+  return LOIKB_OK;
+}
+
+int loikb_avoid_set(loikb_solver* S, const loikb_avoid_params* p)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState::Avoid& A = S->pose.avoid;
+  if (!p) { A.have = false; return LOIKB_OK; }
+  if (!avoid_params_ok(p)) { g_last_error = "avoid_set: need a finite d_safe, a finite d_influence > d_safe, 0 < kappa <= 1 and flags 0"; return LOIKB_ERR_ARG; }
+  if (int rc = avoid_check_model(S, "avoid_set")) return rc;
+  A.prm = *p;
+  A.have = true;
+  return LOIKB_OK;
+}
+
+int loikb_avoid_get(const loikb_solver* S, loikb_avoid_params* out)
+{
+  if (!S || !S->pose.avoid.have) return 0;
+  if (out) *out = S->pose.avoid.prm;
+  return 1;
+}
+
+int loikb_avoid_box(loikb_solver* S, const double* q, int n, int in_flags, double dt, const double* lb, const double* ub, const loikb_avoid_params* p,
+                    double* out_lo, double* out_hi, double* out_pairs, int* out_partner, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  int rc;
+  if ((rc = avoid_check_rows(S, "avoid_box", q, n, out_lo && out_hi && out_pairs && out_partner))) return rc;
+  if (!avoid_params_ok(p)) { g_last_error = "avoid_box: need params with a finite d_safe, a finite d_influence > d_safe, 0 < kappa <= 1 and flags 0"; return LOIKB_ERR_ARG; }
+  if (!(dt > 0.0) || std::isinf(dt)) { g_last_error = "avoid_box: need a finite dt > 0"; return LOIKB_ERR_ARG; }
+  if (!lb || !ub) { g_last_error = "avoid_box: need lb and ub [nv]"; return LOIKB_ERR_ARG; }
+  for (int j = 0; j < S->nb; ++j)
+    if (std::isnan(lb[j]) || std::isnan(ub[j]) || lb[j] > ub[j]) { g_last_error = "avoid_box: DoF " + std::to_string(j) + ": a bound is NaN, or lb > ub"; return LOIKB_ERR_ARG; }
+  if ((rc = avoid_check_model(S, "avoid_box"))) return rc;
+  if (!q && !S->have_q) { g_last_error = "avoid_box: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  loikb_solver_impl::PoseState::Avoid& A = S->pose.avoid;
+  const int ns = S->pose.col.ns, nb = S->nb;
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const size_t bbytes = sizeof(double) * (size_t)n * nb, pbytes = sizeof(double) * 2 * (size_t)n * ns, ibytes = sizeof(int) * 2 * (size_t)n * ns;
+  const void* dq = S->d_q;
+  if (q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) return rc;
+  if ((rc = regrow(A.d_base, sizeof(double) * 2 * nb)) || (!to_dev && (rc = regrow(S->d_getscr[0], 2 * bbytes + pbytes + ibytes)))) {
+    (void)hipStreamSynchronize(S->stream);
+    return rc;
+  }
+  HIPCHK(hipMemcpyAsync(A.d_base, lb, sizeof(double) * nb, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync((double*)A.d_base + nb, ub, sizeof(double) * nb, hipMemcpyHostToDevice, S->stream));
+  AvoidIO io{};
+  io.lb = A.d_base; io.ub = (const double*)A.d_base + nb;
+  char* scr = to_dev ? nullptr : S->d_getscr[0].as<char>();
+  io.out_lo = to_dev ? out_lo : (double*)scr;
+  io.out_hi = to_dev ? out_hi : (double*)(scr + bbytes);
+  io.out_pairs = to_dev ? out_pairs : (double*)(scr + 2 * bbytes);
+  io.out_partner = to_dev ? out_partner : (int*)(scr + 2 * bbytes + pbytes);
+  const AvoidPrm prm{p->d_safe, p->d_influence, p->kappa, dt};
+  if ((rc = avoid_launch(S, AVD_QUERY, (const double*)dq, n, prm, io))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  if (!to_dev) {
+    HIPCHK(hipMemcpyAsync(out_lo, io.out_lo, bbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(out_hi, io.out_hi, bbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(out_pairs, io.out_pairs, pbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(out_partner, io.out_partner, ibytes, hipMemcpyDeviceToHost, S->stream));
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q, lb and ub have been read)
+  return LOIKB_OK;
+}
+
+int loikb_avoid_get_result(loikb_solver* S, int field, void* out, int out_flags)
+{
+  if (!S || !out) return LOIKB_ERR_ARG;
+  loikb_solver_impl::PoseState::Avoid& A = S->pose.avoid;
+  if (field < LOIKB_AVOID_F_MIN_SEEN || field > LOIKB_AVOID_F_FLAGS) { g_last_error = "avoid_get_result: unknown field"; return LOIKB_ERR_ARG; }
+  if (S->pose.nc == 0 || !A.valid) { g_last_error = "avoid_get_result: the last pose loop ran without collision avoidance (loikb_avoid_set), or there was none"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipSetDevice(S->device));
+  const size_t B = (size_t)S->B;
+  switch (field) {
+  case LOIKB_AVOID_F_MIN_SEEN: return get_copy_out(S, A.d_minseen, sizeof(double) * B, out, out_flags);
+  case LOIKB_AVOID_F_ACTIVE_STEPS: return get_copy_out(S, A.d_asteps, sizeof(int) * B, out, out_flags);
+  default: return get_copy_out(S, A.d_aflags, sizeof(int) * B * S->nb, out, out_flags);
+  }
 }
 
 // ---- include/loik_amd_motion.h (kernels in loik_pose_motion.hpp) ---------------------------------------------------------------
