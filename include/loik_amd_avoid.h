@@ -111,6 +111,8 @@ enum { LOIKB_AVOID_F_MIN_SEEN = 0,   /* double [B]: the least overall clearance 
        LOIKB_AVOID_F_ACTIVE_STEPS,   /* int [B]: the steps in which a constraint narrowed the instance's box                         */
        LOIKB_AVOID_F_FLAGS };        /* int [B][nv]: bit 0 = lower side narrowed, bit 1 = upper side narrowed, at the instance's last
                                         step that moved it (the convention of loikb_pose_get_limit_flags)                            */
+/* With step control (loik_amd_step.h) the box is narrowed before the search, so a step whose search ends LOIKB_POSE_ST_STALLED -- which
+ * neither moves the instance nor counts in its steps -- still counts in ACTIVE_STEPS and MIN_SEEN, and FLAGS are those of that step. */
 int loikb_avoid_get_result(loikb_solver *s, int field, void *out, int out_flags);
 
 #ifdef __cplusplus

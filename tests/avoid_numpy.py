@@ -210,6 +210,27 @@ def clearance_gradient(model, q, links, spheres, ws=(), wb=(), pairs=()):
     return out
 
 
+def narrower(model, col, avoid, dt, B):
+    """the `narrow` hook of pose_path_numpy.lockstep_path_loop, pose_track_numpy.lockstep_track_loop and
+    pose_step_numpy.lockstep_pose_loop_step: a callable narrow(b, q_b, lo, hi) -> (lo2, hi2) that narrows the step's interval as
+    lockstep_pose_loop_avoid does and accumulates, in its attribute `results`, that function's avoid_min_seen [B], avoid_active_steps
+    [B], avoid_flags [B][nv] (of the last call for the instance) and near [B].  One call = one step the instance ran."""
+    res = dict(avoid_min_seen=np.full(B, np.inf), avoid_active_steps=np.zeros(B, dtype=np.int32),
+               avoid_flags=np.zeros((B, model.nv), dtype=np.int32), near=np.zeros(B, dtype=bool))
+
+    def narrow_step(b, q_b, lo, hi):
+        cons, nr, t = constraints(model, q_b[None], col["links"], col["spheres"], col["ws"], col["wb"], col["pairs"], avoid["d_influence"], d_safe=avoid["d_safe"])
+        res["near"][b] |= bool(nr[0])
+        res["avoid_min_seen"][b] = min(res["avoid_min_seen"][b], float(np.min(t["pairs"][0])))
+        nlo, nhi = narrow(cons[0], lo, hi, avoid["d_safe"], avoid["kappa"], dt)[:2]
+        res["avoid_flags"][b] = (nlo > lo).astype(np.int32) | ((nhi < hi).astype(np.int32) << 1)
+        res["avoid_active_steps"][b] += int(np.any(res["avoid_flags"][b] != 0))
+        return nlo, nhi
+
+    narrow_step.results = res
+    return narrow_step
+
+
 def lockstep_pose_loop_avoid(model, prm, q0, H_ref, v_ref, links, A, lb, ub, targets, dt, gain, tol, max_steps, q_lo, q_hi, col, avoid,
                              a_max=None, integrate=P.integrate):
     """pose_limits_numpy.lockstep_pose_loop_limits with the avoidance box of include/loik_amd_avoid.h behind the step box: per step and

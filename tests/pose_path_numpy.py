@@ -21,11 +21,13 @@ PATH_COMPLETE, PATH_STALLED = 1, 2
 
 
 def lockstep_path_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, waypoints, dt, gain, tol, max_steps, budget=0,
-                       integrate=P.integrate, q_lo=None, q_hi=None, kinds=None, frames=None):
+                       integrate=P.integrate, q_lo=None, q_hi=None, kinds=None, frames=None, narrow=None):
     """waypoints [B][T][nc][12]; A [nc][6][6] shared or [B][nc][6][6] (ignored with kinds: A_c = S_c X_c^-1 then); budget = steps per
     waypoint at most (0: none).  q_lo / q_hi [nv]: joint position limits, step for step as
     pose_limits_numpy.lockstep_pose_loop_limits has them (SolveInit with the step's box and the running-maximum b: its docstring
-    says why).  kinds [nc] (+ frames [nc][12], None = identity): the task law of pose_tasks_numpy.
+    says why).  narrow(b, q_b, lo, hi) -> (lo2, hi2): applied to the step's box right behind step_box (avoid_numpy.narrower); given
+    without q_lo / q_hi the loop takes the limits branch with infinite limits.  kinds [nc] (+ frames [nc][12], None = identity): the
+    task law of pose_tasks_numpy.
     Returns lockstep_pose_loop's dict (steps = the total, err = against waypoint min(cursor, T - 1)) plus cursor [B], wsteps [B][T]
     (at the cursor: the steps so far), path_status [B], q_path [B][T][nq] (NaN rows from the cursor on), n_solves = the length
     of the loop, and limit_flags [B][nv] with limits."""
@@ -42,9 +44,11 @@ def lockstep_path_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, waypoints
         errors = lambda qb, tg: P.pose_errors(model, qb, links, tg)[0]
     A = np.asarray(A, dtype=float)
     A_of = (lambda b: A[b]) if A.ndim == 4 else (lambda b: A)
-    limits = q_lo is not None
+    limits = q_lo is not None or narrow is not None
     if limits:
         import pose_limits_numpy as PL
+        if q_lo is None:   # (the hook alone: the limits branch with no limit, so that the base box is the step box)
+            q_lo, q_hi = np.full(model.nv, -np.inf), np.full(model.nv, np.inf)
         q_lo, q_hi = np.asarray(q_lo, dtype=float), np.asarray(q_hi, dtype=float)
         qidx = PL.limit_q_index(model)
         flags = np.zeros((B, model.nv), dtype=np.int32)
@@ -99,6 +103,8 @@ def lockstep_path_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, waypoints
                 if np.max(np.abs(bs)) > norm_max:
                     bis_max, norm_max = bs, float(np.max(np.abs(bs)))
                 lo, hi, flags[b], inside = PL.step_box(q[b], q_lo, q_hi, lb, ub, dt, qidx)
+                if narrow is not None:
+                    lo, hi = narrow(b, q[b], lo, hi)
                 r.SolveInit(q[b], H_ref, v_ref, ids, A_of(b), bis_max, lo, hi)
             for c, l in enumerate(links):
                 r.UpdateEqConstraint(l, bs[c])

@@ -28,11 +28,14 @@ def merit(e):
 
 
 def lockstep_pose_loop_step(model, prm, q0, H_ref, v_ref, links, A, lb, ub, targets, dt, gain, tol, max_steps, shrink=0.5,
-                            sufficient=1e-4, max_backtracks=6, patience=0, q_lo=None, q_hi=None, tasks=None, integrate=P.integrate):
+                            sufficient=1e-4, max_backtracks=6, patience=0, q_lo=None, q_hi=None, tasks=None, integrate=P.integrate, narrow=None):
     """pose_numpy.lockstep_pose_loop with the rule above.  q_lo / q_hi [nv]: joint position limits, the loop is then
     pose_limits_numpy.lockstep_pose_loop_limits (its per-step SolveInit and why: that function's docstring).  tasks = (kinds [nc],
     frames [nc][12] or None): the handle has tasks, A is ignored (A_c = S_c X_c^-1), the error is the masked task-frame error and
-    b_c = (gain / dt) e_c, as pose_tasks_numpy.lockstep_pose_loop_tasks has it (axis kinds included).
+    b_c = (gain / dt) e_c, as pose_tasks_numpy.lockstep_pose_loop_tasks has it (axis kinds included).  narrow(b, q_b, lo, hi) ->
+    (lo2, hi2): applied to the step's box right behind step_box (avoid_numpy.narrower), once per step whose inner solve ran -- a
+    search that ends STALLED included, since the box is narrowed before the search; given without q_lo / q_hi the loop takes the
+    limits branch with infinite limits.
     Returns those functions' dict plus
       alpha [B]       alpha of the last step that moved the instance, 0 if none
       backtracks [B]  sum over the accepted searches of the accepted m
@@ -58,8 +61,10 @@ def lockstep_pose_loop_step(model, prm, q0, H_ref, v_ref, links, A, lb, ub, targ
     A_of = (lambda b: A[b]) if A.ndim == 4 else (lambda b: A)
     lb, ub = np.asarray(lb, dtype=float), np.asarray(ub, dtype=float)
     box_of = (lambda b: (lb[b], ub[b])) if lb.ndim == 2 else (lambda b: (lb, ub))
-    limits = q_lo is not None
+    limits = q_lo is not None or narrow is not None
     if limits:
+        if q_lo is None:   # (the hook alone: the limits branch with no limit, so that the base box is the step box)
+            q_lo, q_hi = np.full(model.nv, -np.inf), np.full(model.nv, np.inf)
         q_lo, q_hi = np.asarray(q_lo, dtype=float), np.asarray(q_hi, dtype=float)
         qidx = PL.limit_q_index(model)
     ids = np.asarray(links, dtype=np.int32)
@@ -112,6 +117,8 @@ def lockstep_pose_loop_step(model, prm, q0, H_ref, v_ref, links, A, lb, ub, targ
                 if np.max(np.abs(bs)) > norm_max:
                     bis_max, norm_max = bs, float(np.max(np.abs(bs)))
                 lo, hi, flags[b], inside = PL.step_box(q[b], q_lo, q_hi, lb_b, ub_b, dt, qidx)
+                if narrow is not None:
+                    lo, hi = narrow(b, q[b], lo, hi)
                 r.SolveInit(q[b], H_ref, v_ref, ids, A_of(b), bis_max, lo, hi)
             for c, l in enumerate(links):
                 r.UpdateEqConstraint(l, bs[c])

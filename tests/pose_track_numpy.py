@@ -46,11 +46,12 @@ def feedforward(kind, R, t, X0, X1, dt):
 
 
 def lockstep_track_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, samples, dt, gain, tol, ff=FF_DIFFERENCE,
-                        integrate=P.integrate, q_lo=None, q_hi=None, kinds=None, frames=None):
+                        integrate=P.integrate, q_lo=None, q_hi=None, kinds=None, frames=None, narrow=None):
     """samples [B][T+1][nc][12]; A [nc][6][6] shared or [B][nc][6][6] (ignored with kinds: A_c = S_c X_c^-1 then).  q_lo / q_hi
     [nv]: joint position limits, step for step as pose_limits_numpy.lockstep_pose_loop_limits has them (SolveInit with the
-    step's box and the running-maximum b: its docstring says why).  kinds [nc] (+ frames [nc][12], None = identity): the task
-    law of pose_tasks_numpy.
+    step's box and the running-maximum b: its docstring says why).  narrow(b, q_b, lo, hi) -> (lo2, hi2): applied to the step's box
+    right behind step_box (avoid_numpy.narrower); given without q_lo / q_hi the loop takes the limits branch with infinite limits.
+    kinds [nc] (+ frames [nc][12], None = identity): the task law of pose_tasks_numpy.
     Returns lockstep_pose_loop's dict (err = against X_T, reached all False) plus q_traj [B][T+1][nq] and z_traj [B][T][nv] (NaN
     rows after a stop), errmax [B][T+1] (NaN from a stop on), inner [B][T], ontrack [B], worst [B] / worst_at [B] (the first
     maximum of errmax[b][1:] over its finite entries; NaN / -1 without one), and limit_flags [B][nv] with limits."""
@@ -70,9 +71,11 @@ def lockstep_track_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, samples,
         kind_of = lambda c: PT.TASK_POSE
     A = np.asarray(A, dtype=float)
     A_of = (lambda b: A[b]) if A.ndim == 4 else (lambda b: A)
-    limits = q_lo is not None
+    limits = q_lo is not None or narrow is not None
     if limits:
         import pose_limits_numpy as PL
+        if q_lo is None:   # (the hook alone: the limits branch with no limit, so that the base box is the step box)
+            q_lo, q_hi = np.full(model.nv, -np.inf), np.full(model.nv, np.inf)
         q_lo, q_hi = np.asarray(q_lo, dtype=float), np.asarray(q_hi, dtype=float)
         qidx = PL.limit_q_index(model)
         flags = np.zeros((B, model.nv), dtype=np.int32)
@@ -117,6 +120,8 @@ def lockstep_track_loop(model, prm, q0, H_ref, v_ref, links, A, lb, ub, samples,
                 if np.max(np.abs(bs)) > norm_max:
                     bis_max, norm_max = bs, float(np.max(np.abs(bs)))
                 lo, hi, flags[b], inside = PL.step_box(q[b], q_lo, q_hi, lb, ub, dt, qidx)
+                if narrow is not None:
+                    lo, hi = narrow(b, q[b], lo, hi)
                 r.SolveInit(q[b], H_ref, v_ref, ids, A_of(b), bis_max, lo, hi)
                 if flags[b].any():
                     inner[b, k] |= IN_LIMIT
