@@ -29,6 +29,7 @@
 #include "../loik_amd_collision.h"
 #include "../loik_amd_motion.h"
 #include "../loik_amd_avoid.h"
+#include "../loik_amd_shortcut.h"
 
 #include <array>
 #include <map>
@@ -633,6 +634,44 @@ public:
     check(loikb_motion_clearance_path(h_, q_path.data(), (int)B, T, 0, &p, val.data(), info.data(), 0));
     return motion_result(val, info);
   }
+  // ---- shortcutting (include/loik_amd_shortcut.h).  ShortcutPaths: per path of q_path [B][T][nq] `rounds` draws of a sub-path whose
+  // straight joint-space segment replaces it when the check of MotionClearance certifies the segment FREE.  n_waypoints [B]: the leading
+  // rows of each path that are waypoints (empty: T everywhere)
+  struct ShortcutResult {
+    DVec q_path;                         // [B][T][nq]: the kept waypoints, the last one repeated
+    std::vector<int> n_waypoints, keep;  // [B]; [B][T] input row indices, -1 after the kept ones
+    std::vector<int> tried, accepted, blocked, undecided, invalid;   // [B]
+    DVec length_in, length_out;          // [B], as PathLength
+  };
+  ShortcutResult ShortcutPaths(const DVec& q_path, int T, const std::vector<int>& n_waypoints = {}, int rounds = 64, unsigned long long seed = 0,
+                               double margin = 0.0, double tol = 1e-3, int max_evals = 256) const
+  {
+    const std::size_t B = path_count(q_path, T, n_waypoints);
+    const loikb_shortcut_params p{margin, tol, max_evals, rounds, seed, 0};
+    ShortcutResult r;
+    r.q_path.resize(q_path.size());
+    r.keep.resize(B * (std::size_t)(T > 0 ? T : 0));
+    std::vector<int> info(6 * B);
+    DVec val(2 * B);
+    check(loikb_shortcut_paths(h_, q_path.data(), n_waypoints.empty() ? nullptr : n_waypoints.data(), (int)B, T, 0, &p, r.q_path.data(), r.keep.data(),
+                               info.data(), val.data(), 0));
+    for (std::vector<int>* v : {&r.n_waypoints, &r.tried, &r.accepted, &r.blocked, &r.undecided, &r.invalid}) v->resize(B);
+    r.length_in.resize(B); r.length_out.resize(B);
+    for (std::size_t b = 0; b < B; ++b) {
+      r.n_waypoints[b] = info[6 * b]; r.tried[b] = info[6 * b + 1]; r.accepted[b] = info[6 * b + 2];
+      r.blocked[b] = info[6 * b + 3]; r.undecided[b] = info[6 * b + 4]; r.invalid[b] = info[6 * b + 5];
+      r.length_in[b] = val[2 * b]; r.length_out[b] = val[2 * b + 1];
+    }
+    return r;
+  }
+  // the joint-space length [B] of the paths: the sum over consecutive waypoints of the norm of their Difference
+  DVec PathLength(const DVec& q_path, int T, const std::vector<int>& n_waypoints = {}) const
+  {
+    const std::size_t B = path_count(q_path, T, n_waypoints);
+    DVec length(B);
+    check(loikb_path_length(h_, q_path.data(), n_waypoints.empty() ? nullptr : n_waypoints.data(), (int)B, T, 0, length.data(), 0));
+    return length;
+  }
   // ---- collision avoidance (include/loik_amd_avoid.h): every later pose loop narrows the velocity box of each step so that the spheres
   // keep away from the world and from each other; clear: as if never set.  CollisionAvoidance(&p) returns whether it is set
   void SetCollisionAvoidance(double d_safe, double d_influence, double kappa = 0.5)
@@ -1105,6 +1144,14 @@ private:
     if (q0->size() == G * (std::size_t)model_.nq) return 0;
     if (q0->size() == (std::size_t)model_.nq) return LOIKB_Q_SHARED;
     throw std::runtime_error("loik_amd: q0 must hold model.nq values (shared by the goals) or goals * model.nq");
+  }
+  // B of q_path [B][T][nq] with n_waypoints [B] or empty
+  std::size_t path_count(const DVec& q_path, int T, const std::vector<int>& n_waypoints) const
+  {
+    const std::size_t per = (std::size_t)(T > 0 ? T : 1) * (std::size_t)model_.nq, B = q_path.size() / per;
+    if (q_path.size() != B * per) throw std::runtime_error("loik_amd: q_path is not a whole number of paths of T samples");
+    if (!n_waypoints.empty() && n_waypoints.size() != B) throw std::runtime_error("loik_amd: n_waypoints is not one count per path");
+    return B;
   }
   // out_val [n][3], out_info [n][5] of loik_amd_motion.h by field
   static MotionResult motion_result(const DVec& val, const std::vector<int>& info)

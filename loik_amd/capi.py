@@ -197,6 +197,9 @@ AVOID_SYMBOLS = ["loikb_avoid_version", "loikb_clearance_gradient", "loikb_avoid
                  "loikb_avoid_get_result"]
 AVOID_MAX_SPHERES = 256
 AVOID_F_MIN_SEEN, AVOID_F_ACTIVE_STEPS, AVOID_F_FLAGS = range(3)
+# include/loik_amd_shortcut.h: certified shortcutting of joint-space paths and their lengths; its own header and version
+SHORTCUT_ABI_VERSION = 1
+SHORTCUT_SYMBOLS = ["loikb_shortcut_version", "loikb_shortcut_paths", "loikb_path_length"]
 
 
 class PoseParams(C.Structure):
@@ -221,6 +224,10 @@ class MotionParams(C.Structure):
 
 class AvoidParams(C.Structure):
     _fields_ = [("d_safe", C.c_double), ("d_influence", C.c_double), ("kappa", C.c_double), ("flags", C.c_int)]
+
+
+class ShortcutParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("max_evals", C.c_int), ("rounds", C.c_int), ("seed", C.c_ulonglong), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -338,6 +345,9 @@ def lib():
     L.loikb_avoid_box.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, _dp, _dp, C.POINTER(AvoidParams), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_avoid_get_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_shortcut_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ShortcutParams), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_path_length.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1328,6 +1338,69 @@ class BatchedLoik:
                                                   info.ctypes.data_as(C.c_void_p), 0))
         r = self._motion_result(val, info)
         return {k: v.reshape((B, T - 1) + v.shape[1:]) for k, v in r.items()}
+
+    # ---- shortcutting (include/loik_amd_shortcut.h) ---------------------------------------------------------------
+    def _paths(self, who, q_path, n_waypoints):
+        """q_path [B][T][nq] and n_waypoints [B] (or None) on the host, or both on the device (n_waypoints then int32) ->
+        (void* q, void* len, B, T, is_device, keep-alive)"""
+        shape = tuple(q_path.shape)
+        if len(shape) != 3 or shape[2] != self.model.nq:
+            raise ValueError("%s: q_path must be [B][T][nq]" % who)
+        B, T = int(shape[0]), int(shape[1])
+        pq, _, dev, keep = self._rows(q_path, self.model.nq)
+        pl, kl = None, None
+        if n_waypoints is not None:
+            if hasattr(n_waypoints, "data_ptr") and getattr(n_waypoints, "is_cuda", False):
+                if not dev:
+                    raise ValueError("%s: q_path and n_waypoints differ in where they live" % who)
+                pl, kl = C.c_void_p(n_waypoints.data_ptr()), n_waypoints
+            else:
+                if dev:
+                    raise ValueError("%s: q_path and n_waypoints differ in where they live" % who)
+                kl = np.ascontiguousarray(n_waypoints.numpy() if hasattr(n_waypoints, "numpy") else n_waypoints, dtype=np.int32).reshape(-1)
+                if kl.size != B:
+                    raise ValueError("%s: n_waypoints must be [B]" % who)
+                pl = kl.ctypes.data_as(C.c_void_p)
+        return pq, pl, B, T, dev, (keep, kl)
+
+    def shortcut_paths(self, q_path, n_waypoints=None, rounds=64, seed=0, margin=0.0, tol=1e-3, max_evals=256, out=None):
+        """certified shortcutting of the paths q_path [B][T][nq] (loikb_shortcut_paths): per path `rounds` draws of a sub-path whose straight
+        joint-space segment replaces it when the check of motion_clearance certifies the segment FREE.  n_waypoints [B]: the leading rows
+        of each path that are waypoints (None: T), e.g. the cursor of SolvePosePath.  q_path and n_waypoints both on the host or both on
+        the device (n_waypoints then int32).  Returns dict(q_path [B][T][nq], n_waypoints [B], keep [B][T] (input row indices, -1 after),
+        tried, accepted, blocked, undecided, invalid [B], length_in, length_out [B]), or with out = (path_dev, keep_dev, info_dev, val_dev)
+        device buffers of B T nq float64 / B T int32 / 6 B int32 / 2 B float64 (keep_dev and val_dev may be None) writes there and
+        returns out."""
+        pq, pl, B, T, dev, alive = self._paths("shortcut_paths", q_path, n_waypoints)
+        prm = ShortcutParams(float(margin), float(tol), int(max_evals), int(rounds), int(seed) % (1 << 64), 0)
+        if out is not None:
+            _check(self.L.loikb_shortcut_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, C.byref(prm), _ptr(out[0])[0], _ptr(out[1])[0],
+                                               _ptr(out[2])[0], _ptr(out[3])[0], OUT_DEVICE))
+            return out
+        path, keep = np.empty((B, T, self.model.nq)), np.empty((B, T), dtype=np.int32)
+        info, val = np.empty((B, 6), dtype=np.int32), np.empty((B, 2))
+        _check(self.L.loikb_shortcut_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, C.byref(prm), path.ctypes.data_as(C.c_void_p),
+                                           keep.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), 0))
+        return self._shortcut_result(path, keep, info, val)
+
+    @staticmethod
+    def _shortcut_result(path, keep, info, val):
+        r = dict(q_path=path, n_waypoints=info[:, 0].copy(), keep=keep)
+        for k, name in enumerate(("tried", "accepted", "blocked", "undecided", "invalid")):
+            r[name] = info[:, k + 1].copy()
+        r["length_in"], r["length_out"] = val[:, 0].copy(), val[:, 1].copy()
+        return r
+
+    def path_length(self, q_path, n_waypoints=None, out=None):
+        """the joint-space length [B] of the paths q_path [B][T][nq] (loikb_path_length): the sum over consecutive waypoints of the norm of
+        their difference().  n_waypoints as shortcut_paths takes it; with out = a device buffer of B float64 writes there and returns out."""
+        pq, pl, B, T, dev, alive = self._paths("path_length", q_path, n_waypoints)
+        if out is not None:
+            _check(self.L.loikb_path_length(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, _ptr(out)[0], OUT_DEVICE))
+            return out
+        length = np.empty(B)
+        _check(self.L.loikb_path_length(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, length.ctypes.data_as(C.c_void_p), 0))
+        return length
 
     def set_multistart_clearance(self, margin=0.0):
         """every later SolvePoseMultiStart answers a goal only with a reached seed whose clearance is >= margin

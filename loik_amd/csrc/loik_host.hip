@@ -28,6 +28,7 @@
 #include "loik_pose_jacobian.hpp"
 #include "loik_pose_collision.hpp"
 #include "loik_pose_motion.hpp"
+#include "loik_pose_shortcut.hpp"
 #include "loik_pose_avoid.hpp"
 #include "loik_flat_inst.hpp"
 #include "loik_devmem.hpp"
@@ -54,6 +55,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_collision.h"
 #include "../../include/loik_amd_motion.h"
 #include "../../include/loik_amd_avoid.h"
+#include "../../include/loik_amd_shortcut.h"
 
 #include <algorithm>
 #include <atomic>

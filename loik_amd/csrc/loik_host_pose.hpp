@@ -1478,6 +1478,120 @@ int loikb_motion_clearance_path(loikb_solver* S, const double* q_path, int B, in
   return LOIKB_OK;
 }
 
+// ---- include/loik_amd_shortcut.h (kernels in loik_pose_shortcut.hpp) -----------------------------------------------------------
+int loikb_shortcut_version(void) { return LOIKB_SHORTCUT_VERSION; }
+
+// wavefronts of k_shortcut_paths<false>: each keeps a path to its end and strides on, and each has a keep row in the scratch
+constexpr int SHORTCUT_WAVES = 8192;
+
+// the arguments the two entry points share
+static int shortcut_check_paths(const char* who, const double* q_path, int B, int T)
+{
+  if (T < 2) { g_last_error = std::string(who) + ": need T >= 2"; return LOIKB_ERR_ARG; }
+  if (B < 0 || (size_t)B * (size_t)T > (size_t)0x7fffffff || (B > 0 && !q_path)) {
+    g_last_error = std::string(who) + ": need B >= 0, B * T < 2^31 and q_path when B > 0";
+    return LOIKB_ERR_ARG;
+  }
+  return LOIKB_OK;
+}
+
+// The launch of loikb_shortcut_paths and the copies back.  Queued
+static int shortcut_run(loikb_solver_impl* S, const double* dq, const int* dlen, int B, int T, const loikb_shortcut_params& p, double* out_path,
+                        int* out_keep, int* out_info, double* out_val, bool to_dev)
+{
+  Collision& C = S->pose.col;
+  const int ncar = (int)C.car.size();
+  const size_t aux = shortcut_aux_doubles(S->nb, ncar, C.ns);
+  // the LDS the compiler keeps for itself (difference_joint's dynamically indexed rotation) counts against the 64 KB
+  hipFuncAttributes fa;
+  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_shortcut_paths<false>)));
+  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) + fa.sharedSizeBytes > 65536;
+  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
+  const int waves = std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES);
+  const size_t pbytes = sizeof(double) * (size_t)B * T * S->nq, vbytes = out_val ? sizeof(double) * 2 * (size_t)B : 0;
+  const size_t ibytes = sizeof(int) * 6 * (size_t)B, kbytes = out_keep ? sizeof(int) * (size_t)B * T : 0;
+  int rc;
+  if (!to_dev && (rc = regrow(S->d_getscr[0], pbytes + vbytes + ibytes + kbytes))) return rc;
+  if (!out_keep && (rc = regrow(S->d_getscr[1], sizeof(int) * (size_t)waves * T))) return rc;
+  char* scr = to_dev ? nullptr : S->d_getscr[0].as<char>();
+  double* d_path = to_dev ? out_path : (double*)scr;
+  double* d_val = !out_val ? nullptr : to_dev ? out_val : (double*)(scr + pbytes);
+  int* d_info = to_dev ? out_info : (int*)(scr + pbytes + vbytes);
+  int* d_keep = !out_keep ? nullptr : to_dev ? out_keep : (int*)(scr + pbytes + vbytes + ibytes);
+  int* d_kscr = out_keep ? nullptr : S->d_getscr[1].as<int>();
+  int lp = 0;
+  while (lp < 6 && (1 << lp) < C.ns) ++lp;
+  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, ncar, C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const ShortcutPrm prm{p.margin, p.tol, p.max_evals, p.rounds, p.seed};
+  if (slab) {
+    const size_t need = sizeof(double) * aux * (size_t)waves;
+    if (need > C.d_mslab.bytes()) {
+      HIPCHK(hipStreamSynchronize(S->stream));
+      BUFCHK(C.d_mslab.regrow(need));
+    }
+    hipLaunchKernelGGL(k_shortcut_paths<true>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
+                       C.d_mslab.as<double>(), d_kscr, d_path, d_keep, d_info, d_val);
+  } else {
+    hipLaunchKernelGGL(k_shortcut_paths<false>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
+                       (double*)nullptr, d_kscr, d_path, d_keep, d_info, d_val);
+  }
+  HIPCHK(hipGetLastError());
+  if (!to_dev) {
+    HIPCHK(hipMemcpyAsync(out_path, d_path, pbytes, hipMemcpyDeviceToHost, S->stream));
+    if (out_val) HIPCHK(hipMemcpyAsync(out_val, d_val, vbytes, hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipMemcpyAsync(out_info, d_info, ibytes, hipMemcpyDeviceToHost, S->stream));
+    if (out_keep) HIPCHK(hipMemcpyAsync(out_keep, d_keep, kbytes, hipMemcpyDeviceToHost, S->stream));
+  }
+  return LOIKB_OK;
+}
+
+int loikb_shortcut_paths(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, const loikb_shortcut_params* p,
+                         double* out_path, int* out_keep, int* out_info, double* out_val, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  int rc;
+  if ((rc = shortcut_check_paths("shortcut_paths", q_path, B, T))) return rc;
+  if (!out_path || !out_info) { g_last_error = "shortcut_paths: need out_path and out_info"; return LOIKB_ERR_ARG; }
+  const loikb_motion_params mp{p ? p->margin : 0.0, p ? p->tol : 0.0, p ? p->max_evals : 0, p ? p->flags : 0};
+  if ((rc = motion_check_params(p ? &mp : nullptr, "shortcut_paths"))) return rc;
+  if (p->rounds < 0 || p->rounds > 1048576) { g_last_error = "shortcut_paths: rounds is outside 0 .. 1048576"; return LOIKB_ERR_ARG; }
+  if (out_path == q_path) { g_last_error = "shortcut_paths: out_path == q_path"; return LOIKB_ERR_ARG; }
+  if (S->pose.col.ns == 0) { g_last_error = "shortcut_paths: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (B == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const double *dq, *dlen;
+  if (!(rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)))
+    rc = shortcut_run(S, dq, (const int*)dlen, B, T, *p, out_path, out_keep, out_info, out_val, out_flags & LOIKB_OUT_DEVICE);
+  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
+  return LOIKB_OK;
+}
+
+int loikb_path_length(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, double* out_length, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  int rc;
+  if ((rc = shortcut_check_paths("path_length", q_path, B, T))) return rc;
+  if (!out_length) { g_last_error = "path_length: need out_length"; return LOIKB_ERR_ARG; }
+  if (B == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
+  const size_t lbytes = sizeof(double) * (size_t)B;
+  const double *dq, *dlen;
+  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
+      (!to_dev && (rc = regrow(S->d_getscr[0], lbytes)))) {
+    (void)hipStreamSynchronize(S->stream);
+    return rc;
+  }
+  double* d_len = to_dev ? out_length : S->d_getscr[0].as<double>();
+  hipLaunchKernelGGL(k_path_length, dim3(std::min(B, SHORTCUT_WAVES)), dim3(64), 0, S->stream, dq, (const int*)dlen, B, T, S->nq, S->d_jd, S->d_idx_q,
+                     S->nb, d_len);
+  HIPCHK(hipGetLastError());
+  if (!to_dev) HIPCHK(hipMemcpyAsync(out_length, d_len, lbytes, hipMemcpyDeviceToHost, S->stream));
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
+  return LOIKB_OK;
+}
+
 // the buffers of the collision-aware selection, on first use
 static int ms_clr_alloc(loikb_solver_impl* S)
 {
