@@ -543,6 +543,17 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _outs(out, specs):
+    """the outputs of a query call, one per (shape, dtype) of specs.  out None: fresh numpy arrays; else the caller's buffer, or
+    with several outputs a tuple of them (an entry None where the C call takes NULL), each as _ptr takes it
+    -> ([void* per output], out_flags, the fresh arrays or None)"""
+    if out is None:
+        arrs = [np.empty(shape, dtype=dtype) for shape, dtype in specs]
+        return [a.ctypes.data_as(C.c_void_p) for a in arrs], 0, arrs
+    ptrs = [_ptr(o) for o in (out if len(specs) > 1 else (out,))]
+    return [p for p, _ in ptrs], OUT_DEVICE if any(dev for _, dev in ptrs) else 0, None
+
+
 class DeviceArray:
     """a float64 array resident in the HBM of `device` (hipMalloc + one hipMemcpy): what a caller who keeps its inputs on the GPU
     hands to SolveInit / the tailored Solve (LOIKB_IN_DEVICE) -- the bindings take anything with data_ptr() / is_cuda, e.g. a
@@ -1069,13 +1080,9 @@ class BatchedLoik:
                 raise ValueError("reference %r: expected one of %s" % (reference, sorted(JAC_REFERENCES)))
             reference = JAC_REFERENCES[reference]
         fp = None if f is None else f.ctypes.data_as(_dp)
-        if out is not None:
-            p, dev = _ptr(out)
-            _check(self.L.loikb_frame_jacobians(self.h, links.ctypes.data_as(_ip), fp, n, int(reference), p, OUT_DEVICE if dev else 0))
-            return out
-        arr = np.empty((self.batch, n, 6, self.model.nv))
-        _check(self.L.loikb_frame_jacobians(self.h, links.ctypes.data_as(_ip), fp, n, int(reference), arr.ctypes.data_as(C.c_void_p), 0))
-        return arr
+        (p,), oflags, new = _outs(out, [((self.batch, n, 6, self.model.nv), np.float64)])
+        _check(self.L.loikb_frame_jacobians(self.h, links.ctypes.data_as(_ip), fp, n, int(reference), p, oflags))
+        return out if new is None else new[0]
 
     def frame_dexterity(self, links=None, frames=None, rows=None, length=1.0):
         """singular values, Yoshikawa manipulability and inverse condition number of the task Jacobian of the resident q
@@ -1163,26 +1170,12 @@ class BatchedLoik:
         else [n][nq] on the host, or a device pointer / torch tensor (then give n rows by its numel; a raw pointer as (ptr, n)).
         Returns dict(min [n], min_world [n], min_self [n], witness [n][3] = (CLR_* kind, robot sphere, obstacle or other sphere)), or
         with out = (min_dev, witness_dev) device buffers of 3 n float64 / 3 n int32 (witness_dev may be None) writes there and returns out."""
-        nq = self.model.nq
-        flags = 0
-        keep = None
-        if q is None:
-            qp, n = None, self.batch
-        elif isinstance(q, tuple):
-            qp, n, flags = C.c_void_p(int(q[0])), int(q[1]), IN_DEVICE
-        elif hasattr(q, "data_ptr") and getattr(q, "is_cuda", False):
-            qp, n, flags = C.c_void_p(q.data_ptr()), int(q.numel()) // nq, IN_DEVICE
-        else:
-            keep = _f64(q.numpy() if hasattr(q, "numpy") else q).reshape(-1, nq)
-            qp, n = keep.ctypes.data_as(C.c_void_p), int(keep.shape[0])
-        if out is not None:
-            mp, _ = _ptr(out[0])
-            wp, _ = _ptr(out[1])
-            _check(self.L.loikb_clearance(self.h, qp, n, flags, mp, wp, OUT_DEVICE))
+        qp, n, flags, keep = self._q_rows(q)
+        (mp, wp), oflags, new = _outs(out, [((n, 3), np.float64), ((n, 3), np.int32)])
+        _check(self.L.loikb_clearance(self.h, qp, n, flags, mp, wp, oflags))
+        if new is None:
             return out
-        mins = np.empty((n, 3))
-        wit = np.empty((n, 3), dtype=np.int32)
-        _check(self.L.loikb_clearance(self.h, qp, n, flags, mins.ctypes.data_as(C.c_void_p), wit.ctypes.data_as(C.c_void_p), 0))
+        mins, wit = new
         return dict(min=mins[:, 0].copy(), min_world=mins[:, 1].copy(), min_self=mins[:, 2].copy(), witness=wit)
 
     # ---- collision avoidance (include/loik_amd_avoid.h) -------------------------------------------------------------
@@ -1230,12 +1223,11 @@ class BatchedLoik:
         under integrate.  With out = (min_dev, witness_dev, grad_dev) device buffers of 3 n float64 / 3 n int32 / n nv float64 writes there
         and returns out."""
         qp, n, flags, keep = self._q_rows(q)
-        if out is not None:
-            _check(self.L.loikb_clearance_gradient(self.h, qp, n, flags, _ptr(out[0])[0], _ptr(out[1])[0], _ptr(out[2])[0], OUT_DEVICE))
+        (mp, wp, gp), oflags, new = _outs(out, [((n, 3), np.float64), ((n, 3), np.int32), ((n, self.model.nv), np.float64)])
+        _check(self.L.loikb_clearance_gradient(self.h, qp, n, flags, mp, wp, gp, oflags))
+        if new is None:
             return out
-        mins, wit, grad = np.empty((n, 3)), np.empty((n, 3), dtype=np.int32), np.empty((n, self.model.nv))
-        _check(self.L.loikb_clearance_gradient(self.h, qp, n, flags, mins.ctypes.data_as(C.c_void_p), wit.ctypes.data_as(C.c_void_p),
-                                               grad.ctypes.data_as(C.c_void_p), 0))
+        mins, wit, grad = new
         return dict(min=mins[:, 0].copy(), min_world=mins[:, 1].copy(), min_self=mins[:, 2].copy(), witness=wit, grad=grad)
 
     def avoidance_box(self, q, dt, lb, ub, d_safe, d_influence, kappa=0.5, out=None):
@@ -1248,17 +1240,10 @@ class BatchedLoik:
         lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), (nv,)))
         ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), (nv,)))
         prm = AvoidParams(float(d_safe), float(d_influence), float(kappa), 0)
-        if out is not None:
-            _check(self.L.loikb_avoid_box(self.h, qp, n, flags, float(dt), lb.ctypes.data_as(_dp), ub.ctypes.data_as(_dp), C.byref(prm),
-                                          _ptr(out[0])[0], _ptr(out[1])[0], _ptr(out[2])[0], _ptr(out[3])[0], OUT_DEVICE))
-            return out
         ns = getattr(self, "_n_spheres", 0)
-        lo, hi = np.empty((n, nv)), np.empty((n, nv))
-        pairs, partner = np.empty((n, ns, 2)), np.empty((n, ns, 2), dtype=np.int32)
-        _check(self.L.loikb_avoid_box(self.h, qp, n, flags, float(dt), lb.ctypes.data_as(_dp), ub.ctypes.data_as(_dp), C.byref(prm),
-                                      lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), pairs.ctypes.data_as(C.c_void_p),
-                                      partner.ctypes.data_as(C.c_void_p), 0))
-        return dict(lo=lo, hi=hi, pairs=pairs, partner=partner)
+        ptrs, oflags, new = _outs(out, [((n, nv), np.float64), ((n, nv), np.float64), ((n, ns, 2), np.float64), ((n, ns, 2), np.int32)])
+        _check(self.L.loikb_avoid_box(self.h, qp, n, flags, float(dt), lb.ctypes.data_as(_dp), ub.ctypes.data_as(_dp), C.byref(prm), *ptrs, oflags))
+        return out if new is None else dict(zip(("lo", "hi", "pairs", "partner"), new))
 
     # ---- motions (include/loik_amd_motion.h) ----------------------------------------------------------------------
     def _rows(self, a, width):
@@ -1277,12 +1262,9 @@ class BatchedLoik:
         p1, n1, dev1, k1 = self._rows(q1, self.model.nq)
         if n != n1 or dev != dev1:
             raise ValueError("difference: q0 and q1 differ in rows or in where they live")
-        if out is not None:
-            _check(self.L.loikb_difference(self.h, p0, p1, n, IN_DEVICE if dev else 0, _ptr(out)[0], OUT_DEVICE))
-            return out
-        v = np.empty((n, self.model.nv))
-        _check(self.L.loikb_difference(self.h, p0, p1, n, IN_DEVICE if dev else 0, v.ctypes.data_as(C.c_void_p), 0))
-        return v
+        (pv,), oflags, new = _outs(out, [((n, self.model.nv), np.float64)])
+        _check(self.L.loikb_difference(self.h, p0, p1, n, IN_DEVICE if dev else 0, pv, oflags))
+        return out if new is None else new[0]
 
     @staticmethod
     def _motion_result(val, info):
@@ -1307,17 +1289,13 @@ class BatchedLoik:
         if n != nd or dev != devd:
             raise ValueError("motion_clearance: qa and dv differ in rows or in where they live")
         prm = MotionParams(float(margin), float(tol), int(max_evals), 0)
+        (pv, pi), oflags, new = _outs(out, [((n, 3), np.float64), ((n, 5), np.int32)])
         try:
-            if out is not None:
-                _check(self.L.loikb_motion_clearance(self.h, pa, pd, n, IN_DEVICE if dev else 0, C.byref(prm), _ptr(out[0])[0], _ptr(out[1])[0], OUT_DEVICE))
-                return out
-            val, info = np.empty((n, 3)), np.empty((n, 5), dtype=np.int32)
-            _check(self.L.loikb_motion_clearance(self.h, pa, pd, n, IN_DEVICE if dev else 0, C.byref(prm), val.ctypes.data_as(C.c_void_p),
-                                                 info.ctypes.data_as(C.c_void_p), 0))
+            _check(self.L.loikb_motion_clearance(self.h, pa, pd, n, IN_DEVICE if dev else 0, C.byref(prm), pv, pi, oflags))
         finally:
             if tmp is not None:
                 tmp.free()
-        return self._motion_result(val, info)
+        return out if new is None else self._motion_result(*new)
 
     def path_clearance(self, q_path, margin=0.0, tol=1e-3, max_evals=256, out=None):
         """the certified check of every segment between consecutive samples of q_path [B][T][nq] (loikb_motion_clearance_path; a host array,
@@ -1329,14 +1307,12 @@ class BatchedLoik:
         B, T = int(shape[0]), int(shape[1])
         pq, _, dev, keep = self._rows(q_path, self.model.nq)
         prm = MotionParams(float(margin), float(tol), int(max_evals), 0)
-        if out is not None:
-            _check(self.L.loikb_motion_clearance_path(self.h, pq, B, T, IN_DEVICE if dev else 0, C.byref(prm), _ptr(out[0])[0], _ptr(out[1])[0], OUT_DEVICE))
-            return out
         n = B * max(T - 1, 0)
-        val, info = np.empty((n, 3)), np.empty((n, 5), dtype=np.int32)
-        _check(self.L.loikb_motion_clearance_path(self.h, pq, B, T, IN_DEVICE if dev else 0, C.byref(prm), val.ctypes.data_as(C.c_void_p),
-                                                  info.ctypes.data_as(C.c_void_p), 0))
-        r = self._motion_result(val, info)
+        (pv, pi), oflags, new = _outs(out, [((n, 3), np.float64), ((n, 5), np.int32)])
+        _check(self.L.loikb_motion_clearance_path(self.h, pq, B, T, IN_DEVICE if dev else 0, C.byref(prm), pv, pi, oflags))
+        if new is None:
+            return out
+        r = self._motion_result(*new)
         return {k: v.reshape((B, T - 1) + v.shape[1:]) for k, v in r.items()}
 
     # ---- shortcutting (include/loik_amd_shortcut.h) ---------------------------------------------------------------
@@ -1373,15 +1349,9 @@ class BatchedLoik:
         returns out."""
         pq, pl, B, T, dev, alive = self._paths("shortcut_paths", q_path, n_waypoints)
         prm = ShortcutParams(float(margin), float(tol), int(max_evals), int(rounds), int(seed) % (1 << 64), 0)
-        if out is not None:
-            _check(self.L.loikb_shortcut_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, C.byref(prm), _ptr(out[0])[0], _ptr(out[1])[0],
-                                               _ptr(out[2])[0], _ptr(out[3])[0], OUT_DEVICE))
-            return out
-        path, keep = np.empty((B, T, self.model.nq)), np.empty((B, T), dtype=np.int32)
-        info, val = np.empty((B, 6), dtype=np.int32), np.empty((B, 2))
-        _check(self.L.loikb_shortcut_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, C.byref(prm), path.ctypes.data_as(C.c_void_p),
-                                           keep.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p), val.ctypes.data_as(C.c_void_p), 0))
-        return self._shortcut_result(path, keep, info, val)
+        ptrs, oflags, new = _outs(out, [((B, T, self.model.nq), np.float64), ((B, T), np.int32), ((B, 6), np.int32), ((B, 2), np.float64)])
+        _check(self.L.loikb_shortcut_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, C.byref(prm), *ptrs, oflags))
+        return out if new is None else self._shortcut_result(*new)
 
     @staticmethod
     def _shortcut_result(path, keep, info, val):
@@ -1395,12 +1365,9 @@ class BatchedLoik:
         """the joint-space length [B] of the paths q_path [B][T][nq] (loikb_path_length): the sum over consecutive waypoints of the norm of
         their difference().  n_waypoints as shortcut_paths takes it; with out = a device buffer of B float64 writes there and returns out."""
         pq, pl, B, T, dev, alive = self._paths("path_length", q_path, n_waypoints)
-        if out is not None:
-            _check(self.L.loikb_path_length(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, _ptr(out)[0], OUT_DEVICE))
-            return out
-        length = np.empty(B)
-        _check(self.L.loikb_path_length(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, length.ctypes.data_as(C.c_void_p), 0))
-        return length
+        (pn,), oflags, new = _outs(out, [((B,), np.float64)])
+        _check(self.L.loikb_path_length(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, pn, oflags))
+        return out if new is None else new[0]
 
     def set_multistart_clearance(self, margin=0.0):
         """every later SolvePoseMultiStart answers a goal only with a reached seed whose clearance is >= margin

@@ -5,7 +5,9 @@
 // belongs to: it is no header of its own.
 //
 // What the solves share is here once: pose_check_targets (the check before anything of the handle changes), pose_begin,
-// pose_loop (the step loop around the caller's re-target) with pose_step, and get_copy_out / get_timing_out for the getters.
+// pose_loop (the step loop around the caller's re-target) with pose_step, get_copy_out / get_timing_out for the getters of resident
+// results, and for the queries QueryOut (where their outputs land, and their failure path) with the launch-shape rules lds_waves,
+// regrow_drained and clr_model.
 
 // ---- batched pose IK (include/loik_amd_pose.h, kernels in loik_pose.hpp) ---------------------------------------------------
 static int pose_alloc(loikb_solver_impl* S)
@@ -155,6 +157,120 @@ static int get_timing_out(const double* timing, size_t nbytes, void* out, bool t
 {
   if (!to_dev) { memcpy(out, timing, nbytes); return LOIKB_OK; }
   HIPCHK(hipMemcpy(out, timing, nbytes, hipMemcpyHostToDevice));
+  return LOIKB_OK;
+}
+
+// The outputs of a query call.  add() declares them in the order the scratch holds them (unpadded: every caller's doubles come
+// before its ints) and names where the kernel writes each: the caller's array itself with LOIKB_OUT_DEVICE, else a slice of
+// S->d_getscr[0], which reserve() grows once, for all of them, before it hands any slice out.  A NULL array is an output the caller
+// does not want: a NULL device pointer on both routes, and no scratch.  finish() queues the copies to the caller's host arrays and
+// drains the stream.  The scope is the failure path of the call as well: it opens before the call queues anything that reads the
+// caller's memory, and every return that is not a finish() that went through drains the stream.
+class QueryOut {
+ public:
+  QueryOut(loikb_solver_impl* S, int out_flags) : S_(S), to_dev_(out_flags & LOIKB_OUT_DEVICE) {}
+  QueryOut(const QueryOut&) = delete;
+  QueryOut& operator=(const QueryOut&) = delete;
+  ~QueryOut() { if (!done_) (void)hipStreamSynchronize(S_->stream); }
+
+  template <class T> void add(T* user, size_t bytes, T** dev)
+  {
+    *dev = user;
+    if (user && !to_dev_) o_[n_++] = Item{user, bytes, dev, [](void* slot, void* p) { *static_cast<T**>(slot) = static_cast<T*>(p); }};
+  }
+  int reserve()
+  {
+    if (n_ == 0) return LOIKB_OK;
+    size_t total = 0;
+    for (int i = 0; i < n_; ++i) total += o_[i].bytes;
+    if (int rc = regrow(S_->d_getscr[0], total)) return rc;
+    char* p = S_->d_getscr[0].as<char>();
+    for (int i = 0; i < n_; p += o_[i++].bytes) o_[i].set(o_[i].slot, p);
+    return LOIKB_OK;
+  }
+  int finish()
+  {
+    const char* p = S_->d_getscr[0].as<char>();
+    for (int i = 0; i < n_; p += o_[i++].bytes) HIPCHK(hipMemcpyAsync(o_[i].user, p, o_[i].bytes, hipMemcpyDeviceToHost, S_->stream));
+    HIPCHK(hipStreamSynchronize(S_->stream));
+    done_ = true;
+    return LOIKB_OK;
+  }
+
+ private:
+  struct Item { void* user; size_t bytes; void* slot; void (*set)(void* slot, void* p); };
+  loikb_solver_impl* S_;
+  bool to_dev_, done_ = false;
+  Item o_[4];
+  int n_ = 0;
+};
+
+// the largest power-of-two number of wavefronts, at most `max`, whose `per` bytes each fit the 64 KB of LDS of a workgroup (1 where not
+// even one does: the caller's case)
+static int lds_waves(int max, size_t per)
+{
+  int waves = max;
+  while (waves > 1 && waves * per > 65536) waves >>= 1;
+  return waves;
+}
+
+// `buf` grown to `need` bytes (OwnedBuf::regrow: never shrunk, the contents not kept).  What is queued may still use the buffer that
+// goes: the stream is drained first
+template <class Buf> static int regrow_drained(loikb_solver_impl* S, Buf& buf, size_t need)
+{
+  if (need <= buf.bytes()) return LOIKB_OK;
+  HIPCHK(hipStreamSynchronize(S->stream));
+  return regrow(buf, need);
+}
+
+// iMf [12] = (R row-major, p): finite, R orthonormal with determinant 1 within 1e-9 per entry (k_pose_check_targets' rule)
+static bool frame_ok(const double* F)
+{
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(F[k])) return false;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      const double g = F[a] * F[b] + F[3 + a] * F[3 + b] + F[6 + a] * F[6 + b] - (a == b ? 1.0 : 0.0);
+      if (!(std::fabs(g) <= 1e-9)) return false;
+    }
+  const double det = F[0] * (F[4] * F[8] - F[5] * F[7]) - F[1] * (F[3] * F[8] - F[5] * F[6]) + F[2] * (F[3] * F[7] - F[4] * F[6]);
+  return std::fabs(det - 1.0) <= 1e-9;
+}
+
+// what the getters of placements, Jacobians and dexterity ask of (links, frames) given by the caller; `fn` goes into loikb_last_error()
+static int jac_check_entries(const loikb_solver_impl* S, const char* fn, const int* links, const double* frames, int n)
+{
+  for (int e = 0; e < n; ++e) {
+    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = std::string(fn) + ": link id out of range"; return LOIKB_ERR_ARG; }
+    if (frames && !frame_ok(frames + 12 * e)) {
+      g_last_error = std::string(fn) + ": a frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)";
+      return LOIKB_ERR_ARG;
+    }
+  }
+  return LOIKB_OK;
+}
+
+// ... and the device joints of those links
+static std::vector<int> device_links(const loikb_solver_impl* S, const int* links, int n)
+{
+  std::vector<int> dl(n);
+  for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
+  return dl;
+}
+
+// scratch 1 of those getters: the frames [n][12], then the device joints [n], then (d_rows != NULL) room for the row masks [n], which
+// `rows` fills when given; queued
+static int jac_stage_entries(loikb_solver_impl* S, const int* dl, const double* fr, const int* rows, int n, double** d_fr, int** d_dl, int** d_rows)
+{
+  const size_t fbytes = sizeof(double) * (size_t)n * 12, ibytes = sizeof(int) * (size_t)n;
+  int rc;
+  if ((rc = regrow(S->d_getscr[1], fbytes + (d_rows ? 2 : 1) * ibytes))) return rc;
+  *d_fr = S->d_getscr[1].as<double>();
+  *d_dl = (int*)(S->d_getscr[1].as<char>() + fbytes);
+  if (d_rows) *d_rows = *d_dl + n;
+  HIPCHK(hipMemcpyAsync(*d_fr, fr, fbytes, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(*d_dl, dl, ibytes, hipMemcpyHostToDevice, S->stream));
+  if (rows) HIPCHK(hipMemcpyAsync(*d_rows, rows, ibytes, hipMemcpyHostToDevice, S->stream));
   return LOIKB_OK;
 }
 
@@ -338,26 +454,21 @@ int loikb_pose_version(void) { return LOIKB_POSE_VERSION; }
 int loikb_forward_kinematics(loikb_solver* S, const int* links, int n, double* out, int out_flags)
 {
   if (!S || n < 0 || (n > 0 && (!links || !out))) return LOIKB_ERR_ARG;
-  for (int e = 0; e < n; ++e)
-    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = "forward_kinematics: link id out of range"; return LOIKB_ERR_ARG; }
+  int rc;
+  if ((rc = jac_check_entries(S, "forward_kinematics", links, nullptr, n))) return rc;
   if (!S->have_q) { g_last_error = "forward_kinematics: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
   if (n == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  std::vector<int> dl(n);
-  for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
-  const size_t bytes = sizeof(double) * (size_t)S->B * n * 12;
-  int rc;
-  if ((rc = regrow(S->d_getscr[1], sizeof(int) * (size_t)n))) return rc;
-  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) return rc;
-  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
+  const std::vector<int> dl = device_links(S, links, n);
+  QueryOut o(S, out_flags);
+  double* dst;
+  o.add(out, sizeof(double) * (size_t)S->B * n * 12, &dst);
+  if ((rc = regrow(S->d_getscr[1], sizeof(int) * (size_t)n)) || (rc = o.reserve())) return rc;
   HIPCHK(hipMemcpyAsync(S->d_getscr[1], dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
   hipLaunchKernelGGL(k_link_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
                      S->d_idx_q, S->d_getscr[1].as<const int>(), n, S->B, dst);
   HIPCHK(hipGetLastError());
-  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));   // (dl is a local)
-  return LOIKB_OK;
+  return o.finish();   // (dl is a local)
 }
 
 int loikb_solve_pose(loikb_solver* S, const double* q, const double* targets, int in_flags, const loikb_pose_params* p)
@@ -591,20 +702,6 @@ int loikb_tasks_version(void) { return LOIKB_TASKS_VERSION; }
 // (include/loik_amd_axis.h: its two kinds are cases of loikb_pose_set_tasks below and of the retarget rule of loik_pose.hpp)
 int loikb_axis_version(void) { return LOIKB_AXIS_VERSION; }
 
-// iMf [12] = (R row-major, p): finite, R orthonormal with determinant 1 within 1e-9 per entry (k_pose_check_targets' rule)
-static bool frame_ok(const double* F)
-{
-  for (int k = 0; k < 12; ++k)
-    if (!std::isfinite(F[k])) return false;
-  for (int a = 0; a < 3; ++a)
-    for (int b = 0; b < 3; ++b) {
-      const double g = F[a] * F[b] + F[3 + a] * F[3 + b] + F[6 + a] * F[6 + b] - (a == b ? 1.0 : 0.0);
-      if (!(std::fabs(g) <= 1e-9)) return false;
-    }
-  const double det = F[0] * (F[4] * F[8] - F[5] * F[7]) - F[1] * (F[3] * F[8] - F[5] * F[6]) + F[2] * (F[3] * F[7] - F[4] * F[6]);
-  return std::fabs(det - 1.0) <= 1e-9;
-}
-
 // S_c of a task kind as six row bits: the base kind's rows, less the rotation about the frame's z with LOIKB_TASK_FREE_Z (loik_amd_axis.h)
 static int task_rows(int kind)
 {
@@ -691,32 +788,21 @@ int loikb_frame_placements(loikb_solver* S, const int* links, const double* fram
 {
   if (!frames) return loikb_forward_kinematics(S, links, n, out, out_flags);
   if (!S || n < 0 || (n > 0 && (!links || !out))) return LOIKB_ERR_ARG;
-  for (int e = 0; e < n; ++e) {
-    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = "frame_placements: link id out of range"; return LOIKB_ERR_ARG; }
-    if (!frame_ok(frames + 12 * e)) { g_last_error = "frame_placements: a frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
-  }
+  int rc;
+  if ((rc = jac_check_entries(S, "frame_placements", links, frames, n))) return rc;
   if (!S->have_q) { g_last_error = "frame_placements: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
   if (n == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  // scratch 1: the frames [n][12], then the device joints [n]
-  std::vector<int> dl(n);
-  for (int e = 0; e < n; ++e) dl[e] = S->link_of[links[e]];
-  const size_t bytes = sizeof(double) * (size_t)S->B * n * 12, fbytes = sizeof(double) * (size_t)n * 12;
-  int rc;
-  if ((rc = regrow(S->d_getscr[1], fbytes + sizeof(int) * (size_t)n))) return rc;
-  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) return rc;
-  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
-  double* d_fr = S->d_getscr[1].as<double>();
-  int* d_dl = (int*)(S->d_getscr[1].as<char>() + fbytes);
-  HIPCHK(hipMemcpyAsync(d_fr, frames, fbytes, hipMemcpyHostToDevice, S->stream));
-  HIPCHK(hipMemcpyAsync(d_dl, dl.data(), sizeof(int) * n, hipMemcpyHostToDevice, S->stream));
+  const std::vector<int> dl = device_links(S, links, n);
+  QueryOut o(S, out_flags);
+  double *dst, *d_fr;
+  int* d_dl;
+  o.add(out, sizeof(double) * (size_t)S->B * n * 12, &dst);
+  if ((rc = jac_stage_entries(S, dl.data(), frames, nullptr, n, &d_fr, &d_dl, nullptr)) || (rc = o.reserve())) return rc;
   hipLaunchKernelGGL(k_frame_placements, grid1((size_t)S->B * n), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd,
                      S->d_idx_q, (const int*)d_dl, (const double*)d_fr, n, S->B, dst);
   HIPCHK(hipGetLastError());
-  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));   // (dl and the caller's frames have been read)
-  return LOIKB_OK;
+  return o.finish();   // (dl and the caller's frames have been read)
 }
 
 // ---- include/loik_amd_jacobian.h (kernels in loik_pose_jacobian.hpp) -----------------------------------------------------------
@@ -726,17 +812,12 @@ static const double IDENT12[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
 
 static bool dex_params_ok(const loikb_dexterity_params* p) { return p && std::isfinite(p->length) && p->length > 0.0 && p->flags == 0; }
 
-// what both getters ask of (links, frames) given by the caller
-static int jac_check_entries(const loikb_solver_impl* S, const char* fn, const int* links, const double* frames, int n)
+// the frames given, or the joint frames
+static std::vector<double> frames_or_identity(const double* frames, int n)
 {
-  for (int e = 0; e < n; ++e) {
-    if (links[e] < 0 || links[e] >= S->ext_nj) { g_last_error = std::string(fn) + ": link id out of range"; return LOIKB_ERR_ARG; }
-    if (frames && !frame_ok(frames + 12 * e)) {
-      g_last_error = std::string(fn) + ": a frame needs a finite translation and a rotation that is orthonormal with determinant 1 (tolerance 1e-9)";
-      return LOIKB_ERR_ARG;
-    }
-  }
-  return LOIKB_OK;
+  std::vector<double> fr((size_t)n * 12);
+  for (int e = 0; e < n; ++e) memcpy(&fr[(size_t)12 * e], frames ? frames + 12 * e : IDENT12, sizeof(IDENT12));
+  return fr;
 }
 
 // "the handle's tasks" (links == NULL of loikb_frame_dexterity): the frames and row masks of the active constraints
@@ -753,21 +834,6 @@ static void dex_task_entries(const loikb_solver_impl* S, std::vector<double>& fr
   }
 }
 
-// scratch 1 of the getters: the frames [n][12], then the device joints [n] and (rows != NULL) the row masks [n]; queued
-static int jac_stage_entries(loikb_solver_impl* S, const int* dl, const double* fr, const int* rows, int n, double** d_fr, int** d_dl, int** d_rows)
-{
-  const size_t fbytes = sizeof(double) * (size_t)n * 12, ibytes = sizeof(int) * (size_t)n;
-  int rc;
-  if ((rc = regrow(S->d_getscr[1], fbytes + 2 * ibytes))) return rc;
-  *d_fr = S->d_getscr[1].as<double>();
-  *d_dl = (int*)(S->d_getscr[1].as<char>() + fbytes);
-  *d_rows = *d_dl + n;
-  HIPCHK(hipMemcpyAsync(*d_fr, fr, fbytes, hipMemcpyHostToDevice, S->stream));
-  HIPCHK(hipMemcpyAsync(*d_dl, dl, ibytes, hipMemcpyHostToDevice, S->stream));
-  if (rows) HIPCHK(hipMemcpyAsync(*d_rows, rows, ibytes, hipMemcpyHostToDevice, S->stream));
-  return LOIKB_OK;
-}
-
 int loikb_frame_jacobians(loikb_solver* S, const int* links, const double* frames, int n, int reference_frame, double* out, int out_flags)
 {
   if (!S || !out || n < 0 || (n > 0 && !links)) return LOIKB_ERR_ARG;
@@ -777,29 +843,23 @@ int loikb_frame_jacobians(loikb_solver* S, const int* links, const double* frame
   if (!S->have_q) { g_last_error = "frame_jacobians: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
   if (n == 0) return LOIKB_OK;
   // the wavefronts of a workgroup: as many of JAC_WAVES as 64 KB of LDS hold root paths for
-  int waves = JAC_WAVES;
-  while (waves > 1 && waves * jac_wave_doubles(S->nb) * sizeof(double) > 65536) waves >>= 1;
-  const size_t lds = waves * jac_wave_doubles(S->nb) * sizeof(double);
+  const size_t per = jac_wave_doubles(S->nb) * sizeof(double);
+  const int waves = lds_waves(JAC_WAVES, per);
+  const size_t lds = waves * per;
   if (lds > 65536) { g_last_error = "frame_jacobians: the model has more DoFs than one wavefront's root path fits in 64 KB of LDS for (630)"; return LOIKB_ERR_ARG; }
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  std::vector<int> dl(n);
-  std::vector<double> fr((size_t)n * 12);
-  for (int e = 0; e < n; ++e) {
-    dl[e] = S->link_of[links[e]];
-    memcpy(&fr[(size_t)12 * e], frames ? frames + 12 * e : IDENT12, sizeof(IDENT12));
-  }
-  const size_t pairs = (size_t)S->B * n, bytes = sizeof(double) * pairs * 6 * S->nb;
-  double* d_fr; int *d_dl, *d_rows;
-  if ((rc = jac_stage_entries(S, dl.data(), fr.data(), nullptr, n, &d_fr, &d_dl, &d_rows))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
+  const std::vector<int> dl = device_links(S, links, n);
+  const std::vector<double> fr = frames_or_identity(frames, n);
+  const size_t pairs = (size_t)S->B * n;
+  QueryOut o(S, out_flags);
+  double *dst, *d_fr;
+  int *d_dl, *d_rows;   // (the room for row masks: what this getter has always asked of scratch 1)
+  o.add(out, sizeof(double) * pairs * 6 * S->nb, &dst);
+  if ((rc = jac_stage_entries(S, dl.data(), fr.data(), nullptr, n, &d_fr, &d_dl, &d_rows)) || (rc = o.reserve())) return rc;
   hipLaunchKernelGGL(k_frame_jacobians, dim3((unsigned)((pairs + waves - 1) / waves)), dim3(64 * waves), lds, S->stream, (const double*)S->d_q, S->nq,
                      S->d_jd, S->d_idx_q, (const int*)d_dl, (const double*)d_fr, n, S->B, S->nb, reference_frame, dst);
   HIPCHK(hipGetLastError());
-  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));   // (dl and fr are locals)
-  return LOIKB_OK;
+  return o.finish();   // (dl and fr are locals)
 }
 
 int loikb_frame_dexterity(loikb_solver* S, const int* links, const double* frames, const int* rows, int n, const loikb_dexterity_params* p,
@@ -819,30 +879,26 @@ int loikb_frame_dexterity(loikb_solver* S, const int* links, const double* frame
   if (!S->have_q) { g_last_error = "frame_dexterity: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
   if (n == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  std::vector<int> dl(n), rw(n, 0x3f);
-  std::vector<double> fr((size_t)n * 12);
+  std::vector<int> dl, rw(n, 0x3f);
+  std::vector<double> fr;
   if (!links) {
-    for (int c = 0; c < n; ++c) dl[c] = S->link_of[S->active_ids[c]];
+    dl = device_links(S, S->active_ids.data(), n);
     dex_task_entries(S, fr, rw);
   } else {
-    for (int e = 0; e < n; ++e) {
-      dl[e] = S->link_of[links[e]];
-      memcpy(&fr[(size_t)12 * e], frames ? frames + 12 * e : IDENT12, sizeof(IDENT12));
-      if (rows) rw[e] = rows[e];
-    }
+    dl = device_links(S, links, n);
+    fr = frames_or_identity(frames, n);
+    if (rows) rw.assign(rows, rows + n);
   }
-  const size_t pairs = (size_t)S->B * n, bytes = sizeof(double) * pairs * DEX_N;
-  double* d_fr; int *d_dl, *d_rows;
-  if ((rc = jac_stage_entries(S, dl.data(), fr.data(), rw.data(), n, &d_fr, &d_dl, &d_rows))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev && (rc = regrow(S->d_getscr[0], bytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* dst = to_dev ? out : S->d_getscr[0].as<double>();
+  const size_t pairs = (size_t)S->B * n;
+  QueryOut o(S, out_flags);
+  double *dst, *d_fr;
+  int *d_dl, *d_rows;
+  o.add(out, sizeof(double) * pairs * DEX_N, &dst);
+  if ((rc = jac_stage_entries(S, dl.data(), fr.data(), rw.data(), n, &d_fr, &d_dl, &d_rows)) || (rc = o.reserve())) return rc;
   hipLaunchKernelGGL(k_frame_dexterity, grid1(pairs), dim3(256), 0, S->stream, (const double*)S->d_q, S->nq, S->d_jd, S->d_idx_q, (const int*)d_dl,
                      (const double*)d_fr, (const int*)d_rows, n, S->B, p->length, dst);
   HIPCHK(hipGetLastError());
-  if (!to_dev) HIPCHK(hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));   // (dl, fr and rw are locals)
-  return LOIKB_OK;
+  return o.finish();   // (dl, fr and rw are locals)
 }
 
 int loikb_dexterity_set_multistart_pick(loikb_solver* S, const loikb_dexterity_params* p)
@@ -1036,6 +1092,15 @@ int loikb_collision_set_self_pairs(loikb_solver* S, int enable, const int* ignor
 
 int loikb_collision_num_self_pairs(const loikb_solver* S) { return S ? (int)(S->pose.col.pairs.size() / 2) : 0; }
 
+// the handle's collision model as every kernel that reads it takes it
+static ClrModel clr_model(const loikb_solver_impl* S)
+{
+  const Collision& C = S->pose.col;
+  int lp = 0;
+  while (lp < 6 && (1 << lp) < C.ns) ++lp;
+  return ClrModel{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, (int)C.car.size(), C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+}
+
 // One clearance launch over n rows of the device array dq [n][nq] into d_min [n][3] and d_wit [n][3] (or nullptr).  Queued.
 // As many of CLR_WAVES configurations per workgroup as 64 KB of LDS hold; a model of which one does not fit takes the carriers'
 // placements from k_link_placements through C.d_place
@@ -1045,18 +1110,11 @@ static int col_launch(loikb_solver_impl* S, const double* dq, int n, double* d_m
   const int ncar = (int)C.car.size();
   const bool hbm = clr_wave_doubles(S->nb, ncar, C.ns, false) * sizeof(double) > 65536;
   const size_t per = clr_wave_doubles(S->nb, ncar, C.ns, hbm) * sizeof(double);
-  int waves = CLR_WAVES;
-  while (waves > 1 && waves * per > 65536) waves >>= 1;
-  int lp = 0;
-  while (lp < 6 && (1 << lp) < C.ns) ++lp;
-  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, ncar, C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const int waves = lds_waves(CLR_WAVES, per);
+  const ClrModel m = clr_model(S);
   const dim3 grid((unsigned)(((size_t)n + waves - 1) / waves)), block(64 * waves);
   if (hbm) {
-    const size_t need = sizeof(double) * (size_t)n * ncar * 12;
-    if (need > C.d_place.bytes()) {
-      HIPCHK(hipStreamSynchronize(S->stream));
-      BUFCHK(C.d_place.regrow(need));
-    }
+    if (int rc = regrow_drained(S, C.d_place, sizeof(double) * (size_t)n * ncar * 12)) return rc;
     hipLaunchKernelGGL(k_link_placements, grid1((size_t)n * ncar), dim3(256), 0, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, (const int*)C.d_car,
                        ncar, n, C.d_place);
     HIPCHK(hipGetLastError());
@@ -1079,21 +1137,17 @@ int loikb_clearance(loikb_solver* S, const double* q, int n, int in_flags, doubl
   if (!q && !S->have_q) { g_last_error = "clearance: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
   if (n == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  const size_t mbytes = sizeof(double) * 3 * (size_t)n, wbytes = sizeof(int) * 3 * (size_t)n;
+  QueryOut o(S, out_flags);
+  double* d_min;
+  int* d_wit;
+  o.add(out_min, sizeof(double) * 3 * (size_t)n, &d_min);
+  o.add(out_witness, sizeof(int) * 3 * (size_t)n, &d_wit);
   int rc;
   const void* dq = S->d_q;
-  if (q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) return rc;
-  if (!to_dev && (rc = regrow(S->d_getscr[0], mbytes + wbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* d_min = to_dev ? out_min : S->d_getscr[0].as<double>();
-  int* d_wit = to_dev ? out_witness : (out_witness ? (int*)(S->d_getscr[0].as<char>() + mbytes) : nullptr);
-  if ((rc = col_launch(S, (const double*)dq, n, d_min, d_wit))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev) {
-    HIPCHK(hipMemcpyAsync(out_min, d_min, mbytes, hipMemcpyDeviceToHost, S->stream));
-    if (out_witness) HIPCHK(hipMemcpyAsync(out_witness, d_wit, wbytes, hipMemcpyDeviceToHost, S->stream));
-  }
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q has been read)
-  return LOIKB_OK;
+  if ((q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) || (rc = o.reserve()) ||
+      (rc = col_launch(S, (const double*)dq, n, d_min, d_wit)))
+    return rc;
+  return o.finish();   // (the caller's q has been read)
 }
 
 int loikb_clearance_set_multistart(loikb_solver* S, const loikb_clearance_params* p)
@@ -1150,20 +1204,13 @@ static int avoid_launch(loikb_solver_impl* S, int mode, const double* dq, int n,
   loikb_solver_impl::PoseState::Avoid& A = S->pose.avoid;
   const bool hbm = avd_wave_doubles(S->nb, C.ns, false) * sizeof(double) > 65536;
   const size_t per = avd_wave_doubles(S->nb, C.ns, hbm) * sizeof(double);
-  int waves = CLR_WAVES;
-  while (waves > 1 && waves * per > 65536) waves >>= 1;
-  int lp = 0;
-  while (lp < 6 && (1 << lp) < C.ns) ++lp;
-  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, (int)C.car.size(), C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const int waves = lds_waves(CLR_WAVES, per);
+  const ClrModel m = clr_model(S);
   const dim3 grid((unsigned)(((size_t)n + waves - 1) / waves)), block(64 * waves);
   const size_t lds = waves * per;
   const double* place = nullptr;
   if (hbm) {
-    const size_t need = sizeof(double) * (size_t)n * S->nb * 12;
-    if (need > A.d_place.bytes()) {
-      HIPCHK(hipStreamSynchronize(S->stream));
-      BUFCHK(A.d_place.regrow(need));
-    }
+    if (int rc = regrow_drained(S, A.d_place, sizeof(double) * (size_t)n * S->nb * 12)) return rc;
     // (the rounding of the LDS stages: the centres have the bits of k_avoid_box<false> and of k_clearance<false>)
     hipLaunchKernelGGL(k_avoid_placements, grid1((size_t)n * S->nb), dim3(256), 0, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, S->nb, n, (double*)A.d_place);
     HIPCHK(hipGetLastError());
@@ -1230,24 +1277,16 @@ int loikb_clearance_gradient(loikb_solver* S, const double* q, int n, int in_fla
   if (!q && !S->have_q) { g_last_error = "clearance_gradient: no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
   if (n == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  const size_t mbytes = sizeof(double) * 3 * (size_t)n, gbytes = sizeof(double) * (size_t)n * S->nb, wbytes = sizeof(int) * 3 * (size_t)n;
-  const void* dq = S->d_q;
-  if (q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) return rc;
-  if (!to_dev && (rc = regrow(S->d_getscr[0], mbytes + gbytes + wbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  QueryOut o(S, out_flags);
   AvoidIO io{};
-  io.out_min = to_dev ? out_min : S->d_getscr[0].as<double>();
-  io.out_grad = to_dev ? out_grad : (double*)(S->d_getscr[0].as<char>() + mbytes);
-  io.out_wit = to_dev ? out_witness : (int*)(S->d_getscr[0].as<char>() + mbytes + gbytes);
+  o.add(out_min, sizeof(double) * 3 * (size_t)n, &io.out_min);
+  o.add(out_grad, sizeof(double) * (size_t)n * S->nb, &io.out_grad);
+  o.add(out_witness, sizeof(int) * 3 * (size_t)n, &io.out_wit);
+  const void* dq = S->d_q;
+  if ((q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) || (rc = o.reserve())) return rc;
   const AvoidPrm prm{0.0, 0.0, 1.0, 1.0};
-  if ((rc = avoid_launch(S, AVD_GRAD, (const double*)dq, n, prm, io))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev) {
-    HIPCHK(hipMemcpyAsync(out_min, io.out_min, mbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHK(hipMemcpyAsync(out_grad, io.out_grad, gbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHK(hipMemcpyAsync(out_witness, io.out_wit, wbytes, hipMemcpyDeviceToHost, S->stream));
-  }
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q has been read)
-  return LOIKB_OK;
+  if ((rc = avoid_launch(S, AVD_GRAD, (const double*)dq, n, prm, io))) return rc;
+  return o.finish();   // (the caller's q has been read)
 }
 
 int loikb_avoid_set(loikb_solver* S, const loikb_avoid_params* p)
@@ -1286,33 +1325,23 @@ int loikb_avoid_box(loikb_solver* S, const double* q, int n, int in_flags, doubl
   HIPCHK(hipSetDevice(S->device));
   loikb_solver_impl::PoseState::Avoid& A = S->pose.avoid;
   const int ns = S->pose.col.ns, nb = S->nb;
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  const size_t bbytes = sizeof(double) * (size_t)n * nb, pbytes = sizeof(double) * 2 * (size_t)n * ns, ibytes = sizeof(int) * 2 * (size_t)n * ns;
+  const size_t bbytes = sizeof(double) * (size_t)n * nb;
+  QueryOut o(S, out_flags);
+  AvoidIO io{};
+  o.add(out_lo, bbytes, &io.out_lo);
+  o.add(out_hi, bbytes, &io.out_hi);
+  o.add(out_pairs, sizeof(double) * 2 * (size_t)n * ns, &io.out_pairs);
+  o.add(out_partner, sizeof(int) * 2 * (size_t)n * ns, &io.out_partner);
   const void* dq = S->d_q;
-  if (q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) return rc;
-  if ((rc = regrow(A.d_base, sizeof(double) * 2 * nb)) || (!to_dev && (rc = regrow(S->d_getscr[0], 2 * bbytes + pbytes + ibytes)))) {
-    (void)hipStreamSynchronize(S->stream);
+  if ((q && (rc = to_device(S, q, sizeof(double) * (size_t)n * S->nq, in_flags & LOIKB_IN_DEVICE, &dq))) || (rc = regrow(A.d_base, sizeof(double) * 2 * nb)) ||
+      (rc = o.reserve()))
     return rc;
-  }
   HIPCHK(hipMemcpyAsync(A.d_base, lb, sizeof(double) * nb, hipMemcpyHostToDevice, S->stream));
   HIPCHK(hipMemcpyAsync((double*)A.d_base + nb, ub, sizeof(double) * nb, hipMemcpyHostToDevice, S->stream));
-  AvoidIO io{};
   io.lb = A.d_base; io.ub = (const double*)A.d_base + nb;
-  char* scr = to_dev ? nullptr : S->d_getscr[0].as<char>();
-  io.out_lo = to_dev ? out_lo : (double*)scr;
-  io.out_hi = to_dev ? out_hi : (double*)(scr + bbytes);
-  io.out_pairs = to_dev ? out_pairs : (double*)(scr + 2 * bbytes);
-  io.out_partner = to_dev ? out_partner : (int*)(scr + 2 * bbytes + pbytes);
   const AvoidPrm prm{p->d_safe, p->d_influence, p->kappa, dt};
-  if ((rc = avoid_launch(S, AVD_QUERY, (const double*)dq, n, prm, io))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev) {
-    HIPCHK(hipMemcpyAsync(out_lo, io.out_lo, bbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHK(hipMemcpyAsync(out_hi, io.out_hi, bbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHK(hipMemcpyAsync(out_pairs, io.out_pairs, pbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHK(hipMemcpyAsync(out_partner, io.out_partner, ibytes, hipMemcpyDeviceToHost, S->stream));
-  }
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's q, lb and ub have been read)
-  return LOIKB_OK;
+  if ((rc = avoid_launch(S, AVD_QUERY, (const double*)dq, n, prm, io))) return rc;
+  return o.finish();   // (the caller's q, lb and ub have been read)
 }
 
 int loikb_avoid_get_result(loikb_solver* S, int field, void* out, int out_flags)
@@ -1355,18 +1384,16 @@ int loikb_difference(loikb_solver* S, const double* q0, const double* q1, int n,
   if (n < 0 || (n > 0 && (!q0 || !q1 || !out_v))) { g_last_error = "difference: need n >= 0 and q0, q1, out_v when n > 0"; return LOIKB_ERR_ARG; }
   if (n == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  const size_t qbytes = sizeof(double) * (size_t)n * S->nq, vbytes = sizeof(double) * (size_t)n * S->nv;
+  const size_t qbytes = sizeof(double) * (size_t)n * S->nq;
+  QueryOut o(S, out_flags);
   const double *d0, *d1;
+  double* d_v;
+  o.add(out_v, sizeof(double) * (size_t)n * S->nv, &d_v);
   int rc;
-  if ((rc = motion_inputs(S, q0, qbytes, q1, qbytes, in_flags & LOIKB_IN_DEVICE, &d0, &d1))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  if (!to_dev && (rc = regrow(S->d_getscr[0], vbytes))) { (void)hipStreamSynchronize(S->stream); return rc; }
-  double* d_v = to_dev ? out_v : S->d_getscr[0].as<double>();
+  if ((rc = motion_inputs(S, q0, qbytes, q1, qbytes, in_flags & LOIKB_IN_DEVICE, &d0, &d1)) || (rc = o.reserve())) return rc;
   hipLaunchKernelGGL(k_difference, grid1((size_t)n, 64), dim3(64), 0, S->stream, d0, d1, S->nq, S->d_jd, S->d_idx_q, S->nb, n, 0, d_v);
   HIPCHK(hipGetLastError());
-  if (!to_dev) HIPCHK(hipMemcpyAsync(out_v, d_v, vbytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
-  return LOIKB_OK;
+  return o.finish();   // (the caller's arrays have been read)
 }
 
 static int motion_check_params(const loikb_motion_params* p, const char* who)
@@ -1393,17 +1420,11 @@ static int motion_launch(loikb_solver_impl* S, const double* dqa, const double* 
   const size_t aux = motion_aux_doubles(S->nb, ncar, C.ns);
   const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) > 65536;
   const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
-  int lp = 0;
-  while (lp < 6 && (1 << lp) < C.ns) ++lp;
-  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, ncar, C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const ClrModel m = clr_model(S);
   const MotionPrm prm{p.margin, p.tol, p.max_evals};
   if (slab) {
     const int waves = std::min(n, MOTION_SLAB_WAVES);
-    const size_t need = sizeof(double) * aux * (size_t)waves;
-    if (need > C.d_mslab.bytes()) {
-      HIPCHK(hipStreamSynchronize(S->stream));
-      BUFCHK(C.d_mslab.regrow(need));
-    }
+    if (int rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves)) return rc;
     hipLaunchKernelGGL(k_motion_clearance<true>, dim3(waves), dim3(64), lds, S->stream, dqa, ddv, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T, m, prm,
                        C.d_mslab, d_val, d_info);
   } else {
@@ -1414,11 +1435,11 @@ static int motion_launch(loikb_solver_impl* S, const double* dqa, const double* 
   return LOIKB_OK;
 }
 
-// the shared body of the two checks: dqa as motion_launch takes it, ddv [n][nv] or nullptr = the differences of the path (T > 0)
+// the shared body of the two checks: dqa as motion_launch takes it, ddv [n][nv] or nullptr = the differences of the path (T > 0).
+// Queued; the caller finishes `o`
 static int motion_run(loikb_solver_impl* S, const double* dqa, const double* ddv, int n, int T, const loikb_motion_params& p, double* out_val,
-                      int* out_info, bool to_dev)
+                      int* out_info, QueryOut& o)
 {
-  const size_t vbytes = sizeof(double) * 3 * (size_t)n, ibytes = sizeof(int) * 5 * (size_t)n;
   int rc;
   if (!ddv) {
     if ((rc = regrow(S->d_getscr[1], sizeof(double) * (size_t)n * S->nv))) return rc;
@@ -1427,15 +1448,12 @@ static int motion_run(loikb_solver_impl* S, const double* dqa, const double* ddv
     HIPCHK(hipGetLastError());
     ddv = S->d_getscr[1].as<const double>();
   }
-  if (!to_dev && (rc = regrow(S->d_getscr[0], vbytes + ibytes))) return rc;
-  double* d_val = to_dev ? out_val : S->d_getscr[0].as<double>();
-  int* d_info = to_dev ? out_info : (int*)(S->d_getscr[0].as<char>() + vbytes);
-  if ((rc = motion_launch(S, dqa, ddv, n, T, p, d_val, d_info))) return rc;
-  if (!to_dev) {
-    HIPCHK(hipMemcpyAsync(out_val, d_val, vbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHK(hipMemcpyAsync(out_info, d_info, ibytes, hipMemcpyDeviceToHost, S->stream));
-  }
-  return LOIKB_OK;
+  double* d_val;
+  int* d_info;
+  o.add(out_val, sizeof(double) * 3 * (size_t)n, &d_val);
+  o.add(out_info, sizeof(int) * 5 * (size_t)n, &d_info);
+  if ((rc = o.reserve())) return rc;
+  return motion_launch(S, dqa, ddv, n, T, p, d_val, d_info);
 }
 
 int loikb_motion_clearance(loikb_solver* S, const double* qa, const double* dv, int n, int in_flags, const loikb_motion_params* p, double* out_val,
@@ -1448,12 +1466,12 @@ int loikb_motion_clearance(loikb_solver* S, const double* qa, const double* dv, 
   if (S->pose.col.ns == 0) { g_last_error = "motion_clearance: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
   if (n == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
+  QueryOut o(S, out_flags);
   const double *dqa, *ddv;
-  if (!(rc = motion_inputs(S, qa, sizeof(double) * (size_t)n * S->nq, dv, sizeof(double) * (size_t)n * S->nv, in_flags & LOIKB_IN_DEVICE, &dqa, &ddv)))
-    rc = motion_run(S, dqa, ddv, n, 0, *p, out_val, out_info, out_flags & LOIKB_OUT_DEVICE);
-  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
-  return LOIKB_OK;
+  if ((rc = motion_inputs(S, qa, sizeof(double) * (size_t)n * S->nq, dv, sizeof(double) * (size_t)n * S->nv, in_flags & LOIKB_IN_DEVICE, &dqa, &ddv)) ||
+      (rc = motion_run(S, dqa, ddv, n, 0, *p, out_val, out_info, o)))
+    return rc;
+  return o.finish();   // (the caller's arrays have been read)
 }
 
 int loikb_motion_clearance_path(loikb_solver* S, const double* q_path, int B, int T, int in_flags, const loikb_motion_params* p, double* out_val,
@@ -1470,12 +1488,12 @@ int loikb_motion_clearance_path(loikb_solver* S, const double* q_path, int B, in
   if (S->pose.col.ns == 0) { g_last_error = "motion_clearance_path: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
   if (B == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
+  QueryOut o(S, out_flags);
   const double *dq, *none;
-  if (!(rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, nullptr, 0, in_flags & LOIKB_IN_DEVICE, &dq, &none)))
-    rc = motion_run(S, dq, nullptr, B * (T - 1), T, *p, out_val, out_info, out_flags & LOIKB_OUT_DEVICE);
-  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
-  HIPCHK(hipStreamSynchronize(S->stream));
-  return LOIKB_OK;
+  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, nullptr, 0, in_flags & LOIKB_IN_DEVICE, &dq, &none)) ||
+      (rc = motion_run(S, dq, nullptr, B * (T - 1), T, *p, out_val, out_info, o)))
+    return rc;
+  return o.finish();
 }
 
 // ---- include/loik_amd_shortcut.h (kernels in loik_pose_shortcut.hpp) -----------------------------------------------------------
@@ -1495,9 +1513,9 @@ static int shortcut_check_paths(const char* who, const double* q_path, int B, in
   return LOIKB_OK;
 }
 
-// The launch of loikb_shortcut_paths and the copies back.  Queued
+// The launch of loikb_shortcut_paths.  Queued; the caller finishes `o`
 static int shortcut_run(loikb_solver_impl* S, const double* dq, const int* dlen, int B, int T, const loikb_shortcut_params& p, double* out_path,
-                        int* out_keep, int* out_info, double* out_val, bool to_dev)
+                        int* out_keep, int* out_info, double* out_val, QueryOut& o)
 {
   Collision& C = S->pose.col;
   const int ncar = (int)C.car.size();
@@ -1508,27 +1526,20 @@ static int shortcut_run(loikb_solver_impl* S, const double* dq, const int* dlen,
   const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) + fa.sharedSizeBytes > 65536;
   const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
   const int waves = std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES);
-  const size_t pbytes = sizeof(double) * (size_t)B * T * S->nq, vbytes = out_val ? sizeof(double) * 2 * (size_t)B : 0;
-  const size_t ibytes = sizeof(int) * 6 * (size_t)B, kbytes = out_keep ? sizeof(int) * (size_t)B * T : 0;
+  double *d_path, *d_val;
+  int *d_info, *d_keep;
+  o.add(out_path, sizeof(double) * (size_t)B * T * S->nq, &d_path);
+  o.add(out_val, sizeof(double) * 2 * (size_t)B, &d_val);
+  o.add(out_info, sizeof(int) * 6 * (size_t)B, &d_info);
+  o.add(out_keep, sizeof(int) * (size_t)B * T, &d_keep);
   int rc;
-  if (!to_dev && (rc = regrow(S->d_getscr[0], pbytes + vbytes + ibytes + kbytes))) return rc;
+  if ((rc = o.reserve())) return rc;
   if (!out_keep && (rc = regrow(S->d_getscr[1], sizeof(int) * (size_t)waves * T))) return rc;
-  char* scr = to_dev ? nullptr : S->d_getscr[0].as<char>();
-  double* d_path = to_dev ? out_path : (double*)scr;
-  double* d_val = !out_val ? nullptr : to_dev ? out_val : (double*)(scr + pbytes);
-  int* d_info = to_dev ? out_info : (int*)(scr + pbytes + vbytes);
-  int* d_keep = !out_keep ? nullptr : to_dev ? out_keep : (int*)(scr + pbytes + vbytes + ibytes);
   int* d_kscr = out_keep ? nullptr : S->d_getscr[1].as<int>();
-  int lp = 0;
-  while (lp < 6 && (1 << lp) < C.ns) ++lp;
-  const ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, ncar, C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  const ClrModel m = clr_model(S);
   const ShortcutPrm prm{p.margin, p.tol, p.max_evals, p.rounds, p.seed};
   if (slab) {
-    const size_t need = sizeof(double) * aux * (size_t)waves;
-    if (need > C.d_mslab.bytes()) {
-      HIPCHK(hipStreamSynchronize(S->stream));
-      BUFCHK(C.d_mslab.regrow(need));
-    }
+    if ((rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves))) return rc;
     hipLaunchKernelGGL(k_shortcut_paths<true>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
                        C.d_mslab.as<double>(), d_kscr, d_path, d_keep, d_info, d_val);
   } else {
@@ -1536,12 +1547,6 @@ static int shortcut_run(loikb_solver_impl* S, const double* dq, const int* dlen,
                        (double*)nullptr, d_kscr, d_path, d_keep, d_info, d_val);
   }
   HIPCHK(hipGetLastError());
-  if (!to_dev) {
-    HIPCHK(hipMemcpyAsync(out_path, d_path, pbytes, hipMemcpyDeviceToHost, S->stream));
-    if (out_val) HIPCHK(hipMemcpyAsync(out_val, d_val, vbytes, hipMemcpyDeviceToHost, S->stream));
-    HIPCHK(hipMemcpyAsync(out_info, d_info, ibytes, hipMemcpyDeviceToHost, S->stream));
-    if (out_keep) HIPCHK(hipMemcpyAsync(out_keep, d_keep, kbytes, hipMemcpyDeviceToHost, S->stream));
-  }
   return LOIKB_OK;
 }
 
@@ -1559,12 +1564,12 @@ int loikb_shortcut_paths(loikb_solver* S, const double* q_path, const int* len, 
   if (S->pose.col.ns == 0) { g_last_error = "shortcut_paths: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
   if (B == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
+  QueryOut o(S, out_flags);
   const double *dq, *dlen;
-  if (!(rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)))
-    rc = shortcut_run(S, dq, (const int*)dlen, B, T, *p, out_path, out_keep, out_info, out_val, out_flags & LOIKB_OUT_DEVICE);
-  if (rc) { (void)hipStreamSynchronize(S->stream); return rc; }
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
-  return LOIKB_OK;
+  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
+      (rc = shortcut_run(S, dq, (const int*)dlen, B, T, *p, out_path, out_keep, out_info, out_val, o)))
+    return rc;
+  return o.finish();   // (the caller's arrays have been read)
 }
 
 int loikb_path_length(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, double* out_length, int out_flags)
@@ -1575,21 +1580,17 @@ int loikb_path_length(loikb_solver* S, const double* q_path, const int* len, int
   if (!out_length) { g_last_error = "path_length: need out_length"; return LOIKB_ERR_ARG; }
   if (B == 0) return LOIKB_OK;
   HIPCHK(hipSetDevice(S->device));
-  const bool to_dev = out_flags & LOIKB_OUT_DEVICE;
-  const size_t lbytes = sizeof(double) * (size_t)B;
+  QueryOut o(S, out_flags);
   const double *dq, *dlen;
+  double* d_len;
+  o.add(out_length, sizeof(double) * (size_t)B, &d_len);
   if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
-      (!to_dev && (rc = regrow(S->d_getscr[0], lbytes)))) {
-    (void)hipStreamSynchronize(S->stream);
+      (rc = o.reserve()))
     return rc;
-  }
-  double* d_len = to_dev ? out_length : S->d_getscr[0].as<double>();
   hipLaunchKernelGGL(k_path_length, dim3(std::min(B, SHORTCUT_WAVES)), dim3(64), 0, S->stream, dq, (const int*)dlen, B, T, S->nq, S->d_jd, S->d_idx_q,
                      S->nb, d_len);
   HIPCHK(hipGetLastError());
-  if (!to_dev) HIPCHK(hipMemcpyAsync(out_length, d_len, lbytes, hipMemcpyDeviceToHost, S->stream));
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's arrays have been read)
-  return LOIKB_OK;
+  return o.finish();   // (the caller's arrays have been read)
 }
 
 // the buffers of the collision-aware selection, on first use
