@@ -30,6 +30,7 @@
 #include "../loik_amd_motion.h"
 #include "../loik_amd_avoid.h"
 #include "../loik_amd_shortcut.h"
+#include "../loik_amd_retime.h"
 
 #include <array>
 #include <map>
@@ -671,6 +672,45 @@ public:
     DVec length(B);
     check(loikb_path_length(h_, q_path.data(), n_waypoints.empty() ? nullptr : n_waypoints.data(), (int)B, T, 0, length.data(), 0));
     return length;
+  }
+  // ---- retiming (include/loik_amd_retime.h).  RetimePaths: the paths q_path [B][T][nq] as samples q(t), v(t) at the period dt under the
+  // per-DoF limits v_max, a_max [nv], every segment from rest to rest on a trapezoid of its path parameter; every sample lies on a segment
+  // of the input.  max_samples = the rows S of the result; < 0 sizes S to the largest n_samples with a timing-only call first, 0 is a
+  // timing-only call.  snap stretches every segment to whole samples (LOIKB_RETIME_SNAP)
+  struct RetimeResult {
+    int S = 0;                                            // rows of q_traj / v_traj per path
+    DVec q_traj, v_traj;                                  // [B][S][nq], [B][S][nv]
+    std::vector<int> n_samples, n_waypoints, moved, flags;   // [B]; flags: LOIKB_RETIME_TRUNCATED / INVALID / SKIPPED
+    DVec duration, seg;                                   // [B]; [B][T-1][4] = (t_start, duration, t_acc, peak)
+  };
+  RetimeResult RetimePaths(const DVec& q_path, int T, const DVec& v_max, const DVec& a_max, double dt, const std::vector<int>& n_waypoints = {},
+                           int max_samples = -1, bool snap = false) const
+  {
+    const std::size_t B = path_count(q_path, T, n_waypoints);
+    if (v_max.size() != (std::size_t)model_.nv || a_max.size() != (std::size_t)model_.nv)
+      throw std::runtime_error("loik_amd: v_max and a_max must hold model.nv values");
+    const loikb_retime_params p{dt, snap ? LOIKB_RETIME_SNAP : 0};
+    const int* len = n_waypoints.empty() ? nullptr : n_waypoints.data();
+    RetimeResult r;
+    r.duration.resize(B);
+    r.seg.resize(4 * B * (std::size_t)(T > 1 ? T - 1 : 0));
+    std::vector<int> info(4 * B);
+    if (max_samples < 0) {
+      check(loikb_retime_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, 0, nullptr, nullptr, r.seg.data(),
+                               r.duration.data(), info.data(), 0));
+      max_samples = 1;
+      for (std::size_t b = 0; b < B; ++b) max_samples = std::max(max_samples, info[4 * b]);
+    }
+    r.S = max_samples;
+    r.q_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nq);
+    r.v_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nv);
+    check(loikb_retime_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, r.S, r.S > 0 ? r.q_traj.data() : nullptr,
+                             r.S > 0 ? r.v_traj.data() : nullptr, r.seg.data(), r.duration.data(), info.data(), 0));
+    for (std::vector<int>* v : {&r.n_samples, &r.n_waypoints, &r.moved, &r.flags}) v->resize(B);
+    for (std::size_t b = 0; b < B; ++b) {
+      r.n_samples[b] = info[4 * b]; r.n_waypoints[b] = info[4 * b + 1]; r.moved[b] = info[4 * b + 2]; r.flags[b] = info[4 * b + 3];
+    }
+    return r;
   }
   // ---- collision avoidance (include/loik_amd_avoid.h): every later pose loop narrows the velocity box of each step so that the spheres
   // keep away from the world and from each other; clear: as if never set.  CollisionAvoidance(&p) returns whether it is set

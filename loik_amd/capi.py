@@ -200,6 +200,11 @@ AVOID_F_MIN_SEEN, AVOID_F_ACTIVE_STEPS, AVOID_F_FLAGS = range(3)
 # include/loik_amd_shortcut.h: certified shortcutting of joint-space paths and their lengths; its own header and version
 SHORTCUT_ABI_VERSION = 1
 SHORTCUT_SYMBOLS = ["loikb_shortcut_version", "loikb_shortcut_paths", "loikb_path_length"]
+# include/loik_amd_retime.h: time-optimal retiming of joint-space paths; its own header and version
+RETIME_ABI_VERSION = 1
+RETIME_SYMBOLS = ["loikb_retime_version", "loikb_retime_paths"]
+RETIME_SNAP = 1
+RETIME_TRUNCATED, RETIME_INVALID, RETIME_SKIPPED = 1, 2, 4
 
 
 class PoseParams(C.Structure):
@@ -228,6 +233,10 @@ class AvoidParams(C.Structure):
 
 class ShortcutParams(C.Structure):
     _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("max_evals", C.c_int), ("rounds", C.c_int), ("seed", C.c_ulonglong), ("flags", C.c_int)]
+
+
+class RetimeParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -348,6 +357,8 @@ def lib():
     L.loikb_shortcut_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(ShortcutParams), C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_path_length.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.loikb_retime_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(RetimeParams), C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1368,6 +1379,48 @@ class BatchedLoik:
         (pn,), oflags, new = _outs(out, [((B,), np.float64)])
         _check(self.L.loikb_path_length(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, pn, oflags))
         return out if new is None else new[0]
+
+    # ---- retiming (include/loik_amd_retime.h) --------------------------------------------------------------------
+    def retime_paths(self, q_path, v_max, a_max, dt, n_waypoints=None, max_samples=None, snap=False, out=None):
+        """time-optimal retiming of the paths q_path [B][T][nq] under the per-DoF limits v_max, a_max [nv] (host, or scalars) at the sample
+        period dt (loikb_retime_paths): every segment from rest to rest on a trapezoid of its path parameter, so that every sample lies on
+        a segment of the input.  n_waypoints as shortcut_paths takes it.  max_samples = the rows S of the result; None sizes S to the
+        largest n_samples with a timing-only call first, 0 is a timing-only call.  snap stretches every segment to whole samples
+        (RETIME_SNAP).  Returns dict(q_traj [B][S][nq], v_traj [B][S][nv], n_samples, n_waypoints, moved, flags [B], duration [B], seg
+        [B][T-1][4] = (t_start, duration, t_acc, peak)); q_traj and v_traj are None after a timing-only call.  With out = (traj_dev,
+        vel_dev, seg_dev, duration_dev, info_dev) device buffers of B S nq / B S nv / 4 B (T-1) / B float64 and 4 B int32 (the first three
+        may be None; max_samples is then required) writes there and returns out."""
+        pq, pl, B, T, dev, alive = self._paths("retime_paths", q_path, n_waypoints)
+        nq, nv = self.model.nq, self.model.nv
+        vm = np.ascontiguousarray(np.broadcast_to(_f64(v_max), (nv,)))
+        am = np.ascontiguousarray(np.broadcast_to(_f64(a_max), (nv,)))
+        prm = RetimeParams(float(dt), RETIME_SNAP if snap else 0)
+
+        def call(S, ptrs, oflags):
+            _check(self.L.loikb_retime_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, vm.ctypes.data_as(_dp), am.ctypes.data_as(_dp),
+                                             C.byref(prm), S, *ptrs, oflags))
+        if out is not None:
+            if max_samples is None:
+                raise ValueError("retime_paths: out needs max_samples")
+            ptrs, oflags, _ = _outs(out, [None] * 5)
+            call(int(max_samples), ptrs, oflags)
+            return out
+        seg, dur, info = np.empty((B, max(T - 1, 0), 4)), np.empty(B), np.empty((B, 4), dtype=np.int32)
+        tail = [a.ctypes.data_as(C.c_void_p) for a in (seg, dur, info)]
+        if max_samples is None:
+            call(0, [None, None] + tail, 0)
+            max_samples = max(int(info[:, 0].max(initial=1)), 1)
+        S = int(max_samples)
+        traj = vel = None
+        if S > 0:
+            traj, vel = np.empty((B, S, nq)), np.empty((B, S, nv))
+        call(S, [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in (traj, vel)] + tail, 0)
+        return self._retime_result(traj, vel, seg, dur, info)
+
+    @staticmethod
+    def _retime_result(traj, vel, seg, dur, info):
+        return dict(q_traj=traj, v_traj=vel, n_samples=info[:, 0].copy(), n_waypoints=info[:, 1].copy(), moved=info[:, 2].copy(),
+                    flags=info[:, 3].copy(), duration=dur, seg=seg)
 
     def set_multistart_clearance(self, margin=0.0):
         """every later SolvePoseMultiStart answers a goal only with a reached seed whose clearance is >= margin

@@ -201,7 +201,7 @@ class QueryOut {
   struct Item { void* user; size_t bytes; void* slot; void (*set)(void* slot, void* p); };
   loikb_solver_impl* S_;
   bool to_dev_, done_ = false;
-  Item o_[4];
+  Item o_[5];
   int n_ = 0;
 };
 
@@ -1590,6 +1590,79 @@ int loikb_path_length(loikb_solver* S, const double* q_path, const int* len, int
   hipLaunchKernelGGL(k_path_length, dim3(std::min(B, SHORTCUT_WAVES)), dim3(64), 0, S->stream, dq, (const int*)dlen, B, T, S->nq, S->d_jd, S->d_idx_q,
                      S->nb, d_len);
   HIPCHK(hipGetLastError());
+  return o.finish();   // (the caller's arrays have been read)
+}
+
+// ---- include/loik_amd_retime.h (kernel in loik_pose_retime.hpp) -----------------------------------------------------------------
+int loikb_retime_version(void) { return LOIKB_RETIME_VERSION; }
+
+// The launch of loikb_retime_paths.  The two limit rows go side by side into S->d_getscr[1]; the tables of a wavefront are LDS when
+// they fit beside what the compiler keeps for itself, else a slab per resident wavefront (the motion check's, and its grid).  Queued; the
+// caller finishes `o`
+static int retime_run(loikb_solver_impl* S, const double* dq, const int* dlen, int B, int T, const double* v_max, const double* a_max,
+                      const loikb_retime_params& p, int n_rows, double* out_traj, double* out_vel, double* out_seg, double* out_duration,
+                      int* out_info, QueryOut& o)
+{
+  const size_t tab = retime_tab_doubles(T, S->nb) * sizeof(double);
+  hipFuncAttributes fa;
+  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_retime_paths<false>)));
+  const bool slab = tab + fa.sharedSizeBytes > 65536;
+  const int waves = std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES);
+  double *d_traj, *d_vel, *d_seg, *d_dur;
+  int* d_info;
+  o.add(out_traj, sizeof(double) * (size_t)B * n_rows * S->nq, &d_traj);
+  o.add(out_vel, sizeof(double) * (size_t)B * n_rows * S->nv, &d_vel);
+  o.add(out_seg, sizeof(double) * (size_t)B * (T - 1) * 4, &d_seg);
+  o.add(out_duration, sizeof(double) * (size_t)B, &d_dur);
+  o.add(out_info, sizeof(int) * 4 * (size_t)B, &d_info);
+  int rc;
+  const size_t row = sizeof(double) * (size_t)S->nv;
+  if ((rc = o.reserve()) || (rc = regrow(S->d_getscr[1], 2 * row))) return rc;
+  HIPCHK(hipMemcpyAsync(S->d_getscr[1], v_max, row, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(S->d_getscr[1].as<char>() + row, a_max, row, hipMemcpyHostToDevice, S->stream));
+  const double* d_lim = S->d_getscr[1].as<const double>();
+  const RetimePrm prm{p.dt, (p.flags & LOIKB_RETIME_SNAP) != 0, n_rows};
+  if (slab) {
+    Collision& C = S->pose.col;
+    if ((rc = regrow_drained(S, C.d_mslab, tab * (size_t)waves))) return rc;
+    hipLaunchKernelGGL(k_retime_paths<true>, dim3(waves), dim3(64), 0, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, d_lim, prm,
+                       C.d_mslab.as<double>(), d_traj, d_vel, d_seg, d_dur, d_info);
+  } else {
+    hipLaunchKernelGGL(k_retime_paths<false>, dim3(waves), dim3(64), tab, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, d_lim, prm,
+                       (double*)nullptr, d_traj, d_vel, d_seg, d_dur, d_info);
+  }
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+int loikb_retime_paths(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, const double* v_max,
+                       const double* a_max, const loikb_retime_params* p, int n_rows, double* out_traj, double* out_vel, double* out_seg,
+                       double* out_duration, int* out_info, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  int rc;
+  if ((rc = shortcut_check_paths("retime_paths", q_path, B, T))) return rc;
+  const char* bad = !v_max ? "v_max == NULL" : !a_max ? "a_max == NULL" : !p ? "p == NULL" : !out_duration ? "need out_duration"
+                    : !out_info ? "need out_info" : nullptr;
+  for (int j = 0; !bad && j < S->nv; ++j) {
+    if (!(std::isfinite(v_max[j]) && v_max[j] > 0.0)) bad = "a v_max that is not finite and > 0";
+    else if (!(std::isfinite(a_max[j]) && a_max[j] > 0.0)) bad = "an a_max that is not finite and > 0";
+  }
+  if (!bad)
+    bad = !(std::isfinite(p->dt) && p->dt > 0.0) ? "dt is not finite and > 0"
+          : (p->flags & ~LOIKB_RETIME_SNAP) ? "unknown flags"
+          : (out_vel && !out_traj) ? "out_vel without out_traj"
+          : (out_traj && n_rows < 1) ? "out_traj with S < 1"
+          : (out_traj && (size_t)B * (size_t)n_rows > (size_t)0x7fffffff) ? "need B * S < 2^31"
+          : (out_traj && out_traj == q_path) ? "out_traj == q_path" : nullptr;
+  if (bad) { g_last_error = std::string("retime_paths: ") + bad; return LOIKB_ERR_ARG; }
+  if (B == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  QueryOut o(S, out_flags);
+  const double *dq, *dlen;
+  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
+      (rc = retime_run(S, dq, (const int*)dlen, B, T, v_max, a_max, *p, out_traj ? n_rows : 0, out_traj, out_vel, out_seg, out_duration, out_info, o)))
+    return rc;
   return o.finish();   // (the caller's arrays have been read)
 }
 

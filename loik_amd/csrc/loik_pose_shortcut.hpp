@@ -34,6 +34,16 @@ struct ShortcutPrm {
   unsigned long long seed;
 };
 
+// two rows of nq doubles: fin stays set when every entry of both is finite, same when they are equal entry by entry; the caller sets both
+// first (path_length_wave and the segment pass of k_retime_paths, loik_pose_retime.hpp, ask the same question of a segment's ends)
+__device__ __forceinline__ void rows_fin_same(const double* a, const double* b, int nq, bool& fin, bool& same)
+{
+  for (int k = 0; k < nq; ++k) {
+    fin = fin && isfinite(a[k]) && isfinite(b[k]);
+    same = same && a[k] == b[k];
+  }
+}
+
 // The length of the path q[keep[0]], ..., q[keep[L - 1]] (keep == nullptr: q[0], ..., q[L - 1]) of rows of nq doubles: the sum over
 // k < L - 1 of || difference(q_k, q_{k+1}) ||_2.  A lane per segment computes its difference joint by joint as k_difference does and sums
 // the squares in DoF order; the segments are then summed in path order, so every lane returns the same bits.  A segment with an end
@@ -50,10 +60,7 @@ __device__ __forceinline__ double path_length_wave(const double* __restrict__ q,
       const double* a = q + (size_t)(keep ? keep[t] : t) * nq;
       const double* b = q + (size_t)(keep ? keep[t + 1] : t + 1) * nq;
       bool fin = true, same = true;
-      for (int k = 0; k < nq; ++k) {
-        fin = fin && isfinite(a[k]) && isfinite(b[k]);
-        same = same && a[k] == b[k];
-      }
+      rows_fin_same(a, b, nq, fin, same);
       if (!fin) nrm = __longlong_as_double(0x7ff8000000000000ll);
       else if (!same) {   // (equal rows are 0 apart, exactly: a repeated waypoint adds nothing, whatever log3 makes of a quaternion's rounding)
         double acc = 0.0;
