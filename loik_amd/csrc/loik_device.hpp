@@ -126,6 +126,8 @@ enum : int {
   MODE_MU_OSQP = 16,     // UpdateMu: OSQP's rule instead of the DEFAULT decade steps (update_mu below)
   MODE_ZERO_STATE = 32,  // the launch takes every instance straight from a cold reset (vis = fis = g = w = z = 0 in every record:
                          // IkIdData::Reset(false) / ResetRecursion): the flat engine does not fetch those pairs
+  MODE_FLAT_PREP = 64,   // k_fslots of this launch left a prepared record of every listed instance (loik_flat_prep.hpp): k_flat2 takes
+                         // fresh instances from it
 };
 
 

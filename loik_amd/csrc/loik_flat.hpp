@@ -38,6 +38,7 @@
 #pragma once
 
 #include "loik_lean.hpp"
+#include "loik_flat_prep.hpp"
 
 namespace loikb {
 
@@ -1048,12 +1049,14 @@ __global__ void __launch_bounds__(WAVE)
 k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, const TailTopo* __restrict__ topo,
          const int* __restrict__ child_list, const FlatLane* __restrict__ fl, int maxdepth, int nanc, int frows, int njmp,
          const int* __restrict__ slots, int nslots, int G, T* __restrict__ fslots, int kexp_lo, int ndec, int dw0, int nw,
-         unsigned int* __restrict__ fmask)
+         unsigned int* __restrict__ fmask, T* __restrict__ prep)
 {
   // dw0, nw: the decades to build NOW, [dw0, dw0 + nw) of the table's [0, ndec) -- the table is addressed for its whole range and
   // populated lazily: k_flat2<.., MUR = 2> builds the other decades of an instance in-wave if the instance ever gets there
   // (flat_build_slot, loik_flat2.hpp) and notes it in fmask (bit d: decade d is there; bit 16 + d: written during the launch, by a
   // wavefront of whatever XCD: coherent loads).
+  // prep != nullptr: the instances' prepared records for k_flat2 (loik_flat_prep.hpp; G = PREP_G, at most PREP_NC constraints:
+  // the host checks both).
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const Layout& L = P.L;
   constexpr int HX = 22;
@@ -1098,6 +1101,8 @@ k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, 
     for (int k = 0; k < NA; ++k) arow[k] = (k < FLAT_MAXA && F.anc[k] >= 0) ? gbase + F.anc[k] : WAVE;
     const char* rec = ip + (size_t)jl * JREC * pair_bytes<T>();
     const typename Vec2<T>::type cs = ldp<T>(rec, JP_CS);
+    FlatPrepIn<T> pin;
+    if (prep != nullptr) flat_prep_fetch<T>(pin, has_inst, P, Bf, ip, rec, jlane, isj_lane);   // (the same trip to memory)
     T R0[9], t0[3];
     joint_xform<T>(d, rec, cs.x, cs.y, R0, t0);
     if (!isj_lane) {
@@ -1124,6 +1129,9 @@ k_fslots(const Params<T> P, const Bufs<T> Bf, const JointDesc* __restrict__ jd, 
 #pragma unroll
     for (int k = 0; k < 6; ++k) swt[lane * 6 + k] = Sw[k];
     if (lane < 6) swt[WAVE * 6 + lane] = T(0);
+    // (the placement rows in xch are done with, pass A's first write to them comes behind the next tail_sync)
+    if (prep != nullptr)
+      flat_prep_write<T>(prep + (size_t)sidx * flat_prep_stride(L.nc), has_inst, P, pin, jlane, cslot, R0, t0, Sw, xch + sub * L.nc * C2D);
     // the base terms at the world origin
     {
       const T mass = (!isj_lane || (d.flags & JF_MASSLESS)) ? T(0) : T(1);

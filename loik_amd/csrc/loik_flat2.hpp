@@ -44,14 +44,9 @@ __host__ __device__ __forceinline__ int flat2_park_stride(int nc, bool has_hv)
 }
 constexpr int F2W = 32;  // row stride of the [ancestor][joint] arrays (W rows, W tau products): lane (j, h) touches row 2 i + h
 
-// Constraint block of an instance in the LDS of k_flat2 / k_flat1 (doubles; every 6-vector starts at an even offset).  What the loop
-// needs of a task constraint (A, b) on joint c is its image at the world origin: AW = X*_{0<-c} A^T ([world component k][row q],
-// and transposed), because  A v_c = AW^T v^w_c  (the constrained link's velocity as the path sum leaves it, no frame change) and
-// X* (A^T y) = AW y.  A itself stays for the stored record's A^T y.
-enum : int { C2_LANE = 0, C2_B = 2, C2_Y = 8, C2_ATYW = 14 /* A^T y at the world origin: the next FwdPass1's */, C2_ATBW = 20,
-             C2_ATYF = 26 /* the constraint's force in this iteration's f */, C2_CW = 32, C2_DLT = 38 /* first-iteration corrections */,
-             C2_VC = 44 /* v^w of the constrained joint */, C2_ATY = 50 /* A^T y as the record brought it */, C2_AW = 56, C2_AWT = 92,
-             C2_A = 128, C2D = 164 };
+// (the constraint block of an instance in LDS, C2_*: loik_flat_prep.hpp -- k_fslots writes the blocks of fresh instances)
+static_assert(FI_BNORM == PRS_BNORM && FI_TGIN == PRS_TGIN && FI_STY == PRS_STY && FI_TOLP == 3 && FI_TOLD == 4 && FI_DYQP == 5 && FI_ATDY == 6 &&
+              FI_UBP == 7 && FI_LBM == 8 && FI_C1 == 9 && FI_C2 == 10, "the prepared record's scalar row starts with the instance's LDS scalars");
 
 // v_max_f64 / v_min_f64 as the hardware does them.  __builtin_fmax on a value the compiler cannot prove quiet (anything that came
 // through a DPP / permlane move, an LDS read, a fabs) is preceded by a canonicalising v_max_f64 x, x, x in IEEE mode: 93 of the
@@ -641,7 +636,7 @@ k_flat2(const Params<double> P, const Bufs<double> Bf, const JointDesc* __restri
   // (what only the in-wave builder and the lazily populated table need comes through ONE pointer and the spare bits of has_hv: every
   //  kernel argument is a scalar register the iteration loop then lacks -- five more arguments cost the loop twenty v_readlane per iteration)
   // has_hv_pk: bit 0 = the reference target is not zero, bits 8..15 = the tree's depth, bits 16..31 = the decades k_fslots built for this
-  // launch (win_bits); aux[0] = TailTopo*, aux[1] = the children's list, aux[2] = fmask
+  // launch (win_bits); aux[0] = TailTopo*, aux[1] = the children's list, aux[2] = fmask, aux[3] = the prepared records (loik_flat_prep.hpp)
   const int has_hv = has_hv_pk & 1;
 #define topo (reinterpret_cast<const TailTopo*>(aux[0]))
 #define child_list (reinterpret_cast<const int*>(aux[1]))
@@ -1053,6 +1048,130 @@ k_flat2(const Params<double> P, const Bufs<double> Bf, const JointDesc* __restri
     any_iter = true;
     TAIL_TP(16)
   };
+  // subtree sums of the state the instance arrives with (cold start: v = 0) and of the reference term
+  auto arrive_sums = [&](const T* v, bool zero_state, T* SE) {
+    T vw[6], E[6];
+    T a[3], l[3], c[3], c1[3], c2[3];
+    mat3_vec(R0, v, l);
+    mat3_vec(R0, v + 3, a);
+    cross3(t0, a, c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { vw[k] = l[k] + c[k]; vw[3 + k] = a[k]; }
+    // E = mass * (R0 v_l, R0 v_a + t0 x R0 v_l), from the world-frame motion: R0 v_l = vw_l - t0 x vw_a
+    cross3(t0, vw + 3, c1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) E[k] = vw[k] - c1[k];
+    cross3(t0, E, c2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) E[3 + k] = vw[3 + k] + c2[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) E[k] *= mass;
+    if (zero_state) {   // (v = 0 in every record: the subtree sums are zeros -- five window-doubling exchanges not made)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) SE[k] = T(0);
+    } else {
+      flat_subtree_sum<T>(xb, j, j, G, size, nscan, E, SE);
+    }
+    if (has_hv) {
+      T hv[6], hw[6], Sh[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) hv[k] = mass * (HM == 3 ? hrow[36 + k] : P.Hv[k]);
+      act_force(R0, t0, hv, hw);
+      flat_subtree_sum<T>(xb, j, j, G, size, nscan, hw, Sh);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) shv[j * 6 + k] = Sh[k];
+    }
+  };
+  // A fresh instance from the PREPARED record k_fslots of this launch left (loik_flat_prep.hpp: the host says so with MODE_FLAT_PREP):
+  // placements, S^w, the constraint blocks at the world origin and the record's scalars come in rows, in one trip and without an LDS
+  // round; only a warm start's state is fetched from the tiles.  Every value is the one the load below computes.
+  auto take_prepared = [&](int slot) {
+    const T* pb = reinterpret_cast<const T*>(aux[3]) + (size_t)slot * flat_prep_stride(L.nc);
+    const bool zero_state = (P.mode & MODE_ZERO_STATE) != 0;
+    const int dsl0 = -kexp_lo;
+    const bool slot0 = zero_state && dsl0 >= 0 && dsl0 < ndec && (MUR != 2 || ((win_bits >> dsl0) & 1));
+    T win0[NH + 1];
+#pragma unroll
+    for (int i = 0; i <= NH; ++i) {
+      const int k = 2 * i + (h ? 1 : 0);
+      win0[i] = (slot0 && isj_lane && (k == NA || k < fdm1)) ? fslots[fslotW_at(slot, ndec, dsl0, frows, fcol + (k == NA ? fdm1 : k))] : T(0);
+    }
+    const int nce = L.nc * cs;
+    T cbl[FLAT2_PARK_BATCH];
+#pragma unroll
+    for (int k = 0; k < FLAT2_PARK_BATCH; ++k) { const int e = k * WAVE + lane; cbl[k] = e < nce ? pb[PR_C + e] : T(0); }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) R0[k] = pb[PR_RT + k * G + j];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) t0[k] = pb[PR_RT + (9 + k) * G + j];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Sw3[k] = pb[PR_SW + k * WAVE + lane];
+    nu = pb[PR_JS + j]; s = pb[PR_JS + G + j];
+    if (P.mode & MODE_BND_SHARED) {
+      lbi = isj_lane ? Bf.uni[L.nc * 57 + jl] : T(0);
+      ubi = isj_lane ? Bf.uni[L.nc * 57 + L.nb + jl] : T(0);
+    } else {
+      lbi = pb[PR_JS + 2 * G + j]; ubi = pb[PR_JS + 3 * G + j];
+    }
+    const T sc = lane < PRS_N ? pb[PR_SC + lane] : T(0);   // (lane k: entry k of the scalar row)
+    T v[6], f[6], g[6], SE[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) { v[k] = T(0); f[k] = T(0); g[k] = T(0); SE[k] = T(0); }
+    w = T(0); z = T(0);
+    if (!zero_state && isj_lane) {
+      const typename Vec2<T>::type wz = rldp<T, false>(rec, JP_WZ);
+      rld6<T, false>(rec, JP_V, v);
+      rld6<T, false>(rec, JP_F, f);
+      rld6<T, false>(rec, JP_G, g);
+      w = wz.x; z = wz.y;
+    }
+    TAIL_TP(13)
+    TAIL_TP(14)
+    tail_sync();
+#pragma unroll
+    for (int k = 0; k < FLAT2_PARK_BATCH; ++k) { const int e = k * WAVE + lane; if (e < nce) cdi[e] = cbl[k]; }
+    for (int e0 = FLAT2_PARK_BATCH * WAVE; e0 < nce; e0 += FLAT2_PARK_BATCH * WAVE) {   // (more than three task constraints)
+#pragma unroll
+      for (int k = 0; k < FLAT2_PARK_BATCH; ++k) { const int e = e0 + k * WAVE + lane; cbl[k] = e < nce ? pb[PR_C + e] : T(0); }
+#pragma unroll
+      for (int k = 0; k < FLAT2_PARK_BATCH; ++k) { const int e = e0 + k * WAVE + lane; if (e < nce) cdi[e] = cbl[k]; }
+    }
+    if (lane <= FI_C2) isc[lane] = sc;
+    if (lane == FI_MULAST) isc[FI_MULAST] = T(-1);
+    tail_sync();
+    cbits = 0u;
+    for (int c = 0; c < L.nc; ++c) {
+      const int cl = (int)cdi[c * cs + C2_LANE];
+      if (isj_lane && cl >= j && cl < j + size) cbits |= 1u << c;
+    }
+    TAIL_TP(15)
+    if (!zero_state || has_hv) arrive_sums(v, zero_state, SE);
+    half(v, v3); half(f, f3); half(g, g3); half(SE, SE3);
+    if constexpr (JCL) { jc[j * 3] = lbi; jc[j * 3 + 1] = ubi; jc[j * 3 + 2] = s; }
+    mu = uniform_of(sc, PRS_MU);
+    kexp = (int)uniform_of(sc, PRS_KEXP);
+    kslot = -(1 << 30); kslot_o = -(1 << 30);
+    if (slot0) {
+      wsel = 0;
+#pragma unroll
+      for (int i = 0; i <= NH; ++i) {
+        const int k = 2 * i + (h ? 1 : 0);
+        if (k <= NA) wl[k * GW + j] = win0[i];
+      }
+      kslot = 0;
+      n_slot_loads = (n_slot_loads + 0x10000u) | (1u << dsl0);
+    }
+    status = (int)uniform_of(sc, PRS_STATUS);
+    iter = (int)uniform_of(sc, PRS_ITER);
+    tail_it = (int)uniform_of(sc, PRS_TAILIT);
+    nflip = (int)uniform_of(sc, PRS_FLIP);
+    done = (status & ST_DONE) != 0;
+    if (!done && !(status & ST_TAIL) && iter + 1 >= P.max_iter) { done = true; status |= ST_DONE; }
+    tail_sync();
+    my_iters = 0;
+    any_iter = false;
+    TAIL_TP(16)
+  };
   int next_slot = -2;  // (plain queue) the entry store_instance fetched while its stores were in flight; -2: none
   auto load_instance = [&]() {
     const int slot_in = next_slot != -2 ? next_slot : fetch();
@@ -1069,6 +1188,9 @@ k_flat2(const Params<double> P, const Bufs<double> Bf, const JointDesc* __restri
     lidx = slot;
     ip = lane_ptr<T>(Bf.tiles, L, slot);
     rec = ip + (size_t)jl * JREC * pair_bytes<T>();
+    if constexpr (!LOG && MUR != 1) {
+      if (P.mode & MODE_FLAT_PREP) { take_prepared(slot); return; }
+    }
     const char* srec = ip + (size_t)L.off_s * pair_bytes<T>();
     // the scalar record travels with the joints' records (one round trip to HBM, not two: the loads are independent)
     const typename Vec2<T>::type mu2 = rldp<T, false>(srec, SP_MU), bi2 = rldp<T, false>(srec, SP_BI), st2 = rldp<T, false>(srec, SP_ST);
@@ -1218,40 +1340,7 @@ k_flat2(const Params<double> P, const Bufs<double> Bf, const JointDesc* __restri
       if (resumed) ccb[C2_ATYW + k] = aw;  // (what the loop had left there)
     }
     TAIL_TP(15)
-    // subtree sums of the state the instance arrives with (cold start: v = 0) and of the reference term
-    {
-      T vw[6], E[6];
-      T a[3], l[3], c[3], c1[3], c2[3];
-      mat3_vec(R0, v, l);
-      mat3_vec(R0, v + 3, a);
-      cross3(t0, a, c);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { vw[k] = l[k] + c[k]; vw[3 + k] = a[k]; }
-      // E = mass * (R0 v_l, R0 v_a + t0 x R0 v_l), from the world-frame motion: R0 v_l = vw_l - t0 x vw_a
-      cross3(t0, vw + 3, c1);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) E[k] = vw[k] - c1[k];
-      cross3(t0, E, c2);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) E[3 + k] = vw[3 + k] + c2[k];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) E[k] *= mass;
-      if (zero_state) {   // (v = 0 in every record: the subtree sums are zeros -- five window-doubling exchanges not made)
-#pragma unroll
-        for (int k = 0; k < 6; ++k) SE[k] = T(0);
-      } else {
-        flat_subtree_sum<T>(xb, j, j, G, size, nscan, E, SE);
-      }
-      if (has_hv) {
-        T hv[6], hw[6], Sh[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) hv[k] = mass * (HM == 3 ? hrow[36 + k] : P.Hv[k]);
-        act_force(R0, t0, hv, hw);
-        flat_subtree_sum<T>(xb, j, j, G, size, nscan, hw, Sh);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) shv[j * 6 + k] = Sh[k];
-      }
-    }
+    arrive_sums(v, zero_state, SE);
     half(Sw, Sw3); half(v, v3); half(f, f3); half(g, g3); half(SE, SE3);
     if constexpr (JCL) { jc[j * 3] = lbi; jc[j * 3 + 1] = ubi; jc[j * 3 + 2] = s; }
     mu = mu2.x;

@@ -135,6 +135,8 @@ struct Tuning {
                                 //   synchronisation, as before (1: k_small_finish writes the counters into the pinned host copy; one synchronisation per Solve())
   int flat_slice = -1;          // LOIKB_FLAT_SLICE=q: k_flat2's / k_flat1's round-robin time slice in iterations (0: never; default: 288 for
                                 // launches in arrival order of >= 32 768 instances, see flat_slice_for / run_tail)
+  bool flat_prep = true;        // LOIKB_FLAT_PREP=0: k_flat2 sets every fresh instance up from the tile records itself; default: from the prepared record
+                                //   k_fslots leaves (loik_flat_prep.hpp) wherever the handle has the buffer
   bool flat_zero_state = true;  // LOIKB_FLAT_ZERO_STATE=0: k_flat2 / k_flat1 fetch vis, fis, g, w, z of every instance even straight after a cold reset
   int flat_order_holdoff = 4;   // LOIKB_FLAT_ORDER_HOLDOFF=n: solves in arrival order after an ordered launch that was not shorter (0: never hold off)
   bool flat_order = true;       // LOIKB_FLAT_ORDER=0: the flat engine takes its instances in arrival order even when the handle's previous
@@ -168,6 +170,7 @@ struct Tuning {
     if (const char* e = getenv("LOIKB_FLAT_SMALL_BATCH")) flat_small_batch = std::max(0, atoi(e));
     if (const char* e = getenv("LOIKB_FLAT_ORDER")) flat_order = atoi(e) != 0;
     if (const char* e = getenv("LOIKB_FLAT_ZERO_STATE")) flat_zero_state = atoi(e) != 0;
+    if (const char* e = getenv("LOIKB_FLAT_PREP")) flat_prep = atoi(e) != 0;
     if (const char* e = getenv("LOIKB_FLAT_ORDER_HOLDOFF")) flat_order_holdoff = std::max(0, atoi(e));
     geti("LOIKB_TAIL_WAVES", tail_waves); tail_waves = std::max(1, std::min(TAIL_WAVES, tail_waves));
     geti("LOIKB_LEAN_DECADES", lean_decades); lean_decades = std::max(1, std::min(15, lean_decades));   // (15: a parked instance's ring entry says "no slot" with decade code 15 -- ADVICE r05)
@@ -344,6 +347,7 @@ struct loikb_solver_impl {
     DevBuf<> d_hslots;                   // decade slots of the lean tail kernel (H, Dinv, UDinv per joint and decade)
     DevBuf<> d_fslots;                   // decade slots of the flat engine (W rows, Dinv per joint and decade)
     DevBuf<> d_park;                     // k_flat2<.., SLICED>: where instances whose time slice is used up are parked
+    DevBuf<> d_prep;                     // k_flat2: the prepared records of fresh instances, written by k_fslots (loik_flat_prep.hpp)
     DevBuf<unsigned int> d_fmask;        // k_flat2<.., MUR = 2>: per instance, which decades of the slot table are populated
     DevBuf<void*> d_aux;                 // k_flat2's cold pointers behind one argument: {TailTopo*, child list, fmask}
     const void* aux_h[4] = {nullptr, nullptr, nullptr, nullptr};   // (what d_aux holds)
@@ -1539,6 +1543,13 @@ int flat_slice_for(const loikb_solver_impl* S, int n, bool ordered)
   return FLAT_SLICE_DEFAULT | (FLAT_SLICE_LATER << 16);
 }
 
+// k_fslots builds an instance's constraint blocks in its placement rows, two instances per wavefront (loik_flat_prep.hpp): up to four
+// task constraints; the block is laid out for 32 lanes per instance, fp64 (k_flat2's robots)
+static bool flat_prep_fits(const loikb_solver_impl* S)
+{
+  return S->esz == sizeof(double) && lanes_per_instance(S) == PREP_G && S->nc <= PREP_NC;
+}
+
 int ensure_hslots(loikb_solver_impl* S)
 {
   if (S->plan.flat && S->have_problem && !flat_applicable(S)) {
@@ -1569,6 +1580,13 @@ int ensure_hslots(loikb_solver_impl* S)
       for (Chunk& C : S->chunks) {
         const size_t need = (size_t)C.B * flat2_park_stride(S->nc, true) * sizeof(double);
         if (!C.d_park.regrow(need) && !(release_getscr(S) > 0 && C.d_park.regrow(need))) (void)hipGetLastError();
+      }
+    }
+    // prepared records of fresh instances (k_flat2 only, ~7 KB per instance): a handle that cannot have them runs as without
+    if (flat_kind(S) == FlatKind::Flat2 && S->tune.flat_prep && flat_prep_fits(S)) {
+      for (Chunk& C : S->chunks) {
+        const size_t need = (size_t)C.B * flat_prep_stride(S->nc) * sizeof(double);
+        if (!C.d_prep.regrow(need) && !(release_getscr(S) > 0 && C.d_prep.regrow(need))) (void)hipGetLastError();
       }
     }
     if (flat_applicable(S) || !S->plan.lean) return LOIKB_OK;
@@ -2150,6 +2168,7 @@ struct FlatLaunch {
   int mur;
   int ndec, kexp_lo, dw0, nw;   // the table's range, the window of it k_fslots builds now
   int slice;                    // flat_launch_slice
+  bool prep;                    // k_fslots leaves prepared records, k_flat2 takes fresh instances from them (loik_flat_prep.hpp)
   double cu_sh; dim3 grid;      // the chunk's share of the CUs, the iteration kernel's grid
 };
 
@@ -2214,7 +2233,7 @@ static int launch_flat_kernel(TailCtx<T>& X, FlatLaunch& F)
   if (one_per_wave(F.kind)) {   // (what only the in-wave builder / the lazily populated table read, behind one kernel argument)
     // (uploaded when one of the pointers changes -- synchronously, from the chunk's own copy: ADVICE r05)
     BUFCHK(C->d_aux.regrow(4 * sizeof(void*)));
-    const void* auxh[4] = {S->d_topo, S->d_child_list, C->d_fmask, nullptr};
+    const void* auxh[4] = {S->d_topo, S->d_child_list, C->d_fmask, C->d_prep.as<double>()};   // (the prepared records: read under MODE_FLAT_PREP only)
     if (memcmp(auxh, C->aux_h, sizeof(auxh)) != 0) {
       memcpy(C->aux_h, auxh, sizeof(auxh));
       HIPCHK(hipStreamSynchronize(C->stream));
@@ -2304,9 +2323,9 @@ static int flat_read_back(TailCtx<T>& X, const FlatLaunch& F, OrderUse use, bool
   if (one_per_wave(F.kind) && X.whole_set && n_first == n_cur) judge_order(S, C, n_cur, use, (double)ms - (double)hms);
   if (S->tune.trace)
     fprintf(stderr, "[loikb] flat engine: %6d instances on %u workgroups, done at %8.3f ms (slots %6.3f ms)  "
-                    "inst-iters %9u  wave-iters %7u  slot loads %7u (+ %u served from LDS)  escaped %u  still iterating %u\n",
+                    "inst-iters %9u  wave-iters %7u  slot loads %7u (+ %u served from LDS)  escaped %u  still iterating %u%s\n",
             n_first, F.grid.x, ms, hms, C->h_counters[1], C->h_counters[5], C->h_counters[6],
-            C->h_counters[FLAT_COUNTERS_SLOT_HITS], escaped, C->h_counters[3]);
+            C->h_counters[FLAT_COUNTERS_SLOT_HITS], escaped, C->h_counters[3], F.prep ? "  fresh instances from prepared records" : "");
   C->stats.lean_escaped += (int)escaped;
   C->tail_iv.emplace_back(t0, t0 + ms);
   X.total_ms = ms; X.n = (int)C->h_counters[3]; X.list = next;
@@ -2351,6 +2370,13 @@ static int launch_flat(TailCtx<T>& X)
   F.nw = F.ndec;
   if (F.mur == 2) flat_table_window(S, F, n);
   if (F.mur == 0) { F.ndec = X.ndec; F.kexp_lo = X.kexp_lo; F.nw = F.ndec; F.dw0 = 0; }   // (the range the handle's history asks for, as ever)
+  // The prepared records (loik_flat_prep.hpp): k_fslots covers the whole list, so every fresh instance of the launch has one.  First
+  // launches of a solve only -- a relaunch's instances have iterated, k_tail's are not k_flat2's -- and not under OSQP's rule or logging,
+  // whose builds keep the old load.
+  const bool prep = F.kind == FlatKind::Flat2 && S->tune.flat_prep && F.ndec > 0 && F.mur != 1 && !S->opt.logging && whole_set && n == n_cur &&
+                    flat_prep_fits(S) && X.G == PREP_G && C->d_prep && (size_t)n_cur * flat_prep_stride(S->nc) * sizeof(double) <= C->d_prep.bytes();
+  if (prep) P.mode |= MODE_FLAT_PREP;
+  F.prep = prep;
   if (F.ndec > 0) {
     const dim3 hgrid((unsigned)((n + X.ipw - 1) / X.ipw));
     // [65][22] exchange rows (pass B's L columns, [NA + 1][64], live in them afterwards) + [65][6] S^w + the constraints' A^T A + the decades' mu
@@ -2359,7 +2385,8 @@ static int launch_flat(TailCtx<T>& X)
     auto* fslots = F.small_na ? k_fslots<T, FLAT_NA_SMALL> : k_fslots<T, FLAT_MAXA>;
     hipLaunchKernelGGL(fslots, hgrid, dim3(WAVE), slds, C->stream, P, X.Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
                        (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth, F.nanc, F.frows, S->flat.njmp, X.list, n,
-                       X.G, C->d_fslots.as<T>(), F.kexp_lo, F.ndec, F.dw0, F.nw, F.mur == 2 ? C->d_fmask : (unsigned int*)nullptr);
+                       X.G, C->d_fslots.as<T>(), F.kexp_lo, F.ndec, F.dw0, F.nw, F.mur == 2 ? C->d_fmask : (unsigned int*)nullptr,
+                       prep ? C->d_prep.as<T>() : (T*)nullptr);
     HIPCHK(hipGetLastError());
   }
   // (no event between k_fslots and the engine in the short sequence: loikb_stats::hslots_ms reads 0 there -- an event costs a lone
