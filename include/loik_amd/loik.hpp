@@ -31,6 +31,7 @@
 #include "../loik_amd_avoid.h"
 #include "../loik_amd_shortcut.h"
 #include "../loik_amd_retime.h"
+#include "../loik_amd_plan.h"
 
 #include <array>
 #include <map>
@@ -709,6 +710,38 @@ public:
     for (std::vector<int>* v : {&r.n_samples, &r.n_waypoints, &r.moved, &r.flags}) v->resize(B);
     for (std::size_t b = 0; b < B; ++b) {
       r.n_samples[b] = info[4 * b]; r.n_waypoints[b] = info[4 * b + 1]; r.moved[b] = info[4 * b + 2]; r.flags[b] = info[4 * b + 3];
+    }
+    return r;
+  }
+  // ---- planning (include/loik_amd_plan.h).  PlanPaths: certified RRT-Connect from q_start [B][nq] to q_goal [B][nq]; two trees per query
+  // grow towards samples drawn from the ranges s_lo, s_hi [nv] (a DoF is sampled iff both are finite) by edges of at most `step`, and every
+  // edge is accepted only when the check of MotionClearance certifies it FREE.  T = the rows of a result path
+  struct PlanResult {
+    DVec q_path;                         // [B][T][nq]: NaN unless FOUND; the rows after n_waypoints repeat the last
+    std::vector<int> n_waypoints, status, iterations;   // [B]; status: LOIKB_PLAN_*
+    std::vector<int> nodes;              // [B][2]: the nodes of the start tree and of the goal tree
+    std::vector<int> edges_checked, edges_free, evals;  // [B]
+    DVec length;                         // [B], as PathLength; NaN unless FOUND
+  };
+  PlanResult PlanPaths(const DVec& q_start, const DVec& q_goal, const DVec& s_lo, const DVec& s_hi, int T, double step = 0.5, int max_iters = 256,
+                       int max_nodes = 256, unsigned long long seed = 0, double margin = 0.0, double tol = 1e-3, int max_evals = 256) const
+  {
+    const std::size_t nq = (std::size_t)model_.nq, B = nq ? q_start.size() / nq : 0;
+    if (q_start.size() != B * nq || q_goal.size() != q_start.size()) throw std::runtime_error("loik_amd: q_start and q_goal must hold the same whole number of rows of nq");
+    if (s_lo.size() != (std::size_t)model_.nv || s_hi.size() != (std::size_t)model_.nv)
+      throw std::runtime_error("loik_amd: s_lo and s_hi must hold model.nv values");
+    const loikb_plan_params p{margin, tol, step, seed, max_evals, max_iters, max_nodes, 0};
+    PlanResult r;
+    r.q_path.resize(B * (std::size_t)(T > 0 ? T : 0) * nq);
+    r.length.resize(B);
+    std::vector<int> info(8 * B);
+    check(loikb_plan_paths(h_, q_start.data(), q_goal.data(), (int)B, 0, s_lo.data(), s_hi.data(), &p, T, r.q_path.data(), info.data(), r.length.data(), 0));
+    for (std::vector<int>* v : {&r.n_waypoints, &r.status, &r.iterations, &r.edges_checked, &r.edges_free, &r.evals}) v->resize(B);
+    r.nodes.resize(2 * B);
+    for (std::size_t b = 0; b < B; ++b) {
+      r.status[b] = info[8 * b]; r.n_waypoints[b] = info[8 * b + 1]; r.iterations[b] = info[8 * b + 2];
+      r.nodes[2 * b] = info[8 * b + 3]; r.nodes[2 * b + 1] = info[8 * b + 4];
+      r.edges_checked[b] = info[8 * b + 5]; r.edges_free[b] = info[8 * b + 6]; r.evals[b] = info[8 * b + 7];
     }
     return r;
   }

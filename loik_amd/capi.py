@@ -205,6 +205,10 @@ RETIME_ABI_VERSION = 1
 RETIME_SYMBOLS = ["loikb_retime_version", "loikb_retime_paths"]
 RETIME_SNAP = 1
 RETIME_TRUNCATED, RETIME_INVALID, RETIME_SKIPPED = 1, 2, 4
+# include/loik_amd_plan.h: certified RRT-Connect planning of joint-space paths; its own header and version
+PLAN_ABI_VERSION = 1
+PLAN_SYMBOLS = ["loikb_plan_version", "loikb_plan_paths"]
+PLAN_FOUND, PLAN_EXHAUSTED_ITERS, PLAN_EXHAUSTED_NODES, PLAN_START_BLOCKED, PLAN_GOAL_BLOCKED, PLAN_TOO_LONG, PLAN_INVALID = range(7)
 
 
 class PoseParams(C.Structure):
@@ -237,6 +241,11 @@ class ShortcutParams(C.Structure):
 
 class RetimeParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("flags", C.c_int)]
+
+
+class PlanParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("step", C.c_double), ("seed", C.c_ulonglong), ("max_evals", C.c_int),
+                ("max_iters", C.c_int), ("max_nodes", C.c_int), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -359,6 +368,8 @@ def lib():
     L.loikb_path_length.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     L.loikb_retime_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(RetimeParams), C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_plan_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.POINTER(PlanParams), C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1421,6 +1432,35 @@ class BatchedLoik:
     def _retime_result(traj, vel, seg, dur, info):
         return dict(q_traj=traj, v_traj=vel, n_samples=info[:, 0].copy(), n_waypoints=info[:, 1].copy(), moved=info[:, 2].copy(),
                     flags=info[:, 3].copy(), duration=dur, seg=seg)
+
+    # ---- planning (include/loik_amd_plan.h) ----------------------------------------------------------------------
+    def plan_paths(self, q_start, q_goal, s_lo, s_hi, T, step=0.5, max_iters=256, max_nodes=256, seed=0, margin=0.0, tol=1e-3, max_evals=256,
+                   out=None):
+        """certified RRT-Connect planning from q_start [B][nq] to q_goal [B][nq] (loikb_plan_paths), both on the host or both on the device:
+        two trees per query grow towards samples drawn from the ranges s_lo, s_hi [nv] (host; a DoF is sampled iff both are finite) by
+        edges of at most `step`, and every edge is accepted only when the check of motion_clearance certifies it FREE.  T = the rows of a
+        result path.  Returns dict(q_path [B][T][nq] (NaN unless FOUND; the rows after n_waypoints repeat the last), n_waypoints [B],
+        status [B] PLAN_*, iterations [B], nodes [B][2], edges_checked, edges_free, evals [B], length [B]), or with out = (path_dev,
+        info_dev, length_dev) device buffers of B T nq float64 / 8 B int32 / B float64 (length_dev may be None) writes there and returns
+        out."""
+        nq, nv = self.model.nq, self.model.nv
+        ps, B, dev, k0 = self._rows(q_start, nq)
+        pg, Bg, devg, k1 = self._rows(q_goal, nq)
+        if B != Bg or dev != devg:
+            raise ValueError("plan_paths: q_start and q_goal differ in rows or in where they live")
+        lo = np.ascontiguousarray(np.broadcast_to(_f64(s_lo), (nv,)))
+        hi = np.ascontiguousarray(np.broadcast_to(_f64(s_hi), (nv,)))
+        T = int(T)
+        prm = PlanParams(float(margin), float(tol), float(step), int(seed) % (1 << 64), int(max_evals), int(max_iters), int(max_nodes), 0)
+        ptrs, oflags, new = _outs(out, [((B, max(T, 0), nq), np.float64), ((B, 8), np.int32), ((B,), np.float64)])
+        _check(self.L.loikb_plan_paths(self.h, ps, pg, B, IN_DEVICE if dev else 0, lo.ctypes.data_as(_dp), hi.ctypes.data_as(_dp), C.byref(prm), T,
+                                       *ptrs, oflags))
+        return out if new is None else self._plan_result(*new)
+
+    @staticmethod
+    def _plan_result(path, info, length):
+        return dict(q_path=path, n_waypoints=info[:, 1].copy(), status=info[:, 0].copy(), iterations=info[:, 2].copy(), nodes=info[:, 3:5].copy(),
+                    edges_checked=info[:, 5].copy(), edges_free=info[:, 6].copy(), evals=info[:, 7].copy(), length=length)
 
     def set_multistart_clearance(self, margin=0.0):
         """every later SolvePoseMultiStart answers a goal only with a reached seed whose clearance is >= margin

@@ -1666,6 +1666,93 @@ int loikb_retime_paths(loikb_solver* S, const double* q_path, const int* len, in
   return o.finish();   // (the caller's arrays have been read)
 }
 
+// ---- include/loik_amd_plan.h (kernel in loik_pose_plan.hpp) ---------------------------------------------------------------------
+int loikb_plan_version(void) { return LOIKB_PLAN_VERSION; }
+
+// The launch of loikb_plan_paths.  lo, hi [nv] and coord [nv] (the coordinate of a sampled DoF, else -1) are the caller's, alive until
+// `o` is finished.  S->d_getscr[1] holds the two range rows, then the trees of every resident wavefront, then the coordinates and the
+// wavefronts' parents and path nodes; the records of a wavefront are LDS when they fit beside what the compiler keeps for itself,
+// else the motion check's slab (and its grid).  Queued; the caller finishes `o`
+static int plan_run(loikb_solver_impl* S, const double* dqs, const double* dqg, int B, int T, const double* lo, const double* hi, const int* coord,
+                    const loikb_plan_params& p, double* out_path, int* out_info, double* out_length, QueryOut& o)
+{
+  Collision& C = S->pose.col;
+  const int ncar = (int)C.car.size(), nv = S->nv;
+  const size_t aux = shortcut_aux_doubles(S->nb, ncar, C.ns);
+  hipFuncAttributes fa;
+  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_plan_paths<false>)));
+  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) + fa.sharedSizeBytes > 65536;
+  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
+  const size_t wd = plan_scr_doubles(p.max_nodes, S->nq), wi = plan_scr_ints(p.max_nodes, T);
+  const size_t per = wd * sizeof(double) + wi * sizeof(int);
+  const size_t fit = std::max<size_t>(1, (size_t)LOIKB_PLAN_SCRATCH_BYTES / per);
+  const int waves = (int)std::min<size_t>((size_t)std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES), fit);
+  double *d_path, *d_len;
+  int* d_info;
+  o.add(out_path, sizeof(double) * (size_t)B * T * S->nq, &d_path);
+  o.add(out_length, sizeof(double) * (size_t)B, &d_len);
+  o.add(out_info, sizeof(int) * 8 * (size_t)B, &d_info);
+  int rc;
+  const size_t dbytes = sizeof(double) * ((size_t)2 * nv + wd * (size_t)waves);
+  if ((rc = o.reserve()) || (rc = regrow(S->d_getscr[1], dbytes + sizeof(int) * ((size_t)nv + wi * (size_t)waves)))) return rc;
+  double* d_lo = S->d_getscr[1].as<double>();
+  int* d_coord = (int*)(S->d_getscr[1].as<char>() + dbytes);
+  HIPCHK(hipMemcpyAsync(d_lo, lo, sizeof(double) * nv, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(d_lo + nv, hi, sizeof(double) * nv, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(d_coord, coord, sizeof(int) * nv, hipMemcpyHostToDevice, S->stream));
+  const ClrModel m = clr_model(S);
+  const PlanPrm prm{p.margin, p.tol, p.step, p.max_evals, p.max_iters, p.max_nodes, p.seed};
+  if (slab) {
+    if ((rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves))) return rc;
+    hipLaunchKernelGGL(k_plan_paths<true>, dim3(waves), dim3(64), lds, S->stream, dqs, dqg, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
+                       (const double*)d_lo, (const double*)(d_lo + nv), (const int*)d_coord, C.d_mslab.as<double>(), d_lo + 2 * nv, d_coord + nv, d_path,
+                       d_info, d_len);
+  } else {
+    hipLaunchKernelGGL(k_plan_paths<false>, dim3(waves), dim3(64), lds, S->stream, dqs, dqg, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
+                       (const double*)d_lo, (const double*)(d_lo + nv), (const int*)d_coord, (double*)nullptr, d_lo + 2 * nv, d_coord + nv, d_path,
+                       d_info, d_len);
+  }
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+int loikb_plan_paths(loikb_solver* S, const double* q_start, const double* q_goal, int B, int in_flags, const double* s_lo, const double* s_hi,
+                     const loikb_plan_params* p, int T, double* out_path, int* out_info, double* out_length, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  int rc;
+  if (T < 2) { g_last_error = "plan_paths: need T >= 2"; return LOIKB_ERR_ARG; }
+  if (B < 0 || (size_t)B * (size_t)T > (size_t)0x7fffffff || (B > 0 && (!q_start || !q_goal))) {
+    g_last_error = "plan_paths: need B >= 0, B * T < 2^31 and q_start, q_goal when B > 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (B > 0 && (!out_path || !out_info)) { g_last_error = "plan_paths: need out_path and out_info"; return LOIKB_ERR_ARG; }
+  const loikb_motion_params mp{p ? p->margin : 0.0, p ? p->tol : 0.0, p ? p->max_evals : 0, p ? p->flags : 0};
+  if ((rc = motion_check_params(p ? &mp : nullptr, "plan_paths"))) return rc;
+  const char* bad = !(std::isfinite(p->step) && p->step > 0.0) ? "step is not finite and > 0"
+                    : (p->max_iters < 0 || p->max_iters > 1048576) ? "max_iters is outside 0 .. 1048576"
+                    : (p->max_nodes < 2 || p->max_nodes > 65536) ? "max_nodes is outside 2 .. 65536" : nullptr;
+  if (bad) { g_last_error = std::string("plan_paths: ") + bad; return LOIKB_ERR_ARG; }
+  if (!s_lo || !s_hi) { g_last_error = "plan_paths: need s_lo and s_hi"; return LOIKB_ERR_ARG; }
+  if ((rc = check_dof_pairs(S, "plan_paths", "s_lo", "s_hi", s_lo, s_hi, S->nv))) return rc;
+  std::vector<int> coord(S->nv, -1);
+  int sampled = 0;
+  for (int j = 0; j < S->nv; ++j)
+    if (std::isfinite(s_lo[j]) && std::isfinite(s_hi[j])) { coord[j] = S->lim_q[j]; ++sampled; }
+  if (sampled == 0) { g_last_error = "plan_paths: no DoF to sample (s_lo and s_hi need a finite pair)"; return LOIKB_ERR_ARG; }
+  if (out_path && (out_path == q_start || out_path == q_goal)) { g_last_error = "plan_paths: out_path == q_start or q_goal"; return LOIKB_ERR_ARG; }
+  if (S->pose.col.ns == 0) { g_last_error = "plan_paths: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (B == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  QueryOut o(S, out_flags);
+  const size_t qbytes = sizeof(double) * (size_t)B * S->nq;
+  const double *dqs, *dqg;
+  if ((rc = motion_inputs(S, q_start, qbytes, q_goal, qbytes, in_flags & LOIKB_IN_DEVICE, &dqs, &dqg)) ||
+      (rc = plan_run(S, dqs, dqg, B, T, s_lo, s_hi, coord.data(), *p, out_path, out_info, out_length, o)))
+    return rc;
+  return o.finish();   // (the caller's arrays have been read)
+}
+
 // the buffers of the collision-aware selection, on first use
 static int ms_clr_alloc(loikb_solver_impl* S)
 {
