@@ -31,6 +31,7 @@
 #include "../loik_amd_avoid.h"
 #include "../loik_amd_shortcut.h"
 #include "../loik_amd_retime.h"
+#include "../loik_amd_blend.h"
 #include "../loik_amd_plan.h"
 
 #include <array>
@@ -710,6 +711,52 @@ public:
     for (std::vector<int>* v : {&r.n_samples, &r.n_waypoints, &r.moved, &r.flags}) v->resize(B);
     for (std::size_t b = 0; b < B; ++b) {
       r.n_samples[b] = info[4 * b]; r.n_waypoints[b] = info[4 * b + 1]; r.moved[b] = info[4 * b + 2]; r.flags[b] = info[4 * b + 3];
+    }
+    return r;
+  }
+  // ---- blending (include/loik_amd_blend.h).  BlendPaths: RetimePaths through the corners -- every corner is replaced by a parabola of
+  // half-length at most `reach` (halved up to max_tries - 1 times) when the advancement of MotionClearance certifies the curve at a
+  // clearance >= margin, and is run through at a constant rate; a corner that is not certified stops.  max_samples as RetimePaths
+  struct BlendResult {
+    int S = 0;                                            // rows of q_traj / v_traj per path
+    DVec q_traj, v_traj;                                  // [B][S][nq], [B][S][nv]
+    std::vector<int> n_samples, n_waypoints, taken, flags;   // [B]; flags: LOIKB_BLEND_TRUNCATED / INVALID / SKIPPED
+    DVec duration;                                        // [B]
+    DVec corner;                                          // [B][T-2][5] = (l, r_in, r_out, rate, min_sampled)
+    std::vector<int> corner_info;                         // [B][T-2][6] = (status LOIKB_BLEND_*, tries, evals, witness kind, a, b)
+    DVec piece;                                           // [B][2T-3][4] = (t_start, duration, v0 or rate, v1 or rate)
+  };
+  BlendResult BlendPaths(const DVec& q_path, int T, const DVec& v_max, const DVec& a_max, double dt, double reach,
+                         const std::vector<int>& n_waypoints = {}, int max_samples = -1, double margin = 0.0, double tol = 1e-3,
+                         int max_evals = 256, int max_tries = 4) const
+  {
+    const std::size_t B = path_count(q_path, T, n_waypoints);
+    if (v_max.size() != (std::size_t)model_.nv || a_max.size() != (std::size_t)model_.nv)
+      throw std::runtime_error("loik_amd: v_max and a_max must hold model.nv values");
+    const loikb_blend_params p{margin, tol, reach, dt, max_evals, max_tries, 0};
+    const int* len = n_waypoints.empty() ? nullptr : n_waypoints.data();
+    const std::size_t nc = T > 2 ? (std::size_t)T - 2 : 0, np = T > 1 ? 2 * (std::size_t)T - 3 : 0;
+    BlendResult r;
+    r.duration.resize(B);
+    r.corner.resize(5 * B * nc);
+    r.corner_info.resize(6 * B * nc);
+    r.piece.resize(4 * B * np);
+    std::vector<int> info(4 * B);
+    if (max_samples < 0) {
+      check(loikb_blend_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, 0, nullptr, nullptr, r.duration.data(),
+                              info.data(), r.corner.data(), r.corner_info.data(), r.piece.data(), 0));
+      max_samples = 1;
+      for (std::size_t b = 0; b < B; ++b) max_samples = std::max(max_samples, info[4 * b]);
+    }
+    r.S = max_samples;
+    r.q_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nq);
+    r.v_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nv);
+    check(loikb_blend_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, r.S, r.S > 0 ? r.q_traj.data() : nullptr,
+                            r.S > 0 ? r.v_traj.data() : nullptr, r.duration.data(), info.data(), r.corner.data(), r.corner_info.data(),
+                            r.piece.data(), 0));
+    for (std::vector<int>* v : {&r.n_samples, &r.n_waypoints, &r.taken, &r.flags}) v->resize(B);
+    for (std::size_t b = 0; b < B; ++b) {
+      r.n_samples[b] = info[4 * b]; r.n_waypoints[b] = info[4 * b + 1]; r.taken[b] = info[4 * b + 2]; r.flags[b] = info[4 * b + 3];
     }
     return r;
   }

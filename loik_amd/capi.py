@@ -209,6 +209,11 @@ RETIME_TRUNCATED, RETIME_INVALID, RETIME_SKIPPED = 1, 2, 4
 PLAN_ABI_VERSION = 1
 PLAN_SYMBOLS = ["loikb_plan_version", "loikb_plan_paths"]
 PLAN_FOUND, PLAN_EXHAUSTED_ITERS, PLAN_EXHAUSTED_NODES, PLAN_START_BLOCKED, PLAN_GOAL_BLOCKED, PLAN_TOO_LONG, PLAN_INVALID = range(7)
+# include/loik_amd_blend.h: certified parabolic blends, retiming through the corners of a path; its own header and version
+BLEND_ABI_VERSION = 1
+BLEND_SYMBOLS = ["loikb_blend_version", "loikb_blend_paths"]
+BLEND_TRUNCATED, BLEND_INVALID, BLEND_SKIPPED = 1, 2, 4
+BLEND_TAKEN, BLEND_BLOCKED, BLEND_UNDECIDED, BLEND_COUPLED, BLEND_ZERO_LEG, BLEND_OFF = range(6)
 
 
 class PoseParams(C.Structure):
@@ -246,6 +251,11 @@ class RetimeParams(C.Structure):
 class PlanParams(C.Structure):
     _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("step", C.c_double), ("seed", C.c_ulonglong), ("max_evals", C.c_int),
                 ("max_iters", C.c_int), ("max_nodes", C.c_int), ("flags", C.c_int)]
+
+
+class BlendParams(C.Structure):
+    _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("reach", C.c_double), ("dt", C.c_double), ("max_evals", C.c_int),
+                ("max_tries", C.c_int), ("flags", C.c_int)]
 
 
 class MultiStartParams(C.Structure):
@@ -370,6 +380,8 @@ def lib():
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_plan_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp, _dp, C.POINTER(PlanParams), C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_blend_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(BlendParams), C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1432,6 +1444,53 @@ class BatchedLoik:
     def _retime_result(traj, vel, seg, dur, info):
         return dict(q_traj=traj, v_traj=vel, n_samples=info[:, 0].copy(), n_waypoints=info[:, 1].copy(), moved=info[:, 2].copy(),
                     flags=info[:, 3].copy(), duration=dur, seg=seg)
+
+    # ---- blending (include/loik_amd_blend.h) ---------------------------------------------------------------------
+    def blend_paths(self, q_path, v_max, a_max, dt, reach, n_waypoints=None, max_samples=None, margin=0.0, tol=1e-3, max_evals=256, max_tries=4,
+                    out=None):
+        """retiming of the paths q_path [B][T][nq] through their corners (loikb_blend_paths): every corner is replaced by a parabola of
+        half-length at most `reach` (halved up to max_tries - 1 times) when the advancement of motion_clearance certifies the curve at a
+        clearance >= margin against the handle's sphere model, and is then run through at a constant rate; a corner that is not
+        certified stops as in retime_paths.  v_max, a_max, dt, n_waypoints and max_samples as retime_paths takes them.  Returns
+        dict(q_traj [B][S][nq], v_traj [B][S][nv], n_samples, n_waypoints, taken, flags [B], duration [B], corner [B][T-2][5] = (l, r_in,
+        r_out, rate, min_sampled), corner_info [B][T-2][6] = (status BLEND_*, tries, evals, witness kind, a, b), piece [B][2T-3][4] =
+        (t_start, duration, v0 or rate, v1 or rate)); q_traj and v_traj are None after a timing-only call.  With out = (traj_dev, vel_dev,
+        duration_dev, info_dev, corner_dev, corner_info_dev, piece_dev) device buffers of B S nq / B S nv / B float64, 4 B int32,
+        5 B (T-2) float64, 6 B (T-2) int32 and 4 B (2T-3) float64 (all but duration_dev and info_dev may be None; max_samples is then
+        required) writes there and returns out."""
+        pq, pl, B, T, dev, alive = self._paths("blend_paths", q_path, n_waypoints)
+        nq, nv = self.model.nq, self.model.nv
+        vm = np.ascontiguousarray(np.broadcast_to(_f64(v_max), (nv,)))
+        am = np.ascontiguousarray(np.broadcast_to(_f64(a_max), (nv,)))
+        prm = BlendParams(float(margin), float(tol), float(reach), float(dt), int(max_evals), int(max_tries), 0)
+
+        def call(S, ptrs, oflags):
+            _check(self.L.loikb_blend_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, vm.ctypes.data_as(_dp), am.ctypes.data_as(_dp),
+                                            C.byref(prm), S, *ptrs, oflags))
+        if out is not None:
+            if max_samples is None:
+                raise ValueError("blend_paths: out needs max_samples")
+            ptrs, oflags, _ = _outs(out, [None] * 7)
+            call(int(max_samples), ptrs, oflags)
+            return out
+        nc, npc = max(T - 2, 0), max(2 * T - 3, 0)
+        dur, info = np.empty(B), np.empty((B, 4), dtype=np.int32)
+        corner, cinfo, piece = np.empty((B, nc, 5)), np.empty((B, nc, 6), dtype=np.int32), np.empty((B, npc, 4))
+        tail = [a.ctypes.data_as(C.c_void_p) for a in (dur, info, corner, cinfo, piece)]
+        if max_samples is None:
+            call(0, [None, None] + tail, 0)
+            max_samples = max(int(info[:, 0].max(initial=1)), 1)
+        S = int(max_samples)
+        traj = vel = None
+        if S > 0:
+            traj, vel = np.empty((B, S, nq)), np.empty((B, S, nv))
+        call(S, [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in (traj, vel)] + tail, 0)
+        return self._blend_result(traj, vel, dur, info, corner, cinfo, piece)
+
+    @staticmethod
+    def _blend_result(traj, vel, dur, info, corner, cinfo, piece):
+        return dict(q_traj=traj, v_traj=vel, n_samples=info[:, 0].copy(), n_waypoints=info[:, 1].copy(), taken=info[:, 2].copy(),
+                    flags=info[:, 3].copy(), duration=dur, corner=corner, corner_info=cinfo, piece=piece)
 
     # ---- planning (include/loik_amd_plan.h) ----------------------------------------------------------------------
     def plan_paths(self, q_start, q_goal, s_lo, s_hi, T, step=0.5, max_iters=256, max_nodes=256, seed=0, margin=0.0, tol=1e-3, max_evals=256,

@@ -30,6 +30,7 @@
 #include "loik_pose_motion.hpp"
 #include "loik_pose_shortcut.hpp"
 #include "loik_pose_retime.hpp"
+#include "loik_pose_blend.hpp"
 #include "loik_pose_plan.hpp"
 #include "loik_pose_avoid.hpp"
 #include "loik_flat_inst.hpp"
@@ -59,6 +60,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_avoid.h"
 #include "../../include/loik_amd_shortcut.h"
 #include "../../include/loik_amd_retime.h"
+#include "../../include/loik_amd_blend.h"
 #include "../../include/loik_amd_plan.h"
 
 #include <algorithm>

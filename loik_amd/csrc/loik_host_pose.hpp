@@ -201,7 +201,7 @@ class QueryOut {
   struct Item { void* user; size_t bytes; void* slot; void (*set)(void* slot, void* p); };
   loikb_solver_impl* S_;
   bool to_dev_, done_ = false;
-  Item o_[5];
+  Item o_[7];
   int n_ = 0;
 };
 
@@ -1662,6 +1662,90 @@ int loikb_retime_paths(loikb_solver* S, const double* q_path, const int* len, in
   const double *dq, *dlen;
   if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
       (rc = retime_run(S, dq, (const int*)dlen, B, T, v_max, a_max, *p, out_traj ? n_rows : 0, out_traj, out_vel, out_seg, out_duration, out_info, o)))
+    return rc;
+  return o.finish();   // (the caller's arrays have been read)
+}
+
+// ---- include/loik_amd_blend.h (kernel in loik_pose_blend.hpp) -------------------------------------------------------------------
+int loikb_blend_version(void) { return LOIKB_BLEND_VERSION; }
+
+// The launch of loikb_blend_paths.  The two limit rows go side by side into S->d_getscr[1], as retime_run puts them; the records and the
+// tables of a wavefront are LDS when they fit beside the centres and what the compiler keeps for itself, else a slab per resident
+// wavefront (the motion check's, and its grid).  Queued; the caller finishes `o`
+static int blend_run(loikb_solver_impl* S, const double* dq, const int* dlen, int B, int T, const double* v_max, const double* a_max,
+                     const loikb_blend_params& p, int n_rows, double* out_traj, double* out_vel, double* out_duration, int* out_info,
+                     double* out_corner, int* out_cinfo, double* out_piece, QueryOut& o)
+{
+  Collision& C = S->pose.col;
+  const int ncar = (int)C.car.size();
+  const size_t aux = blend_aux_doubles(S->nb, ncar, C.ns, T);
+  hipFuncAttributes fa;
+  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_blend_paths<false>)));
+  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) + fa.sharedSizeBytes > 65536;
+  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
+  const int waves = std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES);
+  double *d_traj, *d_vel, *d_dur, *d_corner, *d_piece;
+  int *d_info, *d_cinfo;
+  o.add(out_traj, sizeof(double) * (size_t)B * n_rows * S->nq, &d_traj);
+  o.add(out_vel, sizeof(double) * (size_t)B * n_rows * S->nv, &d_vel);
+  o.add(out_duration, sizeof(double) * (size_t)B, &d_dur);
+  o.add(out_corner, sizeof(double) * (size_t)B * (T - 2) * 5, &d_corner);
+  o.add(out_piece, sizeof(double) * (size_t)B * (2 * (size_t)T - 3) * 4, &d_piece);
+  o.add(out_info, sizeof(int) * 4 * (size_t)B, &d_info);
+  o.add(out_cinfo, sizeof(int) * (size_t)B * (T - 2) * 6, &d_cinfo);
+  int rc;
+  const size_t row = sizeof(double) * (size_t)S->nv;
+  if ((rc = o.reserve()) || (rc = regrow(S->d_getscr[1], 2 * row))) return rc;
+  HIPCHK(hipMemcpyAsync(S->d_getscr[1], v_max, row, hipMemcpyHostToDevice, S->stream));
+  HIPCHK(hipMemcpyAsync(S->d_getscr[1].as<char>() + row, a_max, row, hipMemcpyHostToDevice, S->stream));
+  const double* d_lim = S->d_getscr[1].as<const double>();
+  const ClrModel m = clr_model(S);
+  const BlendPrm prm{p.margin, p.tol, p.reach, p.dt, p.max_evals, p.max_tries, n_rows};
+  if (slab) {
+    if ((rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves))) return rc;
+    hipLaunchKernelGGL(k_blend_paths<true>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, d_lim, prm,
+                       C.d_mslab.as<double>(), d_traj, d_vel, d_dur, d_info, d_corner, d_cinfo, d_piece);
+  } else {
+    hipLaunchKernelGGL(k_blend_paths<false>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, d_lim, prm,
+                       (double*)nullptr, d_traj, d_vel, d_dur, d_info, d_corner, d_cinfo, d_piece);
+  }
+  HIPCHK(hipGetLastError());
+  return LOIKB_OK;
+}
+
+int loikb_blend_paths(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, const double* v_max, const double* a_max,
+                      const loikb_blend_params* p, int n_rows, double* out_traj, double* out_vel, double* out_duration, int* out_info,
+                      double* out_corner, int* out_corner_info, double* out_piece, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  int rc;
+  if ((rc = shortcut_check_paths("blend_paths", q_path, B, T))) return rc;
+  if (T >= (1 << 30)) { g_last_error = "blend_paths: need T < 2^30"; return LOIKB_ERR_ARG; }   // (2 T - 3 pieces are counted in ints)
+  const char* bad = !v_max ? "v_max == NULL" : !a_max ? "a_max == NULL" : !p ? "p == NULL" : !out_duration ? "need out_duration"
+                    : !out_info ? "need out_info" : nullptr;
+  for (int j = 0; !bad && j < S->nv; ++j) {
+    if (!(std::isfinite(v_max[j]) && v_max[j] > 0.0)) bad = "a v_max that is not finite and > 0";
+    else if (!(std::isfinite(a_max[j]) && a_max[j] > 0.0)) bad = "an a_max that is not finite and > 0";
+  }
+  if (bad) { g_last_error = std::string("blend_paths: ") + bad; return LOIKB_ERR_ARG; }
+  const loikb_motion_params mp{p->margin, p->tol, p->max_evals, p->flags};
+  if ((rc = motion_check_params(&mp, "blend_paths"))) return rc;
+  bad = !(std::isfinite(p->reach) && p->reach > 0.0) ? "reach is not finite and > 0"
+        : !(std::isfinite(p->dt) && p->dt > 0.0) ? "dt is not finite and > 0"
+        : (p->max_tries < 0 || p->max_tries > 16) ? "max_tries is outside 0 .. 16"
+        : (out_vel && !out_traj) ? "out_vel without out_traj"
+        : (out_traj && n_rows < 1) ? "out_traj with S < 1"
+        : (out_traj && (size_t)B * (size_t)n_rows > (size_t)0x7fffffff) ? "need B * S < 2^31"
+        : (out_traj && out_traj == q_path) ? "out_traj == q_path" : nullptr;
+  if (bad) { g_last_error = std::string("blend_paths: ") + bad; return LOIKB_ERR_ARG; }
+  if (S->pose.col.ns == 0) { g_last_error = "blend_paths: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (B == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  QueryOut o(S, out_flags);
+  const double *dq, *dlen;
+  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
+      (rc = blend_run(S, dq, (const int*)dlen, B, T, v_max, a_max, *p, out_traj ? n_rows : 0, out_traj, out_vel, out_duration, out_info, out_corner,
+                      out_corner_info, out_piece, o)))
     return rc;
   return o.finish();   // (the caller's arrays have been read)
 }
