@@ -33,6 +33,7 @@
 #include "../loik_amd_retime.h"
 #include "../loik_amd_blend.h"
 #include "../loik_amd_plan.h"
+#include "../loik_amd_grid.h"
 
 #include <array>
 #include <map>
@@ -598,6 +599,42 @@ public:
     loikb_clearance_params p{0.0, 0};
     if (!loikb_clearance_get_multistart(h_, &p)) return false;
     if (margin) *margin = p.margin;
+    return true;
+  }
+  // ---- voxel worlds (include/loik_amd_grid.h): an occupancy grid as one more world object beside the spheres and boxes.  occupancy
+  // [nz][ny][nx] (nonzero = occupied), dims = (nx, ny, nz), origin the low corner of voxel (0, 0, 0), voxel the edge.  The distance field
+  // is built on the device before the call returns; Clearance, the collision-aware multi-start and the motion layer read it.
+  // ClearCollisionGrid: as if never set
+  void SetCollisionGrid(const std::vector<unsigned char>& occupancy, const std::array<int, 3>& dims, const std::array<double, 3>& origin, double voxel)
+  {
+    if (occupancy.empty() || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0 ||
+        occupancy.size() != (std::size_t)dims[0] * (std::size_t)dims[1] * (std::size_t)dims[2])
+      throw std::runtime_error("loik_amd: need nx * ny * nz > 0 occupancy bytes");
+    check(loikb_collision_set_world_grid(h_, occupancy.data(), dims.data(), origin.data(), voxel, 0));
+  }
+  void ClearCollisionGrid() { check(loikb_collision_set_world_grid(h_, nullptr, nullptr, nullptr, 0.0, 0)); }
+  struct CollisionGrid {
+    std::array<int, 3> dims{{0, 0, 0}};          // nx, ny, nz
+    std::array<double, 3> origin{{0.0, 0.0, 0.0}};
+    double voxel = 0.0;
+    std::vector<unsigned int> G;                 // [nz][ny][nx]: (voxel / 2) sqrt(G) is the distance of a voxel's centre to the occupied cubes,
+                                                 // LOIKB_GRID_EMPTY where nothing is occupied; empty with field = false
+  };
+  // whether a grid is set; with out, what was set and (field = true) the distance field
+  bool GetCollisionGrid(CollisionGrid* out = nullptr, bool field = true) const
+  {
+    CollisionGrid g;
+    const int rc = loikb_collision_get_world_grid(h_, g.dims.data(), g.origin.data(), &g.voxel, nullptr, 0);
+    if (rc < 0) check(rc);
+    if (rc == 0) return false;
+    if (out) {
+      if (field) {
+        g.G.resize((std::size_t)g.dims[0] * (std::size_t)g.dims[1] * (std::size_t)g.dims[2]);
+        const int rc2 = loikb_collision_get_world_grid(h_, nullptr, nullptr, nullptr, g.G.data(), 0);
+        if (rc2 < 0) check(rc2);
+      }
+      *out = std::move(g);
+    }
     return true;
   }
   // ---- motions (include/loik_amd_motion.h).  Difference: v [n][nv] with q0 (+) v = q1 under Integrate's arithmetic

@@ -215,6 +215,12 @@ BLEND_SYMBOLS = ["loikb_blend_version", "loikb_blend_paths"]
 BLEND_TRUNCATED, BLEND_INVALID, BLEND_SKIPPED = 1, 2, 4
 BLEND_TAKEN, BLEND_BLOCKED, BLEND_UNDECIDED, BLEND_COUPLED, BLEND_ZERO_LEG, BLEND_OFF = range(6)
 
+# include/loik_amd_grid.h: voxel worlds, an occupancy grid as a world object; its own header and version
+GRID_ABI_VERSION = 1
+GRID_SYMBOLS = ["loikb_grid_version", "loikb_collision_set_world_grid", "loikb_collision_get_world_grid"]
+CLR_WORLD_GRID = 4
+GRID_MAX_DIM, GRID_MAX_VOXELS, GRID_EMPTY = 512, 1 << 26, 0xFFFFFFFF
+
 
 class PoseParams(C.Structure):
     _fields_ = [("dt", C.c_double), ("gain", C.c_double), ("tol_pose", C.c_double), ("max_steps", C.c_int), ("flags", C.c_int)]
@@ -382,6 +388,8 @@ def lib():
                                    C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_blend_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.POINTER(BlendParams), C.c_int,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_collision_set_world_grid.argtypes = [C.c_void_p, C.c_void_p, _ip, _dp, C.c_double, C.c_int]
+    L.loikb_collision_get_world_grid.argtypes = [C.c_void_p, _ip, _dp, _dp, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1211,6 +1219,53 @@ class BatchedLoik:
             return out
         mins, wit = new
         return dict(min=mins[:, 0].copy(), min_world=mins[:, 1].copy(), min_self=mins[:, 2].copy(), witness=wit)
+
+    # ---- voxel worlds (include/loik_amd_grid.h) ---------------------------------------------------------------------
+    def set_collision_grid(self, occupancy, origin=None, voxel=None):
+        """the voxel world every instance shares (loikb_collision_set_world_grid): occupancy [nz][ny][nx] of any integer or bool dtype
+        (nonzero = occupied) on the host, or a uint8 device tensor of that shape; origin [3] the world position of the low corner of
+        voxel (0, 0, 0); voxel the edge.  The distance field is built on the device before the call returns; clearance, the
+        collision-aware multi-start and the motion layer read it beside the world of set_collision_world.  None clears the grid."""
+        if occupancy is None:
+            _check(self.L.loikb_collision_set_world_grid(self.h, None, None, None, 0.0, 0))
+            return
+        if origin is None or voxel is None:
+            raise ValueError("set_collision_grid: an occupancy needs origin and voxel")
+        if hasattr(occupancy, "data_ptr") and getattr(occupancy, "is_cuda", False):
+            if getattr(occupancy, "element_size", lambda: 1)() != 1:
+                raise ValueError("set_collision_grid: a device occupancy must be uint8")
+            if hasattr(occupancy, "is_contiguous") and not occupancy.is_contiguous():
+                raise ValueError("set_collision_grid: a device occupancy must be contiguous")
+            shape, keep, ptr, flags = tuple(int(d) for d in occupancy.shape), occupancy, C.c_void_p(occupancy.data_ptr()), IN_DEVICE
+        else:
+            keep = np.ascontiguousarray(np.asarray(occupancy.numpy() if hasattr(occupancy, "numpy") else occupancy) != 0, dtype=np.uint8)
+            shape, ptr, flags = keep.shape, keep.ctypes.data_as(C.c_void_p), 0
+        if len(shape) != 3:
+            raise ValueError("set_collision_grid: occupancy must be [nz][ny][nx]")
+        dims = np.array([shape[2], shape[1], shape[0]], dtype=np.int32)
+        org = _f64(origin).reshape(3)
+        _check(self.L.loikb_collision_set_world_grid(self.h, ptr, dims.ctypes.data_as(_ip), org.ctypes.data_as(_dp), float(voxel), flags))
+
+    def collision_grid(self, field=True):
+        """dict(dims (nx, ny, nz), origin [3], voxel, G uint32 [nz][ny][nx]) of the grid that is set (loikb_collision_get_world_grid), None
+        when none is.  (voxel / 2) sqrt(G) is the distance from a voxel's centre to the occupied cubes, GRID_EMPTY where nothing is
+        occupied.  field=False leaves G out and copies nothing."""
+        dims = np.zeros(3, dtype=np.int32)
+        org = np.zeros(3)
+        h = C.c_double()
+        rc = self.L.loikb_collision_get_world_grid(self.h, dims.ctypes.data_as(_ip), org.ctypes.data_as(_dp), C.byref(h), None, 0)
+        if rc < 0:
+            _check(rc)
+        if rc == 0:
+            return None
+        out = dict(dims=(int(dims[0]), int(dims[1]), int(dims[2])), origin=org, voxel=h.value)
+        if field:
+            G = np.empty((int(dims[2]), int(dims[1]), int(dims[0])), dtype=np.uint32)
+            rc = self.L.loikb_collision_get_world_grid(self.h, None, None, None, G.ctypes.data_as(C.c_void_p), 0)
+            if rc < 0:
+                _check(rc)
+            out["G"] = G
+        return out
 
     # ---- collision avoidance (include/loik_amd_avoid.h) -------------------------------------------------------------
     def set_collision_avoidance(self, d_safe, d_influence, kappa=0.5):

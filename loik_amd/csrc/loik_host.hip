@@ -27,6 +27,7 @@
 #include "loik_pose_step.hpp"
 #include "loik_pose_jacobian.hpp"
 #include "loik_pose_collision.hpp"
+#include "loik_pose_grid.hpp"
 #include "loik_pose_motion.hpp"
 #include "loik_pose_shortcut.hpp"
 #include "loik_pose_retime.hpp"
@@ -62,6 +63,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_retime.h"
 #include "../../include/loik_amd_blend.h"
 #include "../../include/loik_amd_plan.h"
+#include "../../include/loik_amd_grid.h"
 
 #include <algorithm>
 #include <atomic>
@@ -455,6 +457,13 @@ struct loikb_solver_impl {
       DevBuf<double> d_place;            // [n][ncar][12] k_link_placements' output for k_clearance<true>, grown on demand
       DevBuf<double> d_mslab;            // one slab of Lambda, liM and carrier records per resident wavefront of k_motion_clearance<true>
                                          // (loik_amd_motion.h), grown on demand
+      // the voxel world (loik_amd_grid.h): G of the grid that is set, and the buffer the next set builds in (the two change places when
+      // a build has succeeded, so that a failed set leaves the grid as it was and a set at sensor rate allocates nothing)
+      bool have_grid = false;
+      int gn[3] = {0, 0, 0};
+      double go[3] = {0.0, 0.0, 0.0}, gh = 0.0;
+      DevBuf<unsigned int> d_grid, d_grid_next;   // [nz][ny][nx]
+      DevBuf<unsigned char> d_occ;                // the staged occupancy of a host caller
       bool have_ms = false;              // loikb_clearance_set_multistart set `ms`
       loikb_clearance_params ms = {0.0, 0};
     } col;

@@ -984,7 +984,8 @@ static std::vector<unsigned short> col_build_pairs(const loikb_solver_impl* S, c
 }
 
 // the ordinal of a pair is 32 bits with one value kept for "none"
-static bool col_ordinals_fit(size_t ns, size_t nws, size_t nwb, size_t npairs) { return ns * (nws + nwb) + npairs < (size_t)0x7fffffff; }
+// (a grid is one more world object: a pair per sphere)
+static bool col_ordinals_fit(size_t ns, size_t nws, size_t nwb, bool grid, size_t npairs) { return ns * (nws + nwb + (grid ? 1 : 0)) + npairs < (size_t)0x7fffffff; }
 
 int loikb_collision_set_spheres(loikb_solver* S, const int* links, const double* spheres, int ns)
 {
@@ -1013,7 +1014,7 @@ int loikb_collision_set_spheres(loikb_solver* S, const int* links, const double*
   }
   std::vector<unsigned short> pairs;
   if (ns > 0 && C.self_on) pairs = col_build_pairs(S, lk, C.ignore);
-  if (!col_ordinals_fit(ns, C.nws, C.nwb, pairs.size() / 2)) { g_last_error = "collision_set_spheres: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  if (!col_ordinals_fit(ns, C.nws, C.nwb, C.have_grid, pairs.size() / 2)) { g_last_error = "collision_set_spheres: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
   DevBuf<double> d_sph;
   DevBuf<int> d_scar, d_car;
   DevBuf<unsigned short> d_pairs;
@@ -1049,7 +1050,7 @@ int loikb_collision_set_world(loikb_solver* S, const double* wspheres, int nws, 
       if (!(W[k] > 0.0)) { g_last_error = what + ": a half extent is not > 0"; return LOIKB_ERR_ARG; }
   }
   Collision& C = S->pose.col;
-  if (!col_ordinals_fit(C.ns, nws, nwb, C.pairs.size() / 2)) { g_last_error = "collision_set_world: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  if (!col_ordinals_fit(C.ns, nws, nwb, C.have_grid, C.pairs.size() / 2)) { g_last_error = "collision_set_world: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
   HIPCHK(hipSetDevice(S->device));
   DevBuf<double> d_wsph, d_wbox;
   int rc;
@@ -1078,7 +1079,7 @@ int loikb_collision_set_self_pairs(loikb_solver* S, int enable, const int* ignor
     ignore.assign(ignore_links, ignore_links + 2 * (size_t)ni);
     pairs = col_build_pairs(S, C.links, ignore);
   }
-  if (!col_ordinals_fit(C.ns, C.nws, C.nwb, pairs.size() / 2)) { g_last_error = "collision_set_self_pairs: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  if (!col_ordinals_fit(C.ns, C.nws, C.nwb, C.have_grid, pairs.size() / 2)) { g_last_error = "collision_set_self_pairs: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
   DevBuf<unsigned short> d_pairs;
   int rc;
   if ((rc = col_upload(S, pairs.data(), sizeof(unsigned short) * pairs.size(), d_pairs))) return rc;
@@ -1092,13 +1093,125 @@ int loikb_collision_set_self_pairs(loikb_solver* S, int enable, const int* ignor
 
 int loikb_collision_num_self_pairs(const loikb_solver* S) { return S ? (int)(S->pose.col.pairs.size() / 2) : 0; }
 
+// ---- include/loik_amd_grid.h (kernels in loik_pose_grid.hpp) ---------------------------------------------------------------------
+int loikb_grid_version(void) { return LOIKB_GRID_VERSION; }
+
+static_assert(GRID_MAX_DIM == LOIKB_GRID_MAX_DIM && GRID_MAX_VOXELS == LOIKB_GRID_MAX_VOXELS && GRID_EMPTY == LOIKB_GRID_EMPTY &&
+              CLR_WORLD_GRID == LOIKB_CLR_WORLD_GRID, "the kernels' constants and the header's");
+static_assert((size_t)GRID_MAX_DIM / 2 * 64 * sizeof(unsigned int) <= 65536 && (size_t)GRID_MAX_DIM * 32 * sizeof(unsigned int) <= 65536,
+              "a tile of k_grid_pass fits 64 KB at either width");
+
+// the high corner of the grid's box along one axis: the product rounded, then the sum (loik_amd_grid.h)
+static double grid_hi(double origin, int n, double h)
+{
+  const volatile double e = (double)n * h;   // (volatile: the two operations stay two, whatever the compiler may contract)
+  return origin + e;
+}
+
+int loikb_collision_set_world_grid(loikb_solver* S, const unsigned char* occ, const int* dims, const double* origin, double h, int in_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  Collision& C = S->pose.col;
+  if (!occ) {   // clear: the buffers stay for the next grid
+    HIPCHK(hipSetDevice(S->device));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    C.have_grid = false;
+    return LOIKB_OK;
+  }
+  if (!dims || !origin) { g_last_error = "collision_set_world_grid: need dims and origin with an occupancy"; return LOIKB_ERR_ARG; }
+  if (in_flags & ~LOIKB_IN_DEVICE) { g_last_error = "collision_set_world_grid: in_flags other than LOIKB_IN_DEVICE"; return LOIKB_ERR_ARG; }
+  size_t nvox = 1;
+  for (int k = 0; k < 3; ++k) {
+    if (dims[k] < 1 || dims[k] > LOIKB_GRID_MAX_DIM) {
+      g_last_error = "collision_set_world_grid: a dimension outside 1 .. LOIKB_GRID_MAX_DIM = " + std::to_string(LOIKB_GRID_MAX_DIM);
+      return LOIKB_ERR_ARG;
+    }
+    nvox *= (size_t)dims[k];
+  }
+  if (nvox > GRID_MAX_VOXELS) { g_last_error = "collision_set_world_grid: more than LOIKB_GRID_MAX_VOXELS = 2^26 voxels"; return LOIKB_ERR_ARG; }
+  if (!std::isfinite(h) || !(h > 0.0) || !std::isfinite(1.0 / h)) {
+    g_last_error = "collision_set_world_grid: need a finite voxel edge h > 0 with a finite inverse";
+    return LOIKB_ERR_ARG;
+  }
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(origin[k]) || !std::isfinite(grid_hi(origin[k], dims[k], h))) {
+      g_last_error = "collision_set_world_grid: the origin or a corner of the grid's box is not finite";
+      return LOIKB_ERR_ARG;
+    }
+  if (!col_ordinals_fit(C.ns, C.nws, C.nwb, true, C.pairs.size() / 2)) { g_last_error = "collision_set_world_grid: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  if (S->pose.avoid.have) {
+    g_last_error = "collision_set_world_grid: collision avoidance is set on the handle (loikb_avoid_set), and avoidance cannot read a voxel grid -- clear it first";
+    return LOIKB_ERR_STATE;
+  }
+  HIPCHK(hipSetDevice(S->device));
+  const int nx = dims[0], ny = dims[1], nz = dims[2];
+  const unsigned char* d_occ = occ;
+  if (!(in_flags & LOIKB_IN_DEVICE)) {
+    BUFCHK(C.d_occ.regrow(nvox));
+    HIPCHK(hipMemcpyAsync(C.d_occ, occ, nvox, hipMemcpyHostToDevice, S->stream));
+    d_occ = C.d_occ;
+  }
+  BUFCHK(C.d_grid_next.regrow(sizeof(unsigned int) * nvox));   // (nothing queued reads it: it is not the grid that is set)
+  unsigned int* G = C.d_grid_next;
+  const long long nlines = (long long)ny * nz;
+  const int per = grid_x_lines(nx);
+  hipLaunchKernelGGL(k_grid_x, dim3((unsigned)((nlines + per - 1) / per)), dim3(GRID_THREADS), 0, S->stream, d_occ, G, nx, nlines);
+  HIPCHK(hipGetLastError());
+  if (ny > 1) {   // (an axis of one voxel: the pass is the identity)
+    const int W = grid_tile_width(ny);
+    hipLaunchKernelGGL(k_grid_pass, dim3((unsigned)((nx + W - 1) / W), (unsigned)nz), dim3(GRID_THREADS), sizeof(unsigned int) * (size_t)ny * W, S->stream,
+                       G, ny, nx, (size_t)nx, (size_t)nx * ny, W);
+    HIPCHK(hipGetLastError());
+  }
+  if (nz > 1) {
+    const int W = grid_tile_width(nz);
+    hipLaunchKernelGGL(k_grid_pass, dim3((unsigned)((nx + W - 1) / W), (unsigned)ny), dim3(GRID_THREADS), sizeof(unsigned int) * (size_t)nz * W, S->stream,
+                       G, nz, nx, (size_t)nx * ny, (size_t)nx, W);
+    HIPCHK(hipGetLastError());
+  }
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's occ has been read; nothing queued reads the grid that goes)
+  C.d_grid.swap(C.d_grid_next);
+  for (int k = 0; k < 3; ++k) { C.gn[k] = dims[k]; C.go[k] = origin[k]; }
+  C.gh = h;
+  C.have_grid = true;
+  return LOIKB_OK;
+}
+
+int loikb_collision_get_world_grid(loikb_solver* S, int* dims, double* origin, double* h, unsigned int* G, int out_flags)
+{
+  if (!S) return 0;
+  if (out_flags & ~LOIKB_OUT_DEVICE) { g_last_error = "collision_get_world_grid: out_flags other than LOIKB_OUT_DEVICE"; return LOIKB_ERR_ARG; }
+  if (!S->pose.col.have_grid) return 0;
+  const Collision& C = S->pose.col;
+  for (int k = 0; k < 3; ++k) {
+    if (dims) dims[k] = C.gn[k];
+    if (origin) origin[k] = C.go[k];
+  }
+  if (h) *h = C.gh;
+  if (G) {
+    HIPCHK(hipSetDevice(S->device));
+    const size_t bytes = sizeof(unsigned int) * (size_t)C.gn[0] * C.gn[1] * C.gn[2];
+    HIPCHK(hipMemcpyAsync(G, (const unsigned int*)C.d_grid, bytes, (out_flags & LOIKB_OUT_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, S->stream));
+    HIPCHK(hipStreamSynchronize(S->stream));
+  }
+  return 1;
+}
+
 // the handle's collision model as every kernel that reads it takes it
 static ClrModel clr_model(const loikb_solver_impl* S)
 {
   const Collision& C = S->pose.col;
   int lp = 0;
   while (lp < 6 && (1 << lp) < C.ns) ++lp;
-  return ClrModel{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, (int)C.car.size(), C.nws, C.nwb, (int)(C.pairs.size() / 2), lp};
+  ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, (int)C.car.size(), C.nws, C.nwb, (int)(C.pairs.size() / 2), lp,
+             ClrGrid{nullptr, {0, 0, 0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 0.0, 0.0}};
+  if (C.have_grid) {
+    m.g.G = C.d_grid;
+    for (int k = 0; k < 3; ++k) { m.g.n[k] = C.gn[k]; m.g.o[k] = C.go[k]; m.g.hi[k] = grid_hi(C.go[k], C.gn[k], C.gh); }
+    m.g.h = C.gh;
+    m.g.inv_h = 1.0 / C.gh;
+  }
+  return m;
 }
 
 // One clearance launch over n rows of the device array dq [n][nq] into d_min [n][3] and d_wit [n][3] (or nullptr).  Queued.
@@ -1181,6 +1294,10 @@ static int avoid_check_model(const loikb_solver_impl* S, const char* fn)
   const Collision& C = S->pose.col;
   const std::string f(fn);
   if (C.ns == 0) { g_last_error = f + ": no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+  if (C.have_grid) {
+    g_last_error = f + ": a voxel grid is set (loikb_collision_set_world_grid), and its clearance bound has no gradient for avoidance to follow -- clear the grid first";
+    return LOIKB_ERR_STATE;
+  }
   if (C.ns > LOIKB_AVOID_MAX_SPHERES) {
     g_last_error = f + ": " + std::to_string(C.ns) + " spheres set, more than LOIKB_AVOID_MAX_SPHERES = " + std::to_string(LOIKB_AVOID_MAX_SPHERES);
     return LOIKB_ERR_STATE;

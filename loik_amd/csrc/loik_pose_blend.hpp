@@ -86,7 +86,8 @@ __device__ __forceinline__ MotionAdv blend_advance(const double* q_row, const do
                                                    double* lam, double* xf, double* cp, int lane)
 {
   const double inf = __longlong_as_double(0x7ff0000000000000ll);
-  const unsigned int nps = (unsigned int)m.ns * (unsigned int)m.nws, npb = (unsigned int)m.ns * (unsigned int)m.nwb;
+  const ClrOrdinals no(m);
+  const unsigned int nps = no.nps, self0 = no.self0();
   const int lp = m.lp, P = 1 << lp, S = 64 >> lp;
   const double block_below = prm.margin + prm.tol;
 
@@ -120,7 +121,7 @@ __device__ __forceinline__ MotionAdv blend_advance(const double* q_row, const do
 
   double u_cur = 0.0, min_s = inf, u_min = 0.0;
   unsigned int min_ord = CLR_NO_ORDINAL;
-  int status = MOTION_UNDECIDED, evals = 0;
+  int status = MOTION_UNDECIDED, evals = 0, min_vox = -1;
   for (int k = 0; k < prm.max_evals; ++k) {
     __syncthreads();   // (Lambda is written; the last sample's readers of xf, cp and cen are done)
     // 1. liM of every joint at q(u)
@@ -176,6 +177,12 @@ __device__ __forceinline__ MotionAdv blend_advance(const double* q_row, const do
         if (clr_before(v, ord, best, bord)) { best = v; bord = ord; }
         if (la > 0.0) delta = fmin(delta, (v - prm.margin) / la);
       }
+      if (m.g.G && (lane >> lp) == 0) {
+        const double v = clr_sphere_grid(c[0], c[1], c[2], c[3], m.g).v;
+        const unsigned int ord = no.grid0() + (unsigned int)a;
+        if (clr_before(v, ord, best, bord)) { best = v; bord = ord; }
+        if (la > 0.0) delta = fmin(delta, (v - prm.margin) / la);
+      }
     }
     for (unsigned int i = lane; i < (unsigned int)m.npairs; i += 64) {
       const int a = m.pairs[2 * (size_t)i], b = m.pairs[2 * (size_t)i + 1];
@@ -184,7 +191,7 @@ __device__ __forceinline__ MotionAdv blend_advance(const double* q_row, const do
       const double e0 = c[0] - d[0], e1 = c[1] - d[1], e2 = c[2] - d[2];
       const double v = sqrt(e0 * e0 + e1 * e1 + e2 * e2) - c[3] - d[3];
       const double lab = lam[a] + lam[b];
-      if (clr_before(v, nps + npb + i, best, bord)) { best = v; bord = nps + npb + i; }
+      if (clr_before(v, self0 + i, best, bord)) { best = v; bord = self0 + i; }
       if (lab > 0.0) delta = fmin(delta, (v - prm.margin) / lab);
     }
     // 4. the butterfly: every lane ends with the same (best, bord, delta)
@@ -195,13 +202,13 @@ __device__ __forceinline__ MotionAdv blend_advance(const double* q_row, const do
       delta = fmin(delta, od);
     }
     evals = k + 1;
-    if (k == 0 || best < min_s) { min_s = best; u_min = u_cur; min_ord = bord; }
+    if (k == 0 || best < min_s) { min_s = best; u_min = u_cur; min_ord = bord; min_vox = clr_grid_voxel(bord, no, m, cen); }
     if (best < block_below) { status = MOTION_BLOCKED; break; }
     if (u_cur == 1.0) { status = MOTION_FREE; break; }
     if (k + 1 == prm.max_evals) break;   // UNDECIDED at this sample
     u_cur = fmin(u_cur + delta, 1.0);
   }
-  return MotionAdv{u_cur, min_s, u_min, min_ord, status, evals};
+  return MotionAdv{u_cur, min_s, u_min, min_ord, status, evals, min_vox};
 }
 
 // q_path [B][T][nq], len [B] or nullptr; lim [2][nb] = v_max, a_max -> out_traj [B][S][nq] or nullptr (timing only), out_vel [B][S][nb] or
@@ -232,7 +239,7 @@ k_blend_paths(const double* __restrict__ q_path, const int* __restrict__ len, in
   const int S = out_traj ? prm.S : 0;
   const int NC = T - 2, NP = 2 * T - 3;
   const MotionPrm mprm{prm.margin, prm.tol, prm.max_evals};
-  const unsigned int nps = (unsigned int)m.ns * (unsigned int)m.nws, npb = (unsigned int)m.ns * (unsigned int)m.nwb;
+  const ClrOrdinals no(m);
 
   for (long long b = blockIdx.x; b < B; b += gridDim.x) {   // (64 bits: b + gridDim.x may pass 2^31)
     const int n = len ? len[b] : T;
@@ -313,6 +320,7 @@ k_blend_paths(const double* __restrict__ q_path, const int* __restrict__ len, in
       int status = BLEND_OFF, tries = 0, evals = 0;
       double l_take = 0.0, r_in = 0.0, r_out = 0.0, w = 0.0, min_s = 0.0;
       unsigned int min_ord = CLR_NO_ORDINAL;
+      int min_vox = -1;
       if (prm.max_tries > 0) {
         if (!(n0 > 0.0) || !(n1 > 0.0)) status = BLEND_ZERO_LEG;
         else {
@@ -336,7 +344,7 @@ k_blend_paths(const double* __restrict__ q_path, const int* __restrict__ len, in
               const MotionAdv adv = blend_advance(qk, pc, pc + nb, jd, idx_q, nb, m, mprm, cen, lam, xf, cp, lane);
               tries = i + 1;
               evals += adv.evals;
-              min_s = adv.min_sampled; min_ord = adv.min_ord;
+              min_s = adv.min_sampled; min_ord = adv.min_ord; min_vox = adv.min_vox;
               status = adv.status == MOTION_FREE ? BLEND_TAKEN : adv.status == MOTION_BLOCKED ? BLEND_BLOCKED : BLEND_UNDECIDED;
               if (status == BLEND_TAKEN) { l_take = l; r_in = ri; r_out = ro; break; }
             }
@@ -361,19 +369,9 @@ k_blend_paths(const double* __restrict__ q_path, const int* __restrict__ len, in
         double* r = co + (size_t)5 * (k - 1);
         r[0] = l_take; r[1] = r_in; r[2] = r_out; r[3] = w; r[4] = min_s;
         if (oci) {
-          int kind = CLR_NONE, wa = -1, wb = -1;
-          if (min_ord != CLR_NO_ORDINAL) {
-            if (min_ord < nps) { kind = CLR_WORLD_SPHERE; wa = (int)(min_ord / (unsigned int)m.nws); wb = (int)(min_ord - (unsigned int)wa * (unsigned int)m.nws); }
-            else if (min_ord < nps + npb) {
-              const unsigned int r2 = min_ord - nps;
-              kind = CLR_WORLD_BOX; wa = (int)(r2 / (unsigned int)m.nwb); wb = (int)(r2 - (unsigned int)wa * (unsigned int)m.nwb);
-            } else {
-              const size_t r2 = min_ord - nps - npb;
-              kind = CLR_SELF; wa = m.pairs[2 * r2]; wb = m.pairs[2 * r2 + 1];
-            }
-          }
           int* o = oci + (size_t)6 * (k - 1);
-          o[0] = status; o[1] = tries; o[2] = evals; o[3] = kind; o[4] = wa; o[5] = wb;
+          o[0] = status; o[1] = tries; o[2] = evals;
+          clr_witness(min_ord, min_vox, no, m, o + 3);
         }
       }
     }

@@ -12,8 +12,9 @@
 //                               per sample, steps 1 to 4 of k_clearance on q(s):
 //                               1. a lane per device joint integrates its own coordinates (advance_q_joint) and builds liM;
 //                               2. a lane per carrier composes its world placement, a lane per sphere writes its centre;
-//                               3. the world pairs and the self pairs, each lane keeping its best (clearance, ordinal) and its
-//                                  least (v - margin) / lambda_pair;
+//                               3. the world pairs (with a grid set the sphere's voxel too: clr_sphere_grid, whose value never
+//                                  exceeds the true clearance, so the step below stays valid) and the self pairs, each lane keeping
+//                                  its best (clearance, ordinal) and its least (v - margin) / lambda_pair;
 //                               4. one wave64 butterfly carries the ordered minimum and delta; every lane decides alike.
 //                             The centres [ns][4] are in LDS.  Lambda [ns], liM [nb][12] and the carriers' oMi [ncar][12] sit
 //                             beside them when all of it fits 64 KB; SLAB = true takes those three from a handle-owned global
@@ -113,18 +114,22 @@ struct MotionAdv {
   double s_free, min_sampled, s_at_min;
   unsigned int min_ord;   // the ordinal of min_sampled, CLR_NO_ORDINAL over an empty set of pairs
   int status, evals;
+  int min_vox;            // clr_grid_voxel of min_ord at the sample of min_sampled
 };
 
 // The advancement of one segment q(s) = q_row (+) s d_row by the 64 lanes of one wavefront that is a workgroup of its own, from the motion
 // bound to the status: the body of k_motion_clearance, shared with k_shortcut_paths (loik_pose_shortcut.hpp).  q_row [nq] and d_row
 // [nb] are finite and written before the call (the first barrier below orders d_row when the wavefront itself wrote it); cen [ns][4]
 // is LDS, lam [ns], xf [nb][12] and cp [ncar][12] LDS or the wavefront's slab.  Every lane takes the same way through every branch
+// GRID_CALL: the grid pair behind a call (clr_sphere_grid_call) instead of in line; the values are the same
+template <bool GRID_CALL = false>
 __device__ __forceinline__ MotionAdv motion_advance(const double* q_row, const double* d_row, const JointDesc* __restrict__ jd,
                                                     const int* __restrict__ idx_q, int nb, const ClrModel& m, const MotionPrm& prm, double* cen,
                                                     double* lam, double* xf, double* cp, int lane)
 {
   const double inf = __longlong_as_double(0x7ff0000000000000ll);
-  const unsigned int nps = (unsigned int)m.ns * (unsigned int)m.nws, npb = (unsigned int)m.ns * (unsigned int)m.nwb;
+  const ClrOrdinals no(m);
+  const unsigned int nps = no.nps, self0 = no.self0();
   const int lp = m.lp, P = 1 << lp, S = 64 >> lp;
   const double block_below = prm.margin + prm.tol;
 
@@ -179,7 +184,7 @@ __device__ __forceinline__ MotionAdv motion_advance(const double* q_row, const d
 
   double s_cur = 0.0, min_s = inf, s_min = 0.0;
   unsigned int min_ord = CLR_NO_ORDINAL;
-  int status = MOTION_UNDECIDED, evals = 0;
+  int status = MOTION_UNDECIDED, evals = 0, min_vox = -1;
   for (int k = 0; k < prm.max_evals; ++k) {
     __syncthreads();   // (Lambda is written; the last sample's readers of xf, cp and cen are done)
     // 1. liM of every joint at q(s)
@@ -234,6 +239,12 @@ __device__ __forceinline__ MotionAdv motion_advance(const double* q_row, const d
         if (clr_before(v, ord, best, bord)) { best = v; bord = ord; }
         if (la > 0.0) delta = fmin(delta, (v - prm.margin) / la);
       }
+      if (m.g.G && (lane >> lp) == 0) {
+        const double v = (GRID_CALL ? clr_sphere_grid_call(c[0], c[1], c[2], c[3], m.g) : clr_sphere_grid(c[0], c[1], c[2], c[3], m.g)).v;
+        const unsigned int ord = no.grid0() + (unsigned int)a;
+        if (clr_before(v, ord, best, bord)) { best = v; bord = ord; }
+        if (la > 0.0) delta = fmin(delta, (v - prm.margin) / la);
+      }
     }
     for (unsigned int i = lane; i < (unsigned int)m.npairs; i += 64) {
       const int a = m.pairs[2 * (size_t)i], b = m.pairs[2 * (size_t)i + 1];
@@ -242,7 +253,7 @@ __device__ __forceinline__ MotionAdv motion_advance(const double* q_row, const d
       const double e0 = c[0] - d[0], e1 = c[1] - d[1], e2 = c[2] - d[2];
       const double v = sqrt(e0 * e0 + e1 * e1 + e2 * e2) - c[3] - d[3];
       const double lab = lam[a] + lam[b];
-      if (clr_before(v, nps + npb + i, best, bord)) { best = v; bord = nps + npb + i; }
+      if (clr_before(v, self0 + i, best, bord)) { best = v; bord = self0 + i; }
       if (lab > 0.0) delta = fmin(delta, (v - prm.margin) / lab);
     }
     // 4. the butterfly: every lane ends with the same (best, bord, delta)
@@ -253,13 +264,13 @@ __device__ __forceinline__ MotionAdv motion_advance(const double* q_row, const d
       delta = fmin(delta, od);
     }
     evals = k + 1;
-    if (k == 0 || best < min_s) { min_s = best; s_min = s_cur; min_ord = bord; }
+    if (k == 0 || best < min_s) { min_s = best; s_min = s_cur; min_ord = bord; min_vox = clr_grid_voxel(bord, no, m, cen); }
     if (best < block_below) { status = MOTION_BLOCKED; break; }
     if (s_cur == 1.0) { status = MOTION_FREE; break; }
     if (k + 1 == prm.max_evals) break;   // UNDECIDED at this sample
     s_cur = fmin(s_cur + delta, 1.0);
   }
-  return MotionAdv{s_cur, min_s, s_min, min_ord, status, evals};
+  return MotionAdv{s_cur, min_s, s_min, min_ord, status, evals, min_vox};
 }
 
 // out_val [n][3] = (s_free, min_sampled, s_at_min); out_info [n][5] = (status, evals, kind, a, b).  qa rows by motion_row(i, T),
@@ -277,7 +288,7 @@ k_motion_clearance(const double* __restrict__ qa, const double* __restrict__ dv,
   double* xf = lam + m.ns;
   double* cp = xf + (size_t)12 * nb;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  const unsigned int nps = (unsigned int)m.ns * (unsigned int)m.nws, npb = (unsigned int)m.ns * (unsigned int)m.nwb;
+  const ClrOrdinals no(m);
 
   for (long long seg = blockIdx.x; seg < n; seg += gridDim.x) {   // (64 bits: seg + gridDim.x may pass 2^31)
     const double* q_row = qa + motion_row((int)seg, T) * nq;
@@ -300,19 +311,8 @@ k_motion_clearance(const double* __restrict__ qa, const double* __restrict__ dv,
     double* ov = out_val + (size_t)seg * 3;
     int* oi = out_info + (size_t)seg * 5;
     ov[0] = adv.s_free; ov[1] = adv.min_sampled; ov[2] = adv.s_at_min;
-    int kind = CLR_NONE, wa = -1, wb = -1;
-    const unsigned int min_ord = adv.min_ord;
-    if (min_ord != CLR_NO_ORDINAL) {
-      if (min_ord < nps) { kind = CLR_WORLD_SPHERE; wa = (int)(min_ord / (unsigned int)m.nws); wb = (int)(min_ord - (unsigned int)wa * (unsigned int)m.nws); }
-      else if (min_ord < nps + npb) {
-        const unsigned int r = min_ord - nps;
-        kind = CLR_WORLD_BOX; wa = (int)(r / (unsigned int)m.nwb); wb = (int)(r - (unsigned int)wa * (unsigned int)m.nwb);
-      } else {
-        const size_t r = min_ord - nps - npb;
-        kind = CLR_SELF; wa = m.pairs[2 * r]; wb = m.pairs[2 * r + 1];
-      }
-    }
-    oi[0] = adv.status; oi[1] = adv.evals; oi[2] = kind; oi[3] = wa; oi[4] = wb;
+    oi[0] = adv.status; oi[1] = adv.evals;
+    clr_witness(adv.min_ord, adv.min_vox, no, m, oi + 2);
   }
 }
 

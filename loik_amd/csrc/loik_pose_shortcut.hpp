@@ -168,7 +168,10 @@ k_shortcut_paths(const double* __restrict__ q_path, const int* __restrict__ len,
       }
       if (!ok) { ++invalid; continue; }
       // 3. the certified check of k_motion_clearance
-      const MotionAdv adv = motion_advance(qa, dvr, jd, idx_q, nb, m, mprm, cen, lam, xf, cp, lane);
+      // (the grid pair behind a call in the LDS instantiation only: with it in line the ROCm 7.2 compiler's register allocator crashes on that
+      //  kernel, and on no other.  Nothing about the slab asks for it: profiles/grid_measured.md)
+      constexpr bool GRID_CALL = !SLAB;
+      const MotionAdv adv = motion_advance<GRID_CALL>(qa, dvr, jd, idx_q, nb, m, mprm, cen, lam, xf, cp, lane);
       if (adv.status == MOTION_BLOCKED) { ++blocked; continue; }
       if (adv.status != MOTION_FREE) { ++undecided; continue; }
       // 4. the splice: keep[k - cut] = keep[k] for k = j .. L - 1, in chunks of 64 from the low end (a chunk's writes land below its
