@@ -8,6 +8,7 @@ import math
 import numpy as np
 
 import clearance_numpy as CN
+import grid_numpy as GN
 import motion_numpy as MN
 import pose_numpy as P
 import retime_numpy as RN
@@ -91,11 +92,18 @@ def curve_bound(model, qk, P0, P2, links, spheres):
     return out
 
 
-def advance_curves(model, qk, P0, P2, links, spheres, ws, wb, pairs, margin, tol, max_evals):
+def advance_curves(model, qk, P0, P2, links, spheres, ws, wb, pairs, margin, tol, max_evals, grid=None):
     """the advancement of loik_amd_motion.h on the curves q_k[i] (+) w_i(u), in lock step.  Returns dict(status (MN.FREE / BLOCKED /
-    UNDECIDED), evals, min_sampled, witness [n][3], near [n], samples = per curve the list of (u, min))"""
+    UNDECIDED), evals, min_sampled, witness [n][3], near [n], samples = per curve the list of (u, min)).  grid: a grid_numpy.Grid; the
+    table is then grid_numpy's, a witness of kind 4 names the voxel read at the sample of the minimum, and a centre within
+    grid_numpy.FACE of a voxel face at some sample sets near"""
     n, ns = qk.shape[0], spheres.shape[0]
-    names = MN.pair_names(ns, ws.shape[0], wb.shape[0], pairs)
+    if grid is None:
+        names = MN.pair_names(ns, ws.shape[0], wb.shape[0], pairs)
+        table = lambda cen: (MN.pair_values(cen, spheres[:, 3], ws, wb, pairs), None)
+    else:
+        names = GN.pair_names(ns, ws.shape[0], wb.shape[0], grid, pairs)
+        table = lambda cen: GN.pair_values(cen, spheres[:, 3], ws, wb, grid, pairs)
     out = dict(status=np.full(n, MN.UNDECIDED, dtype=np.int32), evals=np.zeros(n, dtype=np.int32), min_sampled=np.full(n, np.inf),
                witness=np.tile(np.array(_NO_WITNESS, dtype=np.int32), (n, 1)), near=np.zeros(n, dtype=bool), samples=[[] for _ in range(n)])
     lam_pair = np.zeros((n, names.shape[0]))
@@ -110,17 +118,20 @@ def advance_curves(model, qk, P0, P2, links, spheres, ws, wb, pairs, margin, tol
         if run.size == 0:
             break
         q = np.stack([curve_point(model, qk[i], P0[i], P2[i], u[i]) for i in run])
-        V = MN.pair_values(MN.centres(model, q, links, spheres), spheres[:, 3], ws, wb, pairs)
+        cen = MN.centres(model, q, links, spheres)
+        V, vox = table(cen)
         still = []
         for r, i in enumerate(run):
             v = V[r]
+            if grid is not None:
+                out["near"][i] |= bool(GN.near_face(cen[r], grid))
             o = int(np.argmin(v)) if v.size else -1
             m = float(v[o]) if o >= 0 else np.inf
             out["evals"][i] = k + 1
             out["samples"][i].append((float(u[i]), m))
             if k == 0 or m < out["min_sampled"][i]:
                 out["min_sampled"][i] = m
-                out["witness"][i] = names[o] if o >= 0 else _NO_WITNESS
+                out["witness"][i] = GN._name(names, o, None if vox is None else vox[r])
             out["near"][i] |= abs(m - margin - tol) <= NEAR
             if m < margin + tol:
                 out["status"][i] = MN.BLOCKED
@@ -208,8 +219,8 @@ def piece_at(model, rows, dvs, rec, tau):
 
 
 def blend(model, q_path, links, spheres, wspheres, wboxes, pairs, v_max, a_max, dt, reach, margin=0.0, tol=1e-3, max_evals=256, max_tries=4,
-          n_waypoints=None, S=None):
-    """the rule for q_path [B][T][nq].  S None: timing only.  Returns dict(n_samples, n_waypoints, taken, flags [B], duration [B], corner
+          n_waypoints=None, S=None, grid=None):
+    """the rule for q_path [B][T][nq].  S None: timing only.  grid: a grid_numpy.Grid, whose pairs then join the check of a curve.  Returns dict(n_samples, n_waypoints, taken, flags [B], duration [B], corner
     [B][T-2][5], corner_info [B][T-2][6], piece [B][2T-3][4], near [B][T-2] = a decision of the corner's tries lay within NEAR of its
     threshold, w_max [B][T-2] = the rate limits before the passes, records = per path the list of its piece records, dv = per path its
     differences, and with S q_traj [B][S][nq], v_traj [B][S][nv])"""
@@ -275,7 +286,7 @@ def blend(model, q_path, links, spheres, wspheres, wboxes, pairs, v_max, a_max, 
             ri, ro = l / nrm[k - 1], l / nrm[k]
             geo.append((l, ri, ro, -ri * dvs[k - 1], ro * dvs[k]))
         res = advance_curves(model, np.stack([seg[b][0][k] for b, k, _ in pend]), np.stack([g[3] for g in geo]), np.stack([g[4] for g in geo]),
-                             links, spheres, ws, wb, pairs, margin, tol, max_evals)
+                             links, spheres, ws, wb, pairs, margin, tol, max_evals, grid)
         still = []
         for j, (b, k, base) in enumerate(pend):
             info, cor = out["corner_info"][b, k - 1], out["corner"][b, k - 1]

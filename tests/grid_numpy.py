@@ -12,6 +12,7 @@ import motion_numpy as MN
 
 WORLD_GRID = 4
 EMPTY = 0xFFFFFFFF
+FACE = MN.NEAR   # a centre this close (in voxels) to a voxel face may read the voxel on its other side on the device
 
 
 class Grid:
@@ -74,6 +75,27 @@ def sphere_grid(c, r, grid):
         v = np.where(dout > 0, np.sqrt(dout * dout + mp * mp), m) - r
     vox = (i[..., 2] * grid.n[1] + i[..., 1]) * grid.n[0] + i[..., 0]
     return v, vox
+
+
+def near_face(c, grid):
+    """[...]: some centre of c [..., ns, 3] has a component whose clamped value, measured in voxels from the origin, lies within FACE of
+    an integer k with 0 < k < n: a face between two voxels, where a rounding difference reads the other voxel and the pair jumps.  The
+    two faces of the grid's box (k = 0 and k = n, where every clamped component of a centre outside the box lies) are no such place: the
+    index is clamped to 0 and to n - 1 on both sides of them"""
+    c = np.asarray(c, dtype=float)
+    with np.errstate(invalid="ignore"):
+        t = (np.minimum(np.maximum(c, grid.origin), grid.hi) - grid.origin) * grid.inv_h
+        k = np.rint(t)
+        hit = (np.abs(t - k) <= FACE) & (k > 0) & (k < grid.n)
+    return hit.any(axis=(-1, -2))
+
+
+def advance_of(grid):
+    """the advancement that shortcut_numpy and plan_numpy call: motion_numpy.advance without a grid, advance (below) with one, under
+    motion_numpy.advance's signature"""
+    if grid is None:
+        return MN.advance
+    return lambda model, qa, dv, links, spheres, wspheres=(), wboxes=(), pairs=(), **kw: advance(model, qa, dv, links, spheres, wspheres, wboxes, grid, pairs, **kw)
 
 
 def cubes(grid):
@@ -156,7 +178,7 @@ def clearance(model, q, links, spheres, wspheres=(), wboxes=(), grid=None, pairs
 
 def advance(model, qa, dv, links, spheres, wspheres=(), wboxes=(), grid=None, pairs=(), margin=0.0, tol=1e-3, max_evals=256):
     """motion_numpy.advance with the grid pairs in the table: the same loop, decision for decision.  Returns dict(status [n], evals [n],
-    s_free [n], min_sampled [n], s_at_min [n], witness [n][3], near [n], samples)"""
+    s_free [n], min_sampled [n], s_at_min [n], witness [n][3], near [n] (motion_numpy.advance's, or near_face at some sample), samples)"""
     qa, dv = np.atleast_2d(np.asarray(qa, dtype=float)), np.atleast_2d(np.asarray(dv, dtype=float))
     spheres = np.asarray(spheres, dtype=float).reshape(-1, 4)
     ws, wb = np.asarray(wspheres, dtype=float).reshape(-1, 4), np.asarray(wboxes, dtype=float).reshape(-1, 15)
@@ -177,7 +199,10 @@ def advance(model, qa, dv, links, spheres, wspheres=(), wboxes=(), grid=None, pa
         s = 0.0
         for k in range(max_evals):
             q = MN.interpolate(model, qa[i], dv[i], s)[None]
-            V, vox = pair_values(MN.centres(model, q, links, spheres), spheres[:, 3], ws, wb, grid, pairs)
+            cen = MN.centres(model, q, links, spheres)
+            V, vox = pair_values(cen, spheres[:, 3], ws, wb, grid, pairs)
+            if grid is not None:
+                out["near"][i] |= bool(near_face(cen[0], grid))
             v = V[0]
             o = int(np.argmin(v)) if v.size else -1
             m = float(v[o]) if o >= 0 else np.inf

@@ -7,6 +7,7 @@ queries of a batch side by side, so that one batched advancement serves the pend
 as alone.  test_plan_numpy.py proves the rule's claims without a GPU."""
 import numpy as np
 
+import grid_numpy as GN
 import motion_numpy as MN
 import pose_limits_numpy as PL
 import pose_multistart_numpy as MS
@@ -132,8 +133,8 @@ def _query(model, b, q_start, q_goal, s_lo, s_hi, T, step, max_iters, max_nodes,
 
 
 def plan(model, q_start, q_goal, links, spheres, s_lo, s_hi, T, wspheres=(), wboxes=(), pairs=(), step=0.5, max_iters=256, max_nodes=256, seed=0,
-         margin=0.0, tol=1e-3, max_evals=256):
-    """the rule for q_start, q_goal [B][nq].  Returns dict(q_path [B][T][nq], status, n_waypoints, iterations [B], nodes [B][2],
+         margin=0.0, tol=1e-3, max_evals=256, grid=None):
+    """the rule for q_start, q_goal [B][nq]; grid: a grid_numpy.Grid, whose pairs then join the check of an edge (grid_numpy.advance).  Returns dict(q_path [B][T][nq], status, n_waypoints, iterations [B], nodes [B][2],
     edges_checked, edges_free, evals [B], length [B], near [B] = some decision of the query lay within motion_numpy.NEAR of its threshold,
     edges = per query the list of (from, to, status) checked, in order)"""
     import shortcut_numpy as SN
@@ -154,7 +155,7 @@ def plan(model, q_start, q_goal, links, spheres, s_lo, s_hi, T, wspheres=(), wbo
         order = sorted(pending)
         qa = np.stack([pending[b][0] for b in order])
         dv = np.stack([diff(model, *pending[b]) for b in order])
-        res = MN.advance(model, qa, dv, links, spheres, wspheres, wboxes, pairs, margin=margin, tol=tol, max_evals=max_evals)
+        res = GN.advance_of(grid)(model, qa, dv, links, spheres, wspheres, wboxes, pairs, margin=margin, tol=tol, max_evals=max_evals)
         for i, b in enumerate(order):
             one = {k: res[k][i] for k in ("status", "s_free", "evals", "near")}
             one["from"], one["to"] = pending.pop(b)

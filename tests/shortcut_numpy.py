@@ -6,6 +6,7 @@ word(r, b, 1) mod (L - 2 - i); the segment q[keep[i]] (+) s difference(q[keep[i]
 keep[i + 1 .. j - 1].  test_shortcut_numpy.py proves the rule's claims without a GPU."""
 import numpy as np
 
+import grid_numpy as GN
 import motion_numpy as MN
 import pose_multistart_numpy as MS
 
@@ -41,8 +42,8 @@ def _length(model, rows):
 
 
 def shortcut(model, q_path, links, spheres, wspheres=(), wboxes=(), pairs=(), n_waypoints=None, rounds=64, seed=0, margin=0.0, tol=1e-3,
-             max_evals=256):
-    """the rule for q_path [B][T][nq].  Returns dict(keep [B][T] (-1 after the kept indices), n_waypoints, tried, accepted, blocked,
+             max_evals=256, grid=None):
+    """the rule for q_path [B][T][nq]; grid: a grid_numpy.Grid, whose pairs then join the check (grid_numpy.advance).  Returns dict(keep [B][T] (-1 after the kept indices), n_waypoints, tried, accepted, blocked,
     undecided, invalid [B], length_in, length_out [B], q_path [B][T][nq] (the kept rows, the last one repeated), near [B] = some tried
     segment's advance(...)["near"] was set, segments = per path the list of (row i, row j, status) tried).  A path with a count outside
     2 .. T is skipped: counters 0, keep -1, NaN rows and lengths"""
@@ -65,7 +66,7 @@ def shortcut(model, q_path, links, spheres, wspheres=(), wboxes=(), pairs=(), n_
             break
         qa = np.stack([q_path[b, keeps[b][i]] for b, i, j in draws])
         qb = np.stack([q_path[b, keeps[b][j]] for b, i, j in draws])
-        res = MN.advance(model, qa, MN.difference(model, qa, qb), links, spheres, wspheres, wboxes, pairs, margin=margin, tol=tol, max_evals=max_evals)
+        res = GN.advance_of(grid)(model, qa, MN.difference(model, qa, qb), links, spheres, wspheres, wboxes, pairs, margin=margin, tol=tol, max_evals=max_evals)
         for k, (b, i, j) in enumerate(draws):
             st, keep = int(res["status"][k]), keeps[b]
             out["tried"][b] += 1

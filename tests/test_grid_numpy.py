@@ -107,3 +107,111 @@ def test_the_tables_put_the_grid_between_boxes_and_self_pairs():
     assert names[:, 0].tolist() == [CN.WORLD_SPHERE] * 6 + [CN.WORLD_BOX] * 3 + [GN.WORLD_GRID] * 3 + [CN.SELF]
     assert names[9:12, 1].tolist() == [0, 1, 2]
     assert GN.pair_names(3, 2, 1, None, [(0, 2)]).shape[0] == 10
+
+
+# ---- the references of the motion layer with a grid (shortcut_numpy, plan_numpy, blend_numpy: grid=) -------------------------------------
+def test_the_face_predicate_flags_inner_faces_only():
+    grid = GN.Grid(np.zeros((4, 4, 4)), (-0.25, 0.5, -1.0), 0.25)
+    o, h = grid.origin, grid.h
+    at = lambda *p: (o + h * np.array(p))[None]
+    assert GN.near_face(at(1.0, 1.5, 2.5), grid) and GN.near_face(at(0.5, 3.0, 0.5), grid) and GN.near_face(at(1.5, 2.5, 1.0 + 0.5e-9), grid)
+    assert not GN.near_face(at(1.5, 2.5, 1.0 + 1e-8), grid) and not GN.near_face(at(0.5, 0.5, 0.5), grid)
+    # the faces of the box and every centre clamped onto them: the index is 0 or n - 1 whatever the rounding
+    assert not GN.near_face(at(0.0, 0.5, 0.5), grid) and not GN.near_face(at(4.0, 0.5, 4.0), grid) and not GN.near_face(at(-3.0, 9.0, 0.5), grid)
+    assert GN.near_face(at(-3.0, 9.0, 2.0), grid)
+    # [..., ns, 3]: one flag per configuration
+    both = np.stack([np.concatenate([at(0.5, 0.5, 0.5), at(1.0, 0.5, 0.5)]), np.concatenate([at(0.5, 0.5, 0.5), at(0.5, 0.5, 0.5)])])
+    assert GN.near_face(both, grid).tolist() == [True, False]
+
+
+def test_grid_none_is_the_reference_without_a_grid(monkeypatch):
+    """on the inputs of test_shortcut_numpy, test_plan_numpy and test_blend_numpy: grid=None returns what the call without the keyword
+    returns, key by key and bit by bit, and reaches none of grid_numpy's tables"""
+    import blend_numpy as BN
+    import plan_numpy as PN
+    import shortcut_numpy as SN
+    import test_blend_numpy as TB
+    import test_plan_numpy as TP
+    import test_shortcut as TS
+
+    def same(a, b, what):
+        assert a.keys() == b.keys(), what
+        for k in a:
+            if isinstance(a[k], np.ndarray):
+                assert np.array_equal(a[k], b[k], equal_nan=a[k].dtype.kind == "f"), (what, k)
+            else:
+                assert repr(a[k]) == repr(b[k]), (what, k)
+
+    def never(*a, **kw):
+        raise AssertionError("grid_numpy's tables reached without a grid")
+    for fn in ("advance", "pair_values", "pair_names", "near_face", "sphere_grid"):
+        monkeypatch.setattr(GN, fn, never)
+    for name in ("panda7", "multidof13"):
+        c = TS.shortcut_case(name)
+        same(SN.shortcut(c["model"], c["paths"], c["links"], c["spheres"], c["ws"], c["wb"], c["pairs"], grid=None, **c["kw"]), c["want"], "shortcut " + name)
+    for name in ("panda7", "talos32"):
+        c = TP.plan_case(name)
+        same(PN.plan(c["model"], c["start"], c["goal"], c["links"], c["spheres"], c["lo"], c["hi"], TP.T_PLAN, c["ws"], c["wb"], c["pairs"], grid=None, **c["kw"]),
+             c["want"], "plan " + name)
+    for name in ("panda7", "multidof13"):
+        c = TB.blend_case(name)
+        args = (c["model"], c["paths"], c["links"], c["spheres"], c["ws"], c["wb"], c["pairs"], c["v_max"], c["a_max"])
+        same(BN.blend(*args, S=TB.S_ROWS, grid=None, **c["kw"]), c["want"], "blend " + name)
+    # advance_curves on its own, positionally as blend calls it
+    c = TB.blend_case("panda7")
+    model, paths = c["model"], c["paths"]
+    dv = BN.differences(model, paths[0])
+    a = (model, paths[0, 1:3], -0.2 * dv[0:2], 0.2 * dv[1:3], c["links"], c["spheres"], c["ws"], c["wb"], c["pairs"], c["margin"], TB.TOL, TB.MAX_EVALS)
+    same(BN.advance_curves(*a, grid=None), BN.advance_curves(*a), "advance_curves")
+
+
+@pytest.mark.parametrize("name", ["panda7-clear", "panda7"])
+def test_what_the_references_certify_is_clear_of_the_geometry(name):
+    """panda7 among three spheres, two boxes, its self pairs and a grid: every segment that grid_numpy.advance, shortcut_numpy and
+    plan_numpy call FREE and every blend that blend_numpy calls TAKEN, at 257 points, keeps the margin against the spheres, the boxes
+    and the union of the occupied cubes themselves (grid_numpy.exact_clearance, motion_numpy.clearance_min): the references are tied
+    to the geometry, not to one another.
+
+    panda7-clear: spheres that do not overlap, a margin above zero; the exact clearance is the signed one.  panda7: the sphere model of
+    the GPU tests, whose overlapping self pairs put the margin at -0.10, below -r of every sphere.  There a FREE segment may pass through
+    an occupied cube, and does: the pair is <= -r inside one and says nothing about the depth (loik_amd_grid.h), so what FREE bounds
+    against the cubes is the distance to them, zero inside, less r -- not the depth.  (Segment 64 of grid_cases.motion_case("panda7") has a
+    sphere of radius 0.0796 whose centre lies 0.0272 deep in a cube: signed clearance -0.1069 under the margin -0.1041, distance-based
+    clearance -0.0796 above it.)"""
+    import blend_numpy as BN
+    import grid_cases as GC
+    import motion_numpy as MN
+    import plan_numpy as PN
+    ss = np.linspace(0.0, 1.0, 257)
+    depth = name == GC.CLEAR
+
+    def clear(c, q, what):
+        assert (c["margin"] >= 0.0) == depth
+        worst = float(GC.exact_clearance_at(c, q, depth=depth).min())
+        assert worst >= c["margin"], (what, worst, c["margin"])
+        return worst - c["margin"]
+    seen = {}
+    c = GC.motion_case(name)
+    model = c["model"]
+    free = np.flatnonzero(c["want"]["status"] == MN.FREE)
+    slack = [clear(c, MN.interpolate_many(model, c["qa"][i], c["dv"][i], ss), ("segment", i)) for i in free]
+    seen["segments"] = (free.size, min(slack))
+    c = GC.shortcut_case(name)
+    ok = [(b, i, j) for (b, i, j), st in zip(c["tried"], c["tried_want"]["status"]) if st == MN.FREE]
+    slack = [clear(c, MN.interpolate_many(model, c["paths"][b, i], MN.difference(model, c["paths"][b, i], c["paths"][b, j])[0], ss), ("shortcut", b, i, j))
+             for b, i, j in ok]
+    seen["shortcuts"] = (len(ok), min(slack))
+    c = GC.plan_case(name)
+    ok = [(x, y) for b in range(c["B"]) for x, y, st in c["want"]["edges"][b] if st == MN.FREE]
+    slack = [clear(c, MN.interpolate_many(model, x, PN.diff(model, x, y), ss), ("edge", k)) for k, (x, y) in enumerate(ok)]
+    seen["edges"] = (len(ok), min(slack))
+    c = GC.blend_case(name)
+    want = c["want"]
+    taken = np.argwhere(want["corner_info"][:, :, 0] == BN.TAKEN)
+    slack = []
+    for b, k in taken:
+        P0, P2 = want["controls"][(int(b), int(k) + 1)]
+        slack.append(clear(c, np.stack([BN.curve_point(model, c["paths"][b, k + 1], P0, P2, u) for u in ss]), ("blend", b, k)))
+    seen["blends"] = (len(taken), min(slack))
+    print("grid_numpy certificates %s (count, least exact clearance - margin): %s" % (name, seen))
+    assert all(n > 0 for n, _ in seen.values()), seen
