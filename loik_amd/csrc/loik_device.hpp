@@ -128,6 +128,8 @@ enum : int {
                          // IkIdData::Reset(false) / ResetRecursion): the flat engine does not fetch those pairs
   MODE_FLAT_PREP = 64,   // k_fslots of this launch left a prepared record of every listed instance (loik_flat_prep.hpp): k_flat2 takes
                          // fresh instances from it
+  MODE_VIRTUAL_RESET = 128,  // k_fslots only: the solve's ResetRecursion + ResetSolver was not launched (loikb_solve); the prepared record
+                             // takes what that reset would have written as constants, not from the tiles (flat_prep_fetch)
 };
 
 

@@ -82,7 +82,13 @@ __device__ __forceinline__ void flat_prep_fetch(FlatPrepIn<T>& in, bool has_inst
     in.nus = ldp<T>(rec, JP_NUS);
     if (!(P.mode & MODE_BND_SHARED)) in.lu = ldp<T>(rec, JP_LBUB);
   }
-  if (jlane < PRS_N) {
+  // MODE_VIRTUAL_RESET: the tiles have not seen this solve's reset_tile(RS_RECURSION | RS_SOLVER).  What it would have written -- the
+  // scalar record but bnorm (SP_BI's low half) and SP_TAG, and the constraints' y and A^T y -- is taken as the constants it writes:
+  // mu = mu0, everything else +0.  What it keeps (nu, S^T f + w, bnorm, the tag, b, A, the box) is loaded as ever.
+  const bool virt = (P.mode & MODE_VIRTUAL_RESET) != 0;
+  if (virt && jlane < PRS_N && jlane != PRS_BNORM && jlane != PRS_TGIN) {
+    in.sc = jlane == PRS_MU ? P.mu0 : T(0);
+  } else if (jlane < PRS_N) {
     const char* srec = ip + (size_t)L.off_s * pair_bytes<T>();
     // (pair, half) of entry `jlane` of PR_SC
     const int sc_i = jlane == 3 ? SC_TOL_PRIMAL : jlane == 4 ? SC_TOL_DUAL : jlane == 5 ? SC_DELTA_Y_QP : jlane == 6 ? SC_AT_DELTA_Y_QP
@@ -98,7 +104,7 @@ __device__ __forceinline__ void flat_prep_fetch(FlatPrepIn<T>& in, bool has_inst
   for (int c = 0; c < PREP_NC; ++c) {
     if (c >= L.nc) break;
     const char* crec = ip + (size_t)(L.off_c + c * L.crec) * pair_bytes<T>();
-    if (jlane < 18) {
+    if (jlane < (virt ? 6 : 18)) {   // (virtual reset: b only)
       const int which = jlane / 6, k = jlane % 6;
       const int pair = which == 0 ? CP_B : which == 1 ? CP_Y : CP_ATY;
       in.cv[c] = *reinterpret_cast<const T*>(crec + (size_t)(pair + k / 2) * pair_bytes<T>() + (k & 1) * sizeof(T));

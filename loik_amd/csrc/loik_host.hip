@@ -143,6 +143,9 @@ struct Tuning {
                                 // launches in arrival order of >= 32 768 instances, see flat_slice_for / run_tail)
   bool flat_prep = true;        // LOIKB_FLAT_PREP=0: k_flat2 sets every fresh instance up from the tile records itself; default: from the prepared record
                                 //   k_fslots leaves (loik_flat_prep.hpp) wherever the handle has the buffer
+  bool flat_seq = true;         // LOIKB_FLAT_SEQ=0: the flat engine's long sequence as it was -- k_reset in Solve(), k_list_iota + memset + k_ring_fill in front
+                                //   of the engine, k_list_unfinished + memset + k_order_count behind it (default: no reset pass where the prepared records
+                                //   make it unnecessary -- virtual_reset_route --, k_queue_init in front, k_finish_order behind)
   bool flat_zero_state = true;  // LOIKB_FLAT_ZERO_STATE=0: k_flat2 / k_flat1 fetch vis, fis, g, w, z of every instance even straight after a cold reset
   int flat_order_holdoff = 4;   // LOIKB_FLAT_ORDER_HOLDOFF=n: solves in arrival order after an ordered launch that was not shorter (0: never hold off)
   bool flat_order = true;       // LOIKB_FLAT_ORDER=0: the flat engine takes its instances in arrival order even when the handle's previous
@@ -177,6 +180,7 @@ struct Tuning {
     if (const char* e = getenv("LOIKB_FLAT_ORDER")) flat_order = atoi(e) != 0;
     if (const char* e = getenv("LOIKB_FLAT_ZERO_STATE")) flat_zero_state = atoi(e) != 0;
     if (const char* e = getenv("LOIKB_FLAT_PREP")) flat_prep = atoi(e) != 0;
+    if (const char* e = getenv("LOIKB_FLAT_SEQ")) flat_seq = atoi(e) != 0;
     if (const char* e = getenv("LOIKB_FLAT_ORDER_HOLDOFF")) flat_order_holdoff = std::max(0, atoi(e));
     geti("LOIKB_TAIL_WAVES", tail_waves); tail_waves = std::max(1, std::min(TAIL_WAVES, tail_waves));
     geti("LOIKB_LEAN_DECADES", lean_decades); lean_decades = std::max(1, std::min(15, lean_decades));   // (15: a parked instance's ring entry says "no slot" with decade code 15 -- ADVICE r05)
@@ -373,6 +377,8 @@ struct loikb_solver_impl {
   // pass-level debug path (loik_passes.hpp): the data object of the reference, field by field, per instance
   bool pass_active = false;
   bool zero_state = false;   // the solve in progress began with a reset that zeroed vis, fis, g, w, z of every instance
+  int reset_pending = 0;     // loikb_solve only: the reset_home flags of the solve's opening reset while it has not been launched (virtual_reset_route);
+                             //   launch_flat consumes it, every other engine launches it first (flush_pending_reset); 0 outside loikb_solve
   // Anything that changes what a solve computes (SolveInit, a tailored solve's q / constraint, UpdateEqConstraint, UpdateReferences,
   // Add / RemoveEqConstraint, integrate, the setters) bumps this.  A handle's later solves are taken longest first by the previous
   // solve's iteration counts only when those counts were taken on THESE inputs (a cold Solve() of the same problem is
@@ -1186,6 +1192,17 @@ int reset_home(loikb_solver_impl* S, int what, bool with_queue = false)
   });
   HIPCHK(hipGetLastError());
   return LOIKB_OK;
+}
+
+// The opening reset loikb_solve noted instead of launching (loikb_solver_impl::reset_pending), launched now: whoever is about to read
+// the tiles without the prepared records calls this first.  Nothing between loikb_solve and the engines reads or writes what the reset
+// touches, so the late launch leaves the tiles as the early one would have.
+int flush_pending_reset(loikb_solver_impl* S)
+{
+  const int what = S->reset_pending;
+  if (!what) return LOIKB_OK;   // (the chunk threads of a multi-chunk solve all ask, and only read: a reset is pending on one-chunk handles only)
+  S->reset_pending = 0;
+  return reset_home(S, what);
 }
 
 // make `src` (host or device, `bytes`) readable by a kernel: returns a device pointer
@@ -2100,6 +2117,38 @@ static bool bushy_goes_on_chip(const loikb_solver_impl* S)
   return direct_tail_of(S, S->B, std::max(1, batch_tail_max(S)));
 }
 
+// The prepared records (loik_flat_prep.hpp), as far as the handle decides: k_flat2 with a decade table (not OSQP's rule), no SolverInfo
+// lists, a block that fits, and the chunk has the buffer for its n instances.  launch_flat adds what only the launch knows (the list is
+// the whole set, the table has a decade).
+static bool flat_prep_route(const loikb_solver_impl* S, const Chunk* C, int n)
+{
+  return flat_kind(S) == FlatKind::Flat2 && S->tune.flat_prep && !flat_any_mu(S) && !S->opt.logging && flat_prep_fits(S) &&
+         C->d_prep && (size_t)n * flat_prep_stride(S->nc) * sizeof(double) <= C->d_prep.bytes();
+}
+
+// THE test of the virtual reset: a plain Solve() whose one chunk goes, whole, through run_chunk's direct_tail and run_tail's long
+// sequence to launch_flat, and there takes every instance from a prepared record under MODE_ZERO_STATE.  loikb_solve asks it before it
+// leaves the reset out, launch_flat asks it again before it lets k_fslots stand in for the reset; whatever lies between them and every
+// other engine calls flush_pending_reset, so a solve that this test admits and that ends up elsewhere is reset for real, only later.
+//
+// Why nobody misses the pass: reset_tile(RS_RECURSION | RS_SOLVER) writes JP_V .. JP_WZ of every joint, CP_Y / CP_ATY of every constraint,
+// SP_MU, SP_BI's iteration count, SP_ST, SP_FLIP and SP_SCAL ...  Between the reset and the engine's store only flat_prep_fetch reads any
+// of them, and under MODE_VIRTUAL_RESET it takes the constants instead.  store_instance (loik_flat2.hpp) then writes JP_V .. JP_WZ, CP_Y /
+// CP_ATY, SP_MU, SP_TAG, SP_BI, SP_FLIP and SP_ST of every listed instance unconditionally -- parked and resumed, escaped to k_tail or
+// finished alike -- but the SP_SCAL pairs only of an instance that has iterated at least once in the launch.  A fresh instance (status 0,
+// iteration 0, mu0's decade) iterates unless max_iter < 2 stops it at the load or its first decade is neither in the table nor built
+// in-wave: those two cases are excluded here and in launch_flat (decade0), and keep the real reset.
+static bool virtual_reset_route(const loikb_solver_impl* S)
+{
+  if (!S->tune.flat_seq || S->chunks.size() != 1 || S->f32 || S->opt.logging || S->opt.max_iter < 2) return false;
+  if (S->opt.mu_update_strat != LOIKB_MU_DEFAULT) return false;   // (OSQP: no prepared records; MAXEIGENVALUE: start_mu writes the tiles)
+  if (!S->tune.flat_zero_state || !flat_applicable(S) || (S->opt.flags & LOIKB_OPT_NO_H_CACHE)) return false;
+  if (!S->plan.solve_ok && !bushy_goes_on_chip(S)) return false;   // (k_pass_solve)
+  if (!direct_tail_of(S, S->B, std::max(1, batch_tail_max(S)))) return false;   // (the streaming engine first)
+  if (S->B <= S->tune.flat_small_batch || S->B < std::max(1, S->tune.flat_min_batch)) return false;   // (the short sequence; k_tail)
+  return flat_prep_route(S, &S->chunks[0], S->B);
+}
+
 // ---- the on-chip engines: k_fslots + k_flat2 / k_flat1 / k_flat (launch_flat), else k_hslots + k_lean (launch_lean), and k_tail for what
 // they leave (launch_tail_kernel).  run_tail below prepares the list and drives them.
 // What the engines of one run_tail share.  An engine that leaves instances unfinished moves `list` / `n` on to them.
@@ -2113,6 +2162,7 @@ struct TailCtx {
   const int* list; int n;       // the instances still iterating
   double total_ms = 0.0;
   unsigned long long iters = 0;
+  bool list_pending = false;    // run_tail left the whole set's list to launch_flat's k_queue_init (the long sequence, LOIKB_FLAT_SEQ)
 };
 
 // ---- longest first: the bookkeeping the three engines share.  A whole-set launch takes the set in the order the handle's previous solve
@@ -2125,12 +2175,13 @@ struct OrderUse { bool ordered = false, was_stale = false; };
 // Takes up the previous solve's order when the launch is `eligible` (it takes the same whole set) and the order is usable; counts the
 // hold-off down when `count_down` (the flat engine: every launch; k_lean: whole-set launches; k_tail: launches that also leave an order).
 // The decade slots are indexed by the INSTANCE slot, so k_fslots / k_hslots and the engine find them under any order of the list.
-static int take_up_order(const loikb_solver_impl* S, Chunk* C, bool eligible, bool count_down, int n_cur, OrderUse* use)
+// copy = false: the caller's k_queue_init reads d_order itself.
+static int take_up_order(const loikb_solver_impl* S, Chunk* C, bool eligible, bool count_down, int n_cur, OrderUse* use, bool copy = true)
 {
   use->ordered = eligible && order_usable(S, C, n_cur);
   use->was_stale = use->ordered && C->order_epoch != S->inputs_epoch;
   if (count_down && C->order_holdoff > 0) --C->order_holdoff;
-  if (use->ordered) HIPCHK(hipMemcpyAsync(C->d_slots, C->d_order, sizeof(int) * (size_t)n_cur, hipMemcpyDeviceToDevice, C->stream));
+  if (use->ordered && copy) HIPCHK(hipMemcpyAsync(C->d_slots, C->d_order, sizeof(int) * (size_t)n_cur, hipMemcpyDeviceToDevice, C->stream));
   C->stats.flat_ordered += use->ordered ? 1 : 0;
   return LOIKB_OK;
 }
@@ -2138,12 +2189,15 @@ static int take_up_order(const loikb_solver_impl* S, Chunk* C, bool eligible, bo
 // The order for the handle's next solve: longest first by the iteration counts of this one (k_order_*, loik_lean.hpp; an instance that
 // escaped to k_tail counts with what it had when it left).  flat_engine: k_order_count also takes the histogram of the decades the
 // instances ended in (the next sliced launch's table window), and the launch's counters go to the host between count and scan.
+// counted: the flat engine's k_finish_order has filled the bins and the histogram already.
 template <typename T>
-static int leave_order(const loikb_solver_impl* S, Chunk* C, const loikb_solver_impl::Set& A, int n_cur, bool flat_engine)
+static int leave_order(const loikb_solver_impl* S, Chunk* C, const loikb_solver_impl::Set& A, int n_cur, bool flat_engine, bool counted = false)
 {
-  HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
-  hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins,
-                     flat_engine ? C->d_counters + ORDER_DEC_HIST : (unsigned int*)nullptr);
+  if (!counted) {
+    HIPCHK(hipMemsetAsync(C->d_order_bins, 0, sizeof(unsigned int) * 2 * ORDER_BINS, C->stream));
+    hipLaunchKernelGGL(k_order_count<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins,
+                       flat_engine ? C->d_counters + ORDER_DEC_HIST : (unsigned int*)nullptr);
+  }
   if (flat_engine) HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
   hipLaunchKernelGGL(k_order_scan, dim3(1), dim3(ORDER_BINS), 0, C->stream, C->d_order_bins);
   hipLaunchKernelGGL(k_order_scatter<T>, grid1(n_cur), dim3(256), 0, C->stream, A.tiles, S->L, n_cur, S->opt.max_iter, C->d_order_bins, C->d_order);
@@ -2182,6 +2236,7 @@ struct FlatLaunch {
   int ndec, kexp_lo, dw0, nw;   // the table's range, the window of it k_fslots builds now
   int slice;                    // flat_launch_slice
   bool prep;                    // k_fslots leaves prepared records, k_flat2 takes fresh instances from them (loik_flat_prep.hpp)
+  bool virt;                    // ... and the records stand in for the solve's opening reset, which was not launched (virtual_reset_route)
   double cu_sh; dim3 grid;      // the chunk's share of the CUs, the iteration kernel's grid
 };
 
@@ -2299,7 +2354,7 @@ static int launch_flat_kernel(TailCtx<T>& X, FlatLaunch& F)
 
 // what the finished launch reported (the counters are on the host): the handle's history, the statistics, the instances left for k_tail
 template <typename T>
-static int flat_read_back(TailCtx<T>& X, const FlatLaunch& F, OrderUse use, bool order_pass, bool small_finish, bool queue_ready, int* next)
+static int flat_read_back(TailCtx<T>& X, const FlatLaunch& F, OrderUse use, bool order_pass, bool small_finish, bool queue_ready, int* next, bool fused_queue)
 {
   loikb_solver_impl* S = X.S; Chunk* C = X.C;
   const int n_first = X.n, n_cur = X.n_cur;
@@ -2332,13 +2387,15 @@ static int flat_read_back(TailCtx<T>& X, const FlatLaunch& F, OrderUse use, bool
   }
   C->stats.hslots_ms += hms;
   if (C->h_counters[FLAT_COUNTERS_DRY])  // (100 MHz clock, low words: from the ring fill of the last stage to the first empty fetch)
-    C->stats.queue_dry_ms += (double)(unsigned int)(C->h_counters[FLAT_COUNTERS_TDRY] - C->h_counters[FLAT_COUNTERS_T0]) * 1e-5;
+    C->stats.queue_dry_ms += (double)(unsigned int)(C->h_counters[FLAT_COUNTERS_TDRY] - C->h_counters[FLAT_COUNTERS_T0]) * 1e-5
+                             - (fused_queue ? (double)hms : 0.0);   // (k_queue_init took the clock in front of k_fslots: the events' figure for k_fslots comes off)
   if (one_per_wave(F.kind) && X.whole_set && n_first == n_cur) judge_order(S, C, n_cur, use, (double)ms - (double)hms);
   if (S->tune.trace)
     fprintf(stderr, "[loikb] flat engine: %6d instances on %u workgroups, done at %8.3f ms (slots %6.3f ms)  "
                     "inst-iters %9u  wave-iters %7u  slot loads %7u (+ %u served from LDS)  escaped %u  still iterating %u%s\n",
             n_first, F.grid.x, ms, hms, C->h_counters[1], C->h_counters[5], C->h_counters[6],
-            C->h_counters[FLAT_COUNTERS_SLOT_HITS], escaped, C->h_counters[3], F.prep ? "  fresh instances from prepared records" : "");
+            C->h_counters[FLAT_COUNTERS_SLOT_HITS], escaped, C->h_counters[3],
+            F.virt ? "  fresh instances from prepared records, no reset pass" : F.prep ? "  fresh instances from prepared records" : "");
   C->stats.lean_escaped += (int)escaped;
   C->tail_iv.emplace_back(t0, t0 + ms);
   X.total_ms = ms; X.n = (int)C->h_counters[3]; X.list = next;
@@ -2373,12 +2430,20 @@ static int launch_flat(TailCtx<T>& X)
   // (queue_ready: this solve's reset launch left list, ring and counters -- nothing lies between the solve's first event and this point)
   const bool queue_ready = small_flat && C->queue_ready && n_cur == S->B;
   C->queue_ready = false;
-  if (!queue_ready && small_flat) hipLaunchKernelGGL(k_queue_init_iota, grid1(std::max(C->ring_cap, NCOUNTERS)), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, C->d_slots, n_cur, C->d_counters, NCOUNTERS);
+  // (the long sequence, LOIKB_FLAT_SEQ: list -- in the order of the handle's previous solve, if that is taken up --, ring, counters and the
+  //  order pass's bins from ONE kernel; run_tail wrote no list)
+  const bool fused_queue = X.list_pending && !small_flat && whole_set && X.list == C->d_slots && n == n_cur;
+  if (X.list_pending && !fused_queue) { g_last_error = "internal: the flat engine was left a list it cannot write"; return LOIKB_ERR_STATE; }
+  OrderUse use;
+  int rc = LOIKB_OK;
+  if (fused_queue && (rc = take_up_order(S, C, one_per_wave(F.kind), true, n_cur, &use, false))) return rc;
+  if (fused_queue)
+    hipLaunchKernelGGL(k_queue_init, grid1(std::max(std::max(C->ring_cap, n_cur), std::max(NCOUNTERS, ORDER_BINS))), dim3(256), 0, C->stream, C->d_ring, C->ring_cap,
+                       C->d_slots, n_cur, C->d_counters, NCOUNTERS, use.ordered ? (const int*)C->d_order : (const int*)nullptr, (unsigned int*)C->d_order_bins, ORDER_BINS);
+  else if (!queue_ready && small_flat) hipLaunchKernelGGL(k_queue_init, grid1(std::max(C->ring_cap, NCOUNTERS)), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, C->d_slots, n_cur, C->d_counters, NCOUNTERS, (const int*)nullptr, (unsigned int*)nullptr, 0);
   else if (!queue_ready) HIPCHK(hipMemsetAsync(C->d_counters, 0, NCOUNTERS * sizeof(unsigned int), C->stream));
   if (!queue_ready) HIPCHK(hipEventRecord(C->ev_k0, C->stream));
-  OrderUse use;
-  int rc = take_up_order(S, C, !small_flat && whole_set && X.list == C->d_slots && n == n_cur && one_per_wave(F.kind), true, n_cur, &use);
-  if (rc) return rc;
+  if (!fused_queue && (rc = take_up_order(S, C, !small_flat && whole_set && X.list == C->d_slots && n == n_cur && one_per_wave(F.kind), true, n_cur, &use))) return rc;
   F.slice = flat_launch_slice(S, C, F.kind, F.mur, n, n_cur, use.ordered);
   F.nw = F.ndec;
   if (F.mur == 2) flat_table_window(S, F, n);
@@ -2386,17 +2451,26 @@ static int launch_flat(TailCtx<T>& X)
   // The prepared records (loik_flat_prep.hpp): k_fslots covers the whole list, so every fresh instance of the launch has one.  First
   // launches of a solve only -- a relaunch's instances have iterated, k_tail's are not k_flat2's -- and not under OSQP's rule or logging,
   // whose builds keep the old load.
-  const bool prep = F.kind == FlatKind::Flat2 && S->tune.flat_prep && F.ndec > 0 && F.mur != 1 && !S->opt.logging && whole_set && n == n_cur &&
-                    flat_prep_fits(S) && X.G == PREP_G && C->d_prep && (size_t)n_cur * flat_prep_stride(S->nc) * sizeof(double) <= C->d_prep.bytes();
+  const bool prep = flat_prep_route(S, C, n_cur) && F.ndec > 0 && whole_set && n == n_cur && X.G == PREP_G;
   if (prep) P.mode |= MODE_FLAT_PREP;
   F.prep = prep;
+  // The reset loikb_solve left out (virtual_reset_route, where the case is argued) is settled here: k_fslots stands in for it when every
+  // fresh instance comes from its record with a zero state and finds mu0's decade in the table or builds it (then it iterates, and its
+  // store writes the logged scalars too); otherwise the real pass goes in front of k_fslots.
+  const bool decade0 = F.kexp_lo <= 0 && 0 < F.kexp_lo + F.ndec;   // (in the table's range: built by k_fslots, or in-wave under F.mur == 2)
+  const bool virt = S->reset_pending != 0 && virtual_reset_route(S) && prep && (P.mode & MODE_ZERO_STATE) && !small_flat && X.cur == 0 && decade0;
+  F.virt = virt;
+  if (virt) S->reset_pending = 0;
+  else if ((rc = flush_pending_reset(S))) return rc;
   if (F.ndec > 0) {
     const dim3 hgrid((unsigned)((n + X.ipw - 1) / X.ipw));
     // [65][22] exchange rows (pass B's L columns, [NA + 1][64], live in them afterwards) + [65][6] S^w + the constraints' A^T A + the decades' mu
     const size_t slds = (std::max((size_t)(WAVE + 1) * 22, (size_t)((F.small_na ? FLAT_NA_SMALL : FLAT_MAXA) + 1) * WAVE) + (size_t)(WAVE + 1) * 6 +
                          (size_t)X.ipw * S->nc * 21 + 16) * sizeof(T);
     auto* fslots = F.small_na ? k_fslots<T, FLAT_NA_SMALL> : k_fslots<T, FLAT_MAXA>;
-    hipLaunchKernelGGL(fslots, hgrid, dim3(WAVE), slds, C->stream, P, X.Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
+    Params<T> Pf = P;   // (the bit is k_fslots' alone)
+    if (virt) Pf.mode |= MODE_VIRTUAL_RESET;
+    hipLaunchKernelGGL(fslots, hgrid, dim3(WAVE), slds, C->stream, Pf, X.Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
                        (const int*)S->d_child_list, (const FlatLane*)S->flat.d_lanes, S->maxdepth, F.nanc, F.frows, S->flat.njmp, X.list, n,
                        X.G, C->d_fslots.as<T>(), F.kexp_lo, F.ndec, F.dw0, F.nw, F.mur == 2 ? C->d_fmask : (unsigned int*)nullptr,
                        prep ? C->d_prep.as<T>() : (T*)nullptr);
@@ -2405,25 +2479,29 @@ static int launch_flat(TailCtx<T>& X)
   // (no event between k_fslots and the engine in the short sequence: loikb_stats::hslots_ms reads 0 there -- an event costs a lone
   //  problem's Solve() 2.5 us of 116: profiles/r06_o_small_finish_ab.jsonl)
   if (!small_flat) HIPCHK(hipEventRecord(C->ev_k2, C->stream));
-  if (!small_flat) hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, X.list, n, C->d_counters);
+  if (!small_flat && !fused_queue) hipLaunchKernelGGL(k_ring_fill, grid1(C->ring_cap), dim3(256), 0, C->stream, C->d_ring, C->ring_cap, X.list, n, C->d_counters);
   if ((rc = launch_flat_kernel(X, F))) return rc;
   P.mode = mode_keep;
   int* next = (X.list == C->d_slots) ? C->d_slots2 : C->d_slots;
   const bool small_finish = small_flat && S->tune.small_finish;
+  // (the order pass is skipped in the short sequence: every instance gets a wavefront at once, no order to leave)
+  const bool order_pass = !small_flat && S->tune.flat_order && whole_set && n == n_cur && one_per_wave(F.kind) && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
+  const bool fused_finish = fused_queue && order_pass;   // (the bins were zeroed by k_queue_init)
   if (small_finish)   // (one workgroup: the list, the counts, and the launch's counters into the pinned host copy -- loik_lean.hpp)
     hipLaunchKernelGGL(k_small_finish<T>, dim3(1), dim3(256), 0, C->stream, X.A.tiles, S->L, X.list, n, next, C->d_counters, NCOUNTERS, C->h_counters);
+  else if (fused_finish)   // (the list, the counts, the order's bins and the end decades from one pass over the scalar records)
+    hipLaunchKernelGGL(k_finish_order<T>, grid1(n_cur), dim3(256), 0, C->stream, X.A.tiles, S->L, n_cur, S->opt.max_iter, next, C->d_counters + 3,
+                       (unsigned int*)C->d_order_bins, C->d_counters + ORDER_DEC_HIST);
   else
     hipLaunchKernelGGL(k_list_unfinished<T>, grid1(n), dim3(256), 0, C->stream, X.A.tiles, S->L, X.list, n, next, C->d_counters + 3);
   HIPCHK(hipGetLastError());
   C->stats.launches++; C->stats.tail_launches++; C->stats.lean_launches++; C->stats.flat_launches++;
   if (F.kind == FlatKind::Flat2) C->stats.flat_split_launches++;
   HIPCHK(hipEventRecord(C->ev_k1, C->stream));
-  // (the order pass is skipped in the short sequence: every instance gets a wavefront at once, no order to leave)
-  const bool order_pass = !small_flat && S->tune.flat_order && whole_set && n == n_cur && one_per_wave(F.kind) && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS);
   if (!order_pass && !small_finish) HIPCHK(hipMemcpyAsync(C->h_counters, C->d_counters, NCOUNTERS * sizeof(unsigned int), hipMemcpyDeviceToHost, C->stream));
-  if (order_pass && (rc = leave_order<T>(S, C, X.A, n_cur, true))) return rc;
+  if (order_pass && (rc = leave_order<T>(S, C, X.A, n_cur, true, fused_finish))) return rc;
   HIPCHK(hipStreamSynchronize(C->stream));
-  return flat_read_back(X, F, use, order_pass, small_finish, queue_ready, next);
+  return flat_read_back(X, F, use, order_pass, small_finish, queue_ready, next, fused_queue);
 }
 
 // ---- the lean engine: k_hslots + k_lean, two wavefronts per SIMD (loik_lean.hpp).  H_i / Dinv_i / UDinv_i of the listed instances are
@@ -2440,6 +2518,8 @@ static int launch_lean(TailCtx<T>& X)
   const bool whole_set = X.whole_set, per_link = S->per_link;  // (UpdateReferences' table: the PERLINK instantiations of k_hslots / k_lean)
   // decade slots are indexed by the instance's slot in the set (relaunches with shorter lists find them again);
   // the buffer was sized for the chunk at SolveInit (ensure_hslots)
+  int rc = flush_pending_reset(S);   // (k_hslots and k_lean read the tiles)
+  if (rc) return rc;
   const size_t need = (size_t)n_cur * ndec * HSLOT_PAIRS * G * 2 * sizeof(T);
   if (need > C->d_hslots.bytes()) { g_last_error = "internal: decade-slot buffer smaller than the chunk"; return LOIKB_ERR_STATE; }
   const int waves_cu = S->plan.lean_waves_cu;
@@ -2454,8 +2534,7 @@ static int launch_lean(TailCtx<T>& X)
   const int wg_cap = wg_per_cu * std::max(1, (int)(S->ncu * ((double)C->B / (double)S->B) + 0.5));
   HIPCHK(hipEventRecord(C->ev_k0, C->stream));
   OrderUse use;
-  int rc = take_up_order(S, C, whole_set && list == C->d_slots && n == n_cur, whole_set, n_cur, &use);
-  if (rc) return rc;
+  if ((rc = take_up_order(S, C, whole_set && list == C->d_slots && n == n_cur, whole_set, n_cur, &use))) return rc;
   P.max_launch_iters = S->opt.max_iter + 1;
   const int wg_needed = (n + ipw * ltw - 1) / (ipw * ltw);
   const dim3 grid((unsigned)std::min(wg_needed, wg_cap));
@@ -2513,6 +2592,8 @@ static int launch_tail_kernel(TailCtx<T>& X, int tw, size_t lds)
   loikb_solver_impl* S = X.S; Chunk* C = X.C;
   const int n = X.n, n_cur = X.n_cur;
   const int cu_share = std::max(1, (int)(S->ncu * (TAIL_WAVES / tw) * ((double)C->B / (double)S->B) + 0.5));
+  int rc = flush_pending_reset(S);   // (k_tail as the batch's engine reads the tiles; after the flat engine nothing is pending)
+  if (rc) return rc;
   X.P.max_launch_iters = S->opt.max_iter + 1;
   const int wg_needed = (n + X.ipw * tw - 1) / (X.ipw * tw);
   const dim3 grid((unsigned)std::min(wg_needed, cu_share));
@@ -2522,8 +2603,7 @@ static int launch_tail_kernel(TailCtx<T>& X, int tw, size_t lds)
   // previous solve, as in the flat and lean engines (its lane groups pull the list in order)
   const bool tail_whole = X.whole_set && X.list == C->d_slots && n == n_cur && !(S->opt.flags & LOIKB_OPT_FIXED_ITERS) && S->tune.flat_order;
   OrderUse use;
-  int rc = take_up_order(S, C, tail_whole, tail_whole, n_cur, &use);
-  if (rc) return rc;
+  if ((rc = take_up_order(S, C, tail_whole, tail_whole, n_cur, &use))) return rc;
   auto* kernel = S->href_diag ? k_tail<T, true> : k_tail<T, false>;
   hipLaunchKernelGGL(kernel, grid, dim3(WAVE * tw), lds, C->stream, X.P, X.Bf, (const JointDesc*)S->d_jd, (const TailTopo*)S->d_topo,
                      (const int*)S->d_child_list, S->maxdepth, S->maxchild, X.list, n, X.G);
@@ -2565,10 +2645,15 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
   // counted by k_list_unfinished -- 8 launches / copies and one synchronisation less per Solve() (B = 1: 0.168 -> see profiles/r06_*_small_batches)
   const bool small_flat = whole_set && cur == 0 && S->chunks.size() == 1 && flat_1pw && flat_here && n_cur <= S->tune.flat_small_batch &&
                           n_cur >= std::max(1, S->tune.flat_min_batch);
-  if (whole_set && !small_flat) {
-    // every slot of the set (finished instances, if any, stop at once inside the kernel; the short sequence: k_queue_init_iota in launch_flat)
+  // (the flat engine below takes the whole set: its k_queue_init writes the list with the ring -- LOIKB_FLAT_SEQ=0: k_list_iota as before)
+  const bool flat_takes = flat_here && n_live >= (flat_1pw ? std::max(1, S->tune.flat_min_batch) : 64);
+  const bool list_pending = whole_set && !small_flat && S->tune.flat_seq && flat_takes && n_live == n_cur;
+  if (whole_set && !small_flat && !list_pending) {
+    // every slot of the set (finished instances, if any, stop at once inside the kernel; the short sequence: k_queue_init in launch_flat)
     hipLaunchKernelGGL(k_list_iota, grid1(n_cur), dim3(256), 0, C->stream, C->d_slots, n_cur);
   } else if (!whole_set) {
+    int rc0 = flush_pending_reset(S);   // (never pending here -- the streaming engine flushed it --: the rule is that readers of the tiles ask)
+    if (rc0) return rc0;
     C->h_wave.resize(2 * (size_t)nw + 2);
     int* cnt = C->h_wave.data();
     int* off = cnt + nw + 1;
@@ -2583,6 +2668,7 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
   HIPCHK(hipGetLastError());
   const int G = lanes_per_instance(S);
   TailCtx<T> X{S, C, P, make_bufs<T>(S, C, cur), A, cur, n_cur, whole_set, small_flat, G, WAVE / G, S->plan.ndec, S->plan.kexp_lo, C->d_slots, n_live};
+  X.list_pending = list_pending;
   P.B = n_cur;
   int tw = S->tune.tail_waves;  // k_tail's wavefronts per workgroup
   while (tw > 1 && tw * tail_lds_bytes<T>(S->nc, G) > 160 * 1024) --tw;
@@ -2609,7 +2695,7 @@ int run_tail(loikb_solver_impl* S, Chunk* C, Params<T>& P, int cur, int n_cur, i
   int rc = LOIKB_OK;
   bool engine_ran = true;
   // (k_lean's lane groups need whole wavefronts of work to pay: below 64 instances k_tail's direct path is as good)
-  if (flat_here && X.n >= (flat_1pw ? std::max(1, S->tune.flat_min_batch) : 64)) rc = launch_flat(X);
+  if (flat_takes) rc = launch_flat(X);
   else if (S->plan.lean && (P.mode & MODE_CACHE_H) && X.n >= 64) rc = launch_lean(X);
   else engine_ran = false;
   if (rc) return rc;
@@ -2692,6 +2778,9 @@ int run_chunk(loikb_solver_impl* S, Chunk* C)
     C->stats.tail_instances = C->B;
     C->stats.tail_instance_iterations = tit;
     inst_iters = tit;
+  } else {
+    int rc = flush_pending_reset(S);   // (the streaming engine reads the tiles.  One chunk whenever a reset is pending: virtual_reset_route)
+    if (rc) return rc;
   }
   while (!direct_tail) {
     // Latency-bound regime: once the chunk's tiles fit its share of the CUs (one workgroup per CU), an iteration
@@ -2898,7 +2987,7 @@ int run_main_loop(loikb_solver_impl* S)
     return LOIKB_ERR_MU_STRATEGY;
   }
   int rc;
-  if (!S->plan.solve_ok && !bushy_goes_on_chip(S)) rc = run_pass_solve(S, false);   // (the engine of last resort: EnginePlan::solve_ok)
+  if (!S->plan.solve_ok && !bushy_goes_on_chip(S)) { if (!(rc = flush_pending_reset(S))) rc = run_pass_solve(S, false); }   // (the engine of last resort: EnginePlan::solve_ok)
   else if ((rc = start_mu(S))) {}
   else rc = S->f32 ? run_main_loop_t<float>(S) : run_main_loop_t<double>(S);
   return rc;
@@ -3284,6 +3373,16 @@ int loikb_solve(loikb_solver* S)
   HIPCHK(hipSetDevice(S->device));
   int rc;
   // ik_id_data_.ResetRecursion(); ResetSolver()  (hpp:370-374)
+  // Where the solve takes every instance from a record k_fslots prepares (virtual_reset_route), the reset is noted, not launched: 5.5 KB
+  // of stores per Talos-32 instance that nobody reads.  launch_flat settles it; whichever way the solve goes instead launches it first,
+  // and so does this function when it is left with the reset still pending (an error on the way to the engine).
+  if (virtual_reset_route(S)) {
+    S->zero_state = true;   // (what reset_home derives from RS_RECURSION)
+    S->reset_pending = RS_RECURSION | RS_SOLVER;
+    rc = run_main_loop(S);
+    const int rc2 = flush_pending_reset(S);
+    return rc ? rc : rc2;
+  }
   if ((rc = reset_home(S, RS_RECURSION | RS_SOLVER, !S->opt.logging))) return rc;
   return S->opt.logging ? run_logged(S, RS_RECURSION | RS_SOLVER) : run_main_loop(S);
 }
@@ -4164,6 +4263,21 @@ int loikb_debug_device_memory(unsigned long long out[4])
 {
   if (!out) return LOIKB_ERR_ARG;
   for (int k = 0; k < 4; ++k) out[k] = g_devmem[k].load();
+  return LOIKB_OK;
+}
+
+// undeclared debug export: the prepared records (loik_flat_prep.hpp) k_fslots of the handle's last flat launch left in chunk 0, the first
+// `n_inst` instances' blocks of *stride doubles each, as they lie in the buffer.  The tests compare the blocks two launch sequences leave.
+int loikb_debug_flat_prep(loikb_solver* S, double* out, int n_inst, int* stride)
+{
+  if (!S || !out || !stride || n_inst < 0 || S->chunks.empty()) return LOIKB_ERR_ARG;
+  HIPCHK(hipSetDevice(S->device));
+  const Chunk& C = S->chunks[0];
+  *stride = flat_prep_stride(S->nc);
+  const size_t bytes = (size_t)n_inst * *stride * sizeof(double);
+  if (!C.d_prep || bytes > C.d_prep.bytes()) { g_last_error = "the handle has no prepared records of that many instances"; return LOIKB_ERR_STATE; }
+  HIPCHK(hipStreamSynchronize(S->stream));
+  HIPCHK(hipMemcpy(out, C.d_prep.as<double>(), bytes, hipMemcpyDeviceToHost));
   return LOIKB_OK;
 }
 

@@ -904,12 +904,19 @@ __global__ void k_ring_fill(int* __restrict__ ring, int cap, const int* __restri
 
 // small batches (every instance gets a wavefront at once): the identity list, the ring and the launch's counters in ONE kernel -- a lone
 // problem's Solve() is a handful of launches, and each costs the stream ~5 us (tests/loik-loid.cpp:987-1032 times exactly that call)
+// The flat engine's long sequence (whole sets above the small batches) starts with the same kernel in place of k_list_iota, the counters'
+// memset, the copy of the order and k_ring_fill: `order` (may be null) is the list the handle's previous solve left, longest first -- list
+// and ring take it instead of 0 .. n - 1 --, and `bins` (may be null) are the nbins counts of the order pass that follows the launch
+// (k_finish_order adds to them).  The grid covers max(cap, n, ncounters, nbins).
 #ifndef LOIKB_FLAT_KERNELS_TU
-__global__ void k_queue_init_iota(int* __restrict__ ring, int cap, int* __restrict__ list, int n, unsigned int* __restrict__ counters, int ncounters)
+__global__ void k_queue_init(int* __restrict__ ring, int cap, int* __restrict__ list, int n, unsigned int* __restrict__ counters, int ncounters,
+                             const int* __restrict__ order = nullptr, unsigned int* __restrict__ bins = nullptr, int nbins = 0)
 {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < cap) ring[i] = i < n ? i : -1;
-  if (i < n) list[i] = i;
+  const int slot = i < n ? (order != nullptr ? order[i] : i) : -1;
+  if (i < cap) ring[i] = slot;
+  if (i < n) list[i] = slot;
+  if (bins != nullptr && i < nbins) bins[i] = 0u;
   if (i < ncounters) {
     unsigned int v = 0u;
     if (i == LEAN_Q_TAIL) v = (unsigned int)n;
@@ -918,7 +925,7 @@ __global__ void k_queue_init_iota(int* __restrict__ ring, int cap, int* __restri
   }
 }
 // ... and, for the plain Solve() of a small handle (loikb_solve: ResetRecursion + ResetSolver, then the loop -- hpp:370-374), the reset of the
-// home set with it: workgroups [0, ntiles) are k_reset's, the rest k_queue_init_iota's -- one launch less in front of a lone problem's solve
+// home set with it: workgroups [0, ntiles) are k_reset's, the rest k_queue_init's -- one launch less in front of a lone problem's solve
 template <typename T>
 __global__ void __launch_bounds__(WAVE) k_reset_and_queue(char* tiles, Layout L, int what, T mu0, int ntiles, int* __restrict__ ring, int cap,
                                                           int* __restrict__ list, int n, unsigned int* __restrict__ counters, int ncounters)
@@ -1010,6 +1017,33 @@ __global__ void __launch_bounds__(256) k_order_count(char* tiles, Layout L, int 
   __syncthreads();
   if (h[threadIdx.x]) atomicAdd(&bins[threadIdx.x], h[threadIdx.x]);
   if (dec_hist != nullptr && threadIdx.x < 32 && hd[threadIdx.x]) atomicAdd(&dec_hist[threadIdx.x], hd[threadIdx.x]);
+}
+// k_list_unfinished and k_order_count in ONE pass over the scalar records, for a launch that took the whole set (its list is a
+// permutation of 0 .. n - 1, so the pass goes by slot): the instances still iterating into list_out and counter[0], the ones neither
+// converged nor flagged into counter[1], the iteration counts' classes into bins (zeroed beforehand: k_queue_init), the end decades
+// into dec_hist (zeroed with the launch's counters).
+template <typename T>
+__global__ void __launch_bounds__(256) k_finish_order(char* tiles, Layout L, int n, int max_iter, int* __restrict__ list_out,
+                                                      unsigned int* __restrict__ counter, unsigned int* __restrict__ bins,
+                                                      unsigned int* __restrict__ dec_hist)
+{
+  __shared__ unsigned int h[ORDER_BINS], hd[32];
+  h[threadIdx.x] = 0u;
+  if (threadIdx.x < 32) hd[threadIdx.x] = 0u;
+  __syncthreads();
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < n) {
+    const char* srec = lane_ptr<T>(tiles, L, b) + (size_t)L.off_s * pair_bytes<T>();
+    const int status = (int)ldp<T>(srec, SP_ST).x;
+    if (!(status & ST_DONE)) list_out[atomicAdd(counter, 1u)] = b;
+    if (!(status & (ST_CONVERGED | ST_PRIMAL_INF))) atomicAdd(counter + 1, 1u);
+    atomicAdd(&h[order_bin<T>(tiles, L, b, max_iter)], 1u);
+    const int kx = (int)ldp<T>(srec, SP_MU).y;
+    atomicAdd(&hd[kx < -16 ? 0 : kx > 15 ? 31 : kx + 16], 1u);
+  }
+  __syncthreads();
+  if (h[threadIdx.x]) atomicAdd(&bins[threadIdx.x], h[threadIdx.x]);
+  if (threadIdx.x < 32 && hd[threadIdx.x]) atomicAdd(&dec_hist[threadIdx.x], hd[threadIdx.x]);
 }
 // bins[ORDER_BINS .. 2 ORDER_BINS) <- exclusive prefix sums of the counts (one workgroup of ORDER_BINS threads)
 #ifndef LOIKB_FLAT_KERNELS_TU   // (not a template: defined in the host translation unit only)
