@@ -82,7 +82,10 @@ enum {
                                  while mu is unchanged -- bit-identical results, fewer HBM bytes)            */
   LOIKB_OPT_OWN_STREAM = 8,  /* the handle creates its own non-blocking HIP stream instead of launching on the null stream:
                                  two handles on one device then run concurrently (batches in flight from two host threads);
-                                 loikb_set_stream still overrides it                                                  */
+                                 loikb_set_stream still overrides it.  The stream contract at loikb_set_stream holds for this
+                                 stream as for a caller's: the calls named there under 2. leave work queued on it, everything
+                                 else is complete on return, and results are those of the null stream bit for bit (the flat
+                                 engine's time slicing of 32 768+ instances is off on such a handle: same z, another schedule) */
   LOIKB_OPT_NO_COMPACTION = 4, /* never repack live instances into dense wavefronts between launches (default:
                                  repack when at most 85 % of the slots are still iterating; results are
                                  bit-identical, but the inter-sweep temporaries His/pis/UDinv/Dinv/r of
@@ -152,7 +155,26 @@ typedef struct loikb_solver loikb_solver;
  * (loik-loid-data-optimized.hxx:40-104, loik-loid-optimized.hpp:129-162).  The model is copied (hpp:762). */
 int loikb_create(const loikb_model_desc *model, const loikb_options *opts, loikb_solver **out);
 int loikb_destroy(loikb_solver *s);
-/* launch on the caller's HIP stream (a hipStream_t); default is the null stream */
+/* launch on the caller's HIP stream (a hipStream_t); default is the null stream.  The stream contract (tests/test_stream_*.py hold every
+ * entry point to it, on a hipStreamNonBlocking stream behind pending work):
+ *  1. Everything a call puts on the device -- kernels, copies, its reads of LOIKB_IN_DEVICE arrays -- is ordered after everything queued
+ *     on the handle's stream before the call.  A caller may fill a device input with work queued on that stream and call at once.
+ *  2. Every call that reads a caller's array or writes one has done so when it returns, host arrays and LOIKB_OUT_DEVICE arrays alike:
+ *     the solves, every getter and query, the pose loops, loikb_pass, loikb_solve_init.  An output may be read on any stream, or from
+ *     the host, right after the call.  The calls that return with device work still queued on the handle's stream have no output to
+ *     read: loikb_integrate (its kernel), and the formulation edits and setters that end with a reset of the handle's state on the
+ *     device -- loikb_update_eq_constraint, loikb_add_eq_constraint, loikb_remove_eq_constraint, loikb_update_references,
+ *     loikb_set_rho.  Their input arrays have been read on return; what they queued runs before the next call's work (1.), and
+ *     loikb_synchronize or a synchronisation of the stream waits for it.
+ *  3. loikb_set_stream may be called between any two calls and changes no answer.  Moving the handle to ANOTHER stream waits on the
+ *     host until the stream it leaves has run what the handle queued there (a stream synchronisation: the stream must still exist);
+ *     naming the stream the handle is on already costs nothing.  The new stream is not waited for: what the caller queued on it runs
+ *     before the handle's next call (1.).
+ *  4. No call waits explicitly for another stream: a handle synchronises its own stream (and the streams of its own chunks) and
+ *     nothing else, so a call on stream B returns while stream A is held up.  Outside that promise: loikb_synchronize, which is
+ *     hipDeviceSynchronize by design; a call that has to grow or free a device buffer (hipMalloc / hipFree may synchronise the
+ *     device); and whatever the runtime serialises by itself, e.g. copies of several streams that share a transfer engine.
+ * One host thread per handle at a time; hip_stream must outlive the handle or the next loikb_set_stream. */
 int loikb_set_stream(loikb_solver *s, void *hip_stream);
 
 /* SolveInit(q,H_ref,v_ref,active_task_constraint_ids,Ais,bis,lb,ub), loik-loid-optimized.hpp:335-361 */

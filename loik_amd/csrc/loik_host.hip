@@ -3289,6 +3289,13 @@ int loikb_destroy(loikb_solver* S)
 int loikb_set_stream(loikb_solver* S, void* hip_stream)
 {
   if (!S) return LOIKB_ERR_ARG;
+  // What the handle queued on the stream it leaves (loikb_integrate returns with its kernel queued, a formulation edit with its
+  // resets) must have run before the first launch on the new one, and the staging buffers are reused in stream order: the old stream
+  // is drained.  A host wait, between solves and never inside one; moving to the stream the handle is on costs nothing.
+  if ((hipStream_t)hip_stream != S->stream) {
+    HIPCHK(hipSetDevice(S->device));
+    HIPCHK(hipStreamSynchronize(S->stream));
+  }
   S->stream = (hipStream_t)hip_stream;
   return LOIKB_OK;
 }
