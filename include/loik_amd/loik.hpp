@@ -34,6 +34,7 @@
 #include "../loik_amd_blend.h"
 #include "../loik_amd_plan.h"
 #include "../loik_amd_grid.h"
+#include "../loik_amd_gridnear.h"
 
 #include <array>
 #include <map>
@@ -636,6 +637,39 @@ public:
       *out = std::move(g);
     }
     return true;
+  }
+  // ---- the nearest-voxel transform (include/loik_amd_gridnear.h): with the latch on every grid that is set gets its transform F beside
+  // the field, and collision avoidance reads the grid as one more world object of every sphere
+  void SetCollisionGridNearest(bool on = true) { check(loikb_collision_grid_set_nearest(h_, on ? 1 : 0)); }
+  // whether the latch is on and a grid is set; with out, F [nz][ny][nx]: the occupied voxel nearest to each voxel
+  bool GetCollisionGridNearest(std::vector<unsigned int>* out = nullptr) const
+  {
+    const int rc = loikb_collision_grid_get_nearest(h_, nullptr, 0);
+    if (rc < 0) check(rc);
+    if (rc == 0) return false;
+    if (out) {
+      CollisionGrid g;
+      GetCollisionGrid(&g, false);
+      out->resize((std::size_t)g.dims[0] * (std::size_t)g.dims[1] * (std::size_t)g.dims[2]);
+      const int rc2 = loikb_collision_grid_get_nearest(h_, out->data(), 0);
+      if (rc2 < 0) check(rc2);
+    }
+    return true;
+  }
+  struct GridNearestResult {
+    DVec val;              // [n][2]: the lower bound v of the grid header, d_u - r with d_u the distance to the chosen cube
+    std::vector<int> vox;  // [n][2]: the voxel read, the chosen cube (-1 in an empty grid)
+    DVec normal;           // [n][3]: the outward normal of the chosen cube
+  };
+  // the grid pair with a direction of spheres [n][4] = x y z r in the world frame
+  GridNearestResult GridNearest(const DVec& spheres) const
+  {
+    const std::size_t n = spheres.size() / 4;
+    if (spheres.size() != 4 * n) throw std::runtime_error("loik_amd: spheres is not a whole number of (x, y, z, r) rows");
+    GridNearestResult r;
+    r.val.resize(2 * n); r.vox.resize(2 * n); r.normal.resize(3 * n);
+    check(loikb_grid_nearest_query(h_, spheres.data(), (int)n, 0, r.val.data(), r.vox.data(), r.normal.data(), 0));
+    return r;
   }
   // ---- motions (include/loik_amd_motion.h).  Difference: v [n][nv] with q0 (+) v = q1 under Integrate's arithmetic
   DVec Difference(const DVec& q0, const DVec& q1) const

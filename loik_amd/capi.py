@@ -220,6 +220,10 @@ GRID_ABI_VERSION = 1
 GRID_SYMBOLS = ["loikb_grid_version", "loikb_collision_set_world_grid", "loikb_collision_get_world_grid"]
 CLR_WORLD_GRID = 4
 GRID_MAX_DIM, GRID_MAX_VOXELS, GRID_EMPTY = 512, 1 << 26, 0xFFFFFFFF
+# include/loik_amd_gridnear.h: the nearest-voxel transform of a voxel world, and avoidance that reads the grid; its own header and version
+GRIDNEAR_ABI_VERSION = 1
+GRIDNEAR_SYMBOLS = ["loikb_gridnear_version", "loikb_collision_grid_set_nearest", "loikb_collision_grid_get_nearest", "loikb_grid_nearest_query"]
+GRID_NO_VOXEL = 0xFFFFFFFF
 
 
 class PoseParams(C.Structure):
@@ -390,6 +394,9 @@ def lib():
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_collision_set_world_grid.argtypes = [C.c_void_p, C.c_void_p, _ip, _dp, C.c_double, C.c_int]
     L.loikb_collision_get_world_grid.argtypes = [C.c_void_p, _ip, _dp, _dp, C.c_void_p, C.c_int]
+    L.loikb_collision_grid_set_nearest.argtypes = [C.c_void_p, C.c_int]
+    L.loikb_collision_grid_get_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_grid_nearest_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
                           % (_LIB_PATH, L.loikb_version(), ABI_VERSION))
@@ -1266,6 +1273,37 @@ class BatchedLoik:
                 _check(rc)
             out["G"] = G
         return out
+
+    # ---- the nearest-voxel transform (include/loik_amd_gridnear.h) --------------------------------------------------
+    def set_collision_grid_nearest(self, on=True):
+        """the latch of the nearest-voxel transform (loikb_collision_grid_set_nearest): with it on, every grid that is set gets its
+        transform F beside the field, and collision avoidance (set_collision_avoidance, clearance_gradient, avoidance_box) reads the
+        grid as one more world object of every sphere.  on=False drops it."""
+        _check(self.L.loikb_collision_grid_set_nearest(self.h, int(on)))
+
+    def collision_grid_nearest(self):
+        """F uint32 [nz][ny][nx]: for every voxel the linear index (z ny + y) nx + x of the occupied voxel nearest to it, the lowest index
+        among several, GRID_NO_VOXEL in an empty grid (loikb_collision_grid_get_nearest); None without a grid or without the latch"""
+        rc = self.L.loikb_collision_grid_get_nearest(self.h, None, 0)
+        if rc < 0:
+            _check(rc)
+        if rc == 0:
+            return None
+        nx, ny, nz = self.collision_grid(field=False)["dims"]
+        F = np.empty((nz, ny, nx), dtype=np.uint32)
+        rc = self.L.loikb_collision_grid_get_nearest(self.h, F.ctypes.data_as(C.c_void_p), 0)
+        if rc < 0:
+            _check(rc)
+        return F
+
+    def grid_nearest(self, spheres, out=None):
+        """the grid pair with a direction of spheres [n][4] = x y z r in the world frame, host or device (loikb_grid_nearest_query):
+        dict(val [n][2] = (the lower bound v, d_u - r with d_u the distance to the chosen cube), vox [n][2] = (the voxel read, the chosen
+        cube; -1 in an empty grid), normal [n][3]); or with out = (val_dev, vox_dev, normal_dev) writes there and returns out."""
+        sp, n, dev, keep = self._rows(spheres, 4)
+        ptrs, oflags, new = _outs(out, [((n, 2), np.float64), ((n, 2), np.int32), ((n, 3), np.float64)])
+        _check(self.L.loikb_grid_nearest_query(self.h, sp, n, IN_DEVICE if dev else 0, *ptrs, oflags))
+        return out if new is None else dict(zip(("val", "vox", "normal"), new))
 
     # ---- collision avoidance (include/loik_amd_avoid.h) -------------------------------------------------------------
     def set_collision_avoidance(self, d_safe, d_influence, kappa=0.5):

@@ -28,6 +28,7 @@
 #include "loik_pose_jacobian.hpp"
 #include "loik_pose_collision.hpp"
 #include "loik_pose_grid.hpp"
+#include "loik_pose_gridnear.hpp"
 #include "loik_pose_motion.hpp"
 #include "loik_pose_shortcut.hpp"
 #include "loik_pose_retime.hpp"
@@ -64,6 +65,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_blend.h"
 #include "../../include/loik_amd_plan.h"
 #include "../../include/loik_amd_grid.h"
+#include "../../include/loik_amd_gridnear.h"
 
 #include <algorithm>
 #include <atomic>
@@ -470,6 +472,12 @@ struct loikb_solver_impl {
       double go[3] = {0.0, 0.0, 0.0}, gh = 0.0;
       DevBuf<unsigned int> d_grid, d_grid_next;   // [nz][ny][nx]
       DevBuf<unsigned char> d_occ;                // the staged occupancy of a host caller
+      // the nearest-voxel transform (loik_amd_gridnear.h): the latch, F of the grid that is set and the buffer the next build writes (they
+      // change places with G's pair), and the 64-bit keys of a build.  All three are kept while the latch is on (a set at sensor rate
+      // allocates nothing: 16 bytes a voxel in all) and freed when it is turned off
+      bool near_on = false;
+      DevBuf<unsigned int> d_near, d_near_next;   // [nz][ny][nx]
+      DevBuf<unsigned long long> d_nearkey;       // [nz][ny][nx]
       bool have_ms = false;              // loikb_clearance_set_multistart set `ms`
       loikb_clearance_params ms = {0.0, 0};
     } col;

@@ -1108,6 +1108,34 @@ static double grid_hi(double origin, int n, double h)
   return origin + e;
 }
 
+// The nearest-voxel transform of the finished field G [nz][ny][nx] into F (loik_amd_gridnear.h; kernels in loik_pose_gridnear.hpp).
+// Queued; the keys go through C.d_nearkey, which only a build uses
+static int gridnear_build(loikb_solver_impl* S, const unsigned int* G, int nx, int ny, int nz, unsigned int* F)
+{
+  Collision& C = S->pose.col;
+  const size_t nvox = (size_t)nx * ny * nz;
+  if (int rc = regrow_drained(S, C.d_nearkey, sizeof(unsigned long long) * nvox)) return rc;
+  unsigned long long* K = C.d_nearkey;
+  const long long nlines = (long long)ny * nz;
+  const int per = grid_x_lines(nx);
+  hipLaunchKernelGGL(k_gridnear_x, dim3((unsigned)((nlines + per - 1) / per)), dim3(GRID_THREADS), 0, S->stream, G, K,
+                     (ny > 1 || nz > 1) ? (unsigned int*)nullptr : F, nx, nlines);
+  HIPCHK(hipGetLastError());
+  if (ny > 1) {   // (an axis of one voxel: the pass is the identity)
+    const int W = gridnear_tile_width(ny);
+    hipLaunchKernelGGL(k_gridnear_pass, dim3((unsigned)((nx + W - 1) / W), (unsigned)nz), dim3(GRID_THREADS), sizeof(unsigned long long) * (size_t)ny * W,
+                       S->stream, K, nz > 1 ? (unsigned int*)nullptr : F, ny, nx, (size_t)nx, (size_t)nx * ny, W);
+    HIPCHK(hipGetLastError());
+  }
+  if (nz > 1) {
+    const int W = gridnear_tile_width(nz);
+    hipLaunchKernelGGL(k_gridnear_pass, dim3((unsigned)((nx + W - 1) / W), (unsigned)ny), dim3(GRID_THREADS), sizeof(unsigned long long) * (size_t)nz * W,
+                       S->stream, K, F, nz, nx, (size_t)nx * ny, (size_t)nx, W);
+    HIPCHK(hipGetLastError());
+  }
+  return LOIKB_OK;
+}
+
 int loikb_collision_set_world_grid(loikb_solver* S, const unsigned char* occ, const int* dims, const double* origin, double h, int in_flags)
 {
   if (!S) return LOIKB_ERR_ARG;
@@ -1139,8 +1167,9 @@ int loikb_collision_set_world_grid(loikb_solver* S, const unsigned char* occ, co
       return LOIKB_ERR_ARG;
     }
   if (!col_ordinals_fit(C.ns, C.nws, C.nwb, true, C.pairs.size() / 2)) { g_last_error = "collision_set_world_grid: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
-  if (S->pose.avoid.have) {
-    g_last_error = "collision_set_world_grid: collision avoidance is set on the handle (loikb_avoid_set), and avoidance cannot read a voxel grid -- clear it first";
+  if (S->pose.avoid.have && !C.near_on) {
+    g_last_error = "collision_set_world_grid: collision avoidance is set on the handle (loikb_avoid_set), and avoidance cannot read a voxel grid -- clear it first."
+                   "  With the nearest-voxel transform latched (loikb_collision_grid_set_nearest) avoidance reads the grid.";
     return LOIKB_ERR_STATE;
   }
   HIPCHK(hipSetDevice(S->device));
@@ -1169,7 +1198,12 @@ int loikb_collision_set_world_grid(loikb_solver* S, const unsigned char* occ, co
                        G, nz, nx, (size_t)nx * ny, (size_t)nx, W);
     HIPCHK(hipGetLastError());
   }
+  if (C.near_on) {   // F beside G, both in the spare buffers: they change places below, after both builds went through
+    BUFCHK(C.d_near_next.regrow(sizeof(unsigned int) * nvox));
+    if (int rc = gridnear_build(S, G, nx, ny, nz, C.d_near_next)) return rc;
+  }
   HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's occ has been read; nothing queued reads the grid that goes)
+  if (C.near_on) C.d_near.swap(C.d_near_next);
   C.d_grid.swap(C.d_grid_next);
   for (int k = 0; k < 3; ++k) { C.gn[k] = dims[k]; C.go[k] = origin[k]; }
   C.gh = h;
@@ -1204,14 +1238,88 @@ static ClrModel clr_model(const loikb_solver_impl* S)
   int lp = 0;
   while (lp < 6 && (1 << lp) < C.ns) ++lp;
   ClrModel m{C.d_sph, C.d_scar, C.d_car, C.d_wsph, C.d_wbox, C.d_pairs, C.ns, (int)C.car.size(), C.nws, C.nwb, (int)(C.pairs.size() / 2), lp,
-             ClrGrid{nullptr, {0, 0, 0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 0.0, 0.0}};
+             ClrGrid{nullptr, {0, 0, 0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, 0.0, 0.0, nullptr}};
   if (C.have_grid) {
     m.g.G = C.d_grid;
+    if (C.near_on) m.g.F = C.d_near;
     for (int k = 0; k < 3; ++k) { m.g.n[k] = C.gn[k]; m.g.o[k] = C.go[k]; m.g.hi[k] = grid_hi(C.go[k], C.gn[k], C.gh); }
     m.g.h = C.gh;
     m.g.inv_h = 1.0 / C.gh;
   }
   return m;
+}
+
+// ---- include/loik_amd_gridnear.h (kernels in loik_pose_gridnear.hpp) ------------------------------------------------------------
+int loikb_gridnear_version(void) { return LOIKB_GRIDNEAR_VERSION; }
+
+static_assert(GRID_NO_VOXEL == LOIKB_GRID_NO_VOXEL, "the kernels' constant and the header's");
+static_assert((size_t)GRID_MAX_DIM / 2 * 32 * sizeof(unsigned long long) <= 65536 && (size_t)GRID_MAX_DIM * 16 * sizeof(unsigned long long) <= 65536,
+              "a tile of k_gridnear_pass fits 64 KB at either width");
+
+int loikb_collision_grid_set_nearest(loikb_solver* S, int on)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (on != 0 && on != 1) { g_last_error = "collision_grid_set_nearest: on must be 0 or 1"; return LOIKB_ERR_ARG; }
+  Collision& C = S->pose.col;
+  HIPCHK(hipSetDevice(S->device));
+  if (!on) {
+    if (C.have_grid && S->pose.avoid.have) {
+      g_last_error = "collision_grid_set_nearest: a voxel grid is set and collision avoidance is set on the handle (loikb_avoid_set), which reads the grid through the "
+                     "transform -- clear the avoidance or the grid first";
+      return LOIKB_ERR_STATE;
+    }
+    HIPCHK(hipStreamSynchronize(S->stream));   // (nothing queued reads F)
+    C.near_on = false;
+    // "as if never latched": the transform, its spare and the keys go back to the device.  While the latch is on they stay, the keys
+    // included, so that a set at sensor rate allocates nothing
+    C.d_near.release(); C.d_near_next.release(); C.d_nearkey.release();
+    return LOIKB_OK;
+  }
+  if (C.have_grid) {
+    BUFCHK(C.d_near_next.regrow(sizeof(unsigned int) * (size_t)C.gn[0] * C.gn[1] * C.gn[2]));
+    if (int rc = gridnear_build(S, C.d_grid, C.gn[0], C.gn[1], C.gn[2], C.d_near_next)) return rc;
+    HIPCHK(hipStreamSynchronize(S->stream));
+    C.d_near.swap(C.d_near_next);
+  }
+  C.near_on = true;
+  return LOIKB_OK;
+}
+
+int loikb_collision_grid_get_nearest(loikb_solver* S, unsigned int* F, int out_flags)
+{
+  if (!S) return 0;
+  if (out_flags & ~LOIKB_OUT_DEVICE) { g_last_error = "collision_grid_get_nearest: out_flags other than LOIKB_OUT_DEVICE"; return LOIKB_ERR_ARG; }
+  const Collision& C = S->pose.col;
+  if (!C.have_grid || !C.near_on) return 0;
+  if (F) {
+    HIPCHK(hipSetDevice(S->device));
+    if (int rc = get_copy_out(S, (const unsigned int*)C.d_near, sizeof(unsigned int) * (size_t)C.gn[0] * C.gn[1] * C.gn[2], F, out_flags)) return rc;
+  }
+  return 1;
+}
+
+int loikb_grid_nearest_query(loikb_solver* S, const double* spheres, int n, int in_flags, double* out_val, int* out_vox, double* out_normal, int out_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  if (n < 0 || (n > 0 && (!spheres || !out_val || !out_vox || !out_normal))) { g_last_error = "grid_nearest_query: need n >= 0 and every array when n > 0"; return LOIKB_ERR_ARG; }
+  if (in_flags & ~LOIKB_IN_DEVICE) { g_last_error = "grid_nearest_query: in_flags other than LOIKB_IN_DEVICE"; return LOIKB_ERR_ARG; }
+  const Collision& C = S->pose.col;
+  if (!C.have_grid) { g_last_error = "grid_nearest_query: no voxel grid set (loikb_collision_set_world_grid)"; return LOIKB_ERR_STATE; }
+  if (!C.near_on) { g_last_error = "grid_nearest_query: the nearest-voxel transform is not latched (loikb_collision_grid_set_nearest)"; return LOIKB_ERR_STATE; }
+  if (n == 0) return LOIKB_OK;
+  HIPCHK(hipSetDevice(S->device));
+  QueryOut o(S, out_flags);
+  double *d_val, *d_nrm;
+  int* d_vox;
+  o.add(out_val, sizeof(double) * 2 * (size_t)n, &d_val);
+  o.add(out_normal, sizeof(double) * 3 * (size_t)n, &d_nrm);
+  o.add(out_vox, sizeof(int) * 2 * (size_t)n, &d_vox);
+  int rc;
+  const void* ds = nullptr;
+  if ((rc = to_device(S, spheres, sizeof(double) * 4 * (size_t)n, in_flags & LOIKB_IN_DEVICE, &ds)) || (rc = o.reserve())) return rc;
+  hipLaunchKernelGGL(k_grid_nearest_query, grid1((size_t)n), dim3(256), 0, S->stream, (const double*)ds, n, clr_model(S).g, d_val, d_vox, d_nrm);
+  HIPCHK(hipGetLastError());
+  return o.finish();   // (the caller's spheres have been read)
 }
 
 // One clearance launch over n rows of the device array dq [n][nq] into d_min [n][3] and d_wit [n][3] (or nullptr).  Queued.
@@ -1294,8 +1402,9 @@ static int avoid_check_model(const loikb_solver_impl* S, const char* fn)
   const Collision& C = S->pose.col;
   const std::string f(fn);
   if (C.ns == 0) { g_last_error = f + ": no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
-  if (C.have_grid) {
-    g_last_error = f + ": a voxel grid is set (loikb_collision_set_world_grid), and its clearance bound has no gradient for avoidance to follow -- clear the grid first";
+  if (C.have_grid && !C.near_on) {
+    g_last_error = f + ": a voxel grid is set (loikb_collision_set_world_grid), and its clearance bound has no gradient for avoidance to follow -- clear the grid first."
+                       "  With the nearest-voxel transform latched (loikb_collision_grid_set_nearest) avoidance reads the grid.";
     return LOIKB_ERR_STATE;
   }
   if (C.ns > LOIKB_AVOID_MAX_SPHERES) {

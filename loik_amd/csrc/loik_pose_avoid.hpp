@@ -11,7 +11,10 @@
 //                           over the world with a butterfly across the obstacle slots, under clr_before with the ordinal of the object
 //                           (world spheres first, then boxes); the self pairs whose first index is a are one contiguous stretch of the
 //                           sorted list, found by bisection (its trip count depends on the list alone), and a lane per sphere walks it.
-//                           Both go into the table tv / to [ns][2];
+//                           Both go into the table tv / to [ns][2].  A handle that latched the nearest-voxel transform of a voxel world
+//                           (m.g.F not null: loik_pose_gridnear.hpp) has one more world object per sphere, the grid, at ordinal
+//                           nws + nwb: the lane with obstacle slot 0 adds its pair at the lower bound of clr_sphere_grid before the
+//                           butterfly, as k_clearance does, and avd_entry takes the normal of the cube gridnear_cube chooses;
 //                        6. (before 4, its result feeds MODE_GRAD) the overall minimum of the table under clr_before with
 //                           k_clearance's ordinals: the same values under the same total order, so the same bits as k_clearance;
 //                        4. the entries under d_influence are compacted with a ballot and a prefix count into a list; the lane that
@@ -37,7 +40,7 @@
 // fp64 whatever the handle's precision, as loik_pose.hpp.
 #pragma once
 
-#include "loik_pose_collision.hpp"
+#include "loik_pose_gridnear.hpp"
 
 namespace loikb {
 
@@ -92,8 +95,8 @@ __device__ __forceinline__ bool avd_on_path(const unsigned int* anc, int W, int 
   return dj > 0 && ((anc[(size_t)(dj - 1) * W + (j >> 5)] >> (j & 31)) & 1u);
 }
 
-// One list entry at `e`: the pair of sphere a with the world object `o` (world spheres first, then boxes), or with the second sphere of
-// self pair `o`, at clearance d
+// One list entry at `e`: the pair of sphere a with the world object `o` (world spheres first, then boxes, then -- o = nws + nwb, which only
+// a handle that latched the nearest-voxel transform can hold -- the voxel grid), or with the second sphere of self pair `o`, at clearance d
 __device__ __forceinline__ void avd_entry(double* e, const double* cen, const int* sj, const unsigned int* anc, int W, const ClrModel& m, int a,
                                           bool self, unsigned int o, double d, const AvoidPrm& prm)
 {
@@ -107,6 +110,10 @@ __device__ __forceinline__ void avd_entry(double* e, const double* cen, const in
     const double e0 = c[0] - w[0], e1 = c[1] - w[1], e2 = c[2] - w[2];
     const double len = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
     if (len != 0.0) { n0 = e0 / len; n1 = e1 / len; n2 = e2 / len; }
+  } else if (o >= (unsigned int)(m.nws + m.nwb)) {   // the grid: the normal of the cube chosen among the features around the centre
+    GridNearPair gn;
+    gridnear_cube(c[0], c[1], c[2], m.g, gn);
+    n0 = gn.n[0]; n1 = gn.n[1]; n2 = gn.n[2];
   } else {
     const double* __restrict__ Wb = m.wbox + (size_t)15 * (o - (unsigned int)m.nws);
     const double e0 = c[0] - Wb[9], e1 = c[1] - Wb[10], e2 = c[2] - Wb[11];
@@ -232,6 +239,11 @@ k_avoid_box(const double* __restrict__ q, int nq, const JointDesc* __restrict__ 
       const unsigned int ord = (unsigned int)(m.nws + o);
       if (clr_before(v, ord, bv, bo)) { bv = v; bo = ord; }
     }
+    if (m.g.F && (lane >> lp) == 0) {   // (wavefront-uniform: a handle that latched the nearest-voxel transform, with a grid set)
+      const double v = clr_sphere_grid(c[0], c[1], c[2], c[3], m.g).v;
+      const unsigned int ord = (unsigned int)(m.nws + m.nwb);
+      if (clr_before(v, ord, bv, bo)) { bv = v; bo = ord; }
+    }
     for (int off = P; off < 64; off <<= 1) {
       const double ov = __shfl_xor(bv, off);
       const unsigned int oo = (unsigned int)__shfl_xor((int)bo, off);
@@ -265,6 +277,7 @@ k_avoid_box(const double* __restrict__ q, int nq, const JointDesc* __restrict__ 
 
   // 6. the overall minimum with k_clearance's ordinals
   const unsigned int nps = (unsigned int)ns * (unsigned int)m.nws, npb = (unsigned int)ns * (unsigned int)m.nwb;
+  const unsigned int npg = m.g.F ? (unsigned int)ns : 0u, nwo = (unsigned int)(m.nws + m.nwb);   // the grid pairs, grid0() + a of ClrOrdinals
   double best = inf, mw = inf, msf = inf;
   unsigned int bord = CLR_NO_ORDINAL;
   for (int t = lane; t < 2 * ns; t += 64) {
@@ -272,8 +285,11 @@ k_avoid_box(const double* __restrict__ q, int nq, const JointDesc* __restrict__ 
     const unsigned int o = to[t], a = (unsigned int)t >> 1;
     if (o == CLR_NO_ORDINAL) continue;
     unsigned int g;
-    if (t & 1) { g = nps + npb + o; msf = v < msf ? v : msf; }
-    else { g = o < (unsigned int)m.nws ? a * (unsigned int)m.nws + o : nps + a * (unsigned int)m.nwb + (o - (unsigned int)m.nws); mw = v < mw ? v : mw; }
+    if (t & 1) { g = nps + npb + npg + o; msf = v < msf ? v : msf; }
+    else {
+      g = o < (unsigned int)m.nws ? a * (unsigned int)m.nws + o : (o < nwo ? nps + a * (unsigned int)m.nwb + (o - (unsigned int)m.nws) : nps + npb + a);
+      mw = v < mw ? v : mw;
+    }
     if (clr_before(v, g, best, bord)) { best = v; bord = g; }
   }
   for (int off = 32; off > 0; off >>= 1) {
@@ -295,8 +311,12 @@ k_avoid_box(const double* __restrict__ q, int nq, const JointDesc* __restrict__ 
       else if (bord < nps + npb) {
         const unsigned int r = bord - nps;
         kind = CLR_WORLD_BOX; wa = (int)(r / (unsigned int)m.nwb); wb = (int)(r - (unsigned int)wa * (unsigned int)m.nwb); o = (unsigned int)(m.nws + wb);
+      } else if (bord - nps - npb < npg) {
+        kind = CLR_WORLD_GRID; wa = (int)(bord - nps - npb); o = nwo;
+        const double* cw = cen + (size_t)4 * wa;
+        wb = (int)clr_sphere_grid(cw[0], cw[1], cw[2], cw[3], m.g).vox;
       } else {
-        o = bord - nps - npb;
+        o = bord - nps - npb - npg;
         kind = CLR_SELF; wa = m.pairs[2 * (size_t)o]; wb = m.pairs[2 * (size_t)o + 1]; self = true;
       }
       if (lane == 0) avd_entry(list, cen, sj, anc, W, m, wa, self, o, best, prm);

@@ -50,6 +50,7 @@ struct ClrGrid {
   int n[3];                      // nx, ny, nz
   double o[3], hi[3];            // the low corner of voxel (0, 0, 0); the high corner of the grid's box, o + n h as the host rounded it
   double h, inv_h;               // the edge, 1 / edge as the host rounded it
+  const unsigned int* F;         // the nearest-voxel transform (loik_pose_gridnear.hpp), laid out as G; nullptr unless the handle latched it
 };
 
 // the model as the kernel reads it (device pointers)
