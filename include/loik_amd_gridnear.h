@@ -41,6 +41,14 @@
  * below the distance by up to sqrt(3) h, so a sphere cannot come nearer to O than d_safe plus up to sqrt(3) h.  The gradient row is
  * n^T Jc: the derivative of the distance to the chosen cube, not of v, which is piecewise constant in the voxel read.
  *
+ * An empty grid under the latch.  Every grid pair then has v = +inf and still holds its ordinal.  It is under no d_influence and
+ * narrows nothing: the box of loikb_avoid_box and of the pose loops is that of a handle without a grid, bit for bit.  +inf comes after
+ * every number, so beside any other world object the grid is never a sphere's partner, and beside any other pair never the witness.
+ * With no other world object it is the sphere's partner, nws + nwb = 0, at clearance +inf, where a handle without a grid reports -1;
+ * and in a configuration with no other pair at all, where every minimum is +inf, ties go to the lowest ordinal as always: the witness
+ * of loikb_clearance and loikb_clearance_gradient is { LOIKB_CLR_WORLD_GRID, 0, the voxel read for sphere 0 }, where a handle without a
+ * grid reports { LOIKB_CLR_NONE, -1, -1 }, and the gradient row is 0.
+ *
  * loikb_collision_grid_set_nearest(s, 1) sets the latch.  If a grid is set it builds F for it on the handle's stream, complete on
  * return; every later loikb_collision_set_world_grid builds G and F, both into spare buffers that change places with the resident
  * ones after both builds succeeded, so a failed set leaves both as they were.  While the latch is on the handle keeps F, its spare and

@@ -210,6 +210,17 @@ def clearance_gradient(model, q, links, spheres, ws=(), wb=(), pairs=()):
     return out
 
 
+def constraints_of(model, q, col, avoid):
+    """constraints() of a pose loop's collision model col = dict(links, spheres, ws, wb, pairs[, grid]).  With a voxel grid in it
+    (col["grid"], a gridnear_numpy.Grid): gridnear_numpy.constraints, the grid one more world object, clamped as a pose loop clamps.
+    Without one, or with grid = None, the very call this function replaced"""
+    if col.get("grid") is not None:
+        import gridnear_numpy as NN   # (it imports this module)
+        return NN.constraints(model, q, col["links"], col["spheres"], col["ws"], col["wb"], col["pairs"], avoid["d_influence"], col["grid"],
+                              d_safe=avoid["d_safe"], clamped=True)
+    return constraints(model, q, col["links"], col["spheres"], col["ws"], col["wb"], col["pairs"], avoid["d_influence"], d_safe=avoid["d_safe"])
+
+
 def narrower(model, col, avoid, dt, B):
     """the `narrow` hook of pose_path_numpy.lockstep_path_loop, pose_track_numpy.lockstep_track_loop and
     pose_step_numpy.lockstep_pose_loop_step: a callable narrow(b, q_b, lo, hi) -> (lo2, hi2) that narrows the step's interval as
@@ -219,7 +230,7 @@ def narrower(model, col, avoid, dt, B):
                avoid_flags=np.zeros((B, model.nv), dtype=np.int32), near=np.zeros(B, dtype=bool))
 
     def narrow_step(b, q_b, lo, hi):
-        cons, nr, t = constraints(model, q_b[None], col["links"], col["spheres"], col["ws"], col["wb"], col["pairs"], avoid["d_influence"], d_safe=avoid["d_safe"])
+        cons, nr, t = constraints_of(model, q_b[None], col, avoid)
         res["near"][b] |= bool(nr[0])
         res["avoid_min_seen"][b] = min(res["avoid_min_seen"][b], float(np.min(t["pairs"][0])))
         nlo, nhi = narrow(cons[0], lo, hi, avoid["d_safe"], avoid["kappa"], dt)[:2]
@@ -284,7 +295,7 @@ def lockstep_pose_loop_avoid(model, prm, q0, H_ref, v_ref, links, A, lb, ub, tar
             else:
                 import pose_accel_numpy as PA
                 lo, hi, flags[b], inside = PA.dyn_box(q[b], zp, np.asarray(a_max, dtype=float), q_lo, q_hi, lb_b, ub_b, dt, qidx)
-            cons, nr, t = constraints(model, q[b:b + 1], col["links"], col["spheres"], col["ws"], col["wb"], col["pairs"], avoid["d_influence"], d_safe=avoid["d_safe"])
+            cons, nr, t = constraints_of(model, q[b:b + 1], col, avoid)
             near[b] |= bool(nr[0])
             min_seen[b] = min(min_seen[b], float(np.min(t["pairs"][0])))
             nlo, nhi = narrow(cons[0], lo, hi, avoid["d_safe"], avoid["kappa"], dt)[:2]

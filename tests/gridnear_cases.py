@@ -130,6 +130,92 @@ def fd_case():
     return _CACHE["fd"]
 
 
+# ---- 3b. the sizes and the worlds of the grid branch ---------------------------------------------------------------------------------------
+# lp = 0, 1, 2 and 6 sphere slots a wavefront, partial last trips on either side of 64, and the largest model
+SIZE_NS = [1, 2, 3, 33, 63, 64, 65, 256]
+# ((world spheres, boxes) beside the grid, self pairs on): the grid alone (nws == 0 and nwb == 0: the ordinal arithmetic of the grid pair
+# with nothing before it), one kind of object missing, and a full world
+SIZE_WORLDS = (((0, 0), False), ((0, 0), True), ((1, 0), False), ((0, 1), True), ((33, 32), False), ((33, 32), True))
+SIZE_WORLD_SCALE = 0.25   # the radii and half extents of the full world, against test_clearance._world's
+SIZE_ROWS = 17   # configurations (9 at 256 spheres): a last workgroup with idle wavefronts; the reference is O(n ns^2)
+# the seed of each size's worlds: the first from 0 on for which test_gridnear_numpy.test_size_inputs_with_a_grid holds
+SIZE_SEEDS = {1: 1}   # (the one sphere of ns = 1 sits on the universe: the first draw puts the world's sphere nearer to it than any cube)
+
+
+def size_grid():
+    """the grid of every size: test_grid_clearance._grid around panda7's base at a density of 2 %"""
+    if "sgrid" not in _CACHE:
+        import test_grid_clearance as TG
+        _CACHE["sgrid"] = NN.of(TG._grid(3300, frac=0.02))
+    return _CACHE["sgrid"]
+
+
+def size_inputs(ns):
+    """test_avoid_box.size_inputs(ns) -- panda7, the spheres dealt round-robin to the links 0..7 -- with the worlds of SIZE_WORLDS beside
+    size_grid(); a world with self pairs on is left out where the spheres have none (ns <= 2)"""
+    if ("sizes", ns) not in _CACHE:
+        import test_avoid_box as TB
+        import test_clearance as TC
+        base = TB.size_inputs(ns)[0]
+        model, links, spheres = base["model"], base["links"], base["spheres"]
+        q = base["q"][:SIZE_ROWS]
+        pairs_on = CN.self_pairs(model.parents, links)
+        rng = np.random.default_rng(3310 + 100 * SIZE_SEEDS.get(ns, 0) + ns)
+        out = []
+        for split, self_on in SIZE_WORLDS:
+            if self_on and not pairs_on:
+                continue
+            ws, wb = TC._world(rng, *split)
+            if split[0] > 1:   # (65 objects of the stock size hold the overall minimum in every row: no grid witness would occur)
+                ws[:, 3] *= SIZE_WORLD_SCALE
+                wb[:, 12:15] *= SIZE_WORLD_SCALE
+            pairs = pairs_on if self_on else []
+            out.append(dict(what="panda7 ns=%d world=%d+%d+grid self=%d" % (ns, split[0], split[1], len(pairs)), model=model, q=q, links=links,
+                            spheres=spheres, ws=ws, wb=wb, pairs=pairs, split=split, self_on=self_on, grid=size_grid()))
+        _CACHE[("sizes", ns)] = out
+    return _CACHE[("sizes", ns)]
+
+
+def size_ref(inp):
+    """the numpy box and gradient of one of those inputs, computed once"""
+    key = ("sizeref", inp["what"])
+    if key not in _CACHE:
+        import test_avoid_box as TB
+        args = (inp["model"], inp["q"], inp["links"], inp["spheres"], inp["ws"], inp["wb"], inp["pairs"])
+        _CACHE[key] = dict(box=NN.avoidance_box(*args, TB.DT, -np.inf, np.inf, grid=inp["grid"], **TB.PRM),
+                           grad=NN.clearance_gradient(*args, grid=inp["grid"]))
+    return _CACHE[key]
+
+
+def half_grid_case():
+    """avoid_case("panda7") against the middle half of size_grid()'s extent along every axis (the query grid's box and voxel, at a density
+    that leaves an eighth of the volume some cubes): the arm leaves the grid's box, so many centres are clamped into it (dout > 0, and
+    clamped indices among the candidates)"""
+    if "half" not in _CACHE:
+        import test_avoid_box as TB
+        c = dict(avoid_case("panda7"))
+        g = size_grid()
+        nz, ny, nx = g.occ.shape
+        z0, y0, x0 = nz // 4, ny // 4, nx // 4
+        occ = np.ascontiguousarray(g.occ[z0:z0 + (nz + 1) // 2, y0:y0 + (ny + 1) // 2, x0:x0 + (nx + 1) // 2])
+        c["grid"] = NN.Grid(occ, g.origin + g.h * np.array([x0, y0, z0], dtype=float), g.h)
+        args = (c["model"], c["q"], c["links"], c["spheres"], c["ws"], c["wb"], c["pairs"])
+        c["box"] = NN.avoidance_box(*args, TB.DT, -np.inf, np.inf, grid=c["grid"], **TB.PRM)
+        c["grad"] = NN.clearance_gradient(*args, grid=c["grid"])
+        cen = c["box"]["centres"]
+        c["outside"] = ((cen < c["grid"].origin) | (cen > c["grid"].hi)).any(axis=-1)   # [n][ns]
+        _CACHE["half"] = c
+    return _CACHE["half"]
+
+
+def empty_grid_case():
+    """avoid_case("panda7") with no voxel occupied"""
+    c = dict(avoid_case("panda7"))
+    g = c["grid"]
+    c["grid"] = NN.Grid(np.zeros_like(g.occ), g.origin, g.h)
+    return c
+
+
 # ---- 4. the pose loops -------------------------------------------------------------------------------------------------------------------
 def pose_workload(name):
     """test_avoid_pose._workload(name, 0) with a grid beside its spheres and boxes.  The robot starts clear of the voxels: a cube within

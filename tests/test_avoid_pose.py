@@ -61,7 +61,7 @@ def _workload(name, variant):
     return _WORK[key]
 
 
-def _latched(w, precision=capi.F64, avoid=AVOID, limits=True, q0=None):
+def _latched(w, precision=capi.F64, avoid=AVOID, limits=True, q0=None, grid=False):
     s = _handle(w["model"], w["B"], w["links"], w["q0"] if q0 is None else q0, w["A"], PRM, precision=precision, box=w["box"])
     c = w["col"]
     s.set_collision_spheres(c["links"], c["spheres"])
@@ -71,9 +71,20 @@ def _latched(w, precision=capi.F64, avoid=AVOID, limits=True, q0=None):
         s.set_joint_limits(w["q_lo"], w["q_hi"])
     if limits and w.get("a_max") is not None:
         s.set_joint_accel_limits(w["a_max"])
+    if grid:
+        _latch_grid(s, c)
     if avoid is not None:
         s.set_collision_avoidance(**avoid)
     return s
+
+
+def _latch_grid(s, col):
+    """_latched(grid=True) on a workload with a voxel grid (col["grid"], gridnear_cases.pose_workload): the nearest-voxel transform
+    latched and the grid set, before avoidance is (the order of test_gridnear_pose._with_grid).  Without one: nothing"""
+    g = col.get("grid")
+    if g is not None:
+        s.set_collision_grid_nearest(True)
+        s.set_collision_grid(g.occ, g.origin, g.h)
 
 
 def _oracle(w, dt, gain, k, avoid=AVOID):

@@ -159,13 +159,20 @@ def back_oracle():
 
 def resting_on_narrowed(w, law):
     """how many entries of the oracle's z of the first step rest (within 1e-9: the inner solve's tolerance) on a narrowed side that is not 0"""
+    lo_hi = resting_entries(w, law, sides=True)
+    return int(lo_hi[0].sum() + lo_hi[1].sum())
+
+
+def resting_entries(w, law, sides=False):
+    """[B][nv] bool: the entries resting_on_narrowed counts (`sides`: those on the lower and those on the upper side, apart)"""
     dt, gain = law
     o, c, nv = TP._oracle(w, dt, gain, 1), w["col"], w["model"].nv
     lb, ub = (np.broadcast_to(x, (w["B"], nv)) for x in w["box"])
     box = AN.avoidance_box(w["model"], w["q0"], c["links"], c["spheres"], c["ws"], c["wb"], c["pairs"], dt, -np.inf * np.ones(nv), np.inf * np.ones(nv), **AVOID)
     lo, hi = np.minimum(np.maximum(box["lo"], lb), ub), np.minimum(np.maximum(box["hi"], lb), ub)
     ran = (o["steps"] == 1)[:, None]
-    return int(((np.abs(o["z"] - lo) < 1e-9) & (lo > lb) & (lo != 0.0) & ran).sum() + ((np.abs(o["z"] - hi) < 1e-9) & (hi < ub) & (hi != 0.0) & ran).sum())
+    on_lo, on_hi = (np.abs(o["z"] - lo) < 1e-9) & (lo > lb) & (lo != 0.0) & ran, (np.abs(o["z"] - hi) < 1e-9) & (hi < ub) & (hi != 0.0) & ran
+    return (on_lo, on_hi) if sides else on_lo | on_hi
 
 
 def contain_case(box_inst):
@@ -336,11 +343,12 @@ def multistart_workload():
     return _WORK["ms"]
 
 
-def multistart_oracle():
+def multistart_oracle(w=None):
     """pose_multistart_numpy.multistart_loop with lockstep_pose_loop_avoid as the round: dict(q, round, rounds_run, answered, last = the
-    last round's result)"""
-    if "ms" not in _ORACLE:
-        w = multistart_workload()
+    last round's result); of multistart_workload(), or of that workload with another collision model"""
+    w = multistart_workload() if w is None else w
+    key = ("ms", id(w))
+    if key not in _ORACLE:
         model, G, K, lo, hi = w["model"], w["G"], w["K"], w["lo"], w["hi"]
         lb, ub = w["box"]
         tg = np.repeat(w["tg"], K, axis=0)
@@ -354,8 +362,8 @@ def multistart_oracle():
                 break
             q, fresh = M.resample(model, o["q"], o["status"], w["q0g"], K, MS_DRAW, r + 1, lo, hi)
             rnd[fresh] = r + 1
-        _ORACLE["ms"] = dict(q=o["q"], round=rnd, rounds_run=len(answered), answered=answered, last=o)
-    return _ORACLE["ms"]
+        _ORACLE[key] = dict(q=o["q"], round=rnd, rounds_run=len(answered), answered=answered, last=o)
+    return _ORACLE[key]
 
 
 # ---- what the tests share ----------------------------------------------------------------------------------------------------------
@@ -364,6 +372,7 @@ def _arm(s, w, avoid=AVOID):
     s.set_collision_spheres(c["links"], c["spheres"])
     s.set_collision_world(c["ws"], c["wb"])
     s.set_self_collision(True)
+    TP._latch_grid(s, c)
     if avoid is not None:
         s.set_collision_avoidance(**avoid)
     return s
@@ -401,7 +410,7 @@ def _measured(what, out_q, o_q, same, keep, bad, o):
 def _solve_pose_parity(w, dt, gain, k, what, limits, exact=False):
     """the body of test_avoid_pose.test_solve_pose_matches_lockstep_oracle"""
     idx = np.arange(w["B"])
-    s = _latched(w)
+    s = _latched(w, grid=True)   # (a workload of test_gridnear_routes.py names a grid in its collision model; the others none)
     out = s.SolvePose(w["tg"], dt=dt, gain=gain, tol_pose=TOL, max_steps=k)
     q = s.get("q")
     s.close()
@@ -478,6 +487,14 @@ def test_per_instance_base_box_comes_back(precision):
               % (int(o["idle"].sum()), int(told.sum()), o["outside"][keep][same][told], dz[told].max() if told.any() else np.nan))
         assert told.any() and np.all(dz[told] < 1e-7), dz[told]
     assert not np.array_equal(q, t.get("q"))
+    _cold_solve_in_the_base_box(s, t, w, q, dt, gain)
+    s.close(); t.close()
+
+
+def _cold_solve_in_the_base_box(s, t, w, q, dt, gain):
+    """s ran with the latch, its twin t never had it: the latch cleared, both put on q and started cold with a b large enough that the
+    per-instance base box binds -- z and iter bit-equal, z inside the box and on it in half the instances"""
+    lb, ub = w["box"]
     rng = np.random.default_rng(6)
     b = rng.choice([-1.0, 1.0], size=(w["B"], 6)) * (3.0 + rng.random((w["B"], 6)))
     s.clear_collision_avoidance()
@@ -491,7 +508,6 @@ def test_per_instance_base_box_comes_back(precision):
     assert np.array_equal(s.get("iter"), t.get("iter")) and np.array_equal(zs, zt)
     assert np.all(zs >= lb) and np.all(zs <= ub)
     assert ((zs == lb) | (zs == ub)).any(axis=1).mean() >= 0.5, "the per-instance base box does not bind: the test shows nothing"
-    s.close(); t.close()
 
 
 # ---- d. exact containment without limits -------------------------------------------------------------------------------------------------
@@ -508,7 +524,7 @@ def _check_containment(w, precision, what, calls=CONTAIN_CALLS, **kw):
     B, nv = w["B"], w["model"].nv
     lb, ub = (np.broadcast_to(x, (B, nv)) for x in w["box"])
     s = _loop_handle(w, precision=precision, **kw)   # (no limits on these workloads: _latched with the engine's options)
-    ref = s if precision == capi.F64 else _latched(w)   # (the query does not round; an fp64 handle answers it from the same fp64 q)
+    ref = s if precision == capi.F64 else _latched(w, grid=True)   # (the query does not round; an fp64 handle answers it from the same fp64 q)
     inf = np.inf * np.ones(nv)
     q, rests, narrowed, inexact = w["q0"], 0, 0, 0
     for call in range(calls):
@@ -564,8 +580,11 @@ def test_every_engine_honours_the_narrowed_box(engine, monkeypatch):
 def test_path_with_a_budget_matches_the_path_oracle(case):
     """avoid_step is handed the path loop's own status word: an instance the budget stalled is idle, one that reached a waypoint but not
     the last still runs and is narrowed"""
+    _check_path(path_workload(*case), case)
+
+
+def _check_path(w, case):
     from test_pose_path import _path_gate
-    w = path_workload(*case)
     dt, gain = PATH_LAW
     s = _loop_handle(w)
     out = s.SolvePosePath(w["wp"], dt=dt, gain=gain, tol_pose=TOL, max_steps=PATH_STEPS, max_steps_per_waypoint=PATH_BUDGET)
@@ -587,8 +606,11 @@ def test_path_with_a_budget_matches_the_path_oracle(case):
 # ---- f. TrackPose ----------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", TRACKS, ids=lambda c: "%s-%s" % (c[0], "limits" if c[1] else "nolimits"))
 def test_track_with_feedforward_matches_the_track_oracle(case):
+    _check_track(track_workload(*case), case)
+
+
+def _check_track(w, case):
     from test_pose_track import _track_gate
-    w = track_workload(*case)
     dt, gain = TRACK_LAW
     s = _loop_handle(w)
     out = s.TrackPose(w["smp"], dt=dt, gain=gain, tol_track=TRACK_TOL, feedforward="difference")
@@ -645,10 +667,13 @@ def test_track_through_the_wall_keeps_every_z_inside_the_clamped_query():
 def test_step_control_with_the_latch_matches_the_step_oracle(case):
     """the narrowed box under the backtracking search; with patience, a search that ends STALLED after the box was narrowed counts in the
     avoidance results (the sentence of loik_amd_avoid.h)"""
+    _check_step(step_workload(case[0], case[1]), case)
+
+
+def _check_step(w, case):
     from test_pose_step import _assert_parity
     name, seed, ctl = case
-    w = step_workload(name, seed)
-    s = _latched(w)
+    s = _latched(w, grid=True)
     s.set_step_control(**ctl)
     out = s.SolvePose(w["tg"], dt=STEP_DT, gain=STEP_GAIN, tol_pose=TOL, max_steps=STEP_STEPS)
     out["q"] = s.get("q")
@@ -672,8 +697,11 @@ def test_step_control_with_the_latch_matches_the_step_oracle(case):
 def test_multistart_three_rounds_match_the_host_driven_sequence_with_the_latch():
     """test_multistart.test_three_rounds_match_the_host_driven_sequence with the latch on both handles: q, the winners and the three
     avoidance results -- those of the last round -- bit for bit"""
+    _check_multistart(multistart_workload())
+
+
+def _check_multistart(w):
     from test_multistart import _check_selection, _mk, _pose_fields
-    w = multistart_workload()
     model, links, lo, hi, G, K = w["model"], w["links"], w["lo"], w["hi"], w["G"], w["K"]
     q_init = np.repeat(w["q0g"], K, axis=0)
     a, b = _arm(_mk(model, G * K, links, q_init, lo, hi), w), _arm(_mk(model, G * K, links, q_init, lo, hi), w)
@@ -702,6 +730,6 @@ def test_multistart_three_rounds_match_the_host_driven_sequence_with_the_latch()
     assert earlier.any() and np.all(np.isposinf(out["avoid_min_seen"][earlier])) and not out["avoid_active_steps"][earlier].any()
     assert not out["avoid_flags"][earlier].any()
     assert (out["avoid_active_steps"][~earlier] > 0).any()
-    want = multistart_oracle()
+    want = multistart_oracle(w)
     assert np.array_equal(out["round"], want["round"]) and np.array_equal(earlier, want["last"]["reached"] & (want["last"]["steps"] == 0))
     a.close(); b.close()

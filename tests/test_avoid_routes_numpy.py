@@ -235,8 +235,8 @@ def test_step_control_inputs(case):
     assert step_conditions(w, case[2]) == []
 
 
-def multistart_conditions():
-    o = R.multistart_oracle()
+def multistart_conditions(w=None):
+    o = R.multistart_oracle(w)
     last = o["last"]
     earlier = last["reached"] & (last["steps"] == 0)
     miss = [] if last["near"].mean() <= NEAR_SHARE else ["near"]

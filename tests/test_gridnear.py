@@ -12,6 +12,7 @@ from loik_amd import capi
 from test_avoid_box import BOX_BOUND, DT, GRAD_BOUND, PRM, _back, _err, _ints, _rel, _scale
 from test_clearance import BOUND, _open
 from test_grid_build import _DeviceBytes
+import clearance_numpy as CN
 import grid_numpy as GN
 import gridnear_cases as GC
 import gridnear_numpy as NN
@@ -218,6 +219,113 @@ def test_gradient_and_box_match_numpy(name):
         msg = _err(fn, ERR_STATE)
         assert "grid" in msg and "avoidance" in msg and "loikb_collision_grid_set_nearest" in msg
     u.close()
+
+
+def _check_with_grid(s, inp, ref):
+    """test_avoid_box._check_against_numpy with the grid: the box and the gradient of the handle's resident q against ref = dict(box,
+    grad) of gridnear_numpy, under the bounds and with the rows and entries left out as in test_gradient_and_box_match_numpy; the minima
+    and the witness of clearance() bit for bit; 3 and 1 of the rows bit for bit.  Returns (box, gradient) of the device"""
+    what, q, spheres = inp["what"], inp["q"], inp["spheres"]
+    want, wg = ref["box"], ref["grad"]
+    scale = _scale(want["centres"], spheres)
+    gg, plain = s.clearance_gradient(), s.clearance()
+    for k in ("min", "min_world", "min_self", "witness"):
+        assert np.array_equal(gg[k], plain[k]), (what, k)
+    kg, keep = ~wg["near"], ~want["near"]
+    assert np.array_equal(gg["witness"][kg], wg["witness"][kg]), what
+    assert np.all(np.abs(gg["min"][kg] - wg["min"][kg]) <= BOUND * scale), what
+    eg = float(np.max(np.abs(gg["grad"][kg] - wg["grad"][kg]), initial=0.0)) / scale
+    assert eg <= GRAD_BOUND, (what, eg)
+    got = s.avoidance_box(None, DT, -np.inf, np.inf, **PRM)
+    inf = np.isposinf(want["pairs"][keep])
+    assert np.array_equal(np.isposinf(got["pairs"][keep]), inf), what
+    e = float(np.max(np.abs(got["pairs"][keep][~inf] - want["pairs"][keep][~inf]), initial=0.0))
+    assert e <= BOUND * scale, (what, e, scale)
+    assert np.array_equal(got["partner"][keep], want["partner"][keep]), what
+    assert np.all(got["lo"] <= 0.0) and np.all(got["hi"] >= 0.0), what
+    mask = keep[:, None] & ~want["tiny"]
+    worst = max(_rel(got["lo"][mask], want["lo"][mask], what), _rel(got["hi"][mask], want["hi"][mask], what))
+    print("gridnear_measured %s: box max relative error %.3e, gradient %.3e / scale, clearances %.3e / scale %.3f, left out %d + %d rows, %d grid witnesses"
+          % (what, worst, eg, e, scale, int((~keep).sum()), int((~kg).sum()), int((gg["witness"][:, 0] == GN.WORLD_GRID).sum())))
+    assert worst <= BOX_BOUND, (what, worst)
+    for n in (3, 1):   # an explicit q, n != B: a last workgroup with idle wavefronts
+        sub, subg = s.avoidance_box(q[:n], DT, -np.inf, np.inf, **PRM), s.clearance_gradient(q[:n])
+        assert all(np.array_equal(sub[k], got[k][:n]) for k in got), (what, n)
+        assert all(np.array_equal(subg[k], gg[k][:n]) for k in gg), (what, n)
+    return got, gg
+
+
+@pytest.mark.parametrize("ns", GC.SIZE_NS)
+def test_sizes_with_a_grid(ns):
+    """test_avoid_box.test_sizes with a grid latched: 2^lp = 1, 2, 4 and 64 sphere slots a wavefront, partial last trips, and the worlds in
+    which the grid's ordinal arithmetic degenerates -- the grid alone (nws == nwb == 0), one kind of object missing -- self pairs off
+    and on; a grid witness in every world (test_gridnear_numpy.test_size_inputs_with_a_grid says so of the reference)"""
+    inputs = GC.size_inputs(ns)
+    model, q, links, spheres, g = (inputs[0][k] for k in ("model", "q", "links", "spheres", "grid"))
+    s = _open(model, q)
+    s.set_collision_spheres(links, spheres)
+    s.set_collision_grid_nearest(True)
+    s.set_collision_grid(g.occ, g.origin, g.h)
+    for inp in inputs:
+        s.set_collision_world(inp["ws"], inp["wb"])
+        s.set_self_collision(inp["self_on"])
+        got, gg = _check_with_grid(s, inp, GC.size_ref(inp))
+        assert (gg["witness"][:, 0] == GN.WORLD_GRID).any(), inp["what"]
+        nwo = inp["ws"].shape[0] + inp["wb"].shape[0]
+        assert (got["partner"][:, :, 0] == nwo).any(), inp["what"]
+        if not inp["self_on"]:
+            assert np.all(np.isposinf(got["pairs"][:, :, 1])) and np.all(got["partner"][:, :, 1] == -1)
+        if inp["split"] == (0, 0):   # the grid is every sphere's only world object
+            assert np.all(got["partner"][:, :, 0] == 0) and np.isfinite(got["pairs"][:, :, 0]).all()
+    s.close()
+
+
+def test_the_robot_leaves_the_grids_box():
+    """half the extent: most centres lie outside the grid's box and are clamped into it (the dout > 0 branch of clr_sphere_grid, clamped
+    indices among the candidates of gridnear_cube)"""
+    c = GC.half_grid_case()
+    s = _open_case(c)
+    got, gg = _check_with_grid(s, dict(c, what="panda7 half grid"), c)
+    nwo = c["ws"].shape[0] + c["wb"].shape[0]
+    assert (c["outside"] & (got["partner"][:, :, 0] == nwo)).any() and (gg["witness"][:, 0] == GN.WORLD_GRID).any()
+    s.close()
+
+
+def test_an_empty_grid_under_the_latch():
+    """no voxel occupied: every grid pair is +inf (loik_amd_gridnear.h).  Beside other world objects it is never a partner nor the
+    witness, and box, table and gradient are those of a handle without a grid, bit for bit.  With nothing else in the world it is each
+    sphere's partner at +inf, narrows nothing, and is the witness only of a configuration with no other pair at all"""
+    c = GC.empty_grid_case()
+    s, t = _open_case(c), _open_case(c, latch=False)
+    t.set_collision_grid(None)
+    for world in (True, False):
+        if not world:
+            for h in (s, t):
+                h.set_collision_world(np.zeros((0, 4)), np.zeros((0, 15)))
+        a, b = s.avoidance_box(None, DT, -np.inf, np.inf, **PRM), t.avoidance_box(None, DT, -np.inf, np.inf, **PRM)
+        ga, gb, pa = s.clearance_gradient(), t.clearance_gradient(), s.clearance()
+        assert all(np.array_equal(ga[k], pa[k]) for k in ("min", "min_world", "min_self", "witness"))
+        for k in ("lo", "hi", "pairs"):
+            assert np.array_equal(a[k], b[k]), (world, k)
+        assert all(np.array_equal(ga[k], gb[k]) for k in ga), world   # (self pairs: never the grid)
+        assert np.array_equal(a["partner"][:, :, 1], b["partner"][:, :, 1])
+        if world:
+            assert np.array_equal(a["partner"], b["partner"]) and np.isfinite(a["lo"]).any()
+        else:
+            assert np.all(np.isposinf(a["pairs"][:, :, 0])) and np.all(a["partner"][:, :, 0] == 0) and np.all(b["partner"][:, :, 0] == -1)
+    for h in (s, t):
+        h.set_self_collision(False)
+    ga, gb, pa = s.clearance_gradient(), t.clearance_gradient(), s.clearance()
+    assert all(np.array_equal(ga[k], pa[k]) for k in ("min", "min_world", "min_self", "witness"))
+    assert np.all(np.isposinf(ga["min"])) and np.all(np.isposinf(gb["min"])) and not ga["grad"].any() and not gb["grad"].any()
+    g = c["grid"]
+    vox = GN.sphere_grid(CN.centres(c["model"], c["q"], c["links"][:1], c["spheres"][:1])[:, 0], c["spheres"][0, 3], g)[1]
+    assert np.all(gb["witness"] == (CN.NONE, -1, -1)) and np.all(ga["witness"][:, 0] == GN.WORLD_GRID) and np.all(ga["witness"][:, 1] == 0)
+    keep = ~GN.near_face(CN.centres(c["model"], c["q"], c["links"][:1], c["spheres"][:1]), g)
+    assert keep.mean() >= 0.9 and np.array_equal(ga["witness"][keep, 2], vox[keep])
+    a = s.avoidance_box(None, DT, -1.0, 1.0, **PRM)
+    assert np.all(a["lo"] == -1.0) and np.all(a["hi"] == 1.0)
+    s.close(); t.close()
 
 
 def test_gradient_is_the_derivative_of_the_distance_to_the_chosen_cube():

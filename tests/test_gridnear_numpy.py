@@ -181,6 +181,50 @@ def test_share_of_configurations_left_out(name):
     assert all(np.array_equal(a[k], b[k]) for k in ("lo", "hi", "pairs", "partner", "near"))
 
 
+def size_conditions(inp):
+    """what an input of test_gridnear.test_sizes_with_a_grid misses (empty: nothing): no row is near (at 17 and 9 rows a share means
+    nothing), and a grid witness"""
+    ref = GC.size_ref(inp)
+    miss = []
+    for k in ("box", "grad"):
+        if ref[k]["near"].any():
+            miss.append((k, "near", int(ref[k]["near"].sum())))
+    if not (ref["grad"]["witness"][~ref["grad"]["near"], 0] == GN.WORLD_GRID).any():
+        miss.append("no grid witness")
+    nwo = inp["ws"].shape[0] + inp["wb"].shape[0]
+    if not (ref["box"]["partner"][~ref["box"]["near"]][:, :, 0] == nwo).any():
+        miss.append("no grid partner")
+    return miss
+
+
+@pytest.mark.parametrize("ns", GC.SIZE_NS)
+def test_size_inputs_with_a_grid(ns):
+    inputs = GC.size_inputs(ns)
+    assert len(inputs) == (len(GC.SIZE_WORLDS) if ns > 2 else 3)
+    for inp in inputs:
+        assert size_conditions(inp) == [], inp["what"]
+    # with no other world object every sphere's world partner is the grid, at ordinal 0
+    alone = GC.size_ref(inputs[0])["box"]
+    assert inputs[0]["split"] == (0, 0) and np.all(alone["partner"][:, :, 0] == 0)
+
+
+def test_half_grid_and_empty_grid_inputs():
+    """the robot leaves the half grid's box: centres outside it among the grid partners and the active grid constraints; the share left out"""
+    c = GC.half_grid_case()
+    assert c["box"]["near"].mean() <= GC.NEAR_SHARE and c["grad"]["near"].mean() <= GC.NEAR_SHARE
+    nwo = c["ws"].shape[0] + c["wb"].shape[0]
+    keep = ~c["box"]["near"]
+    assert c["outside"].mean() >= 0.1 and (c["outside"] & (c["box"]["partner"][:, :, 0] == nwo) & keep[:, None]).any()
+    active = [(i, k["a"]) for i, row in enumerate(c["box"]["cons"]) if keep[i] for k in row if k["kind"] == 0 and k["partner"] == nwo]
+    assert any(c["outside"][i, a] for i, a in active) and any(not c["outside"][i, a] for i, a in active)
+    assert ((c["grad"]["witness"][:, 0] == GN.WORLD_GRID) & ~c["grad"]["near"]).any()
+    # an empty grid: every pair of it is +inf, so the reference's box is the box without a grid
+    e = GC.empty_grid_case()
+    args = (e["model"], e["q"][:5], e["links"], e["spheres"], e["ws"], e["wb"], e["pairs"])
+    a, b = NN.avoidance_box(*args, 0.25, -1.0, 1.0, 0.02, 0.15, 0.5, grid=e["grid"]), AN.avoidance_box(*args, 0.25, -1.0, 1.0, 0.02, 0.15, 0.5)
+    assert all(np.array_equal(a[k], b[k]) for k in ("lo", "hi", "pairs", "partner"))
+
+
 # ---- the pose loops ------------------------------------------------------------------------------------------------------------------
 # The wall of voxels.  The rule promises, to first order in dt |z|, d(next) - d_safe >= (1 - kappa) (d - d_safe) for the clearance d it
 # reads, which here is the lower bound v <= the exact clearance: no recorded configuration may come nearer to the cubes than d_safe less
