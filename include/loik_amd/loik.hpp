@@ -729,13 +729,8 @@ public:
     DVec val(2 * B);
     check(loikb_shortcut_paths(h_, q_path.data(), n_waypoints.empty() ? nullptr : n_waypoints.data(), (int)B, T, 0, &p, r.q_path.data(), r.keep.data(),
                                info.data(), val.data(), 0));
-    for (std::vector<int>* v : {&r.n_waypoints, &r.tried, &r.accepted, &r.blocked, &r.undecided, &r.invalid}) v->resize(B);
-    r.length_in.resize(B); r.length_out.resize(B);
-    for (std::size_t b = 0; b < B; ++b) {
-      r.n_waypoints[b] = info[6 * b]; r.tried[b] = info[6 * b + 1]; r.accepted[b] = info[6 * b + 2];
-      r.blocked[b] = info[6 * b + 3]; r.undecided[b] = info[6 * b + 4]; r.invalid[b] = info[6 * b + 5];
-      r.length_in[b] = val[2 * b]; r.length_out[b] = val[2 * b + 1];
-    }
+    split_info(info, 6, {&r.n_waypoints, &r.tried, &r.accepted, &r.blocked, &r.undecided, &r.invalid});
+    split_info(val, 2, {&r.length_in, &r.length_out});
     return r;
   }
   // the joint-space length [B] of the paths: the sum over consecutive waypoints of the norm of their Difference
@@ -760,29 +755,17 @@ public:
                            int max_samples = -1, bool snap = false) const
   {
     const std::size_t B = path_count(q_path, T, n_waypoints);
-    if (v_max.size() != (std::size_t)model_.nv || a_max.size() != (std::size_t)model_.nv)
-      throw std::runtime_error("loik_amd: v_max and a_max must hold model.nv values");
     const loikb_retime_params p{dt, snap ? LOIKB_RETIME_SNAP : 0};
     const int* len = n_waypoints.empty() ? nullptr : n_waypoints.data();
     RetimeResult r;
     r.duration.resize(B);
     r.seg.resize(4 * B * (std::size_t)(T > 1 ? T - 1 : 0));
     std::vector<int> info(4 * B);
-    if (max_samples < 0) {
-      check(loikb_retime_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, 0, nullptr, nullptr, r.seg.data(),
-                               r.duration.data(), info.data(), 0));
-      max_samples = 1;
-      for (std::size_t b = 0; b < B; ++b) max_samples = std::max(max_samples, info[4 * b]);
-    }
-    r.S = max_samples;
-    r.q_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nq);
-    r.v_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nv);
-    check(loikb_retime_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, r.S, r.S > 0 ? r.q_traj.data() : nullptr,
-                             r.S > 0 ? r.v_traj.data() : nullptr, r.seg.data(), r.duration.data(), info.data(), 0));
-    for (std::vector<int>* v : {&r.n_samples, &r.n_waypoints, &r.moved, &r.flags}) v->resize(B);
-    for (std::size_t b = 0; b < B; ++b) {
-      r.n_samples[b] = info[4 * b]; r.n_waypoints[b] = info[4 * b + 1]; r.moved[b] = info[4 * b + 2]; r.flags[b] = info[4 * b + 3];
-    }
+    r.S = timed_paths(B, v_max, a_max, max_samples, info, r.q_traj, r.v_traj, [&](int S, double* traj, double* vel) {
+      check(loikb_retime_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, S, traj, vel, r.seg.data(), r.duration.data(),
+                               info.data(), 0));
+    });
+    split_info(info, 4, {&r.n_samples, &r.n_waypoints, &r.moved, &r.flags});
     return r;
   }
   // ---- blending (include/loik_amd_blend.h).  BlendPaths: RetimePaths through the corners -- every corner is replaced by a parabola of
@@ -802,8 +785,6 @@ public:
                          int max_evals = 256, int max_tries = 4) const
   {
     const std::size_t B = path_count(q_path, T, n_waypoints);
-    if (v_max.size() != (std::size_t)model_.nv || a_max.size() != (std::size_t)model_.nv)
-      throw std::runtime_error("loik_amd: v_max and a_max must hold model.nv values");
     const loikb_blend_params p{margin, tol, reach, dt, max_evals, max_tries, 0};
     const int* len = n_waypoints.empty() ? nullptr : n_waypoints.data();
     const std::size_t nc = T > 2 ? (std::size_t)T - 2 : 0, np = T > 1 ? 2 * (std::size_t)T - 3 : 0;
@@ -813,22 +794,11 @@ public:
     r.corner_info.resize(6 * B * nc);
     r.piece.resize(4 * B * np);
     std::vector<int> info(4 * B);
-    if (max_samples < 0) {
-      check(loikb_blend_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, 0, nullptr, nullptr, r.duration.data(),
-                              info.data(), r.corner.data(), r.corner_info.data(), r.piece.data(), 0));
-      max_samples = 1;
-      for (std::size_t b = 0; b < B; ++b) max_samples = std::max(max_samples, info[4 * b]);
-    }
-    r.S = max_samples;
-    r.q_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nq);
-    r.v_traj.resize(B * (std::size_t)r.S * (std::size_t)model_.nv);
-    check(loikb_blend_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, r.S, r.S > 0 ? r.q_traj.data() : nullptr,
-                            r.S > 0 ? r.v_traj.data() : nullptr, r.duration.data(), info.data(), r.corner.data(), r.corner_info.data(),
-                            r.piece.data(), 0));
-    for (std::vector<int>* v : {&r.n_samples, &r.n_waypoints, &r.taken, &r.flags}) v->resize(B);
-    for (std::size_t b = 0; b < B; ++b) {
-      r.n_samples[b] = info[4 * b]; r.n_waypoints[b] = info[4 * b + 1]; r.taken[b] = info[4 * b + 2]; r.flags[b] = info[4 * b + 3];
-    }
+    r.S = timed_paths(B, v_max, a_max, max_samples, info, r.q_traj, r.v_traj, [&](int S, double* traj, double* vel) {
+      check(loikb_blend_paths(h_, q_path.data(), len, (int)B, T, 0, v_max.data(), a_max.data(), &p, S, traj, vel, r.duration.data(), info.data(),
+                              r.corner.data(), r.corner_info.data(), r.piece.data(), 0));
+    });
+    split_info(info, 4, {&r.n_samples, &r.n_waypoints, &r.taken, &r.flags});
     return r;
   }
   // ---- planning (include/loik_amd_plan.h).  PlanPaths: certified RRT-Connect from q_start [B][nq] to q_goal [B][nq]; two trees per query
@@ -854,13 +824,9 @@ public:
     r.length.resize(B);
     std::vector<int> info(8 * B);
     check(loikb_plan_paths(h_, q_start.data(), q_goal.data(), (int)B, 0, s_lo.data(), s_hi.data(), &p, T, r.q_path.data(), info.data(), r.length.data(), 0));
-    for (std::vector<int>* v : {&r.n_waypoints, &r.status, &r.iterations, &r.edges_checked, &r.edges_free, &r.evals}) v->resize(B);
+    split_info<int>(info, 8, {&r.status, &r.n_waypoints, &r.iterations, nullptr, nullptr, &r.edges_checked, &r.edges_free, &r.evals});
     r.nodes.resize(2 * B);
-    for (std::size_t b = 0; b < B; ++b) {
-      r.status[b] = info[8 * b]; r.n_waypoints[b] = info[8 * b + 1]; r.iterations[b] = info[8 * b + 2];
-      r.nodes[2 * b] = info[8 * b + 3]; r.nodes[2 * b + 1] = info[8 * b + 4];
-      r.edges_checked[b] = info[8 * b + 5]; r.edges_free[b] = info[8 * b + 6]; r.evals[b] = info[8 * b + 7];
-    }
+    for (std::size_t b = 0; b < B; ++b) { r.nodes[2 * b] = info[8 * b + 3]; r.nodes[2 * b + 1] = info[8 * b + 4]; }
     return r;
   }
   // ---- collision avoidance (include/loik_amd_avoid.h): every later pose loop narrows the velocity box of each step so that the spheres
@@ -1343,6 +1309,34 @@ private:
     if (q_path.size() != B * per) throw std::runtime_error("loik_amd: q_path is not a whole number of paths of T samples");
     if (!n_waypoints.empty() && n_waypoints.size() != B) throw std::runtime_error("loik_amd: n_waypoints is not one count per path");
     return B;
+  }
+  // column k of info [B][stride] into *cols[k], a nullptr skipping its column
+  template <class T> static void split_info(const std::vector<T>& info, std::size_t stride, std::initializer_list<std::vector<T>*> cols)
+  {
+    const std::size_t B = info.size() / stride;
+    std::size_t k = 0;
+    for (std::vector<T>* c : cols) {
+      if (c) c->resize(B);
+      for (std::size_t b = 0; c && b < B; ++b) (*c)[b] = info[stride * b + k];
+      ++k;
+    }
+  }
+  // what RetimePaths and BlendPaths share: v_max and a_max checked, S = max_samples or, when that is < 0, the largest n_samples of a
+  // timing-only call, traj and vel sized to S rows, then the real call.  call(S, traj, vel) is the C call, which fills info [B][4]
+  template <class Call> int timed_paths(std::size_t B, const DVec& v_max, const DVec& a_max, int max_samples, const std::vector<int>& info, DVec& traj,
+                                        DVec& vel, Call&& call) const
+  {
+    if (v_max.size() != (std::size_t)model_.nv || a_max.size() != (std::size_t)model_.nv)
+      throw std::runtime_error("loik_amd: v_max and a_max must hold model.nv values");
+    if (max_samples < 0) {
+      call(0, nullptr, nullptr);
+      max_samples = 1;
+      for (std::size_t b = 0; b < B; ++b) max_samples = std::max(max_samples, info[4 * b]);
+    }
+    traj.resize(B * (std::size_t)max_samples * (std::size_t)model_.nq);
+    vel.resize(B * (std::size_t)max_samples * (std::size_t)model_.nv);
+    call(max_samples, max_samples > 0 ? traj.data() : nullptr, max_samples > 0 ? vel.data() : nullptr);
+    return max_samples;
   }
   // out_val [n][3], out_info [n][5] of loik_amd_motion.h by field
   static MotionResult motion_result(const DVec& val, const std::vector<int>& info)

@@ -7,7 +7,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libloik_amd.so")
 SOURCES = ["loik_host.hip", "loik_flat_kernels.hip", "models.c"]
-HEADERS = ["loik_device.hpp", "loik_tail.hpp", "loik_lean.hpp", "loik_flat.hpp", "loik_flat2.hpp", "loik_flat_prep.hpp", "loik_flat_inst.hpp", "loik_passes.hpp", "loik_pose.hpp", "loik_pose_tasks.hpp", "loik_pose_multistart.hpp", "loik_pose_path.hpp", "loik_pose_track.hpp", "loik_pose_accel.hpp", "loik_pose_step.hpp", "loik_pose_jacobian.hpp", "loik_pose_collision.hpp", "loik_pose_grid.hpp", "loik_pose_gridnear.hpp", "loik_pose_motion.hpp", "loik_pose_shortcut.hpp", "loik_pose_retime.hpp", "loik_pose_blend.hpp", "loik_pose_plan.hpp", "loik_pose_avoid.hpp", "loik_host_pose.hpp", "loik_devmem.hpp",
+HEADERS = ["loik_device.hpp", "loik_tail.hpp", "loik_lean.hpp", "loik_flat.hpp", "loik_flat2.hpp", "loik_flat_prep.hpp", "loik_flat_inst.hpp", "loik_passes.hpp", "loik_pose.hpp", "loik_pose_tasks.hpp", "loik_pose_multistart.hpp", "loik_pose_path.hpp", "loik_pose_track.hpp", "loik_pose_accel.hpp", "loik_pose_step.hpp", "loik_pose_jacobian.hpp", "loik_pose_collision.hpp", "loik_pose_grid.hpp", "loik_pose_gridnear.hpp", "loik_pose_motion.hpp", "loik_pose_shortcut.hpp", "loik_pose_retime.hpp", "loik_pose_blend.hpp", "loik_pose_plan.hpp", "loik_pose_avoid.hpp", "loik_host_pose.hpp", "loik_host_motion.hpp", "loik_devmem.hpp",
            os.path.join("..", "..", "include", "loik_amd.h"), os.path.join("..", "..", "include", "loik_amd_models.h"),
            os.path.join("..", "..", "include", "loik_amd_pose.h"), os.path.join("..", "..", "include", "loik_amd_limits.h"),
            os.path.join("..", "..", "include", "loik_amd_tasks.h"), os.path.join("..", "..", "include", "loik_amd_multistart.h"),

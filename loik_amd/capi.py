@@ -1364,13 +1364,16 @@ class BatchedLoik:
         the other sphere, or -1), or with out = (lo_dev, hi_dev, pairs_dev, partner_dev) writes there and returns out."""
         qp, n, flags, keep = self._q_rows(q)
         nv = self.model.nv
-        lb = np.ascontiguousarray(np.broadcast_to(_f64(lb), (nv,)))
-        ub = np.ascontiguousarray(np.broadcast_to(_f64(ub), (nv,)))
+        lb, ub = self._dof_row(lb), self._dof_row(ub)
         prm = AvoidParams(float(d_safe), float(d_influence), float(kappa), 0)
         ns = getattr(self, "_n_spheres", 0)
         ptrs, oflags, new = _outs(out, [((n, nv), np.float64), ((n, nv), np.float64), ((n, ns, 2), np.float64), ((n, ns, 2), np.int32)])
         _check(self.L.loikb_avoid_box(self.h, qp, n, flags, float(dt), lb.ctypes.data_as(_dp), ub.ctypes.data_as(_dp), C.byref(prm), *ptrs, oflags))
         return out if new is None else dict(zip(("lo", "hi", "pairs", "partner"), new))
+
+    def _dof_row(self, x):
+        """a scalar or [nv] -> a contiguous float64 [nv]"""
+        return np.ascontiguousarray(np.broadcast_to(_f64(x), (self.model.nv,)))
 
     # ---- motions (include/loik_amd_motion.h) ----------------------------------------------------------------------
     def _rows(self, a, width):
@@ -1497,6 +1500,32 @@ class BatchedLoik:
         return out if new is None else new[0]
 
     # ---- retiming (include/loik_amd_retime.h) --------------------------------------------------------------------
+    def _timed_paths(self, who, fn, prm, q_path, n_waypoints, v_max, a_max, max_samples, out, tail, info_at, pack):
+        """the body retime_paths and blend_paths share.  fn: the C entry point, prm its params struct; tail(B, T): the (shape, dtype) of
+        its outputs after (traj, vel), number info_at of them info [B][4]; pack(traj, vel, *tail arrays): the result"""
+        pq, pl, B, T, dev, alive = self._paths(who, q_path, n_waypoints)
+        vm, am = self._dof_row(v_max), self._dof_row(a_max)
+        specs = tail(B, T)
+
+        def call(S, ptrs, oflags):
+            _check(fn(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, vm.ctypes.data_as(_dp), am.ctypes.data_as(_dp), C.byref(prm), S, *ptrs, oflags))
+        if out is not None:
+            if max_samples is None:
+                raise ValueError("%s: out needs max_samples" % who)
+            ptrs, oflags, _ = _outs(out, [None] * (2 + len(specs)))
+            call(int(max_samples), ptrs, oflags)
+            return out
+        ptail, _, arrs = _outs(None, specs)
+        if max_samples is None:
+            call(0, [None, None] + ptail, 0)
+            max_samples = max(int(arrs[info_at][:, 0].max(initial=1)), 1)
+        S = int(max_samples)
+        traj = vel = None
+        if S > 0:
+            traj, vel = np.empty((B, S, self.model.nq)), np.empty((B, S, self.model.nv))
+        call(S, [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in (traj, vel)] + ptail, 0)
+        return pack(traj, vel, *arrs)
+
     def retime_paths(self, q_path, v_max, a_max, dt, n_waypoints=None, max_samples=None, snap=False, out=None):
         """time-optimal retiming of the paths q_path [B][T][nq] under the per-DoF limits v_max, a_max [nv] (host, or scalars) at the sample
         period dt (loikb_retime_paths): every segment from rest to rest on a trapezoid of its path parameter, so that every sample lies on
@@ -1506,32 +1535,10 @@ class BatchedLoik:
         [B][T-1][4] = (t_start, duration, t_acc, peak)); q_traj and v_traj are None after a timing-only call.  With out = (traj_dev,
         vel_dev, seg_dev, duration_dev, info_dev) device buffers of B S nq / B S nv / 4 B (T-1) / B float64 and 4 B int32 (the first three
         may be None; max_samples is then required) writes there and returns out."""
-        pq, pl, B, T, dev, alive = self._paths("retime_paths", q_path, n_waypoints)
-        nq, nv = self.model.nq, self.model.nv
-        vm = np.ascontiguousarray(np.broadcast_to(_f64(v_max), (nv,)))
-        am = np.ascontiguousarray(np.broadcast_to(_f64(a_max), (nv,)))
         prm = RetimeParams(float(dt), RETIME_SNAP if snap else 0)
-
-        def call(S, ptrs, oflags):
-            _check(self.L.loikb_retime_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, vm.ctypes.data_as(_dp), am.ctypes.data_as(_dp),
-                                             C.byref(prm), S, *ptrs, oflags))
-        if out is not None:
-            if max_samples is None:
-                raise ValueError("retime_paths: out needs max_samples")
-            ptrs, oflags, _ = _outs(out, [None] * 5)
-            call(int(max_samples), ptrs, oflags)
-            return out
-        seg, dur, info = np.empty((B, max(T - 1, 0), 4)), np.empty(B), np.empty((B, 4), dtype=np.int32)
-        tail = [a.ctypes.data_as(C.c_void_p) for a in (seg, dur, info)]
-        if max_samples is None:
-            call(0, [None, None] + tail, 0)
-            max_samples = max(int(info[:, 0].max(initial=1)), 1)
-        S = int(max_samples)
-        traj = vel = None
-        if S > 0:
-            traj, vel = np.empty((B, S, nq)), np.empty((B, S, nv))
-        call(S, [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in (traj, vel)] + tail, 0)
-        return self._retime_result(traj, vel, seg, dur, info)
+        return self._timed_paths("retime_paths", self.L.loikb_retime_paths, prm, q_path, n_waypoints, v_max, a_max, max_samples, out,
+                                 lambda B, T: [((B, max(T - 1, 0), 4), np.float64), ((B,), np.float64), ((B, 4), np.int32)], 2,
+                                 self._retime_result)
 
     @staticmethod
     def _retime_result(traj, vel, seg, dur, info):
@@ -1551,34 +1558,11 @@ class BatchedLoik:
         duration_dev, info_dev, corner_dev, corner_info_dev, piece_dev) device buffers of B S nq / B S nv / B float64, 4 B int32,
         5 B (T-2) float64, 6 B (T-2) int32 and 4 B (2T-3) float64 (all but duration_dev and info_dev may be None; max_samples is then
         required) writes there and returns out."""
-        pq, pl, B, T, dev, alive = self._paths("blend_paths", q_path, n_waypoints)
-        nq, nv = self.model.nq, self.model.nv
-        vm = np.ascontiguousarray(np.broadcast_to(_f64(v_max), (nv,)))
-        am = np.ascontiguousarray(np.broadcast_to(_f64(a_max), (nv,)))
         prm = BlendParams(float(margin), float(tol), float(reach), float(dt), int(max_evals), int(max_tries), 0)
-
-        def call(S, ptrs, oflags):
-            _check(self.L.loikb_blend_paths(self.h, pq, pl, B, T, IN_DEVICE if dev else 0, vm.ctypes.data_as(_dp), am.ctypes.data_as(_dp),
-                                            C.byref(prm), S, *ptrs, oflags))
-        if out is not None:
-            if max_samples is None:
-                raise ValueError("blend_paths: out needs max_samples")
-            ptrs, oflags, _ = _outs(out, [None] * 7)
-            call(int(max_samples), ptrs, oflags)
-            return out
-        nc, npc = max(T - 2, 0), max(2 * T - 3, 0)
-        dur, info = np.empty(B), np.empty((B, 4), dtype=np.int32)
-        corner, cinfo, piece = np.empty((B, nc, 5)), np.empty((B, nc, 6), dtype=np.int32), np.empty((B, npc, 4))
-        tail = [a.ctypes.data_as(C.c_void_p) for a in (dur, info, corner, cinfo, piece)]
-        if max_samples is None:
-            call(0, [None, None] + tail, 0)
-            max_samples = max(int(info[:, 0].max(initial=1)), 1)
-        S = int(max_samples)
-        traj = vel = None
-        if S > 0:
-            traj, vel = np.empty((B, S, nq)), np.empty((B, S, nv))
-        call(S, [a.ctypes.data_as(C.c_void_p) if a is not None else None for a in (traj, vel)] + tail, 0)
-        return self._blend_result(traj, vel, dur, info, corner, cinfo, piece)
+        return self._timed_paths("blend_paths", self.L.loikb_blend_paths, prm, q_path, n_waypoints, v_max, a_max, max_samples, out,
+                                 lambda B, T: [((B,), np.float64), ((B, 4), np.int32), ((B, max(T - 2, 0), 5), np.float64),
+                                               ((B, max(T - 2, 0), 6), np.int32), ((B, max(2 * T - 3, 0), 4), np.float64)], 1,
+                                 self._blend_result)
 
     @staticmethod
     def _blend_result(traj, vel, dur, info, corner, cinfo, piece):
@@ -1600,8 +1584,7 @@ class BatchedLoik:
         pg, Bg, devg, k1 = self._rows(q_goal, nq)
         if B != Bg or dev != devg:
             raise ValueError("plan_paths: q_start and q_goal differ in rows or in where they live")
-        lo = np.ascontiguousarray(np.broadcast_to(_f64(s_lo), (nv,)))
-        hi = np.ascontiguousarray(np.broadcast_to(_f64(s_hi), (nv,)))
+        lo, hi = self._dof_row(s_lo), self._dof_row(s_hi)
         T = int(T)
         prm = PlanParams(float(margin), float(tol), float(step), int(seed) % (1 << 64), int(max_evals), int(max_iters), int(max_nodes), 0)
         ptrs, oflags, new = _outs(out, [((B, max(T, 0), nq), np.float64), ((B, 8), np.int32), ((B,), np.float64)])

@@ -4335,3 +4335,5 @@ int loikb_debug_tail_prof_all(unsigned long long* out, int reset)   // the phase
 // the pose layer: pose IK, joint limits, tasks, multi-start, paths.  Same translation unit: it shares k_advance_q, grid1 and the
 // handle's internals with the code above.
 #include "loik_host_pose.hpp"
+// the motion layer on top of it: motion checks, shortcutting, retiming, blending, planning
+#include "loik_host_motion.hpp"

@@ -1,8 +1,9 @@
 // loik_host_pose.hpp -- the pose layer of the host driver: batched pose IK (include/loik_amd_pose.h), joint position limits
 // (loik_amd_limits.h) and acceleration limits (loik_amd_accel.h), step control (loik_amd_step.h), tool frames and tasks (loik_amd_tasks.h), frame
-// Jacobians and dexterity (loik_amd_jacobian.h), collision clearance (loik_amd_collision.h), collision avoidance (loik_amd_avoid.h), motion checks (loik_amd_motion.h), multi-start (loik_amd_multistart.h), waypoint paths
+// Jacobians and dexterity (loik_amd_jacobian.h), collision clearance (loik_amd_collision.h), voxel worlds (loik_amd_grid.h, loik_amd_gridnear.h), collision avoidance (loik_amd_avoid.h), multi-start (loik_amd_multistart.h), waypoint paths
 // (loik_amd_path.h) and timed trajectories (loik_amd_track.h).  Included at the end of loik_host.hip, whose translation unit it
-// belongs to: it is no header of its own.
+// belongs to: it is no header of its own.  The motion layer (loik_amd_motion.h, _shortcut.h, _retime.h, _blend.h, _plan.h) follows it in
+// loik_host_motion.hpp.
 //
 // What the solves share is here once: pose_check_targets (the check before anything of the handle changes), pose_begin,
 // pose_loop (the step loop around the caller's re-target) with pose_step, get_copy_out / get_timing_out for the getters of resident
@@ -1583,484 +1584,6 @@ int loikb_avoid_get_result(loikb_solver* S, int field, void* out, int out_flags)
   case LOIKB_AVOID_F_ACTIVE_STEPS: return get_copy_out(S, A.d_asteps, sizeof(int) * B, out, out_flags);
   default: return get_copy_out(S, A.d_aflags, sizeof(int) * B * S->nb, out, out_flags);
   }
-}
-
-// ---- include/loik_amd_motion.h (kernels in loik_pose_motion.hpp) ---------------------------------------------------------------
-int loikb_motion_version(void) { return LOIKB_MOTION_VERSION; }
-
-// the two input arrays of a call on the device: device pointers pass through, host arrays go side by side into the staging buffer
-// (to_device has room for one).  b may be NULL.  Queued
-static int motion_inputs(loikb_solver_impl* S, const double* a, size_t abytes, const double* b, size_t bbytes, bool dev, const double** da,
-                         const double** db)
-{
-  if (dev) { *da = a; *db = b; return LOIKB_OK; }
-  const size_t off = (abytes + 255) & ~(size_t)255;
-  int rc;
-  if ((rc = regrow(S->d_stage, off + bbytes))) return rc;
-  HIPCHK(hipMemcpyAsync(S->d_stage, a, abytes, hipMemcpyHostToDevice, S->stream));
-  if (b) HIPCHK(hipMemcpyAsync(S->d_stage.as<char>() + off, b, bbytes, hipMemcpyHostToDevice, S->stream));
-  *da = S->d_stage.as<const double>();
-  *db = b ? (const double*)(S->d_stage.as<char>() + off) : nullptr;
-  return LOIKB_OK;
-}
-
-int loikb_difference(loikb_solver* S, const double* q0, const double* q1, int n, int in_flags, double* out_v, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  if (n < 0 || (n > 0 && (!q0 || !q1 || !out_v))) { g_last_error = "difference: need n >= 0 and q0, q1, out_v when n > 0"; return LOIKB_ERR_ARG; }
-  if (n == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  const size_t qbytes = sizeof(double) * (size_t)n * S->nq;
-  QueryOut o(S, out_flags);
-  const double *d0, *d1;
-  double* d_v;
-  o.add(out_v, sizeof(double) * (size_t)n * S->nv, &d_v);
-  int rc;
-  if ((rc = motion_inputs(S, q0, qbytes, q1, qbytes, in_flags & LOIKB_IN_DEVICE, &d0, &d1)) || (rc = o.reserve())) return rc;
-  hipLaunchKernelGGL(k_difference, grid1((size_t)n, 64), dim3(64), 0, S->stream, d0, d1, S->nq, S->d_jd, S->d_idx_q, S->nb, n, 0, d_v);
-  HIPCHK(hipGetLastError());
-  return o.finish();   // (the caller's arrays have been read)
-}
-
-static int motion_check_params(const loikb_motion_params* p, const char* who)
-{
-  const char* bad = !p ? "p == NULL"
-                    : !std::isfinite(p->margin) ? "the margin is not finite"
-                    : !(std::isfinite(p->tol) && p->tol >= 1e-9) ? "tol is not finite and >= 1e-9"
-                    : (p->max_evals < 1 || p->max_evals > 65536) ? "max_evals is outside 1 .. 65536"
-                    : p->flags != 0 ? "flags != 0" : nullptr;
-  if (!bad) return LOIKB_OK;
-  g_last_error = std::string(who) + ": " + bad;
-  return LOIKB_ERR_ARG;
-}
-
-// wavefronts that k_motion_clearance<true> keeps a slab for: the grid of a model whose records do not fit the LDS
-constexpr int MOTION_SLAB_WAVES = 512;
-
-// One advancement launch over n segments: qa rows by motion_row(i, T) of dqa, dv [n][nv].  Queued
-static int motion_launch(loikb_solver_impl* S, const double* dqa, const double* ddv, int n, int T, const loikb_motion_params& p, double* d_val,
-                         int* d_info)
-{
-  Collision& C = S->pose.col;
-  const int ncar = (int)C.car.size();
-  const size_t aux = motion_aux_doubles(S->nb, ncar, C.ns);
-  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) > 65536;
-  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
-  const ClrModel m = clr_model(S);
-  const MotionPrm prm{p.margin, p.tol, p.max_evals};
-  if (slab) {
-    const int waves = std::min(n, MOTION_SLAB_WAVES);
-    if (int rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves)) return rc;
-    hipLaunchKernelGGL(k_motion_clearance<true>, dim3(waves), dim3(64), lds, S->stream, dqa, ddv, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T, m, prm,
-                       C.d_mslab, d_val, d_info);
-  } else {
-    hipLaunchKernelGGL(k_motion_clearance<false>, dim3(n), dim3(64), lds, S->stream, dqa, ddv, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T, m, prm,
-                       (double*)nullptr, d_val, d_info);
-  }
-  HIPCHK(hipGetLastError());
-  return LOIKB_OK;
-}
-
-// the shared body of the two checks: dqa as motion_launch takes it, ddv [n][nv] or nullptr = the differences of the path (T > 0).
-// Queued; the caller finishes `o`
-static int motion_run(loikb_solver_impl* S, const double* dqa, const double* ddv, int n, int T, const loikb_motion_params& p, double* out_val,
-                      int* out_info, QueryOut& o)
-{
-  int rc;
-  if (!ddv) {
-    if ((rc = regrow(S->d_getscr[1], sizeof(double) * (size_t)n * S->nv))) return rc;
-    hipLaunchKernelGGL(k_difference, grid1((size_t)n, 64), dim3(64), 0, S->stream, dqa, (const double*)nullptr, S->nq, S->d_jd, S->d_idx_q, S->nb, n, T,
-                       S->d_getscr[1].as<double>());
-    HIPCHK(hipGetLastError());
-    ddv = S->d_getscr[1].as<const double>();
-  }
-  double* d_val;
-  int* d_info;
-  o.add(out_val, sizeof(double) * 3 * (size_t)n, &d_val);
-  o.add(out_info, sizeof(int) * 5 * (size_t)n, &d_info);
-  if ((rc = o.reserve())) return rc;
-  return motion_launch(S, dqa, ddv, n, T, p, d_val, d_info);
-}
-
-int loikb_motion_clearance(loikb_solver* S, const double* qa, const double* dv, int n, int in_flags, const loikb_motion_params* p, double* out_val,
-                           int* out_info, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  if (n < 0 || (n > 0 && (!qa || !dv || !out_val || !out_info))) { g_last_error = "motion_clearance: need n >= 0 and qa, dv, out_val, out_info when n > 0"; return LOIKB_ERR_ARG; }
-  int rc;
-  if ((rc = motion_check_params(p, "motion_clearance"))) return rc;
-  if (S->pose.col.ns == 0) { g_last_error = "motion_clearance: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
-  if (n == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  QueryOut o(S, out_flags);
-  const double *dqa, *ddv;
-  if ((rc = motion_inputs(S, qa, sizeof(double) * (size_t)n * S->nq, dv, sizeof(double) * (size_t)n * S->nv, in_flags & LOIKB_IN_DEVICE, &dqa, &ddv)) ||
-      (rc = motion_run(S, dqa, ddv, n, 0, *p, out_val, out_info, o)))
-    return rc;
-  return o.finish();   // (the caller's arrays have been read)
-}
-
-int loikb_motion_clearance_path(loikb_solver* S, const double* q_path, int B, int T, int in_flags, const loikb_motion_params* p, double* out_val,
-                                int* out_info, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  if (T < 2) { g_last_error = "motion_clearance_path: need T >= 2"; return LOIKB_ERR_ARG; }
-  if (B < 0 || (size_t)B * (size_t)(T - 1) > (size_t)0x7fffffff || (B > 0 && (!q_path || !out_val || !out_info))) {
-    g_last_error = "motion_clearance_path: need B >= 0, fewer than 2^31 segments and q_path, out_val, out_info when B > 0";
-    return LOIKB_ERR_ARG;
-  }
-  int rc;
-  if ((rc = motion_check_params(p, "motion_clearance_path"))) return rc;
-  if (S->pose.col.ns == 0) { g_last_error = "motion_clearance_path: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
-  if (B == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  QueryOut o(S, out_flags);
-  const double *dq, *none;
-  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, nullptr, 0, in_flags & LOIKB_IN_DEVICE, &dq, &none)) ||
-      (rc = motion_run(S, dq, nullptr, B * (T - 1), T, *p, out_val, out_info, o)))
-    return rc;
-  return o.finish();
-}
-
-// ---- include/loik_amd_shortcut.h (kernels in loik_pose_shortcut.hpp) -----------------------------------------------------------
-int loikb_shortcut_version(void) { return LOIKB_SHORTCUT_VERSION; }
-
-// wavefronts of k_shortcut_paths<false>: each keeps a path to its end and strides on, and each has a keep row in the scratch
-constexpr int SHORTCUT_WAVES = 8192;
-
-// the arguments the two entry points share
-static int shortcut_check_paths(const char* who, const double* q_path, int B, int T)
-{
-  if (T < 2) { g_last_error = std::string(who) + ": need T >= 2"; return LOIKB_ERR_ARG; }
-  if (B < 0 || (size_t)B * (size_t)T > (size_t)0x7fffffff || (B > 0 && !q_path)) {
-    g_last_error = std::string(who) + ": need B >= 0, B * T < 2^31 and q_path when B > 0";
-    return LOIKB_ERR_ARG;
-  }
-  return LOIKB_OK;
-}
-
-// The launch of loikb_shortcut_paths.  Queued; the caller finishes `o`
-static int shortcut_run(loikb_solver_impl* S, const double* dq, const int* dlen, int B, int T, const loikb_shortcut_params& p, double* out_path,
-                        int* out_keep, int* out_info, double* out_val, QueryOut& o)
-{
-  Collision& C = S->pose.col;
-  const int ncar = (int)C.car.size();
-  const size_t aux = shortcut_aux_doubles(S->nb, ncar, C.ns);
-  // the LDS the compiler keeps for itself (difference_joint's dynamically indexed rotation) counts against the 64 KB
-  hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_shortcut_paths<false>)));
-  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) + fa.sharedSizeBytes > 65536;
-  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
-  const int waves = std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES);
-  double *d_path, *d_val;
-  int *d_info, *d_keep;
-  o.add(out_path, sizeof(double) * (size_t)B * T * S->nq, &d_path);
-  o.add(out_val, sizeof(double) * 2 * (size_t)B, &d_val);
-  o.add(out_info, sizeof(int) * 6 * (size_t)B, &d_info);
-  o.add(out_keep, sizeof(int) * (size_t)B * T, &d_keep);
-  int rc;
-  if ((rc = o.reserve())) return rc;
-  if (!out_keep && (rc = regrow(S->d_getscr[1], sizeof(int) * (size_t)waves * T))) return rc;
-  int* d_kscr = out_keep ? nullptr : S->d_getscr[1].as<int>();
-  const ClrModel m = clr_model(S);
-  const ShortcutPrm prm{p.margin, p.tol, p.max_evals, p.rounds, p.seed};
-  if (slab) {
-    if ((rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves))) return rc;
-    hipLaunchKernelGGL(k_shortcut_paths<true>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
-                       C.d_mslab.as<double>(), d_kscr, d_path, d_keep, d_info, d_val);
-  } else {
-    hipLaunchKernelGGL(k_shortcut_paths<false>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
-                       (double*)nullptr, d_kscr, d_path, d_keep, d_info, d_val);
-  }
-  HIPCHK(hipGetLastError());
-  return LOIKB_OK;
-}
-
-int loikb_shortcut_paths(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, const loikb_shortcut_params* p,
-                         double* out_path, int* out_keep, int* out_info, double* out_val, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  int rc;
-  if ((rc = shortcut_check_paths("shortcut_paths", q_path, B, T))) return rc;
-  if (!out_path || !out_info) { g_last_error = "shortcut_paths: need out_path and out_info"; return LOIKB_ERR_ARG; }
-  const loikb_motion_params mp{p ? p->margin : 0.0, p ? p->tol : 0.0, p ? p->max_evals : 0, p ? p->flags : 0};
-  if ((rc = motion_check_params(p ? &mp : nullptr, "shortcut_paths"))) return rc;
-  if (p->rounds < 0 || p->rounds > 1048576) { g_last_error = "shortcut_paths: rounds is outside 0 .. 1048576"; return LOIKB_ERR_ARG; }
-  if (out_path == q_path) { g_last_error = "shortcut_paths: out_path == q_path"; return LOIKB_ERR_ARG; }
-  if (S->pose.col.ns == 0) { g_last_error = "shortcut_paths: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
-  if (B == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  QueryOut o(S, out_flags);
-  const double *dq, *dlen;
-  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
-      (rc = shortcut_run(S, dq, (const int*)dlen, B, T, *p, out_path, out_keep, out_info, out_val, o)))
-    return rc;
-  return o.finish();   // (the caller's arrays have been read)
-}
-
-int loikb_path_length(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, double* out_length, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  int rc;
-  if ((rc = shortcut_check_paths("path_length", q_path, B, T))) return rc;
-  if (!out_length) { g_last_error = "path_length: need out_length"; return LOIKB_ERR_ARG; }
-  if (B == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  QueryOut o(S, out_flags);
-  const double *dq, *dlen;
-  double* d_len;
-  o.add(out_length, sizeof(double) * (size_t)B, &d_len);
-  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
-      (rc = o.reserve()))
-    return rc;
-  hipLaunchKernelGGL(k_path_length, dim3(std::min(B, SHORTCUT_WAVES)), dim3(64), 0, S->stream, dq, (const int*)dlen, B, T, S->nq, S->d_jd, S->d_idx_q,
-                     S->nb, d_len);
-  HIPCHK(hipGetLastError());
-  return o.finish();   // (the caller's arrays have been read)
-}
-
-// ---- include/loik_amd_retime.h (kernel in loik_pose_retime.hpp) -----------------------------------------------------------------
-int loikb_retime_version(void) { return LOIKB_RETIME_VERSION; }
-
-// The launch of loikb_retime_paths.  The two limit rows go side by side into S->d_getscr[1]; the tables of a wavefront are LDS when
-// they fit beside what the compiler keeps for itself, else a slab per resident wavefront (the motion check's, and its grid).  Queued; the
-// caller finishes `o`
-static int retime_run(loikb_solver_impl* S, const double* dq, const int* dlen, int B, int T, const double* v_max, const double* a_max,
-                      const loikb_retime_params& p, int n_rows, double* out_traj, double* out_vel, double* out_seg, double* out_duration,
-                      int* out_info, QueryOut& o)
-{
-  const size_t tab = retime_tab_doubles(T, S->nb) * sizeof(double);
-  hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_retime_paths<false>)));
-  const bool slab = tab + fa.sharedSizeBytes > 65536;
-  const int waves = std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES);
-  double *d_traj, *d_vel, *d_seg, *d_dur;
-  int* d_info;
-  o.add(out_traj, sizeof(double) * (size_t)B * n_rows * S->nq, &d_traj);
-  o.add(out_vel, sizeof(double) * (size_t)B * n_rows * S->nv, &d_vel);
-  o.add(out_seg, sizeof(double) * (size_t)B * (T - 1) * 4, &d_seg);
-  o.add(out_duration, sizeof(double) * (size_t)B, &d_dur);
-  o.add(out_info, sizeof(int) * 4 * (size_t)B, &d_info);
-  int rc;
-  const size_t row = sizeof(double) * (size_t)S->nv;
-  if ((rc = o.reserve()) || (rc = regrow(S->d_getscr[1], 2 * row))) return rc;
-  HIPCHK(hipMemcpyAsync(S->d_getscr[1], v_max, row, hipMemcpyHostToDevice, S->stream));
-  HIPCHK(hipMemcpyAsync(S->d_getscr[1].as<char>() + row, a_max, row, hipMemcpyHostToDevice, S->stream));
-  const double* d_lim = S->d_getscr[1].as<const double>();
-  const RetimePrm prm{p.dt, (p.flags & LOIKB_RETIME_SNAP) != 0, n_rows};
-  if (slab) {
-    Collision& C = S->pose.col;
-    if ((rc = regrow_drained(S, C.d_mslab, tab * (size_t)waves))) return rc;
-    hipLaunchKernelGGL(k_retime_paths<true>, dim3(waves), dim3(64), 0, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, d_lim, prm,
-                       C.d_mslab.as<double>(), d_traj, d_vel, d_seg, d_dur, d_info);
-  } else {
-    hipLaunchKernelGGL(k_retime_paths<false>, dim3(waves), dim3(64), tab, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, d_lim, prm,
-                       (double*)nullptr, d_traj, d_vel, d_seg, d_dur, d_info);
-  }
-  HIPCHK(hipGetLastError());
-  return LOIKB_OK;
-}
-
-int loikb_retime_paths(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, const double* v_max,
-                       const double* a_max, const loikb_retime_params* p, int n_rows, double* out_traj, double* out_vel, double* out_seg,
-                       double* out_duration, int* out_info, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  int rc;
-  if ((rc = shortcut_check_paths("retime_paths", q_path, B, T))) return rc;
-  const char* bad = !v_max ? "v_max == NULL" : !a_max ? "a_max == NULL" : !p ? "p == NULL" : !out_duration ? "need out_duration"
-                    : !out_info ? "need out_info" : nullptr;
-  for (int j = 0; !bad && j < S->nv; ++j) {
-    if (!(std::isfinite(v_max[j]) && v_max[j] > 0.0)) bad = "a v_max that is not finite and > 0";
-    else if (!(std::isfinite(a_max[j]) && a_max[j] > 0.0)) bad = "an a_max that is not finite and > 0";
-  }
-  if (!bad)
-    bad = !(std::isfinite(p->dt) && p->dt > 0.0) ? "dt is not finite and > 0"
-          : (p->flags & ~LOIKB_RETIME_SNAP) ? "unknown flags"
-          : (out_vel && !out_traj) ? "out_vel without out_traj"
-          : (out_traj && n_rows < 1) ? "out_traj with S < 1"
-          : (out_traj && (size_t)B * (size_t)n_rows > (size_t)0x7fffffff) ? "need B * S < 2^31"
-          : (out_traj && out_traj == q_path) ? "out_traj == q_path" : nullptr;
-  if (bad) { g_last_error = std::string("retime_paths: ") + bad; return LOIKB_ERR_ARG; }
-  if (B == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  QueryOut o(S, out_flags);
-  const double *dq, *dlen;
-  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
-      (rc = retime_run(S, dq, (const int*)dlen, B, T, v_max, a_max, *p, out_traj ? n_rows : 0, out_traj, out_vel, out_seg, out_duration, out_info, o)))
-    return rc;
-  return o.finish();   // (the caller's arrays have been read)
-}
-
-// ---- include/loik_amd_blend.h (kernel in loik_pose_blend.hpp) -------------------------------------------------------------------
-int loikb_blend_version(void) { return LOIKB_BLEND_VERSION; }
-
-// The launch of loikb_blend_paths.  The two limit rows go side by side into S->d_getscr[1], as retime_run puts them; the records and the
-// tables of a wavefront are LDS when they fit beside the centres and what the compiler keeps for itself, else a slab per resident
-// wavefront (the motion check's, and its grid).  Queued; the caller finishes `o`
-static int blend_run(loikb_solver_impl* S, const double* dq, const int* dlen, int B, int T, const double* v_max, const double* a_max,
-                     const loikb_blend_params& p, int n_rows, double* out_traj, double* out_vel, double* out_duration, int* out_info,
-                     double* out_corner, int* out_cinfo, double* out_piece, QueryOut& o)
-{
-  Collision& C = S->pose.col;
-  const int ncar = (int)C.car.size();
-  const size_t aux = blend_aux_doubles(S->nb, ncar, C.ns, T);
-  hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_blend_paths<false>)));
-  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) + fa.sharedSizeBytes > 65536;
-  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
-  const int waves = std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES);
-  double *d_traj, *d_vel, *d_dur, *d_corner, *d_piece;
-  int *d_info, *d_cinfo;
-  o.add(out_traj, sizeof(double) * (size_t)B * n_rows * S->nq, &d_traj);
-  o.add(out_vel, sizeof(double) * (size_t)B * n_rows * S->nv, &d_vel);
-  o.add(out_duration, sizeof(double) * (size_t)B, &d_dur);
-  o.add(out_corner, sizeof(double) * (size_t)B * (T - 2) * 5, &d_corner);
-  o.add(out_piece, sizeof(double) * (size_t)B * (2 * (size_t)T - 3) * 4, &d_piece);
-  o.add(out_info, sizeof(int) * 4 * (size_t)B, &d_info);
-  o.add(out_cinfo, sizeof(int) * (size_t)B * (T - 2) * 6, &d_cinfo);
-  int rc;
-  const size_t row = sizeof(double) * (size_t)S->nv;
-  if ((rc = o.reserve()) || (rc = regrow(S->d_getscr[1], 2 * row))) return rc;
-  HIPCHK(hipMemcpyAsync(S->d_getscr[1], v_max, row, hipMemcpyHostToDevice, S->stream));
-  HIPCHK(hipMemcpyAsync(S->d_getscr[1].as<char>() + row, a_max, row, hipMemcpyHostToDevice, S->stream));
-  const double* d_lim = S->d_getscr[1].as<const double>();
-  const ClrModel m = clr_model(S);
-  const BlendPrm prm{p.margin, p.tol, p.reach, p.dt, p.max_evals, p.max_tries, n_rows};
-  if (slab) {
-    if ((rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves))) return rc;
-    hipLaunchKernelGGL(k_blend_paths<true>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, d_lim, prm,
-                       C.d_mslab.as<double>(), d_traj, d_vel, d_dur, d_info, d_corner, d_cinfo, d_piece);
-  } else {
-    hipLaunchKernelGGL(k_blend_paths<false>, dim3(waves), dim3(64), lds, S->stream, dq, dlen, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, d_lim, prm,
-                       (double*)nullptr, d_traj, d_vel, d_dur, d_info, d_corner, d_cinfo, d_piece);
-  }
-  HIPCHK(hipGetLastError());
-  return LOIKB_OK;
-}
-
-int loikb_blend_paths(loikb_solver* S, const double* q_path, const int* len, int B, int T, int in_flags, const double* v_max, const double* a_max,
-                      const loikb_blend_params* p, int n_rows, double* out_traj, double* out_vel, double* out_duration, int* out_info,
-                      double* out_corner, int* out_corner_info, double* out_piece, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  int rc;
-  if ((rc = shortcut_check_paths("blend_paths", q_path, B, T))) return rc;
-  if (T >= (1 << 30)) { g_last_error = "blend_paths: need T < 2^30"; return LOIKB_ERR_ARG; }   // (2 T - 3 pieces are counted in ints)
-  const char* bad = !v_max ? "v_max == NULL" : !a_max ? "a_max == NULL" : !p ? "p == NULL" : !out_duration ? "need out_duration"
-                    : !out_info ? "need out_info" : nullptr;
-  for (int j = 0; !bad && j < S->nv; ++j) {
-    if (!(std::isfinite(v_max[j]) && v_max[j] > 0.0)) bad = "a v_max that is not finite and > 0";
-    else if (!(std::isfinite(a_max[j]) && a_max[j] > 0.0)) bad = "an a_max that is not finite and > 0";
-  }
-  if (bad) { g_last_error = std::string("blend_paths: ") + bad; return LOIKB_ERR_ARG; }
-  const loikb_motion_params mp{p->margin, p->tol, p->max_evals, p->flags};
-  if ((rc = motion_check_params(&mp, "blend_paths"))) return rc;
-  bad = !(std::isfinite(p->reach) && p->reach > 0.0) ? "reach is not finite and > 0"
-        : !(std::isfinite(p->dt) && p->dt > 0.0) ? "dt is not finite and > 0"
-        : (p->max_tries < 0 || p->max_tries > 16) ? "max_tries is outside 0 .. 16"
-        : (out_vel && !out_traj) ? "out_vel without out_traj"
-        : (out_traj && n_rows < 1) ? "out_traj with S < 1"
-        : (out_traj && (size_t)B * (size_t)n_rows > (size_t)0x7fffffff) ? "need B * S < 2^31"
-        : (out_traj && out_traj == q_path) ? "out_traj == q_path" : nullptr;
-  if (bad) { g_last_error = std::string("blend_paths: ") + bad; return LOIKB_ERR_ARG; }
-  if (S->pose.col.ns == 0) { g_last_error = "blend_paths: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
-  if (B == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  QueryOut o(S, out_flags);
-  const double *dq, *dlen;
-  if ((rc = motion_inputs(S, q_path, sizeof(double) * (size_t)B * T * S->nq, (const double*)len, sizeof(int) * (size_t)B, in_flags & LOIKB_IN_DEVICE, &dq, &dlen)) ||
-      (rc = blend_run(S, dq, (const int*)dlen, B, T, v_max, a_max, *p, out_traj ? n_rows : 0, out_traj, out_vel, out_duration, out_info, out_corner,
-                      out_corner_info, out_piece, o)))
-    return rc;
-  return o.finish();   // (the caller's arrays have been read)
-}
-
-// ---- include/loik_amd_plan.h (kernel in loik_pose_plan.hpp) ---------------------------------------------------------------------
-int loikb_plan_version(void) { return LOIKB_PLAN_VERSION; }
-
-// The launch of loikb_plan_paths.  lo, hi [nv] and coord [nv] (the coordinate of a sampled DoF, else -1) are the caller's, alive until
-// `o` is finished.  S->d_getscr[1] holds the two range rows, then the trees of every resident wavefront, then the coordinates and the
-// wavefronts' parents and path nodes; the records of a wavefront are LDS when they fit beside what the compiler keeps for itself,
-// else the motion check's slab (and its grid).  Queued; the caller finishes `o`
-static int plan_run(loikb_solver_impl* S, const double* dqs, const double* dqg, int B, int T, const double* lo, const double* hi, const int* coord,
-                    const loikb_plan_params& p, double* out_path, int* out_info, double* out_length, QueryOut& o)
-{
-  Collision& C = S->pose.col;
-  const int ncar = (int)C.car.size(), nv = S->nv;
-  const size_t aux = shortcut_aux_doubles(S->nb, ncar, C.ns);
-  hipFuncAttributes fa;
-  HIPCHK(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_plan_paths<false>)));
-  const bool slab = ((size_t)4 * C.ns + aux) * sizeof(double) + fa.sharedSizeBytes > 65536;
-  const size_t lds = ((size_t)4 * C.ns + (slab ? 0 : aux)) * sizeof(double);
-  const size_t wd = plan_scr_doubles(p.max_nodes, S->nq), wi = plan_scr_ints(p.max_nodes, T);
-  const size_t per = wd * sizeof(double) + wi * sizeof(int);
-  const size_t fit = std::max<size_t>(1, (size_t)LOIKB_PLAN_SCRATCH_BYTES / per);
-  const int waves = (int)std::min<size_t>((size_t)std::min(B, slab ? MOTION_SLAB_WAVES : SHORTCUT_WAVES), fit);
-  double *d_path, *d_len;
-  int* d_info;
-  o.add(out_path, sizeof(double) * (size_t)B * T * S->nq, &d_path);
-  o.add(out_length, sizeof(double) * (size_t)B, &d_len);
-  o.add(out_info, sizeof(int) * 8 * (size_t)B, &d_info);
-  int rc;
-  const size_t dbytes = sizeof(double) * ((size_t)2 * nv + wd * (size_t)waves);
-  if ((rc = o.reserve()) || (rc = regrow(S->d_getscr[1], dbytes + sizeof(int) * ((size_t)nv + wi * (size_t)waves)))) return rc;
-  double* d_lo = S->d_getscr[1].as<double>();
-  int* d_coord = (int*)(S->d_getscr[1].as<char>() + dbytes);
-  HIPCHK(hipMemcpyAsync(d_lo, lo, sizeof(double) * nv, hipMemcpyHostToDevice, S->stream));
-  HIPCHK(hipMemcpyAsync(d_lo + nv, hi, sizeof(double) * nv, hipMemcpyHostToDevice, S->stream));
-  HIPCHK(hipMemcpyAsync(d_coord, coord, sizeof(int) * nv, hipMemcpyHostToDevice, S->stream));
-  const ClrModel m = clr_model(S);
-  const PlanPrm prm{p.margin, p.tol, p.step, p.max_evals, p.max_iters, p.max_nodes, p.seed};
-  if (slab) {
-    if ((rc = regrow_drained(S, C.d_mslab, sizeof(double) * aux * (size_t)waves))) return rc;
-    hipLaunchKernelGGL(k_plan_paths<true>, dim3(waves), dim3(64), lds, S->stream, dqs, dqg, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
-                       (const double*)d_lo, (const double*)(d_lo + nv), (const int*)d_coord, C.d_mslab.as<double>(), d_lo + 2 * nv, d_coord + nv, d_path,
-                       d_info, d_len);
-  } else {
-    hipLaunchKernelGGL(k_plan_paths<false>, dim3(waves), dim3(64), lds, S->stream, dqs, dqg, B, T, S->nq, S->d_jd, S->d_idx_q, S->nb, m, prm,
-                       (const double*)d_lo, (const double*)(d_lo + nv), (const int*)d_coord, (double*)nullptr, d_lo + 2 * nv, d_coord + nv, d_path,
-                       d_info, d_len);
-  }
-  HIPCHK(hipGetLastError());
-  return LOIKB_OK;
-}
-
-int loikb_plan_paths(loikb_solver* S, const double* q_start, const double* q_goal, int B, int in_flags, const double* s_lo, const double* s_hi,
-                     const loikb_plan_params* p, int T, double* out_path, int* out_info, double* out_length, int out_flags)
-{
-  if (!S) return LOIKB_ERR_ARG;
-  int rc;
-  if (T < 2) { g_last_error = "plan_paths: need T >= 2"; return LOIKB_ERR_ARG; }
-  if (B < 0 || (size_t)B * (size_t)T > (size_t)0x7fffffff || (B > 0 && (!q_start || !q_goal))) {
-    g_last_error = "plan_paths: need B >= 0, B * T < 2^31 and q_start, q_goal when B > 0";
-    return LOIKB_ERR_ARG;
-  }
-  if (B > 0 && (!out_path || !out_info)) { g_last_error = "plan_paths: need out_path and out_info"; return LOIKB_ERR_ARG; }
-  const loikb_motion_params mp{p ? p->margin : 0.0, p ? p->tol : 0.0, p ? p->max_evals : 0, p ? p->flags : 0};
-  if ((rc = motion_check_params(p ? &mp : nullptr, "plan_paths"))) return rc;
-  const char* bad = !(std::isfinite(p->step) && p->step > 0.0) ? "step is not finite and > 0"
-                    : (p->max_iters < 0 || p->max_iters > 1048576) ? "max_iters is outside 0 .. 1048576"
-                    : (p->max_nodes < 2 || p->max_nodes > 65536) ? "max_nodes is outside 2 .. 65536" : nullptr;
-  if (bad) { g_last_error = std::string("plan_paths: ") + bad; return LOIKB_ERR_ARG; }
-  if (!s_lo || !s_hi) { g_last_error = "plan_paths: need s_lo and s_hi"; return LOIKB_ERR_ARG; }
-  if ((rc = check_dof_pairs(S, "plan_paths", "s_lo", "s_hi", s_lo, s_hi, S->nv))) return rc;
-  std::vector<int> coord(S->nv, -1);
-  int sampled = 0;
-  for (int j = 0; j < S->nv; ++j)
-    if (std::isfinite(s_lo[j]) && std::isfinite(s_hi[j])) { coord[j] = S->lim_q[j]; ++sampled; }
-  if (sampled == 0) { g_last_error = "plan_paths: no DoF to sample (s_lo and s_hi need a finite pair)"; return LOIKB_ERR_ARG; }
-  if (out_path && (out_path == q_start || out_path == q_goal)) { g_last_error = "plan_paths: out_path == q_start or q_goal"; return LOIKB_ERR_ARG; }
-  if (S->pose.col.ns == 0) { g_last_error = "plan_paths: no spheres set (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
-  if (B == 0) return LOIKB_OK;
-  HIPCHK(hipSetDevice(S->device));
-  QueryOut o(S, out_flags);
-  const size_t qbytes = sizeof(double) * (size_t)B * S->nq;
-  const double *dqs, *dqg;
-  if ((rc = motion_inputs(S, q_start, qbytes, q_goal, qbytes, in_flags & LOIKB_IN_DEVICE, &dqs, &dqg)) ||
-      (rc = plan_run(S, dqs, dqg, B, T, s_lo, s_hi, coord.data(), *p, out_path, out_info, out_length, o)))
-    return rc;
-  return o.finish();   // (the caller's arrays have been read)
 }
 
 // the buffers of the collision-aware selection, on first use

@@ -1,5 +1,6 @@
 """CPU: the motion interface (include/loik_amd_motion.h) -- the header declares exactly its four entry points, the library exports them,
-the binding's list, version, enum values and struct match, the mirror names them, and none of it leaks into the older headers."""
+the binding's list, version, enum values and struct match, the mirror names them, none of it leaks into the older headers, and the
+kernel behind the check keeps no static LDS."""
 import os
 import re
 
@@ -60,6 +61,38 @@ def test_binding_and_mirror_have_the_methods():
         assert re.search(r"\b%s\(" % name, mirror), name
     for sym in WANT - {"loikb_motion_version"}:
         assert sym + "(" in mirror, sym
+
+
+def test_motion_check_kernels_have_no_static_lds():
+    """both instantiations of k_motion_clearance in the library's gfx950 code object keep no LDS of their own (all of it is dynamic): the
+    host's LDS-or-slab rule counts a kernel's static LDS against the 64 KB, and for the motion check that term must stay 0 for the rule
+    to be fixed + aux > 65536 alone"""
+    import subprocess
+    import sys
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    import measure_clearance as MC
+    llvm = MC.LLVM
+    found = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        fat = os.path.join(tmp, "fat.bin")
+        subprocess.check_call([os.path.join(llvm, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, capi._LIB_PATH, os.path.join(tmp, "copy.so")])
+        blob = open(fat, "rb").read()
+        magic = b"__CLANG_OFFLOAD_BUNDLE__"
+        starts = [m.start() for m in re.finditer(re.escape(magic), blob)] + [len(blob)]
+        for k in range(len(starts) - 1):
+            part, co = os.path.join(tmp, "bundle%d" % k), os.path.join(tmp, "co%d" % k)
+            open(part, "wb").write(blob[starts[k]:starts[k + 1]])
+            subprocess.check_call([os.path.join(llvm, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                                   "--input=" + part, "--output=" + co])
+            notes = subprocess.check_output([os.path.join(llvm, "llvm-readelf"), "--notes", co], text=True)
+            for rec in notes.split("- .agpr_count:")[1:]:
+                name = re.search(r"\.name:\s+(\S+)", rec)
+                if name and "k_motion_clearance" in name.group(1):
+                    found[name.group(1)] = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", rec).group(1))
+    assert len(found) == 2 and {("ILb0E" in n, "ILb1E" in n) for n in found} == {(True, False), (False, True)}, sorted(found)
+    for name, lds in found.items():
+        assert lds == 0, (name, lds)
 
 
 def test_older_headers_and_lists_are_untouched():
