@@ -35,8 +35,10 @@
 #include "../loik_amd_plan.h"
 #include "../loik_amd_grid.h"
 #include "../loik_amd_gridnear.h"
+#include "../loik_amd_depth.h"
 
 #include <array>
+#include <cmath>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -182,6 +184,28 @@ struct IkIdDataOptimized {
       for (int c = r; c < 6; ++c, ++k) { m[6 * r + c] = p[k]; m[6 * c + r] = p[k]; }
     return m;
   }
+};
+
+// ---- what IntegrateDepth and IntegratePoints of FirstOrderLoikOptimized take and return (include/loik_amd_depth.h)
+// DepthCamera: a pinhole camera; T_world_cam = (R row-major, p) places its frame (x right, y down, z forward) in the world
+struct DepthCamera {
+  int width = 0, height = 0;
+  double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
+  std::array<double, 12> T_world_cam{{1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}};
+  double depth_scale = 1.0, z_min = 0.0, z_max = 0.0;
+};
+struct DepthStats {
+  long long returns = 0, inside = 0, occupied_before = 0, occupied_after = 0;
+};
+// what both calls take beside the sensor's data: fuse = onto the occupancy of the grid that is set (else the frame alone), carve (fuse
+// and a camera only) = less the voxels the frame sees through by more than band; filter_q [n][nq] = configurations whose collision
+// spheres, padded by filter_pad, are cut out; filter_resident > 0 (with an empty filter_q) = the first so many resident configurations.
+// band and filter_pad < 0: (sqrt(3) / 2) voxel, what the header says they must at least cover
+struct DepthOptions {
+  bool fuse = false, carve = false;
+  double band = -1.0, filter_pad = -1.0;
+  DVec filter_q;
+  int filter_resident = 0;
 };
 
 class FirstOrderLoikOptimized {
@@ -670,6 +694,49 @@ public:
     r.val.resize(2 * n); r.vox.resize(2 * n); r.normal.resize(3 * n);
     check(loikb_grid_nearest_query(h_, spheres.data(), (int)n, 0, r.val.data(), r.vox.data(), r.normal.data(), 0));
     return r;
+  }
+  // ---- depth images and point clouds (include/loik_amd_depth.h): the voxel world from what a sensor delivers, integrated on the device.
+  using DepthCamera = loik_amd::DepthCamera;
+  using DepthStats = loik_amd::DepthStats;
+  using DepthOptions = loik_amd::DepthOptions;
+  // depth [height][width] row-major, float metres (times depth_scale)
+  DepthStats IntegrateDepth(const std::vector<float>& depth, const DepthCamera& cam, const std::array<int, 3>& dims, const std::array<double, 3>& origin,
+                            double voxel, const DepthOptions& opt = DepthOptions())
+  {
+    return integrate_depth_(depth.data(), depth.size(), LOIKB_DEPTH_F32, cam, dims, origin, voxel, opt);
+  }
+  // ... or unsigned 16-bit image units (times depth_scale)
+  DepthStats IntegrateDepth(const std::vector<unsigned short>& depth, const DepthCamera& cam, const std::array<int, 3>& dims, const std::array<double, 3>& origin,
+                            double voxel, const DepthOptions& opt = DepthOptions())
+  {
+    return integrate_depth_(depth.data(), depth.size(), LOIKB_DEPTH_U16, cam, dims, origin, voxel, opt);
+  }
+  // points [n][3] in the world frame; nothing is carved
+  DepthStats IntegratePoints(const DVec& points, const std::array<int, 3>& dims, const std::array<double, 3>& origin, double voxel, const DepthOptions& opt = DepthOptions())
+  {
+    const std::size_t n = points.size() / 3;
+    if (points.size() != 3 * n) throw std::runtime_error("loik_amd: points is not a whole number of (x, y, z) rows");
+    int nf = 0;
+    const loikb_depth_params prm = depth_params_(opt, voxel, &nf);
+    long long st[4] = {0, 0, 0, 0};
+    check(loikb_collision_grid_integrate_points(h_, points.data(), (int)n, dims.data(), origin.data(), voxel, &prm, opt.filter_q.empty() ? nullptr : opt.filter_q.data(),
+                                                nf, 0, st));
+    return DepthStats{st[0], st[1], st[2], st[3]};
+  }
+  // whether a grid is set; with out, its occupancy [nz][ny][nx] as 0 / 1 bytes, whichever call set it
+  bool GetCollisionOccupancy(std::vector<unsigned char>* out = nullptr) const
+  {
+    const int rc = loikb_collision_grid_get_occupancy(h_, nullptr, 0);
+    if (rc < 0) check(rc);
+    if (rc == 0) return false;
+    if (out) {
+      CollisionGrid g;
+      GetCollisionGrid(&g, false);
+      out->resize((std::size_t)g.dims[0] * (std::size_t)g.dims[1] * (std::size_t)g.dims[2]);
+      const int rc2 = loikb_collision_grid_get_occupancy(h_, out->data(), 0);
+      if (rc2 < 0) check(rc2);
+    }
+    return true;
   }
   // ---- motions (include/loik_amd_motion.h).  Difference: v [n][nv] with q0 (+) v = q1 under Integrate's arithmetic
   DVec Difference(const DVec& q0, const DVec& q1) const
@@ -1200,6 +1267,32 @@ private:
     if (rc == LOIKB_OK) return;
     const char* msg = (rc <= LOIKB_ERR_ARG || rc == LOIKB_ERR_MODEL) ? loikb_last_error() : loikb_status_string(rc);
     throw std::runtime_error(msg && *msg ? msg : loikb_status_string(rc));
+  }
+  // (include/loik_amd_depth.h) the parameters of a call from its options; *nf: the filter configurations
+  loikb_depth_params depth_params_(const DepthOptions& opt, double voxel, int* nf) const
+  {
+    const std::size_t nq = (std::size_t)model_.nq, rows = opt.filter_q.size() / nq;
+    if (opt.filter_q.size() != rows * nq) throw std::runtime_error("loik_amd: filter_q is not a whole number of configurations");
+    *nf = opt.filter_q.empty() ? opt.filter_resident : (int)rows;
+    const double cover = 0.5 * std::sqrt(3.0) * voxel;
+    return loikb_depth_params{opt.fuse ? LOIKB_DEPTH_FUSE : LOIKB_DEPTH_REPLACE, opt.carve ? 1 : 0, opt.carve ? (opt.band < 0.0 ? cover : opt.band) : 0.0,
+                              opt.filter_pad < 0.0 ? cover : opt.filter_pad, 0};
+  }
+  DepthStats integrate_depth_(const void* depth, std::size_t count, int type, const DepthCamera& cam, const std::array<int, 3>& dims,
+                              const std::array<double, 3>& origin, double voxel, const DepthOptions& opt)
+  {
+    if (cam.width <= 0 || cam.height <= 0 || count != (std::size_t)cam.width * (std::size_t)cam.height)
+      throw std::runtime_error("loik_amd: need width * height > 0 depth pixels");
+    loikb_depth_camera c;
+    c.width = cam.width; c.height = cam.height;
+    c.fx = cam.fx; c.fy = cam.fy; c.cx = cam.cx; c.cy = cam.cy;
+    for (int k = 0; k < 12; ++k) c.T_world_cam[k] = cam.T_world_cam[(std::size_t)k];
+    c.depth_scale = cam.depth_scale; c.z_min = cam.z_min; c.z_max = cam.z_max;
+    int nf = 0;
+    const loikb_depth_params prm = depth_params_(opt, voxel, &nf);
+    long long st[4] = {0, 0, 0, 0};
+    check(loikb_collision_grid_integrate_depth(h_, depth, type, &c, dims.data(), origin.data(), voxel, &prm, opt.filter_q.empty() ? nullptr : opt.filter_q.data(), nf, 0, st));
+    return DepthStats{st[0], st[1], st[2], st[3]};
   }
   void pass(int id)
   {

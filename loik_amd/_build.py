@@ -7,7 +7,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libloik_amd.so")
 SOURCES = ["loik_host.hip", "loik_flat_kernels.hip", "models.c"]
-HEADERS = ["loik_device.hpp", "loik_tail.hpp", "loik_lean.hpp", "loik_flat.hpp", "loik_flat2.hpp", "loik_flat_prep.hpp", "loik_flat_inst.hpp", "loik_passes.hpp", "loik_pose.hpp", "loik_pose_tasks.hpp", "loik_pose_multistart.hpp", "loik_pose_path.hpp", "loik_pose_track.hpp", "loik_pose_accel.hpp", "loik_pose_step.hpp", "loik_pose_jacobian.hpp", "loik_pose_collision.hpp", "loik_pose_grid.hpp", "loik_pose_gridnear.hpp", "loik_pose_motion.hpp", "loik_pose_shortcut.hpp", "loik_pose_retime.hpp", "loik_pose_blend.hpp", "loik_pose_plan.hpp", "loik_pose_avoid.hpp", "loik_host_pose.hpp", "loik_host_motion.hpp", "loik_devmem.hpp",
+HEADERS = ["loik_device.hpp", "loik_tail.hpp", "loik_lean.hpp", "loik_flat.hpp", "loik_flat2.hpp", "loik_flat_prep.hpp", "loik_flat_inst.hpp", "loik_passes.hpp", "loik_pose.hpp", "loik_pose_tasks.hpp", "loik_pose_multistart.hpp", "loik_pose_path.hpp", "loik_pose_track.hpp", "loik_pose_accel.hpp", "loik_pose_step.hpp", "loik_pose_jacobian.hpp", "loik_pose_collision.hpp", "loik_pose_grid.hpp", "loik_pose_gridnear.hpp", "loik_pose_depth.hpp", "loik_pose_motion.hpp", "loik_pose_shortcut.hpp", "loik_pose_retime.hpp", "loik_pose_blend.hpp", "loik_pose_plan.hpp", "loik_pose_avoid.hpp", "loik_host_pose.hpp", "loik_host_motion.hpp", "loik_devmem.hpp",
            os.path.join("..", "..", "include", "loik_amd.h"), os.path.join("..", "..", "include", "loik_amd_models.h"),
            os.path.join("..", "..", "include", "loik_amd_pose.h"), os.path.join("..", "..", "include", "loik_amd_limits.h"),
            os.path.join("..", "..", "include", "loik_amd_tasks.h"), os.path.join("..", "..", "include", "loik_amd_multistart.h"),
@@ -18,7 +18,7 @@ HEADERS = ["loik_device.hpp", "loik_tail.hpp", "loik_lean.hpp", "loik_flat.hpp",
            os.path.join("..", "..", "include", "loik_amd_avoid.h"), os.path.join("..", "..", "include", "loik_amd_shortcut.h"),
            os.path.join("..", "..", "include", "loik_amd_retime.h"), os.path.join("..", "..", "include", "loik_amd_plan.h"),
            os.path.join("..", "..", "include", "loik_amd_blend.h"), os.path.join("..", "..", "include", "loik_amd_grid.h"),
-           os.path.join("..", "..", "include", "loik_amd_gridnear.h")]
+           os.path.join("..", "..", "include", "loik_amd_gridnear.h"), os.path.join("..", "..", "include", "loik_amd_depth.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # Code generation of the flat iteration kernels' translation unit (loik_flat_kernels.hip; why: csrc/loik_flat_inst.hpp): neighbouring LDS
 # accesses stay single 64-bit instructions -- neither the IR load/store vectorizer (128-bit accesses, ds_read2_b64 where the alignment is

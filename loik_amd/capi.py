@@ -224,6 +224,14 @@ GRID_MAX_DIM, GRID_MAX_VOXELS, GRID_EMPTY = 512, 1 << 26, 0xFFFFFFFF
 GRIDNEAR_ABI_VERSION = 1
 GRIDNEAR_SYMBOLS = ["loikb_gridnear_version", "loikb_collision_grid_set_nearest", "loikb_collision_grid_get_nearest", "loikb_grid_nearest_query"]
 GRID_NO_VOXEL = 0xFFFFFFFF
+# include/loik_amd_depth.h: voxel worlds from depth images and point clouds, integrated on the device; its own header and version
+DEPTH_ABI_VERSION = 1
+DEPTH_SYMBOLS = ["loikb_depth_version", "loikb_collision_grid_integrate_depth", "loikb_collision_grid_integrate_points",
+                 "loikb_collision_grid_get_occupancy"]
+DEPTH_F32, DEPTH_U16 = 0, 1
+DEPTH_REPLACE, DEPTH_FUSE = 0, 1
+DEPTH_Q_DEVICE = 2
+DEPTH_MAX_IMAGE, DEPTH_MAX_FILTER = 4096, 64
 
 
 class PoseParams(C.Structure):
@@ -244,6 +252,15 @@ class ClearanceParams(C.Structure):
 
 class MotionParams(C.Structure):
     _fields_ = [("margin", C.c_double), ("tol", C.c_double), ("max_evals", C.c_int), ("flags", C.c_int)]
+
+
+class DepthCamera(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("T_world_cam", C.c_double * 12), ("depth_scale", C.c_double), ("z_min", C.c_double), ("z_max", C.c_double)]
+
+
+class DepthParams(C.Structure):
+    _fields_ = [("mode", C.c_int), ("carve", C.c_int), ("band", C.c_double), ("filter_pad", C.c_double), ("flags", C.c_int)]
 
 
 class AvoidParams(C.Structure):
@@ -396,6 +413,11 @@ def lib():
     L.loikb_collision_get_world_grid.argtypes = [C.c_void_p, _ip, _dp, _dp, C.c_void_p, C.c_int]
     L.loikb_collision_grid_set_nearest.argtypes = [C.c_void_p, C.c_int]
     L.loikb_collision_grid_get_nearest.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.loikb_collision_grid_integrate_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _ip, _dp, C.c_double, C.c_void_p, C.c_void_p, C.c_int,
+                                                       C.c_int, C.c_void_p]
+    L.loikb_collision_grid_integrate_points.argtypes = [C.c_void_p, C.c_void_p, C.c_int, _ip, _dp, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                        C.c_void_p]
+    L.loikb_collision_grid_get_occupancy.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.loikb_grid_nearest_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     if L.loikb_version() != ABI_VERSION:
         raise ImportError("loik_amd: %s has ABI version %d, this binding was written for %d -- rebuild the library"
@@ -1304,6 +1326,85 @@ class BatchedLoik:
         ptrs, oflags, new = _outs(out, [((n, 2), np.float64), ((n, 2), np.int32), ((n, 3), np.float64)])
         _check(self.L.loikb_grid_nearest_query(self.h, sp, n, IN_DEVICE if dev else 0, *ptrs, oflags))
         return out if new is None else dict(zip(("val", "vox", "normal"), new))
+
+    # ---- depth images and point clouds (include/loik_amd_depth.h) ----------------------------------------------------
+    def _depth_call(self, what, dims, origin, voxel, mode, carve, band, filter_q, filter_pad, call):
+        modes = {"replace": DEPTH_REPLACE, "fuse": DEPTH_FUSE}
+        if mode not in modes:
+            raise ValueError("%s: mode must be 'replace' or 'fuse'" % what)
+        edge = float(voxel)
+        cover = 0.5 * np.sqrt(3.0) * edge   # what band and filter_pad must at least cover (loik_amd_depth.h)
+        prm = DepthParams(modes[mode], int(bool(carve)), float(cover if band is None else band) if carve else float(band or 0.0),
+                          float(cover if filter_pad is None else filter_pad), 0)
+        flags, keep = 0, None
+        if filter_q is None:
+            qp, nf = None, 0
+        elif isinstance(filter_q, (int, np.integer)) and not isinstance(filter_q, bool):
+            qp, nf = None, int(filter_q)   # the first n resident configurations
+        else:
+            qp, nf, dev, keep = self._rows(filter_q, self.model.nq)
+            flags = DEPTH_Q_DEVICE if dev else 0
+        dm = np.asarray(dims, dtype=np.int32).reshape(3)
+        org = _f64(origin).reshape(3)
+        st = np.zeros(4, dtype=np.int64)
+        _check(call(dm.ctypes.data_as(_ip), org.ctypes.data_as(_dp), edge, C.byref(prm), qp, nf, flags, st.ctypes.data_as(C.c_void_p)))
+        return dict(returns=int(st[0]), inside=int(st[1]), occupied_before=int(st[2]), occupied_after=int(st[3]))
+
+    def integrate_depth(self, depth, camera, dims, origin, voxel, mode="replace", carve=False, band=None, filter_q=None, filter_pad=None):
+        """a depth image into the voxel world (loikb_collision_grid_integrate_depth): depth [height][width] float32 or uint16, a host array
+        or a device tensor; camera a DepthCamera or a dict(fx, fy, cx, cy, T_world_cam [12] = (R row-major, p), z_min, z_max,
+        depth_scale=1.0) whose width and height come from the image; dims (nx, ny, nz), origin [3] and voxel as set_collision_grid.
+        mode "replace": the frame alone; "fuse": onto the occupancy of the grid that is set, with carve=True less the voxels the frame
+        sees through by more than band.  filter_q: configurations [n][nq] (host or device) whose collision spheres, padded by filter_pad,
+        are cut out; an int n: the first n resident configurations.  band and filter_pad default to (sqrt(3) / 2) voxel.  Returns
+        dict(returns, inside, occupied_before, occupied_after)."""
+        if hasattr(depth, "data_ptr") and getattr(depth, "is_cuda", False):
+            if not depth.is_contiguous():
+                raise ValueError("integrate_depth: a device image must be contiguous")
+            size = depth.element_size()
+            if size not in (2, 4):   # (by element size: four bytes are taken as float32, two as uint16)
+                raise ValueError("integrate_depth: a device image must be float32 or uint16")
+            shape, keep, ptr, dtype, dflag = tuple(int(d) for d in depth.shape), depth, C.c_void_p(depth.data_ptr()), DEPTH_F32 if size == 4 else DEPTH_U16, IN_DEVICE
+        else:
+            a = np.asarray(depth.numpy() if hasattr(depth, "numpy") else depth)
+            if a.dtype not in (np.float32, np.uint16):
+                raise ValueError("integrate_depth: the image must be float32 or uint16")
+            keep = np.ascontiguousarray(a)
+            shape, ptr, dtype, dflag = keep.shape, keep.ctypes.data_as(C.c_void_p), DEPTH_F32 if keep.dtype == np.float32 else DEPTH_U16, 0
+        if len(shape) != 2:
+            raise ValueError("integrate_depth: the image must be [height][width]")
+        if isinstance(camera, DepthCamera):
+            cam = camera
+        else:
+            T = _f64(camera["T_world_cam"]).reshape(12)
+            cam = DepthCamera(int(shape[1]), int(shape[0]), float(camera["fx"]), float(camera["fy"]), float(camera["cx"]), float(camera["cy"]),
+                              (C.c_double * 12)(*T), float(camera.get("depth_scale", 1.0)), float(camera["z_min"]), float(camera["z_max"]))
+        return self._depth_call("integrate_depth", dims, origin, voxel, mode, carve, band, filter_q, filter_pad,
+                                lambda dm, org, edge, prm, qp, nf, qflag, st: self.L.loikb_collision_grid_integrate_depth(
+                                    self.h, ptr, dtype, C.byref(cam), dm, org, edge, prm, qp, nf, dflag | qflag, st))
+
+    def integrate_points(self, points, dims, origin, voxel, mode="replace", filter_q=None, filter_pad=None):
+        """world points [n][3] (host or device float64) into the voxel world (loikb_collision_grid_integrate_points): as integrate_depth
+        from its step 3 on; points have no camera, so nothing is carved"""
+        pp, n, dev, keep = self._rows(points, 3)
+        return self._depth_call("integrate_points", dims, origin, voxel, mode, False, None, filter_q, filter_pad,
+                                lambda dm, org, edge, prm, qp, nf, qflag, st: self.L.loikb_collision_grid_integrate_points(
+                                    self.h, pp, n, dm, org, edge, prm, qp, nf, (IN_DEVICE if dev else 0) | qflag, st))
+
+    def collision_occupancy(self):
+        """uint8 [nz][ny][nx], 1 = occupied: the occupancy of the grid that is set, whichever call set it
+        (loikb_collision_grid_get_occupancy); None without a grid"""
+        rc = self.L.loikb_collision_grid_get_occupancy(self.h, None, 0)
+        if rc < 0:
+            _check(rc)
+        if rc == 0:
+            return None
+        nx, ny, nz = self.collision_grid(field=False)["dims"]
+        occ = np.empty((nz, ny, nx), dtype=np.uint8)
+        rc = self.L.loikb_collision_grid_get_occupancy(self.h, occ.ctypes.data_as(C.c_void_p), 0)
+        if rc < 0:
+            _check(rc)
+        return occ
 
     # ---- collision avoidance (include/loik_amd_avoid.h) -------------------------------------------------------------
     def set_collision_avoidance(self, d_safe, d_influence, kappa=0.5):

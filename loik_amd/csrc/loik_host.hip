@@ -29,6 +29,7 @@
 #include "loik_pose_collision.hpp"
 #include "loik_pose_grid.hpp"
 #include "loik_pose_gridnear.hpp"
+#include "loik_pose_depth.hpp"
 #include "loik_pose_motion.hpp"
 #include "loik_pose_shortcut.hpp"
 #include "loik_pose_retime.hpp"
@@ -66,6 +67,7 @@ int loikb_flat_prof_read(unsigned long long* out, int which, int reset);   // (l
 #include "../../include/loik_amd_plan.h"
 #include "../../include/loik_amd_grid.h"
 #include "../../include/loik_amd_gridnear.h"
+#include "../../include/loik_amd_depth.h"
 
 #include <algorithm>
 #include <atomic>
@@ -478,6 +480,11 @@ struct loikb_solver_impl {
       bool near_on = false;
       DevBuf<unsigned int> d_near, d_near_next;   // [nz][ny][nx]
       DevBuf<unsigned long long> d_nearkey;       // [nz][ny][nx]
+      // depth images and point clouds (loik_amd_depth.h): the staged image or points and filter configurations of a host caller, the
+      // padded filter spheres [n_filter][ns][4] and the four counters.  They only grow; the occupancy of a frame is written into d_occ
+      DevBuf<> d_dsrc;
+      DevBuf<double> d_dq, d_dcen;
+      DevBuf<unsigned long long> d_dstats;
       bool have_ms = false;              // loikb_clearance_set_multistart set `ms`
       loikb_clearance_params ms = {0.0, 0};
     } col;

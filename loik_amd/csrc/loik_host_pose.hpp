@@ -1137,50 +1137,48 @@ static int gridnear_build(loikb_solver_impl* S, const unsigned int* G, int nx, i
   return LOIKB_OK;
 }
 
-int loikb_collision_set_world_grid(loikb_solver* S, const unsigned char* occ, const int* dims, const double* origin, double h, int in_flags)
+// What loikb_collision_set_world_grid asks of a grid and of the handle before anything changes (loik_amd_grid.h); `fn` goes into
+// loikb_last_error().  *nvox: the voxels of the grid
+static int grid_check(const loikb_solver_impl* S, const char* fn, const int* dims, const double* origin, double h, size_t* nvox)
 {
-  if (!S) return LOIKB_ERR_ARG;
-  Collision& C = S->pose.col;
-  if (!occ) {   // clear: the buffers stay for the next grid
-    HIPCHK(hipSetDevice(S->device));
-    HIPCHK(hipStreamSynchronize(S->stream));
-    C.have_grid = false;
-    return LOIKB_OK;
-  }
-  if (!dims || !origin) { g_last_error = "collision_set_world_grid: need dims and origin with an occupancy"; return LOIKB_ERR_ARG; }
-  if (in_flags & ~LOIKB_IN_DEVICE) { g_last_error = "collision_set_world_grid: in_flags other than LOIKB_IN_DEVICE"; return LOIKB_ERR_ARG; }
-  size_t nvox = 1;
+  const Collision& C = S->pose.col;
+  const std::string f(fn);
+  size_t n = 1;
   for (int k = 0; k < 3; ++k) {
     if (dims[k] < 1 || dims[k] > LOIKB_GRID_MAX_DIM) {
-      g_last_error = "collision_set_world_grid: a dimension outside 1 .. LOIKB_GRID_MAX_DIM = " + std::to_string(LOIKB_GRID_MAX_DIM);
+      g_last_error = f + ": a dimension outside 1 .. LOIKB_GRID_MAX_DIM = " + std::to_string(LOIKB_GRID_MAX_DIM);
       return LOIKB_ERR_ARG;
     }
-    nvox *= (size_t)dims[k];
+    n *= (size_t)dims[k];
   }
-  if (nvox > GRID_MAX_VOXELS) { g_last_error = "collision_set_world_grid: more than LOIKB_GRID_MAX_VOXELS = 2^26 voxels"; return LOIKB_ERR_ARG; }
+  if (n > GRID_MAX_VOXELS) { g_last_error = f + ": more than LOIKB_GRID_MAX_VOXELS = 2^26 voxels"; return LOIKB_ERR_ARG; }
   if (!std::isfinite(h) || !(h > 0.0) || !std::isfinite(1.0 / h)) {
-    g_last_error = "collision_set_world_grid: need a finite voxel edge h > 0 with a finite inverse";
+    g_last_error = f + ": need a finite voxel edge h > 0 with a finite inverse";
     return LOIKB_ERR_ARG;
   }
   for (int k = 0; k < 3; ++k)
     if (!std::isfinite(origin[k]) || !std::isfinite(grid_hi(origin[k], dims[k], h))) {
-      g_last_error = "collision_set_world_grid: the origin or a corner of the grid's box is not finite";
+      g_last_error = f + ": the origin or a corner of the grid's box is not finite";
       return LOIKB_ERR_ARG;
     }
-  if (!col_ordinals_fit(C.ns, C.nws, C.nwb, true, C.pairs.size() / 2)) { g_last_error = "collision_set_world_grid: more than 2^31 pairs"; return LOIKB_ERR_ARG; }
+  if (!col_ordinals_fit(C.ns, C.nws, C.nwb, true, C.pairs.size() / 2)) { g_last_error = f + ": more than 2^31 pairs"; return LOIKB_ERR_ARG; }
   if (S->pose.avoid.have && !C.near_on) {
-    g_last_error = "collision_set_world_grid: collision avoidance is set on the handle (loikb_avoid_set), and avoidance cannot read a voxel grid -- clear it first."
-                   "  With the nearest-voxel transform latched (loikb_collision_grid_set_nearest) avoidance reads the grid.";
+    g_last_error = f + ": collision avoidance is set on the handle (loikb_avoid_set), and avoidance cannot read a voxel grid -- clear it first."
+                       "  With the nearest-voxel transform latched (loikb_collision_grid_set_nearest) avoidance reads the grid.";
     return LOIKB_ERR_STATE;
   }
-  HIPCHK(hipSetDevice(S->device));
+  *nvox = n;
+  return LOIKB_OK;
+}
+
+// The tail of every call that sets a grid: the field G of the device occupancy d_occ [nz][ny][nx] (and with the latch F) into the spare
+// buffers, which change places with the resident ones after the stream has drained; a failure leaves the handle as it was.  Complete on
+// return: whatever was queued before, the reads of a caller's memory included, has run
+static int grid_build_swap(loikb_solver_impl* S, const unsigned char* d_occ, const int* dims, const double* origin, double h)
+{
+  Collision& C = S->pose.col;
   const int nx = dims[0], ny = dims[1], nz = dims[2];
-  const unsigned char* d_occ = occ;
-  if (!(in_flags & LOIKB_IN_DEVICE)) {
-    BUFCHK(C.d_occ.regrow(nvox));
-    HIPCHK(hipMemcpyAsync(C.d_occ, occ, nvox, hipMemcpyHostToDevice, S->stream));
-    d_occ = C.d_occ;
-  }
+  const size_t nvox = (size_t)nx * ny * nz;
   BUFCHK(C.d_grid_next.regrow(sizeof(unsigned int) * nvox));   // (nothing queued reads it: it is not the grid that is set)
   unsigned int* G = C.d_grid_next;
   const long long nlines = (long long)ny * nz;
@@ -1203,13 +1201,37 @@ int loikb_collision_set_world_grid(loikb_solver* S, const unsigned char* occ, co
     BUFCHK(C.d_near_next.regrow(sizeof(unsigned int) * nvox));
     if (int rc = gridnear_build(S, G, nx, ny, nz, C.d_near_next)) return rc;
   }
-  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's occ has been read; nothing queued reads the grid that goes)
+  HIPCHK(hipStreamSynchronize(S->stream));   // (the caller's memory has been read; nothing queued reads the grid that goes)
   if (C.near_on) C.d_near.swap(C.d_near_next);
   C.d_grid.swap(C.d_grid_next);
   for (int k = 0; k < 3; ++k) { C.gn[k] = dims[k]; C.go[k] = origin[k]; }
   C.gh = h;
   C.have_grid = true;
   return LOIKB_OK;
+}
+
+int loikb_collision_set_world_grid(loikb_solver* S, const unsigned char* occ, const int* dims, const double* origin, double h, int in_flags)
+{
+  if (!S) return LOIKB_ERR_ARG;
+  Collision& C = S->pose.col;
+  if (!occ) {   // clear: the buffers stay for the next grid
+    HIPCHK(hipSetDevice(S->device));
+    HIPCHK(hipStreamSynchronize(S->stream));
+    C.have_grid = false;
+    return LOIKB_OK;
+  }
+  if (!dims || !origin) { g_last_error = "collision_set_world_grid: need dims and origin with an occupancy"; return LOIKB_ERR_ARG; }
+  if (in_flags & ~LOIKB_IN_DEVICE) { g_last_error = "collision_set_world_grid: in_flags other than LOIKB_IN_DEVICE"; return LOIKB_ERR_ARG; }
+  size_t nvox = 0;
+  if (int rc = grid_check(S, "collision_set_world_grid", dims, origin, h, &nvox)) return rc;
+  HIPCHK(hipSetDevice(S->device));
+  const unsigned char* d_occ = occ;
+  if (!(in_flags & LOIKB_IN_DEVICE)) {
+    BUFCHK(C.d_occ.regrow(nvox));
+    HIPCHK(hipMemcpyAsync(C.d_occ, occ, nvox, hipMemcpyHostToDevice, S->stream));
+    d_occ = C.d_occ;
+  }
+  return grid_build_swap(S, d_occ, dims, origin, h);
 }
 
 int loikb_collision_get_world_grid(loikb_solver* S, int* dims, double* origin, double* h, unsigned int* G, int out_flags)
@@ -1321,6 +1343,182 @@ int loikb_grid_nearest_query(loikb_solver* S, const double* spheres, int n, int 
   hipLaunchKernelGGL(k_grid_nearest_query, grid1((size_t)n), dim3(256), 0, S->stream, (const double*)ds, n, clr_model(S).g, d_val, d_vox, d_nrm);
   HIPCHK(hipGetLastError());
   return o.finish();   // (the caller's spheres have been read)
+}
+
+// ---- include/loik_amd_depth.h (kernels in loik_pose_depth.hpp) --------------------------------------------------------------------
+int loikb_depth_version(void) { return LOIKB_DEPTH_VERSION; }
+
+static_assert(DEPTH_F32 == LOIKB_DEPTH_F32 && DEPTH_U16 == LOIKB_DEPTH_U16, "the kernels' constants and the header's");
+
+// what is integrated: the pixels of a camera (points == nullptr) or n world points
+struct DepthSource {
+  const loikb_depth_camera* cam;
+  const void* data;   // the image or the points, as the caller gave them
+  int type;
+  long long n;        // pixels or points
+  size_t bytes;
+};
+
+// Steps 1 to 5 of loik_amd_depth.h behind both entry points.  The occupancy is written into C.d_occ, which no call keeps anything in
+static int depth_integrate(loikb_solver_impl* S, const char* fn, const DepthSource& src, const int* dims, const double* origin, double h,
+                           const loikb_depth_params* prm, const double* q_filter, int n_filter, int in_flags, long long* stats)
+{
+  const std::string f(fn);
+  Collision& C = S->pose.col;
+  if (!dims || !origin || !prm) { g_last_error = f + ": need dims, origin and params"; return LOIKB_ERR_ARG; }
+  if (in_flags & ~(LOIKB_IN_DEVICE | LOIKB_DEPTH_Q_DEVICE)) { g_last_error = f + ": in_flags other than LOIKB_IN_DEVICE | LOIKB_DEPTH_Q_DEVICE"; return LOIKB_ERR_ARG; }
+  if (prm->mode != LOIKB_DEPTH_REPLACE && prm->mode != LOIKB_DEPTH_FUSE) { g_last_error = f + ": mode is neither LOIKB_DEPTH_REPLACE nor LOIKB_DEPTH_FUSE"; return LOIKB_ERR_ARG; }
+  if (prm->carve != 0 && prm->carve != 1) { g_last_error = f + ": carve must be 0 or 1"; return LOIKB_ERR_ARG; }
+  if (prm->carve && prm->mode != LOIKB_DEPTH_FUSE) { g_last_error = f + ": carve needs LOIKB_DEPTH_FUSE"; return LOIKB_ERR_ARG; }
+  if (prm->carve && !src.cam) { g_last_error = f + ": points have no camera to carve from: carve must be 0"; return LOIKB_ERR_ARG; }
+  if (!(std::isfinite(prm->band) && prm->band >= 0.0) || !(std::isfinite(prm->filter_pad) && prm->filter_pad >= 0.0)) {
+    g_last_error = f + ": band and filter_pad must be finite and >= 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (prm->flags != 0) { g_last_error = f + ": params flags other than 0"; return LOIKB_ERR_ARG; }
+  if (n_filter < 0 || n_filter > LOIKB_DEPTH_MAX_FILTER) {
+    g_last_error = f + ": n_filter outside 0 .. LOIKB_DEPTH_MAX_FILTER = " + std::to_string(LOIKB_DEPTH_MAX_FILTER);
+    return LOIKB_ERR_ARG;
+  }
+  size_t nvox = 0;
+  if (int rc = grid_check(S, fn, dims, origin, h, &nvox)) return rc;
+  const bool fuse = prm->mode == LOIKB_DEPTH_FUSE && C.have_grid;
+  if (fuse && !(C.gn[0] == dims[0] && C.gn[1] == dims[1] && C.gn[2] == dims[2] && C.go[0] == origin[0] && C.go[1] == origin[1] && C.go[2] == origin[2] && C.gh == h)) {
+    g_last_error = f + ": LOIKB_DEPTH_FUSE onto a grid of other dims, origin or h than the one that is set";
+    return LOIKB_ERR_STATE;
+  }
+  if (n_filter > 0) {
+    if (C.ns == 0) { g_last_error = f + ": a self-filter needs collision spheres (loikb_collision_set_spheres)"; return LOIKB_ERR_STATE; }
+    if (!q_filter && n_filter > S->B) { g_last_error = f + ": q_filter == NULL (the resident q) needs n_filter <= the batch"; return LOIKB_ERR_STATE; }
+    if (!q_filter && !S->have_q) { g_last_error = f + ": no configurations resident on the device yet"; return LOIKB_ERR_STATE; }
+  }
+  HIPCHK(hipSetDevice(S->device));
+
+  DepthCam cam{};
+  DepthGrid g{};
+  for (int k = 0; k < 3; ++k) { g.n[k] = dims[k]; g.o[k] = origin[k]; }
+  g.h = h;
+  g.inv_h = 1.0 / h;
+  const void* d_src = src.data;
+  if (src.n > 0 && !(in_flags & LOIKB_IN_DEVICE)) {
+    if (int rc = regrow_drained(S, C.d_dsrc, src.bytes)) return rc;
+    HIPCHK(hipMemcpyAsync(C.d_dsrc, src.data, src.bytes, hipMemcpyHostToDevice, S->stream));
+    d_src = C.d_dsrc;
+  }
+  if (src.cam) {
+    const loikb_depth_camera& c = *src.cam;
+    cam.img = d_src; cam.type = src.type; cam.width = c.width; cam.height = c.height;
+    cam.fx = c.fx; cam.fy = c.fy; cam.cx = c.cx; cam.cy = c.cy;
+    for (int k = 0; k < 9; ++k) cam.R[k] = c.T_world_cam[k];
+    for (int k = 0; k < 3; ++k) cam.p[k] = c.T_world_cam[9 + k];
+    cam.scale = c.depth_scale; cam.z_min = c.z_min; cam.z_max = c.z_max;
+  }
+  int rc;
+  if ((rc = regrow_drained(S, C.d_occ, nvox)) || (rc = regrow_drained(S, C.d_dstats, 4 * sizeof(unsigned long long)))) return rc;
+  unsigned char* occ = C.d_occ;
+  unsigned long long* d_stats = C.d_dstats;
+  HIPCHK(hipMemsetAsync(d_stats, 0, 4 * sizeof(unsigned long long), S->stream));
+  // 1, 2: the prior, less what the frame sees through
+  if (fuse) {
+    hipLaunchKernelGGL(k_depth_prior_carve, dim3(depth_blocks(nvox, DEPTH_RUN)), dim3(DEPTH_THREADS), 0, S->stream, (const unsigned int*)C.d_grid, occ, nvox,
+                       g, cam, prm->carve, prm->band, d_stats);
+    HIPCHK(hipGetLastError());
+  } else {
+    HIPCHK(hipMemsetAsync(occ, 0, nvox, S->stream));
+  }
+  // 3: the points
+  if (src.n > 0) {
+    hipLaunchKernelGGL(k_depth_scatter, grid1((size_t)src.n), dim3(DEPTH_THREADS), 0, S->stream, cam, src.cam ? (const double*)nullptr : (const double*)d_src,
+                       src.n, g, occ, d_stats);
+    HIPCHK(hipGetLastError());
+  }
+  // 4: the self-filter
+  if (n_filter > 0) {
+    const double* dq = S->d_q;
+    if (q_filter) {
+      dq = q_filter;
+      if (!(in_flags & LOIKB_DEPTH_Q_DEVICE)) {
+        const size_t qb = sizeof(double) * (size_t)n_filter * S->nq;
+        if ((rc = regrow_drained(S, C.d_dq, qb))) return rc;
+        HIPCHK(hipMemcpyAsync(C.d_dq, q_filter, qb, hipMemcpyHostToDevice, S->stream));
+        dq = C.d_dq;
+      }
+    }
+    const int ncar = (int)C.car.size();
+    const size_t rows = (size_t)n_filter * C.ns;
+    if ((rc = regrow_drained(S, C.d_place, sizeof(double) * (size_t)n_filter * ncar * 12)) || (rc = regrow_drained(S, C.d_dcen, sizeof(double) * 4 * rows))) return rc;
+    hipLaunchKernelGGL(k_link_placements, grid1((size_t)n_filter * ncar), dim3(256), 0, S->stream, dq, S->nq, S->d_jd, S->d_idx_q, (const int*)C.d_car,
+                       ncar, n_filter, C.d_place);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_depth_centres, grid1(rows), dim3(256), 0, S->stream, (const double*)C.d_place, clr_model(S), n_filter, prm->filter_pad, (double*)C.d_dcen);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_depth_filter, dim3((unsigned)((rows + DEPTH_THREADS / 64 - 1) / (DEPTH_THREADS / 64))), dim3(DEPTH_THREADS), 0, S->stream,
+                       (const double*)C.d_dcen, (int)rows, g, occ);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_depth_count, dim3(depth_blocks(nvox, 16)), dim3(DEPTH_THREADS), 0, S->stream, (const unsigned char*)occ, nvox, d_stats);
+  HIPCHK(hipGetLastError());
+  unsigned long long st[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpyAsync(st, d_stats, sizeof(st), hipMemcpyDeviceToHost, S->stream));
+  // 5: the build, which drains the stream: st is complete, and the caller's image, points and q have been read
+  if ((rc = grid_build_swap(S, occ, dims, origin, h))) { (void)hipStreamSynchronize(S->stream); return rc; }
+  if (stats) {   // (k_depth_scatter keeps its two counters in one word)
+    stats[0] = (long long)(st[0] & 0xffffffffull); stats[1] = (long long)(st[0] >> 32);
+    stats[2] = (long long)st[2]; stats[3] = (long long)st[3];
+  }
+  return LOIKB_OK;
+}
+
+int loikb_collision_grid_integrate_depth(loikb_solver* S, const void* depth, int depth_type, const loikb_depth_camera* cam, const int* dims, const double* origin,
+                                         double h, const loikb_depth_params* prm, const double* q_filter, int n_filter, int in_flags, long long* stats)
+{
+  const char* fn = "collision_grid_integrate_depth";
+  const std::string f(fn);
+  if (!S) return LOIKB_ERR_ARG;
+  if (!depth || !cam) { g_last_error = f + ": need an image and a camera"; return LOIKB_ERR_ARG; }
+  if (depth_type != LOIKB_DEPTH_F32 && depth_type != LOIKB_DEPTH_U16) { g_last_error = f + ": depth_type is neither LOIKB_DEPTH_F32 nor LOIKB_DEPTH_U16"; return LOIKB_ERR_ARG; }
+  if (cam->width < 1 || cam->width > LOIKB_DEPTH_MAX_IMAGE || cam->height < 1 || cam->height > LOIKB_DEPTH_MAX_IMAGE) {
+    g_last_error = f + ": width or height outside 1 .. LOIKB_DEPTH_MAX_IMAGE = " + std::to_string(LOIKB_DEPTH_MAX_IMAGE);
+    return LOIKB_ERR_ARG;
+  }
+  if (!std::isfinite(cam->fx) || !std::isfinite(cam->fy) || !std::isfinite(cam->cx) || !std::isfinite(cam->cy) || !(cam->fx > 0.0) || !(cam->fy > 0.0)) {
+    g_last_error = f + ": the intrinsics must be finite with fx, fy > 0";
+    return LOIKB_ERR_ARG;
+  }
+  if (!frame_ok(cam->T_world_cam)) { g_last_error = f + ": T_world_cam is not finite or its rotation not orthonormal with determinant 1 (tolerance 1e-9)"; return LOIKB_ERR_ARG; }
+  if (!(std::isfinite(cam->depth_scale) && cam->depth_scale > 0.0)) { g_last_error = f + ": depth_scale must be finite and > 0"; return LOIKB_ERR_ARG; }
+  if (!(cam->z_min > 0.0 && cam->z_min <= cam->z_max && std::isfinite(cam->z_max))) { g_last_error = f + ": need 0 < z_min <= z_max < inf"; return LOIKB_ERR_ARG; }
+  const long long n = (long long)cam->width * cam->height;
+  const DepthSource src{cam, depth, depth_type, n, (size_t)n * (depth_type == LOIKB_DEPTH_F32 ? sizeof(float) : sizeof(unsigned short))};
+  return depth_integrate(S, fn, src, dims, origin, h, prm, q_filter, n_filter, in_flags, stats);
+}
+
+int loikb_collision_grid_integrate_points(loikb_solver* S, const double* points, int n, const int* dims, const double* origin, double h,
+                                          const loikb_depth_params* prm, const double* q_filter, int n_filter, int in_flags, long long* stats)
+{
+  const char* fn = "collision_grid_integrate_points";
+  if (!S) return LOIKB_ERR_ARG;
+  if (n < 0 || (n > 0 && !points)) { g_last_error = std::string(fn) + ": need n >= 0 and points when n > 0"; return LOIKB_ERR_ARG; }
+  const DepthSource src{nullptr, points, 0, (long long)n, sizeof(double) * 3 * (size_t)n};
+  return depth_integrate(S, fn, src, dims, origin, h, prm, q_filter, n_filter, in_flags, stats);
+}
+
+int loikb_collision_grid_get_occupancy(loikb_solver* S, unsigned char* occ, int out_flags)
+{
+  if (!S) return 0;
+  if (out_flags & ~LOIKB_OUT_DEVICE) { g_last_error = "collision_grid_get_occupancy: out_flags other than LOIKB_OUT_DEVICE"; return LOIKB_ERR_ARG; }
+  Collision& C = S->pose.col;
+  if (!C.have_grid) return 0;
+  if (occ) {
+    HIPCHK(hipSetDevice(S->device));
+    const size_t nvox = (size_t)C.gn[0] * C.gn[1] * C.gn[2];
+    if (int rc = regrow_drained(S, C.d_occ, nvox)) return rc;   // (through the handle's buffer: the caller's need not be aligned)
+    hipLaunchKernelGGL(k_depth_occupancy, grid1((nvox + DEPTH_RUN - 1) / DEPTH_RUN), dim3(DEPTH_THREADS), 0, S->stream, (const unsigned int*)C.d_grid,
+                       (unsigned char*)C.d_occ, nvox);
+    HIPCHK(hipGetLastError());
+    if (int rc = get_copy_out(S, (const unsigned char*)C.d_occ, nvox, occ, out_flags)) return rc;
+  }
+  return 1;
 }
 
 // One clearance launch over n rows of the device array dq [n][nq] into d_min [n][3] and d_wit [n][3] (or nullptr).  Queued.
